@@ -20,12 +20,18 @@ evaluation sees the drift a real solve produces (votes leaving their LDS windows
                     the headline, and the process-per-GPU form is self-spawned (torch.distributed.run) as a nested leg.  Fewer
                     devices than N: what is there runs, `n_gpus` says how many, an `error` field says why; exit status 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|frontend|backend] [--no-backend] [--no-cpu-baseline]
-Rank 0 prints ONE JSON line on stdout, at most LINE_BUDGET bytes: the contract's keys, `roofline`, `cpu_baseline`, `summary`.
-Everything else measured in the run (per-kernel table, per-packet / per-window pipelines, launch-default shapes, front end beside
-back end, group, large launch, concurrent contexts, the nested back-end leg in full) goes to bench_detail.json (--detail-out) and,
-as one line, to stderr.  Every number is measured in this run except `roofline.traffic` / `kernels[].pmc_bytes`, which are
-read from profiles/pmc_traffic.json (rocprofv3 --pmc passes of this same command, see profiles/README.md).
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full] [--workload auto|frontend|backend] ...
+A plain run measures the headline alone: set-up, warm-up, the K timed steps, the result line.  --full adds everything else this
+file measures or checks -- per-kernel calibration and `roofline`, cost-only and pipelined loops, CMax solves, `cpu_baseline`, the
+nested legs (config 3 at N = 1, config 5 and parity against one GPU at N > 1, the process-per-GPU child of a plain --gpus N) and
+the extras (--no-* options switch parts of it off).  --dump-outputs DIR writes what the timed path returned in its last step
+(contrast.npy, gradient.npy: float64); the same arguments give the same inputs in every run (see CONFIG2_POINTS, record_trajectory).
+Rank 0 prints ONE JSON line on stdout, at most LINE_BUDGET bytes: the contract's keys and, with --full, `roofline`, `cpu_baseline`,
+`summary`.  Everything else measured in the run (per-kernel table, per-packet / per-window pipelines, launch-default shapes, front
+end beside back end, group, large launch, concurrent contexts, the nested back-end leg in full) goes to bench_detail.json
+(--detail-out) and, as one line, to stderr.  Every number is measured in this run except `roofline.traffic` /
+`kernels[].pmc_bytes`, which are read from profiles/pmc_traffic.json (rocprofv3 --pmc passes of this same command with --full,
+see profiles/README.md).
 """
 import argparse
 import json
@@ -44,6 +50,19 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 # at 4 clocks, fp32 / integer at 2): pricing every one of them at the fp64 rate is the generous-to-the-hardware reading, frac <= 1.
 VALU_FP64_PEAK_TLANE = 256 * 4 * 2.4e9 / 4 * 64 / 1e12
 METRIC = "warped-events/sec/GPU (1M ev, 640x480 IWE) + CMax iters/sec"
+# The headline's evaluation points (config 2, 1M events, one context): the FR-CG solve from zero with solver.FRONTEND's settings,
+# recorded once by the CPU oracle's front end (oracle/) and thinned as record_trajectory() thins it.  Held fixed so that
+# every build of the project times, and with --dump-outputs returns, the same evaluations.
+CONFIG2_POINTS = (
+    (0.0, 0.0, 0.0),
+    (0.16566449213982137, -0.2500736468420134, 0.004295020278305433),
+    (0.8283224606991069, -1.2503682342100668, 0.02147510139152716),
+    (0.6035635062751382, -0.9110903921860716, 0.01564799713694183),
+    (0.8390746803338682, -1.1787553766887533, 0.10986286673381776),
+    (0.6083506781863686, -0.9141107148239087, 0.019990823084175997),
+    (0.5962210974989257, -0.9034022621168715, 0.011602111437526156),
+    (0.6186485460190174, -0.9232020621269035, 0.027112738181606626),
+)
 
 
 # ---------------------------------------------------------------------------------------------- byte models
@@ -186,7 +205,9 @@ class Runner:
 
 def record_trajectory(ev, x0, kind, params, max_points=8):
     """Evaluation points of one real FR-CG solve (the restated driver over THIS evaluator, python callbacks, untimed),
-    thinned to <= max_points spread over the solve: first point, accepted iterates, trial points, last point."""
+    thinned to <= max_points spread over the solve: first point, accepted iterates, trial points, last point.  The solve runs on the
+    production path with CMX_OPT_DETERMINISTIC on (bitwise reproducible evaluations), so the same workload gives the same points in
+    every run; it leaves the evaluator non-deterministic, and the caller chooses its path afterwards."""
     from cmax_slam_amd import solver
     pts = []
 
@@ -194,7 +215,12 @@ def record_trajectory(ev, x0, kind, params, max_points=8):
         pts.append(np.array(x, dtype=np.float64))
         c, g = ev.eval(x, wg)
         return -c, (-g if wg else None)
-    solver.frcg_minimize(fdf, x0, **params)
+    ev.set_fast_path()
+    ev.set_deterministic(True)
+    try:
+        solver.frcg_minimize(fdf, x0, **params)
+    finally:
+        ev.set_deterministic(False)
     uniq = []
     for p in pts:
         if not any(np.array_equal(p, q) for q in uniq):
@@ -205,9 +231,10 @@ def record_trajectory(ev, x0, kind, params, max_points=8):
     return uniq
 
 
-def measure(run, points, steps, warmup, kind, order, n_local, n_total, npix, nb, P, adjoint, pmc_prefix):
+def measure(run, points, steps, warmup, kind, order, n_local, n_total, npix, nb, P, adjoint, pmc_prefix, full=True):
     """Warm-up, per-kernel calibration (HIP events carried by every kernel class), then the timed region (EXACTLY `steps`
-    fdf evaluations between two fences, dominant kernel timed live on ~12 of them), then the cost-only loop."""
+    fdf evaluations between two fences), the dominant kernel's live sample pass behind it, then the cost-only loop.
+    full=False (a plain run): warm-up and the timed region only."""
     ev = run.ev
     npts = len(points)
     # the GPU drops its clocks while the host works (set-up, the recorded solve's python callbacks, the previous workload's
@@ -224,23 +251,24 @@ def measure(run, points, steps, warmup, kind, order, n_local, n_total, npix, nb,
             i += 1
     for i in range(warmup):
         run.step(points[i % npts], True)
-    # ---- calibration (untimed): every kernel class, fdf then cost-only
-    ncal = max(8 * npts, 64)  # (16 evaluations gave per-kernel means that moved by 10 % from run to run)
-    ev.timing_enable(True)
-    ev.timing_get()
-    for i in range(ncal):
-        run.step(points[i % npts], True)
-    run.torch.cuda.synchronize()
-    cal = ev.timing_get()
-    for i in range(ncal):
-        run.step(points[i % npts], False)
-    run.torch.cuda.synchronize()
-    cal_f = ev.timing_get()
-    kernel_ms = {k: v[0] / v[1] for k, v in cal.items() if v[1] and k not in ("zero",)}
-    kernel_ms_f = {k: v[0] / v[1] for k, v in cal_f.items() if v[1] and k not in ("zero",)}
-    per_eval = {k: v[1] / ncal for k, v in cal.items() if v[1]}
-    compute = [k for k in kernel_ms if k != "comm"]
-    dom = max(compute, key=lambda k: kernel_ms[k])
+    if full:
+        # ---- calibration (untimed): every kernel class, fdf then cost-only
+        ncal = max(8 * npts, 64)  # (16 evaluations gave per-kernel means that moved by 10 % from run to run)
+        ev.timing_enable(True)
+        ev.timing_get()
+        for i in range(ncal):
+            run.step(points[i % npts], True)
+        run.torch.cuda.synchronize()
+        cal = ev.timing_get()
+        for i in range(ncal):
+            run.step(points[i % npts], False)
+        run.torch.cuda.synchronize()
+        cal_f = ev.timing_get()
+        kernel_ms = {k: v[0] / v[1] for k, v in cal.items() if v[1] and k not in ("zero",)}
+        kernel_ms_f = {k: v[0] / v[1] for k, v in cal_f.items() if v[1] and k not in ("zero",)}
+        per_eval = {k: v[1] / ncal for k, v in cal.items() if v[1]}
+        compute = [k for k in kernel_ms if k != "comm"]
+        dom = max(compute, key=lambda k: kernel_ms[k])
     # ---- timed region
     # The K timed steps are issued by ONE native call (cmx_*_eval_each): exactly K calls of cmx_*_eval, each waited for before
     # the next is issued -- the C++ loop of the reference's host (GSL inside a ROS node), without ~2 us of Python interpreter
@@ -267,6 +295,15 @@ def measure(run, points, steps, warmup, kind, order, n_local, n_total, npix, nb,
     run.fence()
     elapsed = time.perf_counter() - t0
     region_split = {"loop_ms": (t_loop - t0) * 1e3, "closing_fence_ms": elapsed * 1e3 - (t_loop - t0) * 1e3}
+    timed_loop = ("native: one cmx_*_eval_each call issues the K evaluations one after the other (each waited for)" if native_loop
+                  else "python: K calls of the sharded evaluator")
+    if not full:  # a plain run: the headline and nothing else
+        if run.world > 1:
+            t = run.torch.tensor([elapsed], dtype=run.torch.float64, device=run.device)
+            run.dist.all_reduce(t, op=run.dist.ReduceOp.MAX)
+            elapsed = float(t[0].item())
+        return {"ms_per_step": elapsed / steps * 1e3, "value": n_total * steps / elapsed, "timed_loop": timed_loop,
+                "timed_region_split": region_split, "trajectory_points": npts, "contrast": c, "_last": (c, g)}
     # ---- sample pass behind the region: the dominant kernel's live duration (HIP events carried by its dispatches)
     # (24 launches read 10-25 % above rocprofv3's average of the same kernel in the same loop -- 20.9 against 16.9 us, tools/live_vs_trace.py:
     #  the first launches that carry events pay for the events themselves and a mean of 24 keeps that; primed and over 200+ launches
@@ -425,8 +462,7 @@ def measure(run, points, steps, warmup, kind, order, n_local, n_total, npix, nb,
             "ratio_8d_bytes_to_peak": whole_eval_bytes_8d(kind, order, n_local, npix, P) / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
             "note": "ratio_8d_bytes_to_peak prices the REFERENCE's data flow (1+P planes scattered, blurred, reduced) at this run's time: the "
                     "adjoint gradient never moves most of those bytes; frac is what this implementation must move"},
-        "timed_loop": ("native: one cmx_*_eval_each call issues the K evaluations one after the other (each waited for)" if native_loop
-                       else "python: K calls of the sharded evaluator"),
+        "timed_loop": timed_loop,
         "timed_region_split": region_split,
         "trajectory_points": npts, "rebins": stats["rebins"], "fallback_frac_last": stats["fallback_frac"],
         "launches_per_evaluation": sum(per_eval.get(k, 1.0) for k in kernel_ms if k != "comm"),
@@ -457,17 +493,22 @@ def frontend_workload(args, ctx, per_gpu):
     ev = evaluator.FrontendEvaluator(p.W, p.H, p.lut, device=dev)
     ev.set_packet(p.x[beg:end], p.y[beg:end], p.t_ns[beg:end], p.t_ref_ns, p.fx, p.fy, p.cx, p.cy, p.batch, p.sigma, _lib.VARIANCE)
     adjoint = args.mode == "fast"
-    (ev.set_fast_path if adjoint else ev.set_reference_path)()
+    set_path = ev.set_fast_path if adjoint else ev.set_reference_path
+    set_path()
     run = Runner(ev, world, args.comm, ctx["device"], ctx["torch"], ctx["dist"], force=ctx["sharded"])
-    if not ctx["sharded"]:
+    if not ctx["sharded"] and len(p.x) == 1_000_000:  # the headline workload: its recorded solve, fixed in this file
+        points = [np.array(x) for x in CONFIG2_POINTS]
+    elif not ctx["sharded"]:
         points = record_trajectory(ev, np.zeros(3), "frontend", solver.FRONTEND)
+        set_path()
     else:  # sharded: the trajectory of the whole problem is not available per rank; a line through the solve's range
         points = [np.array([0.6, -0.9, 0.4]) * s for s in (0.0, 0.35, 0.7, 0.9, 1.0)]
     ev.set_option(_lib.OPT_REUSE_IMAGE, 0)  # every timed step is a FULL evaluation (the df-after-f reuse is for solves)
-    iwe = ev.computeImageOfWarpedEvents(points[-1], blur=False)
-    run.nnz_pixels = int(np.count_nonzero(iwe))
+    if args.full:  # (the roofline's byte model counts the non-zero IWE pixels)
+        iwe = ev.computeImageOfWarpedEvents(points[-1], blur=False)
+        run.nnz_pixels = int(np.count_nonzero(iwe))
     m = measure(run, points, args.steps, args.warmup, "frontend", 0, end - beg, len(p.x), p.W * p.H, 0, 3, adjoint,
-                ("frontend_%s" % args.mode) if (world == 1 and per_gpu == 1_000_000) else "none")
+                ("frontend_%s" % args.mode) if (world == 1 and per_gpu == 1_000_000) else "none", full=args.full)
     name = "BASELINE config 2: front-end fdf, %d synthetic events/GPU, 640x480 IWE, batch 100, sigma 1, variance" % per_gpu
     return ev, run, p, m, name, "%dx%d" % (p.W, p.H), points
 
@@ -599,7 +640,8 @@ def backend_workload(args, ctx, which, per_gpu, steps, group_devices=None):
     ev.set_window(w.x, w.y, w.t_ns, w.order, w.knots_init, w.start_ns, w.dt_ns, w.num_fixed, w.t_next_win_beg_ns, w.batch,
                   w.sample_rate, w.sigma, _lib.VARIANCE, IG)
     adjoint = args.mode == "fast"
-    (ev.set_fast_path if adjoint else ev.set_reference_path)()
+    set_path = ev.set_fast_path if adjoint else ev.set_reference_path
+    set_path()
     run = Runner(ev, world, args.comm, ctx["device"], ctx["torch"], ctx["dist"], force=ctx["sharded"] and not group_devices)
     if group_devices:
         run.ev_sharded = True            # (no eval_many on a group; its exchange lives inside the handle)
@@ -607,31 +649,33 @@ def backend_workload(args, ctx, which, per_gpu, steps, group_devices=None):
             n_members, {1: "RCCL via ncclCommInitAll", 2: "direct peer-to-peer kernels"}.get(ev.group_info()["transport"], "plain context"))
     if not ctx["sharded"]:
         points = record_trajectory(ev, np.zeros(w.P), "backend", solver.BACKEND)
+        set_path()
     else:  # every rank must evaluate the same points: a seeded walk of the size of a solve's steps
         rng = np.random.default_rng(77)
         points = [np.zeros(w.P)] + [rng.normal(0, 0.004, w.P) * s for s in (0.3, 0.6, 0.9, 1.0)]
     ev.set_option(_lib.OPT_REUSE_IMAGE, 0)
-    if group_devices and n_members > 1:
-        ev.eval(points[-1], False)   # (a group has no split-phase interface; member 0 holds the exchanged planes)
-    else:
-        ev.accumulate(points[-1], False)
-    il_old, il_new = ev.get_plane(_lib.PLANE_IL_OLD), ev.get_plane(_lib.PLANE_IL_NEW)
-    run.nnz_pixels = int(np.count_nonzero(il_old) + np.count_nonzero(il_new))
-    # the image passes skip 64x16 tiles with nothing (votes or global map) within the filter's reach: count what is left
-    occ = (il_old != 0) | (il_new != 0)
-    if IG is not None:
-        occ |= IG != 0
-    Hp, Wp = occ.shape
-    tiles = occ[:Hp // 16 * 16, :Wp // 64 * 64].reshape(Hp // 16, 16, Wp // 64, 64).any(axis=(1, 3))
-    grown = tiles.copy()
-    for dy in (-1, 0, 1):      # reach of the 2r = 8 pixel halo: the neighbouring tiles
-        for dx in (-1, 0, 1):
-            grown |= np.roll(np.roll(tiles, dy, 0), dx, 1)
-    run.image_pixels = int(min(grown.sum() * 1024, Wp * Hp))
+    if args.full:  # (the roofline's byte model: non-zero pixels of the vote planes, pixels the image passes touch)
+        if group_devices and n_members > 1:
+            ev.eval(points[-1], False)   # (a group has no split-phase interface; member 0 holds the exchanged planes)
+        else:
+            ev.accumulate(points[-1], False)
+        il_old, il_new = ev.get_plane(_lib.PLANE_IL_OLD), ev.get_plane(_lib.PLANE_IL_NEW)
+        run.nnz_pixels = int(np.count_nonzero(il_old) + np.count_nonzero(il_new))
+        # the image passes skip 64x16 tiles with nothing (votes or global map) within the filter's reach: count what is left
+        occ = (il_old != 0) | (il_new != 0)
+        if IG is not None:
+            occ |= IG != 0
+        Hp, Wp = occ.shape
+        tiles = occ[:Hp // 16 * 16, :Wp // 64 * 64].reshape(Hp // 16, 16, Wp // 64, 64).any(axis=(1, 3))
+        grown = tiles.copy()
+        for dy in (-1, 0, 1):      # reach of the 2r = 8 pixel halo: the neighbouring tiles
+            for dx in (-1, 0, 1):
+                grown |= np.roll(np.roll(tiles, dy, 0), dx, 1)
+        run.image_pixels = int(min(grown.sum() * 1024, Wp * Hp))
     n_local = len(w.x) // n_members
     nb = (n_local - 1 + w.batch - 1) // w.batch
     m = measure(run, points, steps, args.warmup, "backend", w.order, n_local, n_local * world * n_members, w.Wp * w.Hp, nb, w.P, adjoint,
-                ("backend_%s" % args.mode) if (which == "config3" and per_gpu == 5_000_000) else "none")
+                ("backend_%s" % args.mode) if (which == "config3" and per_gpu == 5_000_000) else "none", full=args.full)
     desc = {"config3": "BASELINE config 3: back-end BA fdf, %d synthetic events, cubic 10-knot SO(3) spline (P=21), 1024x1024 pano",
             "config4": "BASELINE config 4: back-end BA sliding window fdf, %d synthetic events/GPU (time slab per rank), cubic 10-knot "
                        "spline (P=21), 1024x1024 pano",
@@ -1544,6 +1588,8 @@ def spawn_process_per_gpu(n, args, timeout_s=900):
            "--mode", args.mode, "--comm", args.comm, "--detail-out", os.path.splitext(args.detail_out)[0] + "_ranks.json"]
     if args.events:
         cmd += ["--events", str(args.events)]
+    if getattr(args, "full", False):
+        cmd += ["--full"]
     if args.no_config5:
         cmd += ["--no-config5"]
     if args.no_parity:
@@ -1615,9 +1661,19 @@ def main():
                     help="where everything that is not on the stdout line goes (JSON)")
     ap.add_argument("--force-sharded", action="store_true",
                     help="dry run of the N>1 code path (time slabs, communicator, parity gather) with whatever world size is launched")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: per-kernel calibration and roofline, cost-only and pipelined loops, CMax solves, "
+                         "CPU baseline, nested legs (config 3 / config 5 / parity / process-per-GPU child) and extras; the --no-* options "
+                         "act within it.  Without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path returned in its last step to DIR/contrast.npy and DIR/gradient.npy (float64)")
     args = ap.parse_args()
     if args.steps_backend is None:
         args.steps_backend = args.steps
+    if not args.full:  # a plain run: the headline alone (every leg beside it is behind one of these switches)
+        args.solves = 0
+        args.no_cpu_baseline = args.no_per_packet = args.no_backend = args.no_config5 = args.no_parity = True
+        args.no_extras = args.no_spawn = True
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1659,6 +1715,8 @@ def main():
     if family == "frontend":
         ev, run, p, m, name, img, pts = frontend_workload(args, ctx, args.events or 1_000_000)
         if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, *m["_last"])
             out = line(m, world, args, name, len(p.x), img, run.comm_used, mode_desc)
             if world == 1 and args.solves > 0:
                 out["cmax"] = cmax_solves(args.solves, ev, "frontend", _lib)
@@ -1713,6 +1771,8 @@ def main():
         per_gpu = args.events or 5_000_000
         ev, run, w, m, name, img, pts = backend_workload(args, ctx, which, per_gpu, args.steps, group_devices)
         c, g = m.pop("_last")
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, c, g)
         par = None
         if group_devices and not args.no_parity:  # the whole window on ONE context of this process: what the group must equal
             try:
@@ -1807,6 +1867,13 @@ def main():
             child = spawn_process_per_gpu(plan["spawn"], args)
             out["process_per_gpu"] = child
         emit(out, args)
+
+
+def dump_outputs(d, c, g):
+    """--dump-outputs: what a caller of the timed path received from its last step -- the contrast and its gradient."""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "contrast.npy"), np.array([c], dtype=np.float64))
+    np.save(os.path.join(d, "gradient.npy"), np.asarray(g, dtype=np.float64).reshape(-1))
 
 
 def emit(out, args):

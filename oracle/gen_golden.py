@@ -9,6 +9,9 @@
                        Eigen (fullPivHouseholderQr().solve, incl. rank-deficient ones) + SO3 products by its Sophus:
                        these PIN oracle/traj_init.c's solver.  Plus the oracle's own integrateAngVel / fitCtrlPoses /
                        bearing-LUT outputs on seeded inputs (regression vectors).
+  ref_random_cases.npz the seeded random spline and QR inputs of the two tests that also compare against the compiled
+                       reference live, with the REFERENCE's outputs on them (Basalt spline, Eigen QR): those tests stand
+                       on this file where the compiled reference is absent.
 
 usage: python oracle/gen_golden.py
 """
@@ -202,10 +205,61 @@ def gen_trajinit():
     print("trajinit.npz written; ranks:", sorted(set(zip(*[map(int, rank), [c for _, c in shape]]))))
 
 
+def gen_ref_random_cases():
+    """The seeded random inputs of tests/test_oracle_golden.py::test_live_basalt_when_built and
+    tests/test_trajinit_cpu.py::test_oracle_qr_matches_live_eigen, with the REFERENCE's outputs on them (vendored Basalt spline,
+    vendored Eigen fullPivHouseholderQr): those tests compare the oracle against these where the compiled reference is absent."""
+    po.build()
+    assert po.ref_lib() is not None, "needs the compiled reference (make -C oracle ref)"
+    out = {}
+    # (1) So3Spline<order>::evaluate on knots from the oracle's exp (the test's own draw: seed 99, 100 cases per order)
+    rng = np.random.default_rng(99)
+    order_l, K_l, t_l, knots_l, q_l, R_l, J_l, idx_l = [], [], [], [], [], [], [], []
+    for order in (2, 4):
+        for _ in range(100):
+            K = order + int(rng.integers(0, 5))
+            knots = np.array([po.so3_exp(rng.normal(0, 0.8, 3)) for _ in range(K)])
+            dt = 50_000_000
+            t = 10**9 + int(rng.integers(0, (K - order + 1) * dt))
+            q, R, J, idx = po.spline_eval(order, knots, 10**9, dt, t, use_ref=True)
+            kp = np.zeros((8, 4)); kp[:K] = knots
+            Jp = np.zeros((4, 3, 3)); Jp[:order] = J
+            order_l.append(order); K_l.append(K); t_l.append(t); knots_l.append(kp)
+            q_l.append(q); R_l.append(R); J_l.append(Jp); idx_l.append(idx)
+    out["spl_order"], out["spl_K"], out["spl_t_ns"] = np.array(order_l), np.array(K_l), np.array(t_l, np.int64)
+    out["spl_start_ns"], out["spl_dt_ns"] = np.array(10**9, np.int64), np.array(50_000_000, np.int64)
+    out["spl_knots"], out["spl_quat"], out["spl_R"], out["spl_J"] = np.array(knots_l), np.array(q_l), np.array(R_l), np.array(J_l)
+    out["spl_idx"] = np.array(idx_l)
+    # (2) x = A.fullPivHouseholderQr().solve(b) and the rank (the test's own draw: seed 5, 100 systems up to 29 x 9, padded)
+    rng = np.random.default_rng(5)
+    A_l, b_l, x_l, shape_l, rank_l = [], [], [], [], []
+    for trial in range(100):
+        r, c = int(rng.integers(1, 30)), int(rng.integers(1, 10))
+        A = rng.normal(size=(r, c))
+        if trial % 3 == 1 and c > 1:
+            A[:, -1] = 0
+        if trial % 3 == 2:
+            A[rng.random(A.shape) < 0.6] = 0
+        b = rng.normal(size=r)
+        x, rk = po.fullpiv_qr_solve(A, b, use_ref=True)
+        Ap = np.zeros((29, 9)); Ap[:r, :c] = A
+        bp = np.zeros(29); bp[:r] = b
+        xp = np.zeros(9); xp[:c] = x
+        A_l.append(Ap); b_l.append(bp); x_l.append(xp); shape_l.append((r, c)); rank_l.append(rk)
+    out["qr_A"], out["qr_b"], out["qr_x"] = np.array(A_l), np.array(b_l), np.array(x_l)
+    out["qr_shape"], out["qr_rank"] = np.array(shape_l), np.array(rank_l)
+    np.savez_compressed(os.path.join(OUT, "ref_random_cases.npz"), **out)
+    print("ref_random_cases.npz written: %d spline cases, %d QR systems" % (len(K_l), len(rank_l)))
+
+
 if __name__ == "__main__":
+    if "--only-ref-random-cases" in sys.argv:
+        gen_ref_random_cases()
+        sys.exit(0)
     gen_trajinit()
     if "--only-trajinit" in sys.argv:
         sys.exit(0)
+    gen_ref_random_cases()
     gen_spline()
     gen_frontend()
     gen_backend()

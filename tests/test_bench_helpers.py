@@ -169,3 +169,26 @@ def test_stdout_line_of_the_sharded_and_group_forms():
             assert k in line["summary"], (name, k)
         assert line["summary"]["comm"]["nranks_seen"] in (1, 2) and line["summary"]["parity_vs_1gpu"]["grad_rel_inf"] < 1e-5
         assert "config 4" in line["config"]["workload"]
+
+
+def test_config2_points_are_the_oracles_recorded_solve(oracle):
+    """CONFIG2_POINTS (the fixed evaluation points of the headline) are what record_trajectory() keeps of config 2's FR-CG solve from
+    zero when the CPU oracle is the evaluator."""
+    import numpy as np
+    from cmax_slam_amd import solver, synth
+    p = synth.config2(1_000_000)
+    ref = oracle.Frontend(p.W, p.H, p.lut, p.fx, p.fy, p.cx, p.cy, p.batch, p.sigma, oracle.VARIANCE)
+    ref.set_packet(p.x, p.y, p.t_ns, p.t_ref_ns)
+
+    class OracleEvaluator:  # what record_trajectory() asks of an evaluator
+        def set_fast_path(self):
+            pass
+
+        def set_deterministic(self, on=True):
+            pass
+
+        def eval(self, x, want_grad=True):
+            return ref.eval(x, want_grad)
+    pts = bench.record_trajectory(OracleEvaluator(), np.zeros(3), "frontend", solver.FRONTEND)
+    assert len(pts) == len(bench.CONFIG2_POINTS) == 8
+    np.testing.assert_allclose(np.array(pts), np.array(bench.CONFIG2_POINTS), rtol=0, atol=1e-12)

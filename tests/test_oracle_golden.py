@@ -41,18 +41,20 @@ def test_exp_log_update_match_sophus(oracle, spl):
 
 
 def test_live_basalt_when_built(oracle):
-    """In the build container the compiled reference is present: compare on fresh random inputs too."""
-    if oracle.ref_lib() is None:
-        pytest.skip("oracle/_ref/libbasalt_ref.so not built (no /root/reference on this box)")
-    rng = np.random.default_rng(99)
-    for order in (2, 4):
-        for _ in range(100):
-            K = order + int(rng.integers(0, 5))
-            knots = np.array([oracle.so3_exp(rng.normal(0, 0.8, 3)) for _ in range(K)])
-            dt = 50_000_000
-            t = 10**9 + int(rng.integers(0, (K - order + 1) * dt))
-            a = oracle.spline_eval(order, knots, 10**9, dt, t)
-            b = oracle.spline_eval(order, knots, 10**9, dt, t, use_ref=True)
+    """200 seeded random splines (knots from the oracle's exp): the oracle against Basalt's outputs on them, recorded in
+    ref_random_cases.npz (oracle/gen_golden.py), and against the compiled reference itself where oracle/_ref is built."""
+    rc = np.load(os.path.join(G, "ref_random_cases.npz"))
+    start, dt = int(rc["spl_start_ns"]), int(rc["spl_dt_ns"])
+    live = oracle.ref_lib() is not None
+    assert len(rc["spl_K"]) == 200
+    for order, K, t, knots, q, R, J, idx in zip(rc["spl_order"], rc["spl_K"], rc["spl_t_ns"], rc["spl_knots"], rc["spl_quat"],
+                                                rc["spl_R"], rc["spl_J"], rc["spl_idx"]):
+        order, K = int(order), int(K)
+        refs = [(q, R, J[:order], int(idx))]
+        if live:
+            refs.append(oracle.spline_eval(order, knots[:K], start, dt, int(t), use_ref=True))
+        a = oracle.spline_eval(order, knots[:K], start, dt, int(t))
+        for b in refs:
             assert a[3] == b[3]
             for u, v in zip(a[:3], b[:3]):
                 np.testing.assert_allclose(u, v, rtol=0, atol=5e-14)

@@ -9,7 +9,7 @@ mkdir -p $OUT
 # what is being measured: source hash of cmax_slam_amd/csrc + hash of the library, read back by tools/pmc_to_json.py
 python -c "import sys; sys.path.insert(0, '$REPO'); import bench, hashlib; print(bench.csrc_hash()); print(hashlib.sha256(open('$REPO/cmax_slam_amd/libcmaxhip.so','rb').read()).hexdigest())" > $OUT/stamp.txt
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $REPO/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-per-packet $*"
+BENCH="python $REPO/bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-per-packet $*"
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- $BENCH > $OUT/trace.log 2>&1
 timeout 300 rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc_fetch -o pmc -- $BENCH > $OUT/pmc_fetch.log 2>&1
 timeout 300 rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc_write -o pmc -- $BENCH > $OUT/pmc_write.log 2>&1
