@@ -88,6 +88,7 @@ SYMBOLS = {
     "cmx_frontend_eval_each": (C.c_int, [ctx_p, C.c_int, c_dp, c_dp, c_dp]),
     "cmx_backend_eval_each": (C.c_int, [ctx_p, C.c_int, c_dp, c_dp, c_dp]),
     "cmx_frontend_get_iwe": (C.c_int, [ctx_p, c_dp, C.c_int, c_fp, c_fp]),
+    "cmx_frontend_render_display": (C.c_int, [ctx_p, c_dp, C.POINTER(C.c_uint8)]),
     "cmx_backend_create": (C.c_int, [C.POINTER(ctx_p), C.c_int, C.c_int, C.c_int, c_dp, C.c_int, C.c_int]),
     "cmx_backend_set_window": (C.c_int, [ctx_p, C.c_int64, c_u16p, c_u16p, c_i64p, C.c_int, C.c_int, c_dp, C.c_int64,
                                          C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, c_fp]),
@@ -98,6 +99,7 @@ SYMBOLS = {
     "cmx_backend_mark_visited": (C.c_int, [ctx_p, c_dp, C.c_int]),
     "cmx_backend_reset_map": (C.c_int, [ctx_p]),
     "cmx_backend_get_map": (C.c_int, [ctx_p, c_fp, C.POINTER(C.c_uint8)]),
+    "cmx_backend_render_map": (C.c_int, [ctx_p, C.c_double, c_dp, C.POINTER(C.c_uint8)]),
     "cmx_backend_set_map": (C.c_int, [ctx_p, c_fp, C.POINTER(C.c_uint8)]),
     "cmx_events_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_size_t]),
     "cmx_events_create_group": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_size_t]),

@@ -551,6 +551,33 @@ static int be_set_map_one(cmx_ctx *c, const float *IG, const unsigned char *visi
   return CMX_OK;
 }
 
+// PoseGraphOptimizer::publishEventImage (src/backend/pose_graph_optimizer.cpp:378-413) on the resident map.  Reads IG and the
+// LUT only: no window, no evaluation state is involved.
+int cmx_backend_render_map(cmx_ctx *c, double gamma, const double fov_quat_xyzw[4], unsigned char *out) {
+  if (!c || c->kind != KIND_BE) return fail(c, CMX_ERR_STATE, "not a back-end context");
+  if (!out) return fail(c, CMX_ERR_INVALID_ARG, "null output buffer");
+  if (!std::isfinite(gamma) || !(gamma > 0.0)) return fail(c, CMX_ERR_INVALID_ARG, "gamma must be finite and > 0");
+  Quat q{0, 0, 0, 1};
+  if (fov_quat_xyzw) {
+    const double *v = fov_quat_xyzw;
+    const double nrm = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]);
+    if (!std::isfinite(nrm) || !(nrm > 0.0)) return fail(c, CMX_ERR_INVALID_ARG, "pose quaternion has no direction");
+    q = Quat{v[0] / nrm, v[1] / nrm, v[2] / nrm, v[3] / nrm};
+  }
+  int rc = bind_device(c);
+  if (rc) return rc;
+  const size_t np = (size_t)c->Wp * c->Hp, bytes = fov_quat_xyzw ? 3 * np : np;
+  rc = display_begin(c, bytes);
+  if (rc) return rc;
+  launch_display_range(c->d_IG, nullptr, np, c->d_disp_range, c->stream);
+  launch_display_map(c->d_IG, np, (float)gamma, fov_quat_xyzw != nullptr, c->d_disp_range, c->d_disp, c->stream);
+  if (fov_quat_xyzw) {
+    const Mat3 R = q_to_R(q);
+    launch_display_fov(be_args(c), R.m, c->H, c->d_disp, c->stream);
+  }
+  return display_deliver(c, bytes, out);
+}
+
 int cmx_backend_get_plane(cmx_ctx *c, int which, float *host) {
   if (!c || c->kind != KIND_BE) return fail(c, CMX_ERR_STATE, "not a back-end context");
   if (!c->accumulated) return fail(c, CMX_ERR_STATE, "no evaluation has run in this window");

@@ -271,6 +271,33 @@ int ensure_pinned_dts(cmx_ctx *c, size_t n) {
   return CMX_OK;
 }
 
+// ---- display path: the 8-bit image lives on the device, travels through a pinned buffer of the context (so that the copy is
+// asynchronous on the context's stream whatever the caller's buffer is) and is handed over after the context's usual wait
+int display_begin(cmx_ctx *c, size_t bytes) {
+  int rc = ensure(c, c->d_disp, c->disp_cap, bytes);
+  if (rc) return rc;
+  if (!c->d_disp_range) HIP_TRY(c, hipMalloc((void **)&c->d_disp_range, 2 * sizeof(unsigned)));
+  if (bytes > c->h_disp_cap || !c->h_disp) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->h_disp) HIP_TRY(c, hipHostFree(c->h_disp));
+    c->h_disp = nullptr;
+    c->h_disp_cap = 0;
+    HIP_TRY(c, hipHostMalloc((void **)&c->h_disp, bytes, hipHostMallocDefault));
+    c->h_disp_cap = bytes;
+  }
+  HIP_TRY(c, hipMemsetAsync(c->d_disp_range, 0xff, 2 * sizeof(unsigned), c->stream));
+  return CMX_OK;
+}
+
+int display_deliver(cmx_ctx *c, size_t bytes, unsigned char *out) {
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(c->h_disp, c->d_disp, bytes, hipMemcpyDeviceToHost, c->stream));
+  const int rc = sync_and_collect(c);
+  if (rc) return rc;
+  memcpy(out, c->h_disp, bytes);
+  return CMX_OK;
+}
+
 // =============================================================================================== generic
 const char *cmx_version(void) { return "cmax-hip 0.1 (gfx950)"; }
 
@@ -325,6 +352,9 @@ void cmx_destroy(cmx_ctx *c) {
   if (!c->accum_external) hipFree(c->d_accum);
   hipFree(c->d_accum_alt);
   hipFree(c->d_scratch);
+  hipFree(c->d_disp);
+  hipFree(c->d_disp_range);
+  if (c->h_disp) hipHostFree(c->h_disp);
   hipFree(c->d_partials);
   hipFree(c->d_sums);
   hipFree(c->d_keys); hipFree(c->d_keys_s); hipFree(c->d_idx); hipFree(c->d_idx_s); hipFree(c->d_sxy); hipFree(c->d_sbatch);

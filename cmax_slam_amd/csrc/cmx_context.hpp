@@ -307,6 +307,12 @@ struct cmx_ctx {
   std::vector<hipEvent_t> event_pool;
   double t_ms[CMX_T_COUNT] = {0};
   int64_t t_n[CMX_T_COUNT] = {0};
+
+  // display path (cmx_frontend_render_display / cmx_backend_render_map): 8-bit image on the device, its pinned host copy
+  // (allocated on first use), the two range keys of the reduction
+  unsigned char *d_disp = nullptr, *h_disp = nullptr;
+  size_t disp_cap = 0, h_disp_cap = 0;
+  unsigned *d_disp_range = nullptr;
 };
 
 // device-resident event store: the stream is uploaded once; packets and windows are
@@ -390,6 +396,8 @@ int check_event_args(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y
 int check_events(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t, const EvAos *aos = nullptr);
 int ensure_pinned_xy(cmx_ctx *c, size_t n);
 int ensure_pinned_dts(cmx_ctx *c, size_t n);
+int display_begin(cmx_ctx *c, size_t bytes);                       // device image, pinned copy, range keys reset (queued)
+int display_deliver(cmx_ctx *c, size_t bytes, unsigned char *out);  // device image -> pinned copy -> out, after the context's wait
 
 // kernel_exact = true: the launcher attaches the two events to the kernel itself (hipExtLaunchKernelGGL start / stop:
 // the dispatch's own begin / end timestamps, what rocprofv3 reports); otherwise the events are recorded on the

@@ -433,3 +433,31 @@ int cmx_frontend_get_iwe(cmx_ctx *c, const double omega[3], int blur, float *iwe
   return sync_and_collect(c);
 }
 
+
+// AngVelEstimator::publishEventImage (src/frontend/ang_vel_estimator.cpp:203-233) in one call.  The two vote passes are the ones
+// cmx_frontend_get_iwe(blur = 0) runs, with its bookkeeping (the planes no longer belong to an evaluation point afterwards); the
+// raw-event plane waits in the context's scratch allocation while the second pass votes, so neither ping-pong buffer changes role.
+int cmx_frontend_render_display(cmx_ctx *c, const double omega[3], unsigned char *out) {
+  if (!c || c->kind != KIND_FE) return fail(c, CMX_ERR_STATE, "not a front-end context");
+  if (!c->have_data) return fail(c, CMX_ERR_STATE, "cmx_frontend_set_packet has not succeeded");
+  if (!omega || !out) return fail(c, CMX_ERR_INVALID_ARG, "null argument");
+  int rc = bind_device(c);
+  if (rc) return rc;
+  const size_t np = (size_t)c->W * c->H;
+  const double zero[3] = {0.0, 0.0, 0.0};
+  rc = ensure(c, c->d_scratch, c->scratch_cap, np);
+  if (rc) return rc;
+  rc = display_begin(c, 2 * np);
+  if (rc) return rc;
+  c->last_adjoint = false;
+  rc = fe_accumulate(c, zero, 1);
+  c->x_valid = false;
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->d_scratch, c->d_accum, np * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  rc = fe_accumulate(c, omega, 1);
+  c->x_valid = false;
+  if (rc) return rc;
+  launch_display_range(c->d_scratch, c->d_accum, np, c->d_disp_range, c->stream);
+  launch_display_pair(c->d_scratch, c->d_accum, c->W, c->H, c->d_disp_range, c->d_disp, c->stream);
+  return display_deliver(c, 2 * np, out);
+}

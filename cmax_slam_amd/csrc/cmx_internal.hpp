@@ -427,4 +427,11 @@ void launch_mark_visited(const BeSplatArgs &cam, const double R[9], int sensor_h
 void launch_interleave3(const float *planes, float *out, int npix, hipStream_t s);
 size_t image_lds_bytes(int r);
 
+// display path (cmx_display.hip): range = 2 words, both 0xffffffff before launch_display_range; every launch reads what the one
+// before it wrote, on the same stream
+void launch_display_range(const float *p0, const float *p1 /* or null */, size_t n, unsigned *range, hipStream_t s);
+void launch_display_pair(const float *A, const float *B, int W, int H, const unsigned *range, unsigned char *out, hipStream_t s);
+void launch_display_map(const float *IG, size_t n, float gamma, bool bgr, const unsigned *range, unsigned char *out, hipStream_t s);
+void launch_display_fov(const BeSplatArgs &cam, const double R[9], int sensor_h, unsigned char *bgr, hipStream_t s);
+
 }  // namespace cmx

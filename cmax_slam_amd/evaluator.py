@@ -383,6 +383,14 @@ class FrontendEvaluator(_Evaluator):
                                               d.ctypes.data_as(c_fp) if want_deriv else None))
         return (iwe, d) if want_deriv else iwe
 
+    def publishEventImage(self, ang_vel):
+        """AngVelEstimator::publishEventImage: (H, 2W) uint8, raw events left, motion-compensated at `ang_vel` right,
+        one common range, dark events on white.  Tone-mapped on the device."""
+        om = _c(ang_vel, np.float64)
+        out = np.empty((self.H, 2 * self.W), np.uint8)
+        self._ck(self._L.cmx_frontend_render_display(self._ctx, _dp(om), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
     def contrast_fdf(self, v):
         c, g = self.eval(v, True)
         return -c, -g
@@ -555,6 +563,15 @@ class BackendEvaluator(_Evaluator):
         self._ck(self._L.cmx_backend_get_map(self._ctx, ig.ctypes.data_as(c_fp),
                                              v.ctypes.data_as(C.POINTER(C.c_uint8)) if with_visits else None))
         return (ig, v) if with_visits else ig
+
+    def publishEventImage(self, gamma=0.75, fov_quat=None):
+        """PoseGraphOptimizer::publishEventImage on the resident map: (Hp, Wp) uint8, or (Hp, Wp, 3) BGR uint8 with the
+        sensor outline at pose `fov_quat` (xyzw) drawn in (255, 0, 0).  Tone-mapped on the device."""
+        q = _c(fov_quat, np.float64) if fov_quat is not None else None
+        out = np.empty((self.Hp, self.Wp) if q is None else (self.Hp, self.Wp, 3), np.uint8)
+        self._ck(self._L.cmx_backend_render_map(self._ctx, float(gamma), _dp(q) if q is not None else None,
+                                                out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
 
     def setIG(self, IG=None, visits=None):
         ig = _c(IG, np.float32) if IG is not None else None

@@ -59,8 +59,23 @@ class Params:
     deterministic = False           # CMX_OPT_DETERMINISTIC on both contexts: the same bits on every run
 
 
-def run_pipeline(stream, prm=None, use_event_store=True, log=None):
-    """stream: synth.EventStream (or anything with x, y, t_ns, W, H, fx, fy, cx, cy, lut).  Returns a dict."""
+def write_display_images(fe, be, ang_vel, pose, prefix, gamma=0.75):
+    """The two images the reference publishes, tone-mapped on the device, as binary PGM / PPM files:
+    <prefix>_local_iwe.pgm (raw | motion-compensated events of the packet `fe` holds) and <prefix>_pano.ppm (the resident
+    map with the sensor outline at `pose`).  Returns the two paths."""
+    pair = fe.publishEventImage(ang_vel)
+    pano = be.publishEventImage(gamma, pose)
+    paths = (prefix + "_local_iwe.pgm", prefix + "_pano.ppm")
+    with open(paths[0], "wb") as f:
+        f.write(b"P5\n%d %d\n255\n" % (pair.shape[1], pair.shape[0]) + pair.tobytes())
+    with open(paths[1], "wb") as f:  # the image is BGR (cv::Mat order), a PPM is RGB
+        f.write(b"P6\n%d %d\n255\n" % (pano.shape[1], pano.shape[0]) + np.ascontiguousarray(pano[..., ::-1]).tobytes())
+    return paths
+
+
+def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefix=None):
+    """stream: synth.EventStream (or anything with x, y, t_ns, W, H, fx, fy, cx, cy, lut).  Returns a dict.
+    display_prefix: write the final panorama with the last pose's FOV and the last packet's local-IWE pair there."""
     prm = prm or Params()
     x, y, t = stream.x, stream.y, stream.t_ns
     n_total = len(t)
@@ -207,6 +222,10 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None):
         count_window += 1
     if log:
         log("back end: %d windows, %.2f ms per window (set + solve + map upkeep)" % (len(reports), float(np.mean(be_ms))))
+    if display_prefix and pose_latest is not None and len(av_w):
+        paths = write_display_images(fe, be, av_w[-1], pose_latest[1], display_prefix)
+        if log:
+            log("display images: %s, %s" % paths)
     return dict(ang_vel_t=av_t, ang_vel=av_w, traj=traj, dead_reckoning=dead_reckoning, IG=be.getIG(),
                 reports=reports, fe_ms=fe_ms, be_ms=be_ms, windows=count_window)
 
@@ -261,6 +280,8 @@ def main():
     ap.add_argument("--degree", type=int, default=1, choices=(1, 3))
     ap.add_argument("--host-events", action="store_true", help="re-upload events per packet/window (no EventStore)")
     ap.add_argument("--deterministic", action="store_true", help="bitwise reproducible evaluations (CMX_OPT_DETERMINISTIC)")
+    ap.add_argument("--display", metavar="PREFIX", default=None,
+                    help="write PREFIX_pano.ppm (final panorama, last pose's FOV) and PREFIX_local_iwe.pgm (one local-IWE pair)")
     a = ap.parse_args()
     stream = synth.event_stream(a.rate, a.seconds, 240, 180, 200.0, 200.0, 119.5, 89.5, omega_mean=(0.2, 1.8, 0.3),
                                 omega_amp=(1.0, 0.8, 1.0))
@@ -268,7 +289,7 @@ def main():
     prm.spline_degree = a.degree
     prm.deterministic = a.deterministic
     t0 = time.perf_counter()
-    res = run_pipeline(stream, prm, use_event_store=not a.host_events, log=print)
+    res = run_pipeline(stream, prm, use_event_store=not a.host_events, log=print, display_prefix=a.display)
     wall = time.perf_counter() - t0
     m = evaluate_against_truth(stream, res)
     print("%.2f s of events (%d) processed in %.2f s wall" % (a.seconds, len(stream.x), wall))

@@ -180,6 +180,15 @@ int cmx_frontend_eval_each(cmx_ctx *ctx, int m, const double *omegas, double *co
  * fp32 (CV_32FC3 layout) or NULL.  blur = 0 is the display overload (local_image_warped_events.cpp:41-57). */
 int cmx_frontend_get_iwe(cmx_ctx *ctx, const double omega[3], int blur, float *iwe, float *deriv);
 
+/* AngVelEstimator::publishEventImage (src/frontend/ang_vel_estimator.cpp:203-233) in one call: out = H x 2W uint8, row-major
+ * ("mono8"); left half = raw events (omega = 0), right half = motion-compensated at `omega`, both blur-free -- the planes
+ * cmx_frontend_get_iwe(ctx, ., 0, ., NULL) returns -- under ONE common range: with lo / hi the extremes of both halves,
+ * scale = (hi - lo > DBL_EPSILON) ? 255 / (hi - lo) : 0 in fp64 (cv::normalize, NORM_MINMAX), n = S * (float)scale +
+ * (float)(-lo * scale) in fp32, out = saturate_u8(round-half-to-even(255.f - n)).  A packet with no vote inside the image gives
+ * 255 everywhere.  Tone map on the device; `out` may be pageable.  Like cmx_frontend_get_iwe the call leaves no evaluation point
+ * resident (the next evaluation votes again) and never changes a later result. */
+int cmx_frontend_render_display(cmx_ctx *ctx, const double omega[3], unsigned char *out);
+
 /* ------------------------------------------------------------------ back end --------------------------
  * replaces PoseGraphOptimizer::copyAndUpdateTraj + EventWarper::computeImageOfWarpedEvents + computeContrast
  *   (src/backend/trajectory.cpp:240-263,501-522; src/backend/event_pano_warper.cpp:128-336;
@@ -245,6 +254,16 @@ int cmx_backend_mark_visited(cmx_ctx *ctx, const double quat_xyzw[4], int radius
 int cmx_backend_reset_map(cmx_ctx *ctx);
 int cmx_backend_get_map(cmx_ctx *ctx, float *IG, unsigned char *visits);
 int cmx_backend_set_map(cmx_ctx *ctx, const float *IG, const unsigned char *visits);
+/* PoseGraphOptimizer::publishEventImage (src/backend/pose_graph_optimizer.cpp:378-413) on the RESIDENT map IG, in one call:
+ *   v = normalize(IG, 0, 1, NORM_MINMAX);  p = |v|^gamma (cv::pow; gamma = 1 copies);  q = normalize(p, 0, 255, NORM_MINMAX) as
+ *   8 bits (round half to even, saturated; the extremes of p are the images of the extremes of v);  out = 255 - q.
+ * fov_quat_xyzw == NULL: out = Hp x Wp uint8 ("mono8").  Otherwise out = Hp x Wp x 3 uint8 ("bgr8"): three equal channels, then
+ * EventWarper::drawSensorFOV (src/backend/event_pano_warper.cpp:56-79) for that pose: every sensor border pixel is warped to the
+ * panorama, its coordinates rounded half to even (cv::Point2d -> cv::Point) and (B, G, R) = (255, 0, 0) written there.  Border
+ * pixels that land outside the panorama are skipped (the reference writes them out of bounds).  A blank or constant map gives
+ * 255 everywhere.  gamma must be finite and > 0, the quaternion non-zero (it is normalised).  Valid right after
+ * cmx_backend_create; needs no window and touches no evaluation state.  On a group handle it reads member 0. */
+int cmx_backend_render_map(cmx_ctx *ctx, double gamma, const double fov_quat_xyzw[4] /* or NULL */, unsigned char *out);
 /* int64_t(1e9 * (t_beg + idx_traj_beg*dt_knots)) -- the (double)->ns truncation of trajectory.cpp:255-256 */
 int64_t cmx_traj_temp_start_ns(double t_beg, int idx_traj_beg, double dt_knots);
 
@@ -353,7 +372,7 @@ int cmx_comm_info(cmx_ctx *ctx, int *rank, int *nranks, int *transport);
  * devices, add the members' gradients on the calling thread (the gradient is linear in the members' row sums: no second
  * collective) and return ONE contrast / gradient -- the bodies of global_contrast_{f,df,fdf} do not
  * change, there is one optimiser and no launcher.  The map upkeep calls, cmx_set_option and cmx_destroy act on every member
- * (each keeps its own replica of IG); cmx_backend_get_plane / get_alpha / get_map / cmx_get_stats read member 0.  The caller
+ * (each keeps its own replica of IG); cmx_backend_get_plane / get_alpha / get_map / render_map / cmx_get_stats read member 0.  The caller
  * stays single-threaded; the group owns one worker thread per further member (queueing eight devices' launches from one
  * thread would take longer than the evaluation runs).  Not available on a group: the split-phase interface, caller-owned
  * buffers / streams, cmx_comm_attach*, cmx_backend_eval_many.  cmx_backend_set_window_from works on a group when the store was
