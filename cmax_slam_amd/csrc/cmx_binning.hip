@@ -531,7 +531,9 @@ __device__ __forceinline__ void fe_splat_lds_body(FeSplatArgs &a, const BinnedEv
       __syncthreads();
       return ok_sh != 0 && !(f.debug & 2);
     };
-    fused_tile_pass<kFeSplatNT, FUSE == 2>(f, a.planes, a.W, a.H, t, reinterpret_cast<unsigned char *>(win), wait_inputs);
+    // (the one-launch form's register budget -- the gather role's -- was fitted around the one-output-per-thread pass: it keeps it)
+    if constexpr (FUSE == 1) fused_tile_pass<kFeSplatNT, false>(f, a.planes, a.W, a.H, t, reinterpret_cast<unsigned char *>(win), wait_inputs);
+    else fused_tile_pass_legacy<kFeSplatNT, true>(f, a.planes, a.W, a.H, t, reinterpret_cast<unsigned char *>(win), wait_inputs);
     if (FUSE == 2) {  // publish: every wave's write-through stores have left, then the strip's stamp and the launch's strip count
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
@@ -661,8 +663,10 @@ __device__ __forceinline__ void fe_splat_lds_body(FeSplatArgs &a, const BinnedEv
     self_serve_tail<kFeSplatNT>(a, b, f, c, has_chunk, (sfall & kFuseCountMask) != 0u, reinterpret_cast<unsigned char *>(win), ss_sm);
   }
 }
+// (the fused form, FUSE = 1, needs its 413 + 300 workgroups of a 1M-event launch resident together: six waves per SIMD = at most 80
+//  VGPRs; the register-blocked tile pass no longer fits that by accident)
 template <bool FIXED, bool STREAM, int FUSE>
-__global__ __launch_bounds__(kFeSplatNT) void fe_splat_lds_kernel(FeSplatArgs a, BinnedEvents b, FusedArgs f) {
+__global__ __launch_bounds__(kFeSplatNT) __attribute__((amdgpu_waves_per_eu(6, 8))) void fe_splat_lds_kernel(FeSplatArgs a, BinnedEvents b, FusedArgs f) {
   fe_splat_lds_body<FIXED, STREAM, FUSE>(a, b, f);
 }
 // the one-launch form (FUSE = 2): at least six waves per SIMD = three 512-thread workgroups per CU -- the chunk and strip workgroups of

@@ -93,6 +93,7 @@ int upload_gt1(cmx_ctx *c) {
       rc = ensure(c, dm, mcap, M.size());
       if (rc) return rc;
       HIP_TRY(c, hipMemcpy(dm, M.data(), M.size() * sizeof(float), hipMemcpyHostToDevice));
+      memcpy(axis == 0 ? c->Mx_interior : c->My_interior, M.data() + (size_t)2 * r * bw, (size_t)bw * sizeof(float));
       built_axes |= 1 << axis;
     }
   }

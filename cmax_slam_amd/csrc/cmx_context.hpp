@@ -118,6 +118,7 @@ struct cmx_ctx {
   size_t cx_cap = 0, cy_cap = 0;
   float *d_Mx = nullptr, *d_My = nullptr;  // banded G^T G per axis, [L][4r+1] (composite image pass)
   size_t Mx_cap = 0, My_cap = 0;
+  float Mx_interior[4 * kMaxRadius + 1] = {}, My_interior[4 * kMaxRadius + 1] = {};  // row 2r of each table (host copy: FusedArgs)
   int Mx_radius = -1;                      // blur radius the tables were built for (-1: none)
   bool composite_image = true;             // CMX_OPT_COMPOSITE_IMAGE
   bool fold_batch = true;                  // CMX_OPT_FOLD_BATCH

@@ -198,6 +198,8 @@ int fe_accumulate(cmx_ctx *c, const double omega[3], int nplanes, bool allow_fus
         memcpy(f.taps, c->taps, sizeof(f.taps));
         f.Mx = c->d_Mx;
         f.My = c->d_My;
+        for (int i = 0; i < 17; i++) f.M_in[i] = (double)c->Mx_interior[i];
+        f.M_in_ok = memcmp(c->Mx_interior, c->My_interior, 17 * sizeof(float)) == 0;
         f.jt = c->d_itilde;
         f.partials = c->d_fpartials;
         f.macc = c->chain_active ? c->fuse_macc : nullptr;

@@ -298,6 +298,10 @@ struct FusedArgs {
                                 // workgroup stores 0)
   float taps[9];                // radius 4 only
   const float *Mx, *My;         // banded G^T G per axis (cmx_context.cpp upload_gt1)
+  double M_in[17];              // their interior row (row 2r: the same for every column / line at least 2r from the border, and the same
+                                // floating-point sum on both axes) as fp64: a workgroup-uniform operand of the tile pass's FMAs,
+                                // straight from the argument block's SGPRs
+  int M_in_ok;                  // 0: the two tables' rows 2r differ bit-wise -- every tile then takes its rows from the tables
   float *jt;                    // out: G^T G I
   float *zero_ptr;              // the OTHER accumulation buffer: a tile's pass clears its own tile there (ping-pong); may be null
   double *partials;             // [2][tiles * kFuseStrips]: per-strip sum B, sum B^2 (rows of inactive tiles stay zero: written at sort time)

@@ -176,7 +176,9 @@ __device__ __forceinline__ void self_serve_tail(const FeSplatArgs &a, const Binn
     bool ran = false;
     unsigned early = 0u;
     if (tid == 0) early = __hip_atomic_load(f.nbr_cnt + (size_t)t * kFuseCntStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    fused_tile_pass<NT, true>(fq, a.planes, W, a.H, t, lds, [&]() -> bool {
+    // (the one-output-per-thread pass: this kernel's 128-VGPR budget holds the warp state of its events across the pass and has no
+    //  room for the register-blocked pass's windows -- 9 VGPRs spilled with it)
+    fused_tile_pass_legacy<NT, true>(fq, a.planes, W, a.H, t, lds, [&]() -> bool {
       ran = ss_wait_tile_inputs<NT>(f, b.fallback, t, expected, early, sm.ok_sh);
       if (tr && tid == 0) tr[2] = wall_clock64();
       return ran;
