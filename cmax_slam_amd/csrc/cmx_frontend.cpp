@@ -131,9 +131,11 @@ static const char *fuse_trace_path() {
 
 // The adjoint image pass can ride inside the splat launch (FusedArgs, cmx_internal.hpp): gradient evaluations of the production
 // path at the reference's blur (sigma 1 -> radius 4, register-resident operator rows), context-owned ping-pong planes, nothing
-// between splat and blur (no communicator), no bitwise-reproducibility promise to keep.
+// between splat and blur (no communicator), no bitwise-reproducibility promise to keep.  Not the Sobel contrast: the pass that
+// rides in the splat launch computes the variance / mean-square moments with the G^T G tables.
 static bool fe_fuse_ok(const cmx_ctx *c, int nplanes, bool use_lds, bool allow_fuse) {
   return allow_fuse && c->fused_image && use_lds && nplanes == 1 && c->last_adjoint && adjoint_ok(c) && c->composite_image &&
+         c->measure != CMX_GRADIENT_MAGNITUDE &&
          c->radius == 4 && c->d_Mx && c->d_My && c->Mx_radius == 4 && !c->deterministic && !c->sharded() && !c->accum_external &&
          (!c->chain_active || c->fuse_macc) && c->pingpong_planes > 0 && c->fused_bin_id != 0 && c->fused_bin_id == c->binning_id;
 }

@@ -212,6 +212,10 @@ size_t image_adjoint_lds_bytes(int r);
 int image_adjoint_tiles_x(int W);
 int image_adjoint_tiles(int W, int H);
 void launch_image_adjoint(const ImgAdjArgs &a, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+// the same pass for the Sobel gradient-magnitude contrast (front end, contrast_measure = 2): Jt = G^T (Sx^T gx + Sy^T gy),
+// moment row 1 = sum (gx^2 + gy^2); no tile list, no tail, Mx / My unused; tile-occupancy reach 2r+2
+size_t image_adjoint_sobel_lds_bytes(int r);
+void launch_image_adjoint_sobel(const ImgAdjArgs &a, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 
 struct FeGatherArgs {
   FeSplatArgs ev;          // same event / camera description as the splat

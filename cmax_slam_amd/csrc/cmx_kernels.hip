@@ -9,6 +9,8 @@
 //                                                             local_focus_funcs.cpp:9-44, global_focus_funcs.cpp:11-47)
 //   alpha_*         K4  event-density ratio alpha            (reference event_pano_warper.cpp:134-165)
 //   image_adjoint   fused blur + moments + G^T (adjoint gradient), fe/be_gather: gradient by gathering over the events
+//   image_adjoint_sobel  the same for contrast_ImageGradientMagnitude: blur, Sobel moments, Sobel^T, G^T
+//                                                            (reference local_focus_funcs.cpp:47-73)
 //   reduce/finalize     partial moments -> contrast, gradient (fp64)
 //
 // Numerics: geometry in fp64 exactly as the reference, weights/accumulators fp32.  This file is compiled with
@@ -2454,6 +2456,196 @@ __global__ void interleave3_kernel(const float *planes, float *out, int npix) {
 }
 void launch_interleave3(const float *planes, float *out, int npix, hipStream_t s) {
   hipLaunchKernelGGL(interleave3_kernel, dim3(1024), dim3(256), 0, s, planes, out, npix);
+}
+
+// ---------------------------------------------------------------------------------------------- Sobel adjoint
+// Adjoint image pass of contrast_ImageGradientMagnitude (front end, contrast_measure = 2; reference
+// local_focus_funcs.cpp:47-73).  With B = G I, gx = Sx B, gy = Sy B (cv::Sobel 3x3, REFLECT_101):
+//   contrast = (1/N) sum (gx^2 + gy^2),   grad_k = (2/N) <D_k, Jt>,   Jt = G^T (Sx^T gx + Sy^T gy)
+// -- no mean term, so finalize treats the result like mean-square: row 1 of the moments holds sum (gx^2 + gy^2) and the
+// gather consumes Jt unchanged.  One workgroup = one tile of Jt, seven barrier-separated phases:
+//   raw (tile + 2r+2) -> row blur -> B (tile + r+2) -> gx, gy (tile + r+1, 0 outside the image)
+//   -> Hs = Sx^T gx + Sy^T gy (tile + r, 0 outside the image) -> G^T row pass -> G^T column pass -> Jt (the tile)
+// G in the operation order of image_moments_kernel, Sobel in the order of sobel_at (row filter, then column filter).
+// Sobel^T: Sx = smooth_y o diff_x, Sy = diff_y o smooth_x, so the transposes are 3-tap per axis too, and the taps the forward
+// filter reflected at the border (p = 0 reads s = 1, p = L-1 reads s = L-2) fold into the coefficient of the SAME neighbour:
+//   (K^T u)[s] = (k[+1] + [s == 1] k[-1]) u[s-1] + k[0] u[s] + (k[-1] + [s == L-2] k[+1]) u[s+1],   u = 0 outside the image
+// (any L >= 2).  The G^T folds are those of image_adjoint_kernel and need L > 2r+1 -- which is >= 2 for every r: the
+// composed operator keeps the size rule of adjoint_ok().
+// LDS: gx, gy, Hs and the G^T row pass reuse the raw / row-blur / B buffers once those are dead.
+size_t image_adjoint_sobel_lds_bytes(int r) {
+  const size_t aw = kAdjTX + 4 * r + 4, ah = kAdjTY + 4 * r + 4, bw = kAdjTX + 2 * r + 4, bh = kAdjTY + 2 * r + 4;
+  return sizeof(double) * 32 + sizeof(float) * (aw * ah + bw * ah + bw * bh);
+}
+
+template <int R>
+__global__ __launch_bounds__(kAdjThreads) void image_adjoint_sobel_kernel(ImgAdjArgs g) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  constexpr int TX = kAdjTX, TY = kAdjTY, NT = kAdjThreads;
+  if (wg_stop_requested(g.img.skip)) return;
+  const ImgArgs &a = g.img;
+  const int r = (R >= 0) ? R : a.r;
+  const int W = a.W, H = a.H;
+  float taps[2 * kMaxRadius + 1];
+#pragma unroll
+  for (int j = 0; j < 2 * kMaxRadius + 1; j++) taps[j] = (R < 0 || j <= 2 * R) ? a.taps[j] : 0.f;
+  const int aw = TX + 4 * r + 4, ah = TY + 4 * r + 4;  // raw: tile + 2r+2
+  const int bw = TX + 2 * r + 4, bh = TY + 2 * r + 4;  // B: tile + r+2
+  const int gw = TX + 2 * r + 2, gh = TY + 2 * r + 2;  // gx, gy: tile + r+1
+  const int hw = TX + 2 * r, hh = TY + 2 * r;          // Hs: tile + r
+  double *red = reinterpret_cast<double *>(smem_raw);
+  float *bufA = reinterpret_cast<float *>(smem_raw + 32 * sizeof(double));  // raw (front end: one vote plane), aw x ah
+  float *bufR = bufA + aw * ah;                                             // row-blurred raw, bw x ah
+  float *bufB = bufR + bw * ah;                                             // B, bw x bh
+  float *bufGx = bufA;  // gw x gh <= aw x ah  (raw is dead after the row blur)
+  float *bufGy = bufR;  // gw x gh <= bw x ah  (row blur is dead after the column blur)
+  float *bufH = bufB;   // hw x hh <= bw x bh  (B is dead after the Sobel phase)
+  float *bufT = bufA;   // TX x hh <= aw x ah  (gx is dead after the Sobel^T phase)
+  const int tid = threadIdx.x;
+  const int tile = (int)blockIdx.x;
+  const int x0 = (tile % a.tiles_x) * TX, y0 = (tile / a.tiles_x) * TY;
+  if (a.zero_ptr) {  // clear this tile of the other accumulation buffer (ping-pong: no memset launch next time)
+    const bool dirty = !a.flags_other || a.flags_other[tile] != 0;
+    if (dirty) {
+      for (int idx = tid; idx < TX * TY * a.zero_planes; idx += NT) {
+        const int pl = idx / (TX * TY), q = idx - pl * (TX * TY);
+        const int gx = x0 + (q % TX), gy = y0 + (q / TX);
+        if (gx < W && gy < H) a.zero_ptr[(size_t)pl * W * H + (size_t)gy * W + gx] = 0.f;
+      }
+    }
+    __syncthreads();  // every thread has read the flag
+    if (tid == 0 && a.flags_other && dirty) a.flags_other[tile] = 0;
+  }
+  // nothing non-zero within 2r+2 of this tile: B, gx, gy and Jt vanish on it, and no vote cell lies in it
+  if (!tile_active(a, tile % a.tiles_x, tile / a.tiles_x, 2 * r + 2, TX, TY)) {
+    if (tid == 0) {
+      a.partials[(size_t)0 * a.nblk + tile] = 0.0;
+      a.partials[(size_t)1 * a.nblk + tile] = 0.0;
+    }
+    return;
+  }
+
+  for (int idx = tid; idx < aw * ah; idx += NT) {
+    const int ly = idx / aw, lx = idx - ly * aw;
+    const int gx = reflect101(x0 + lx - 2 * r - 2, W), gy = reflect101(y0 + ly - 2 * r - 2, H);
+    bufA[idx] = a.src_a[(size_t)gy * W + gx];
+  }
+  __syncthreads();
+  for (int idx = tid; idx < bw * ah; idx += NT) {  // forward row pass (same op order as image_moments)
+    const int ly = idx / bw, lx = idx - ly * bw;
+    const float *S = bufA + ly * aw + lx;
+    float s = taps[0] * S[0];
+#pragma unroll
+    for (int j = 1; j <= 2 * r; j++) s += taps[j] * S[j];
+    bufR[idx] = s;
+  }
+  __syncthreads();
+  double sB = 0, sG = 0;
+  for (int idx = tid; idx < bw * bh; idx += NT) {  // forward column pass -> B on tile + r+2
+    const int ly = idx / bw, lx = idx - ly * bw;
+    const float *T = bufR + (ly + r) * bw + lx;
+    float s = taps[r] * T[0];
+#pragma unroll
+    for (int t = 1; t <= r; t++) s += taps[r + t] * (T[t * bw] + T[-t * bw]);
+    bufB[idx] = s;
+    const int gx = x0 + lx - r - 2, gy = y0 + ly - r - 2;
+    if (gx >= x0 && gx < x0 + TX && gx < W && gy >= y0 && gy < y0 + TY && gy < H) sB += (double)s;
+  }
+  __syncthreads();
+  for (int idx = tid; idx < gw * gh; idx += NT) {  // Sobel of B at the in-image pixels of tile + r+1 (neighbours by REFLECT_101)
+    const int ly = idx / gw, lx = idx - ly * gw;
+    const int gx = x0 + lx - r - 1, gy = y0 + ly - r - 1;
+    float vx = 0.f, vy = 0.f;
+    if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+      const int bx0 = x0 - r - 2, by0 = y0 - r - 2;  // origin of bufB
+      const int xm = reflect101(gx - 1, W) - bx0, xc = gx - bx0, xp = reflect101(gx + 1, W) - bx0;
+      const float *r0 = bufB + (reflect101(gy - 1, H) - by0) * bw, *r1 = bufB + (gy - by0) * bw, *r2 = bufB + (reflect101(gy + 1, H) - by0) * bw;
+      // dx: row [-1 0 1], column [1 2 1]
+      const float d0 = r0[xp] - r0[xm], d1 = r1[xp] - r1[xm], d2 = r2[xp] - r2[xm];
+      vx = d0 + d1 * 2.f + d2;
+      // dy: row [1 2 1], column [-1 0 1]
+      const float s0 = r0[xm] + r0[xc] * 2.f + r0[xp], s2 = r2[xm] + r2[xc] * 2.f + r2[xp];
+      vy = s2 - s0;
+      if (gx >= x0 && gx < x0 + TX && gy >= y0 && gy < y0 + TY) {
+        const float hf = vx * vx + vy * vy;
+        sG += (double)hf;
+      }
+    }
+    bufGx[idx] = vx;
+    bufGy[idx] = vy;
+  }
+  {
+    double t0, t1;
+    block_sum2(sB, sG, red, NT / 64, t0, t1);  // (its barriers also publish gx, gy)
+    if (tid == 0) {
+      a.partials[(size_t)0 * a.nblk + tile] = t0;
+      a.partials[(size_t)1 * a.nblk + tile] = t1;
+    }
+  }
+  __syncthreads();
+  for (int idx = tid; idx < hw * hh; idx += NT) {  // Hs = Sx^T gx + Sy^T gy on tile + r, reflected taps folded (see above)
+    const int ly = idx / hw, lx = idx - ly * hw;
+    const int gx = x0 + lx - r, gy = y0 + ly - r;
+    float s = 0.f;
+    if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+      const float fxm = gx == 1 ? 1.f : 0.f, fxp = gx == W - 2 ? 1.f : 0.f, fym = gy == 1 ? 1.f : 0.f, fyp = gy == H - 2 ? 1.f : 0.f;
+      const float mxm = 1.f + fxm, mxp = 1.f + fxp, dxm = 1.f - fxm, dxp = fxp - 1.f;  // smooth^T / diff^T along x: u[x-1], u[x+1]
+      const float mym = 1.f + fym, myp = 1.f + fyp, dym = 1.f - fym, dyp = fyp - 1.f;  // ... along y
+      const float *X = bufGx + (ly + 1) * gw + (lx + 1), *Y = bufGy + (ly + 1) * gw + (lx + 1);
+      // Sx^T gx = diff_x^T (smooth_y^T gx)
+      const float ex_m = dxm * X[-gw - 1] + dxp * X[-gw + 1], ex_0 = dxm * X[-1] + dxp * X[1], ex_p = dxm * X[gw - 1] + dxp * X[gw + 1];
+      const float sx = mym * ex_m + ex_0 * 2.f + myp * ex_p;
+      // Sy^T gy = smooth_x^T (diff_y^T gy)
+      const float ey_m = mxm * Y[-gw - 1] + Y[-gw] * 2.f + mxp * Y[-gw + 1], ey_p = mxm * Y[gw - 1] + Y[gw] * 2.f + mxp * Y[gw + 1];
+      const float sy = dym * ey_m + dyp * ey_p;
+      s = sx + sy;
+    }
+    bufH[idx] = s;
+  }
+  __syncthreads();
+  for (int idx = tid; idx < TX * hh; idx += NT) {  // G^T row pass: zero-padded conv + folded reflections
+    const int ly = idx / TX, lx = idx - ly * TX;
+    const float *S = bufH + ly * hw + lx;
+    float s = taps[0] * S[0];
+#pragma unroll
+    for (int j = 1; j <= 2 * r; j++) s += taps[j] * S[j];
+    const int gx = x0 + lx;
+    const float *Srow = bufH + ly * hw;  // column of global x is (x - x0 + r)
+    if (1 <= gx && gx <= r)
+      for (int m = 0; m <= r - gx; m++) s += taps[r + gx + m] * Srow[m - x0 + r];
+    if (W - 1 - r <= gx && gx <= W - 2) {
+      const int d = W - 1 - gx;
+      for (int m = 0; m <= r - d; m++) s += taps[r + d + m] * Srow[(W - 1 - m) - x0 + r];
+    }
+    bufT[idx] = s;
+  }
+  __syncthreads();
+  for (int idx = tid; idx < TX * TY; idx += NT) {  // G^T column pass -> Jt
+    const int ty = idx / TX, tx = idx - ty * TX;
+    const int gy = y0 + ty, gx = x0 + tx;
+    if (gx < W && gy < H) {
+      const int ly = ty + r;
+      const float *T = bufT + ly * TX + tx;
+      float s = taps[r] * T[0];
+#pragma unroll
+      for (int t = 1; t <= r; t++) s += taps[r + t] * (T[t * TX] + T[-t * TX]);
+      const float *Tcol = bufT + tx;  // row of global y is (y - y0 + r)
+      if (1 <= gy && gy <= r)
+        for (int m = 0; m <= r - gy; m++) s += taps[r + gy + m] * Tcol[(m - y0 + r) * TX];
+      if (H - 1 - r <= gy && gy <= H - 2) {
+        const int d = H - 1 - gy;
+        for (int m = 0; m <= r - d; m++) s += taps[r + d + m] * Tcol[((H - 1 - m) - y0 + r) * TX];
+      }
+      g.jt[(size_t)gy * W + gx] = s;
+    }
+  }
+}
+
+void launch_image_adjoint_sobel(const ImgAdjArgs &a, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {
+  const size_t lds = image_adjoint_sobel_lds_bytes(a.img.r);
+  const dim3 g(a.img.nblk);
+  if (a.img.r == 4) CMX_LAUNCH((image_adjoint_sobel_kernel<4>), g, dim3(kAdjThreads), lds, s, t0, t1, a);
+  else CMX_LAUNCH((image_adjoint_sobel_kernel<-1>), g, dim3(kAdjThreads), lds, s, t0, t1, a);
 }
 
 }  // namespace cmx

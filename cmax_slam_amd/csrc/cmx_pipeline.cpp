@@ -264,10 +264,18 @@ BeSplatArgs be_args(const cmx_ctx *c) {
   return a;
 }
 
-bool adjoint_ok(const cmx_ctx *c) {  // G^T folding assumes single reflections: image larger than the kernel
-  if (c->measure == CMX_GRADIENT_MAGNITUDE) return false;  // Sobel contrast: derivative-plane form only
+// G^T folding assumes single reflections: image larger than the kernel.  The Sobel contrast (front end, measure 2) composes
+// G^T with Sobel^T, whose folds stay on the filter's own 3 taps for any side >= 2 (image_adjoint_sobel_kernel) -- and
+// 2r+1 >= 1 makes every side that passes the G^T rule at least 2: one rule for all measures.
+bool adjoint_ok(const cmx_ctx *c) {
   return c->grad_mode == CMX_GRAD_ADJOINT && c->imgW > 2 * c->radius + 1 && c->imgH > 2 * c->radius + 1;
 }
+// the adjoint form of the Sobel gradient-magnitude contrast: its own image pass, everything behind it as for mean-square
+static bool sobel_adjoint(const cmx_ctx *c) { return c->kind == KIND_FE && c->measure == CMX_GRADIENT_MAGNITUDE; }
+// what the finalize of an ADJOINT evaluation computes from the moment rows and the gather's sums.  Gradient magnitude has no
+// mean term: row 1 = sum (gx^2 + gy^2), contrast = row1 / N, grad = 2 S1 / N -- the mean-square expressions.  (measure 2 in
+// FinalizeArgs means the Sobel partial table of the derivative-plane form, run_image_and_finalize.)
+static int adjoint_finalize_measure(const cmx_ctx *c) { return sobel_adjoint(c) ? CMX_MEAN_SQUARE : c->measure; }
 
 // every evaluation ends in exactly one finalize -- its own launch (here) or the tail of the evaluation's last kernel
 // (arm_tail) -- which carries the ticket sync_and_collect() waits for
@@ -484,7 +492,8 @@ int run_adjoint(cmx_ctx *c, int P, int phase) {
     HIP_TRY(c, hipMemsetAsync(c->d_itilde, 0, c->itilde_cap * sizeof(float), c->stream));
   ImgAdjArgs ia{};
   ImgArgs &a = ia.img;
-  if (c->composite_image && c->radius >= 1 && c->d_Mx && c->d_My && c->Mx_radius == c->radius) { ia.Mx = c->d_Mx; ia.My = c->d_My; }
+  const bool sobel = sobel_adjoint(c);  // (no composite-operator form: Sobel sits between G and G^T)
+  if (!sobel && c->composite_image && c->radius >= 1 && c->d_Mx && c->d_My && c->Mx_radius == c->radius) { ia.Mx = c->d_Mx; ia.My = c->d_My; }
   a.W = W; a.H = H; a.r = c->radius;
   memcpy(a.taps, c->taps, sizeof(a.taps));
   a.src_a = c->d_accum;
@@ -535,7 +544,7 @@ int run_adjoint(cmx_ctx *c, int P, int phase) {
   FinalizeArgs f{};
   f.P = 0;
   f.nblk = fused_rows ? c->fused_tiles_x * c->fused_tiles_y * kFuseStrips : a.nblk;
-  f.measure = c->measure;
+  f.measure = adjoint_finalize_measure(c);
   f.npix = (double)np;
   f.partials = fused_rows ? c->d_fpartials : c->d_partials;
   f.sums = c->d_sums;
@@ -548,7 +557,8 @@ int run_adjoint(cmx_ctx *c, int P, int phase) {
     f.chain.stage = phase == 4 ? 1 : 0;
     a.skip = &c->d_chain->done;
   }
-  if (!have_image) {  // large panoramas: compact work list (a pre-pass kernel; partial rows become compact too)
+  // (not the Sobel pass: it has no list form -- front-end images stay below kTileListMin tiles -- and takes its reach, 2r+2, itself)
+  if (!have_image && !sobel) {  // large panoramas: compact work list (a pre-pass kernel; partial rows become compact too)
     rc = maybe_tile_list(c, a, 2 * c->radius);
     if (rc) return rc;
   }
@@ -602,8 +612,9 @@ int run_adjoint(cmx_ctx *c, int P, int phase) {
     Span sp(c, CMX_T_IMAGE, /*exact=*/true);
     // cost-only with Jt kept (phase 3): the three-phase image pass has the registers to carry the finalize as its tail
     // (the five-phase kernel did not: inlined, its taps spilled and the pass went 11 -> 20 us)
-    if (phase == 3 && ia.Mx && c->radius == 4) image_tailed = arm_tail(c, f, a.tail);
-    launch_image_adjoint(ia, c->stream, sp.t0(), sp.t1());
+    if (phase == 3 && !sobel && ia.Mx && c->radius == 4) image_tailed = arm_tail(c, f, a.tail);
+    if (sobel) launch_image_adjoint_sobel(ia, c->stream, sp.t0(), sp.t1());
+    else launch_image_adjoint(ia, c->stream, sp.t0(), sp.t1());
     if (!direct) launch_reduce_partials(f, c->stream);
   }
   if (phase == 3) {  // cost-only: contrast from the moment rows; Jt and the rows stay for a gradient call at the same point

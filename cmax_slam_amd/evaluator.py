@@ -91,7 +91,8 @@ class _Evaluator:
 
     def set_fast_path(self):
         """The production configuration and the library's default: adjoint gradient + LDS-privatised splat (+ image
-        reuse, on by default)."""
+        reuse, on by default).  All three front-end contrast measures have an adjoint form (GRADIENT_MAGNITUDE: Sobel
+        transposes in the image pass); an image with a side <= 2 * blur radius + 1 keeps the derivative-plane form."""
         self.set_grad_mode(_lib.GRAD_ADJOINT)
         self.set_splat_mode(1)
 

@@ -46,7 +46,9 @@ enum {
 
 /* contrast_measure: include/frontend/local_focus_funcs.h:7-11.  As in the reference's switch statements any other
  * value means VARIANCE, and the back end (global_focus_funcs.cpp:61-69) treats GRADIENT_MAGNITUDE as VARIANCE too.
- * GRADIENT_MAGNITUDE (Sobel, front end) always uses the derivative-plane gradient. */
+ * GRADIENT_MAGNITUDE (Sobel, front end) follows CMX_OPT_GRAD_MODE like the other two: with CMX_GRAD_ADJOINT the gradient is
+ * (2/N) <dW_k, G^T (Sx^T gx + Sy^T gy)>, gx / gy = Sobel of the blurred image (same results within fp32 rounding).  The
+ * device-driven solve and the one-launch forms are not available for it: cmx_frontend_solve runs host-driven. */
 enum { CMX_VARIANCE = 0, CMX_MEAN_SQUARE = 1, CMX_GRADIENT_MAGNITUDE = 2 };
 
 /* how the analytic gradient is formed */
