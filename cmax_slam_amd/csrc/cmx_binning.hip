@@ -17,6 +17,7 @@
 
 #include "cmx_internal.hpp"
 #include "cmx_warp.hpp"
+#include "cmx_fixed.hpp"
 #include "cmx_tilepass.hpp"
 #include "cmx_fusedgather.hpp"
 #include "cmx_selfserve.hpp"
@@ -432,10 +433,7 @@ void launch_build_chunks(const int *tile_start, int ntiles, int planes_per_tile,
 // (193 G lane-atomics/s for any address pattern) while ds_add_u64 runs at 1.7 T/s (tools/microbench/lds_atomics.hip).
 // Integer adds also commute, so a window's sum does not depend on the order the votes arrive in; the quantisation
 // (<= 2^-31 per vote) is far below fp32's own rounding of the reference's accumulators.
-typedef unsigned long long fix_t;
-constexpr float kFixScale = 1073741824.0f;        // 2^30
-constexpr double kFixInv = 1.0 / 1073741824.0;
-__device__ __forceinline__ fix_t to_fix(float w) { return (fix_t)(unsigned)(w * kFixScale + 0.5f); }
+// (fix_t, to_fix and the two global vote forms live in cmx_fixed.hpp: the whole-trajectory reconstruction votes the same way)
 __device__ __forceinline__ void lds_add_fix(fix_t *p, fix_t v) {
   __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
@@ -446,25 +444,12 @@ __device__ __forceinline__ void vote4_lds(fix_t *win, int lx, int ly, float dx, 
   lds_add_fix(q + kBinStride, to_fix((1.f - dx) * dy));
   lds_add_fix(q + kBinStride + 1, to_fix(dx * dy));
 }
-__device__ __forceinline__ void vote4_global(float *img, int W, int xx, int yy, float dx, float dy) {
-  float *q = img + (size_t)yy * W + xx;
-  atomic_add_f32(q, (1.f - dx) * (1.f - dy));
-  atomic_add_f32(q + 1, dx * (1.f - dy));
-  atomic_add_f32(q + W, (1.f - dx) * dy);
-  atomic_add_f32(q + W + 1, dx * dy);
-}
 
 // deterministic mode (CMX_OPT_DETERMINISTIC): everything that reaches global memory is a 64-bit INTEGER add into a
 // fixed-point plane -- integer adds commute, so the planes (and everything computed from them) are the same bits on every
 // run, whatever order the workgroups, the tile sort or the atomics happened in.  fixed_to_float then hands the usual
 // fp32 planes to the image kernels and leaves the fixed-point plane all-zero for the next evaluation.
-__device__ __forceinline__ void vote4_global_fix(fix_t *img, int W, int xx, int yy, float dx, float dy) {
-  fix_t *q = img + (size_t)yy * W + xx;
-  atomicAdd(q, to_fix((1.f - dx) * (1.f - dy)));
-  atomicAdd(q + 1, to_fix(dx * (1.f - dy)));
-  atomicAdd(q + W, to_fix((1.f - dx) * dy));
-  atomicAdd(q + W + 1, to_fix(dx * dy));
-}
+// (vote4_global_fix: cmx_fixed.hpp)
 __global__ __launch_bounds__(256) void fixed_to_float_kernel(fix_t *fixed, float *planes, size_t n) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
     const fix_t v = fixed[i];

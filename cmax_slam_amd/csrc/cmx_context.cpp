@@ -331,6 +331,7 @@ void cmx_destroy(cmx_ctx *c) {
   }
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
+  recon_release(c);
   for (auto &s : c->spans) { hipEventDestroy(s.a); hipEventDestroy(s.b); }
   for (auto e : c->event_pool) hipEventDestroy(e);
   hipFree(c->d_lut);

@@ -41,6 +41,7 @@ inline unsigned fallback_flags(double slot) { return fallback_word(slot) & ~cmx:
 struct TimedSpan { int cls; hipEvent_t a, b; };
 typedef struct ncclComm *ncclComm_t;  // as <rccl/rccl.h> declares it; only cmx_comm.cpp includes that header
 
+struct ReconState;  // cmx_reconstruct.cpp: whole-trajectory reconstruction (cmx_backend_recon_*)
 struct cmx_group;  // cmx_group.cpp: one-process multi-GPU group (members, worker threads, transport)
 
 struct cmx_ctx {
@@ -314,6 +315,9 @@ struct cmx_ctx {
   unsigned char *d_disp = nullptr, *h_disp = nullptr;
   size_t disp_cap = 0, h_disp_cap = 0;
   unsigned *d_disp_range = nullptr;
+
+  // whole-trajectory reconstruction (cmx_backend_recon_begin .. _end): its own plane, knots, staging; null outside
+  ReconState *recon = nullptr;
 };
 
 // device-resident event store: the stream is uploaded once; packets and windows are
@@ -488,6 +492,13 @@ int group_set_window_from(cmx_ctx *leader, const cmx_events *e, int64_t first, i
 int be_eval_one(cmx_ctx *c, const double *drotv, double *contrast, double *grad);  // cmx_backend.cpp: one context's evaluation
 #define CMX_NOT_FOR_GROUPS(c, what) \
   do { if ((c) && (c)->group) return fail((c), CMX_ERR_STATE, what " is not available on a group (the group runs its own exchange)"); } while (0)
+
+// ---- cmx_reconstruct.cpp: the bodies behind cmx_backend_recon_add[_aos] and _add_from (events on the host / in the event store)
+int recon_enter(cmx_ctx *c, bool need_begun);  // front door of every cmx_backend_recon_*: plain back-end context, not a group, begun; binds the device
+int recon_add_host(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, const EvAos *aos);
+int recon_add_store(cmx_ctx *c, int64_t n, const uint32_t *d_raw, const int64_t *d_t);
+int recon_diag_slice_events(int n);  // CMX_DIAG_RECON_SLICE_EVENTS (cmax_hip_diag.h)
+void recon_release(cmx_ctx *c);  // frees whatever a reconstruction holds (cmx_backend_recon_end, cmx_destroy)
 
 // ---- cmx_comm.cpp
 int finish_sharded(cmx_ctx *c, int kind, bool exchange_planes, double *contrast, double *grad);

@@ -205,6 +205,18 @@ int cmx_backend_set_window_from(cmx_ctx *c, const cmx_events *e, int64_t first, 
                             event_sample_rate, blur_sigma, contrast_measure, IG);
 }
 
+// cmx_backend_recon_add over events_[first, first+count) of the store: the vote kernel reads the store's own packed events (the
+// per-batch sampling is an index map, nothing is copied) and launch_be_batch_times forms and validates the batch times
+int cmx_backend_recon_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  size_t off = 0;
+  const cmx_events::Replica *r = nullptr;
+  rc = store_range(c, e, first, count, &off, &r);
+  if (rc) return rc;
+  return recon_add_store(c, count, r->d_xy[e->cur] + off, r->d_t[e->cur] + off);
+}
+
 // A window cut from a replicated store on a GROUP: member r cuts ITS batch range (the range group_set_window hands it, the
 // one-event rule included) from the replica on its own device -- no event crosses the host or a link at hand-over
 // (pose_graph_optimizer.cpp:131-165 is the copy this replaces; event_pano_warper.cpp:188-196 the loop being sharded).

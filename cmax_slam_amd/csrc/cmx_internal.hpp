@@ -427,6 +427,32 @@ void launch_be_batch_times(const long long *t, long long n, int B, int nb, long 
 void launch_be_pack_from_store(const uint32_t *raw, const long long *t, long long n, int B, int rate, int per_batch,
                                int n_packed, long long t_next, uint32_t *out, hipStream_t s);
 
+// whole-trajectory reconstruction (cmx_recon.hip): the vote loop of EventWarper::computeImageOfWarpedEvents over a spline of ANY
+// length -- knots and the per-pair logarithms live in device memory, the batch poses in LDS, the votes in one plane
+constexpr int kReconThreads = 256;
+constexpr int kReconMaxRun = 256;  // batch poses a workgroup evaluates at most, less the two a run's ragged ends add
+struct ReconArgs {
+  BeSplatArgs cam;           // W, Wp, Hp, fx, fy, cxp, cyp, lut, lut2 (nothing else is read)
+  int order, K;
+  long long start_ns, dt_ns;
+  double blend[kMaxOrder * kMaxOrder];
+  const Quat *knots;         // [K]
+  const double *delta;       // [K-1][3]: log(knot_i^-1 knot_{i+1})
+  const long long *batch_t;  // [nb] pose time of every batch of this launch
+  int nb;
+  const uint32_t *xy;        // packed events x | y << 16: the launch's sampled events batch by batch (stride 0), or the launch's
+  int B, stride;             // RAW events, of which packed slot k of batch b is event b * B + k * stride (event store: stride > 0)
+  int per_batch, n;          // packed slots per batch; packed events of the launch (the last batch may be short)
+  int run;                   // packed events per workgroup (recon_run)
+  float *plane;              // votes: fp32 atomics ...
+  unsigned long long *fixed; // ... or, when set, 64-bit integer adds into the 2^-30 fixed-point plane
+  unsigned long long *n_inside;
+};
+int recon_run(int per_batch);
+void launch_recon_delta(const Quat *knots, int K, double *delta, hipStream_t s);
+void launch_recon_votes(const ReconArgs &a, hipStream_t s);
+void launch_recon_fixed_to_float(const unsigned long long *fixed, float *plane, size_t n, hipStream_t s);  // non-destructive
+
 // global-map upkeep (once per window)
 void launch_update_map(float *IG, const float *IL_old, const unsigned char *visits, int npix, int max_update_times,
                        hipStream_t s);

@@ -580,6 +580,60 @@ class BackendEvaluator(_Evaluator):
         self._ck(self._L.cmx_backend_set_map(self._ctx, ig.ctypes.data_as(c_fp) if ig is not None else None,
                                              v.ctypes.data_as(C.POINTER(C.c_uint8)) if v is not None else None))
 
+    # --- whole-trajectory reconstruction (cmx_backend_recon_*): all events along the final spline, any knot count
+    def reconstruct_begin(self, order, knots_xyzw, start_ns, dt_ns, event_batch_size=100, event_sample_rate=1):
+        """Start a reconstruction along the spline (order 2 | 4, K >= order knots, no upper bound on K): zeroes a plane that
+        belongs to the reconstruction alone and records the current deterministic setting.  A second call starts over."""
+        k = _c(knots_xyzw, np.float64).reshape(-1, 4)
+        self._ck(self._L.cmx_backend_recon_begin(self._ctx, int(order), k.shape[0], _dp(k), int(start_ns), int(dt_ns),
+                                                 int(event_batch_size), int(event_sample_rate)))
+
+    def reconstruct_add(self, x, y, t_ns):
+        """One vote loop over exactly these events (batches start at the first one), added to the plane."""
+        x, y, t = _c(x, np.uint16), _c(y, np.uint16), _c(t_ns, np.int64)
+        if not (len(x) == len(y) == len(t)):
+            raise ValueError("x, y, t_ns must have equal length")
+        self._ck(self._L.cmx_backend_recon_add(self._ctx, len(x), x.ctypes.data_as(c_u16p), y.ctypes.data_as(c_u16p),
+                                               t.ctypes.data_as(c_i64p)))
+
+    def reconstruct_add_aos(self, events):
+        """The same from a structured array of records with fields x, y, sec, nsec (e.g. _lib.DVS_EVENT_DTYPE)."""
+        ev = np.ascontiguousarray(events)
+        lay = _lib.aos_layout_of(ev)
+        self._ck(self._L.cmx_backend_recon_add_aos(self._ctx, len(ev), ev.ctypes.data_as(C.c_void_p), C.byref(lay)))
+
+    def reconstruct_add_from(self, store, first, count):
+        """The same over events_[first, first+count) of a device-resident EventStore (nothing crosses the host)."""
+        self._ck(self._L.cmx_backend_recon_add_from(self._ctx, store._h, int(first), int(count)))
+
+    def reconstruct_get(self, with_counts=False):
+        """The (Hp, Wp) fp32 plane [, events the sampling selected so far, events that voted so far]."""
+        out = np.empty((self.Hp, self.Wp), np.float32)
+        ns, ni = C.c_int64(), C.c_int64()
+        self._ck(self._L.cmx_backend_recon_get(self._ctx, out.ctypes.data_as(c_fp), C.byref(ns) if with_counts else None,
+                                               C.byref(ni) if with_counts else None))
+        return (out, ns.value, ni.value) if with_counts else out
+
+    def reconstruct_render(self, gamma=0.75, fov_quat=None):
+        """publishEventImage's tone map on the reconstruction: (Hp, Wp) uint8, or (Hp, Wp, 3) BGR with the sensor outline."""
+        q = _c(fov_quat, np.float64) if fov_quat is not None else None
+        out = np.empty((self.Hp, self.Wp) if q is None else (self.Hp, self.Wp, 3), np.uint8)
+        self._ck(self._L.cmx_backend_recon_render(self._ctx, float(gamma), _dp(q) if q is not None else None,
+                                                  out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def reconstruct_end(self):
+        self._ck(self._L.cmx_backend_recon_end(self._ctx))
+
+    def reconstruct(self, x, y, t_ns, order, knots_xyzw, start_ns, dt_ns, **kw):
+        """begin + one add + get + end: the panorama of these events along this spline."""
+        self.reconstruct_begin(order, knots_xyzw, start_ns, dt_ns, **kw)
+        try:
+            self.reconstruct_add(x, y, t_ns)
+            return self.reconstruct_get()
+        finally:
+            self.reconstruct_end()
+
     # --- reference-named entry points
     def computeImageOfWarpedEvents(self, drotv, want_deriv=False):
         """iwe (blurred I = IL + alpha*IGp) [, list of blurred derivative planes] at the updated trajectory."""

@@ -73,9 +73,29 @@ def write_display_images(fe, be, ang_vel, pose, prefix, gamma=0.75):
     return paths
 
 
-def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefix=None):
+def reconstruct_panorama(be, traj, x, y, t, prm, store=None):
+    """All events inside the support of the refined trajectory, re-warped along the WHOLE of it (any number of control poses)
+    into one panorama: BackendEvaluator.reconstruct_* (cmx_backend_recon_*).  Leaves the evaluator's window and map untouched.
+    This function calls reconstruct_begin and adds the events, and returns with the reconstruction OPEN: the caller reads it with
+    be.reconstruct_get() and / or be.reconstruct_render(), then closes it with be.reconstruct_end().
+    Returns (first event, event count)."""
+    t_hi = traj.t_beg_ns + (traj.size() - traj.order + 1) * traj.dt_ns  # end of the knot support
+    i0 = int(np.searchsorted(t, traj.t_beg_ns, side="left"))
+    i1 = int(np.searchsorted(t, t_hi, side="left"))
+    be.reconstruct_begin(traj.order, traj.knots, traj.t_beg_ns, traj.dt_ns, event_batch_size=prm.event_batch_size,
+                         event_sample_rate=prm.backend_event_sample_rate)
+    if store is not None:
+        be.reconstruct_add_from(store, i0, i1 - i0)
+    else:
+        be.reconstruct_add(x[i0:i1], y[i0:i1], t[i0:i1])
+    return i0, i1 - i0
+
+
+def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefix=None, reconstruct=False):
     """stream: synth.EventStream (or anything with x, y, t_ns, W, H, fx, fy, cx, cy, lut).  Returns a dict.
-    display_prefix: write the final panorama with the last pose's FOV and the last packet's local-IWE pair there."""
+    display_prefix: write the final panorama with the last pose's FOV and the last packet's local-IWE pair there.
+    reconstruct: after the last window, re-warp all events along the whole refined trajectory (res["recon"]; with
+    display_prefix also <prefix>_recon.pgm)."""
     prm = prm or Params()
     x, y, t = stream.x, stream.y, stream.t_ns
     n_total = len(t)
@@ -226,8 +246,21 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
         paths = write_display_images(fe, be, av_w[-1], pose_latest[1], display_prefix)
         if log:
             log("display images: %s, %s" % paths)
-    return dict(ang_vel_t=av_t, ang_vel=av_w, traj=traj, dead_reckoning=dead_reckoning, IG=be.getIG(),
-                reports=reports, fe_ms=fe_ms, be_ms=be_ms, windows=count_window)
+    res = dict(ang_vel_t=av_t, ang_vel=av_w, traj=traj, dead_reckoning=dead_reckoning, IG=be.getIG(),
+               reports=reports, fe_ms=fe_ms, be_ms=be_ms, windows=count_window)
+    if reconstruct and traj.size() >= traj.order:
+        t0 = time.perf_counter()
+        _, n_rec = reconstruct_panorama(be, traj, x, y, t, prm, store)
+        res["recon"], n_sampled, n_inside = be.reconstruct_get(with_counts=True)
+        if log:
+            log("reconstruction: %d events along %d control poses in %.2f ms (%d sampled, %d voted)" %
+                (n_rec, traj.size(), (time.perf_counter() - t0) * 1e3, n_sampled, n_inside))
+        if display_prefix:
+            img = be.reconstruct_render(0.75)
+            with open(display_prefix + "_recon.pgm", "wb") as f:
+                f.write(b"P5\n%d %d\n255\n" % (img.shape[1], img.shape[0]) + img.tobytes())
+        be.reconstruct_end()
+    return res
 
 
 def _quat_from_matrix(R):
@@ -282,6 +315,8 @@ def main():
     ap.add_argument("--deterministic", action="store_true", help="bitwise reproducible evaluations (CMX_OPT_DETERMINISTIC)")
     ap.add_argument("--display", metavar="PREFIX", default=None,
                     help="write PREFIX_pano.ppm (final panorama, last pose's FOV) and PREFIX_local_iwe.pgm (one local-IWE pair)")
+    ap.add_argument("--reconstruct", action="store_true",
+                    help="after the last window, re-warp ALL events along the whole refined trajectory (with --display: PREFIX_recon.pgm)")
     a = ap.parse_args()
     stream = synth.event_stream(a.rate, a.seconds, 240, 180, 200.0, 200.0, 119.5, 89.5, omega_mean=(0.2, 1.8, 0.3),
                                 omega_amp=(1.0, 0.8, 1.0))
@@ -289,7 +324,7 @@ def main():
     prm.spline_degree = a.degree
     prm.deterministic = a.deterministic
     t0 = time.perf_counter()
-    res = run_pipeline(stream, prm, use_event_store=not a.host_events, log=print, display_prefix=a.display)
+    res = run_pipeline(stream, prm, use_event_store=not a.host_events, log=print, display_prefix=a.display, reconstruct=a.reconstruct)
     wall = time.perf_counter() - t0
     m = evaluate_against_truth(stream, res)
     print("%.2f s of events (%d) processed in %.2f s wall" % (a.seconds, len(stream.x), wall))
@@ -298,6 +333,9 @@ def main():
     print("refined trajectory orientation error: rms %.3f deg, max %.3f deg" % (m["ba_err_deg_rms"], m["ba_err_deg_max"]))
     print("map: %d x %d, %.0f%% of pixels touched" % (res["IG"].shape[1], res["IG"].shape[0],
                                                        100.0 * float((res["IG"] > 0).mean())))
+    if "recon" in res:
+        print("reconstruction along the whole trajectory: %.0f votes, %.0f%% of pixels touched" %
+              (float(res["recon"].sum(dtype=np.float64)), 100.0 * float((res["recon"] > 0).mean())))
 
 
 if __name__ == "__main__":

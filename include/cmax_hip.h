@@ -302,6 +302,49 @@ int cmx_backend_set_window_from(cmx_ctx *ctx, const cmx_events *ev, int64_t firs
                                 int64_t t_next_win_beg_ns, int event_batch_size, int event_sample_rate,
                                 double blur_sigma, int contrast_measure, const float *IG);
 
+/* ------------------------------------------------------------------ whole-trajectory reconstruction ---------
+ * The panorama of ALL events warped along the FINAL refined trajectory -- the product a rotational event SLAM is run for.
+ * cmx_backend_set_window takes at most 64 control poses (one bundle-adjustment window); these calls take a spline of ANY knot
+ * count (the knots live in device memory; at least 2^20 of them, 32 bytes each) and accumulate into a plane of their own:
+ *     recon_begin(trajectory)   recon_add*(events) ...   recon_get / recon_render (any number of times)   recon_end
+ * They act on an ordinary back-end context (cmx_backend_create) and never change a later evaluation: the window, the resident
+ * evaluation point, IG, the visit counts and the exchange sets are left alone.  On a group handle every one of them returns
+ * CMX_ERR_STATE; add / get / render before begin return CMX_ERR_STATE, end without begin is CMX_OK.
+ *   begin   order = 2 | 4, K >= order knots (copied to the device), start_ns / dt_ns as in cmx_backend_set_window, batch size at most
+ *           2^30 (CMX_ERR_INVALID_ARG above it: a slice is at least one batch and is indexed with 32-bit integers); zeroes the plane
+ *           and both counters; records batch size, sample rate and the value of CMX_OPT_DETERMINISTIC at this moment.  A second begin
+ *           starts over.
+ *   add*    ONE call = the vote loop of EventWarper::computeImageOfWarpedEvents (src/backend/event_pano_warper.cpp:188-196, :233-311)
+ *           over exactly the events handed in, ADDED to the plane: batches start at the call's first event, a trailing batch holding
+ *           a single event is skipped, the batch pose is taken at the batch time cmx_backend_set_window uses, sampling restarts at
+ *           every batch start, and an event votes when 1 <= xx < Wp-2 && 1 <= yy < Hp-2 whatever its time (no old / new split, no
+ *           alpha, no IG, no blur).  add(A) then add(B) therefore equals the sum of two separate loops, and equals the loop over
+ *           A || B exactly when len(A) is a multiple of the batch size.  Checks and status codes are those of
+ *           cmx_backend_set_window[_aos|_from]: CMX_ERR_INVALID_ARG, CMX_ERR_EVENT_RANGE, CMX_ERR_TIME_ORDER, CMX_ERR_SPLINE_RANGE,
+ *           with one rule stated more strictly: on the host paths EVERY event handed in must lie inside the sensor, at every
+ *           sample rate -- the events the sampling skips and a skipped trailing event included (cmx_backend_set_window looks at
+ *           events it does not pack only when it sub-samples: at rate 1 it lets a skipped trailing event pass unseen).
+ *           All of this is validated before the first vote, so a call that fails VALIDATION adds nothing.  A runtime failure
+ *           (CMX_ERR_HIP: an allocation, a copy or a launch refused in the middle of a long input) is outside that promise:
+ *           slices queued before it have voted, and the reconstruction should be begun again.
+ *           n may be anything up to the event limit: long inputs are processed in internal slices of whole batches (packing and
+ *           upload of one slice beside the vote kernel of the one before), staging memory does not grow with n.
+ *   get     pano = Hp*Wp fp32 or NULL (counters only); *n_sampled = events the sampling selected so far (exact), *n_inside = events
+ *           that voted so far; either may be NULL.  Accumulation may continue afterwards.
+ *   render  cmx_backend_render_map's tone map, argument rules and output (mono8, or bgr8 with the sensor outline) on this plane.
+ *   end     frees the plane(s), the knots and the staging.
+ * CMX_OPT_DETERMINISTIC = 1 at begin: votes are 64-bit integer adds into a 2^-30 fixed-point plane (get / render convert to fp32):
+ * bitwise identical from run to run, for any slicing of the same events at batch multiples, and through the three ingest paths.
+ * Otherwise votes are fp32 atomics: equal up to summation order. */
+int cmx_backend_recon_begin(cmx_ctx *ctx, int order, int K, const double *knots_xyzw, int64_t start_ns, int64_t dt_ns,
+                            int event_batch_size, int event_sample_rate);
+int cmx_backend_recon_add(cmx_ctx *ctx, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns);
+int cmx_backend_recon_add_aos(cmx_ctx *ctx, int64_t n, const void *events, const cmx_aos_layout *layout);
+int cmx_backend_recon_add_from(cmx_ctx *ctx, const cmx_events *ev, int64_t first, int64_t count);
+int cmx_backend_recon_get(cmx_ctx *ctx, float *pano /* Hp*Wp or NULL */, int64_t *n_sampled, int64_t *n_inside /* either may be NULL */);
+int cmx_backend_recon_render(cmx_ctx *ctx, double gamma, const double fov_quat_xyzw[4] /* or NULL */, unsigned char *out);
+int cmx_backend_recon_end(cmx_ctx *ctx);
+
 /* ------------------------------------------------------------------ split-phase (multi-GPU) ------------
  * The IWE is a sum over events, the contrast a non-linear function of the SUMMED image, so ranks exchange
  * between splat and blur/reduce.  Each rank loads its contiguous range of event
@@ -513,7 +556,8 @@ int cmx_get_stats(cmx_ctx *ctx, double *stats, int n_stats); /* writes min(n_sta
  *     CMX_OPT_SPIN_WAIT values >= 2 are a spin budget in microseconds for all three waiters (before: "spin"), negative values are
  *     rejected (before: accepted as non-zero);
  *  6: named cmx_get_stats indices, five more of them (the buffer length is the caller's: old callers keep reading what they asked for); cmx_group_transport_info; the *_aos entry points; cmx_set_stream_priority /
- *     cmx_set_cu_mask moved to cmax_hip_diag.h) */
+ *     cmx_set_cu_mask moved to cmax_hip_diag.h;
+ *     added without a bump (no signature or buffer layout changed): the seven cmx_backend_recon_* entry points) */
 #define CMX_ABI_VERSION 6
 int cmx_abi_version(void);
 int cmx_timing_enable(cmx_ctx *ctx, int on);
