@@ -30,128 +30,62 @@ int cmx_backend_create(cmx_ctx **out, int device, int W, int H, const double *lu
   return CMX_OK;
 }
 
-int be_set_window_impl(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns,
-                              const uint32_t *d_raw, const int64_t *d_t, int order, int K, const double *knots_xyzw,
-                              int64_t start_ns, int64_t dt_ns, int num_fixed, int64_t t_next_win_beg_ns,
-                              int event_batch_size, int event_sample_rate, double blur_sigma, int contrast_measure,
-                              const float *IG, const EvAos *aos) {
+int be_set_window_impl(cmx_ctx *c, const EventSource &src, const WindowSpec &w) {
   if (!c || c->kind != KIND_BE) return fail(c, CMX_ERR_STATE, "not a back-end context");
   int rc = bind_device(c);
   if (rc) return rc;
   c->have_data = false;
   c->accumulated = false;
   c->x_valid = false;
+  const KnotSupport &sup = w.sup;
+  const int order = sup.order, K = sup.K, num_fixed = w.num_fixed, B = w.batch, rate = w.rate;
   if (order != 2 && order != 4) return fail(c, CMX_ERR_INVALID_ARG, "spline order %d unsupported (2 = linear, 4 = cubic)", order);
   if (K < order || K > kMaxKnots) return fail(c, CMX_ERR_INVALID_ARG, "K=%d outside [%d, %d]", K, order, kMaxKnots);
   if (num_fixed < 0 || num_fixed > K) return fail(c, CMX_ERR_INVALID_ARG, "num_fixed=%d outside [0, K]", num_fixed);
-  if (!knots_xyzw || dt_ns <= 0) return fail(c, CMX_ERR_INVALID_ARG, "bad spline description");
-  if (event_batch_size <= 0 || event_sample_rate <= 0) return fail(c, CMX_ERR_INVALID_ARG, "batch size / sample rate must be > 0");
+  if (!w.knots || sup.dt_ns <= 0) return fail(c, CMX_ERR_INVALID_ARG, "bad spline description");
+  if (B <= 0 || rate <= 0) return fail(c, CMX_ERR_INVALID_ARG, "batch size / sample rate must be > 0");
   // the back end's switch (global_focus_funcs.cpp:61-69) knows mean square only; everything else is variance
-  if (contrast_measure != CMX_MEAN_SQUARE) contrast_measure = CMX_VARIANCE;
-  if (!d_raw && !aos) {
-    rc = check_event_args(c, n, x, y, t_ns);
-    if (rc) return rc;
-  } else if (n < 0 || n > kMaxEvents) {
-    return fail(c, CMX_ERR_INVALID_ARG, "bad event count %lld", (long long)n);
-  }
-  rc = setup_blur(c, blur_sigma);
+  const int contrast_measure = w.measure == CMX_MEAN_SQUARE ? CMX_MEAN_SQUARE : CMX_VARIANCE;
+  rc = check_event_args(c, src);
+  if (rc) return rc;
+  rc = setup_blur(c, w.sigma);
   if (rc) return rc;
 
-  // Batches: for (beg = 0; beg < n-1; beg += B) { end = (n-beg > B) ? beg+B : n; }  -- a trailing batch holding
-  // exactly the last single event is skipped (event_pano_warper.cpp:188-196); inside a batch events are taken
-  // with stride event_sample_rate restarting at the batch start (:262).
-  const int B = event_batch_size, rate = event_sample_rate;
-  const int per_batch = (B + rate - 1) / rate;
-  const int64_t nb64 = (n > 1) ? (n - 1 + B - 1) / B : 0;
-  if (nb64 > 0x7fffffffLL) return fail(c, CMX_ERR_INVALID_ARG, "too many batches");
-  const int nbatches = (int)nb64;
-  int64_t n_packed_total = 0;
-  if (nbatches > 0) {
-    const int64_t last_beg = (int64_t)(nbatches - 1) * B;
-    const int64_t last_len = (n - last_beg > B) ? B : (n - last_beg);  // a trailing single event is never in a batch
-    n_packed_total = (int64_t)(nbatches - 1) * per_batch + (last_len + rate - 1) / rate;
-  }
+  const int64_t n = src.n;
+  const bool host = !src.on_device();
+  BatchPlan p;
+  if (!plan_batches(n, B, rate, &p)) return fail(c, CMX_ERR_INVALID_ARG, "too many batches");
+  const int nb = p.nb;
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // the pinned staging buffer may still feed the previous upload
-  uint32_t *xy = nullptr;
-  if (!d_raw) {
-    rc = ensure_pinned_xy(c, (size_t)n_packed_total);
+  std::vector<long long> bt(host ? (size_t)nb : 0);  // (windows cut from the event store get their batch times from a kernel, below)
+  if (host) {
+    rc = ensure_pinned_xy(c, (size_t)p.n_packed);
     if (rc) return rc;
-    xy = c->h_xy;
-  }
-  std::vector<long long> bt(d_raw ? 0 : (size_t)nbatches);
-  std::atomic<unsigned> out_of_range(0);  // some event outside the sensor: seen by the packing pass, located afterwards
-  const unsigned sensor_w = (unsigned)c->W, sensor_h = (unsigned)c->H;
-  std::atomic<int> err_kind(0);
-  std::atomic<long long> err_at(-1);
-  if (!d_raw)  // (windows cut from the event store get their batch times from a kernel, below)
-  parallel_ranges(nbatches, [&](int64_t b0, int64_t b1) {
-    for (int64_t b = b0; b < b1; b++) {
-      const int64_t beg = b * B;
-      const int64_t end = (n - beg > B) ? beg + B : n;
-      const int64_t t_first = aos ? aos->T(beg) : t_ns[beg], t_last = aos ? aos->T(end - 1) : t_ns[end - 1];
-      if (t_last < t_first) { err_kind = CMX_ERR_TIME_ORDER; err_at = beg; return; }
-      const long long tb = time_batch_ns(t_first, t_last);
-      const long long st = tb - start_ns;
-      if (st < 0 || st / dt_ns + order > K) { err_kind = CMX_ERR_SPLINE_RANGE; err_at = tb; return; }
-      bt[(size_t)b] = tb;
-      if (rate == 1) continue;  // packed below by a flat, vectorisable loop (packed index == event index)
-      uint32_t *dst = xy + b * per_batch;
-      unsigned acc = 0;
-      for (int64_t e = beg; e < end; e += rate) {
-        const unsigned ex = aos ? aos->X(e) : (unsigned)x[e], ey = aos ? aos->Y(e) : (unsigned)y[e];
-        const int64_t et = aos ? aos->T(e) : t_ns[e];
-        acc |= (unsigned)(ex >= sensor_w) | (unsigned)(ey >= sensor_h);
-        *dst++ = ex | (ey << 16) | ((et < t_next_win_beg_ns) ? 0x80000000u : 0u);
-      }
-      if (acc) out_of_range = 1;
+    BatchTimeError bad;
+    const unsigned outside = src.view([&](const auto &v) {
+      bad = batch_times(v, n, B, 0, nb, &sup, [&](int64_t b, long long tb) { bt[(size_t)b] = tb; });
+      return pack_events<true>(v, n, nb, B, rate, (unsigned)c->W, (unsigned)c->H, w.t_next_win_beg_ns, c->h_xy);
+    });
+    // (with sub-sampling only the sampled events were looked at: the reference reads nothing else either, but the ABI
+    // promises that every event handed over is inside the sensor)
+    if (outside || rate != 1) {
+      rc = check_events(c, src);
+      if (rc) return rc;
     }
-  });
-  if (rate == 1 && !d_raw && aos)  // straight from the host's records (dvs_msgs::Event): no x[] / y[] / t_ns[] vectors in between
-    parallel_ranges(n_packed_total, [&](int64_t a0, int64_t a1) {
-      unsigned acc = 0;
-      for (int64_t e = a0; e < a1; e++) {
-        const unsigned ex = aos->X(e), ey = aos->Y(e);
-        acc |= (unsigned)(ex >= sensor_w) | (unsigned)(ey >= sensor_h);
-        xy[e] = ex | (ey << 16) | ((uint32_t)(aos->T(e) < t_next_win_beg_ns) << 31);
-      }
-      if (acc) out_of_range = 1;
-    });
-  else if (rate == 1 && !d_raw)
-    parallel_ranges(n_packed_total, [&](int64_t a0, int64_t a1) {
-      const uint16_t *__restrict xs = x, *__restrict ys = y;
-      const int64_t *__restrict ts = t_ns;
-      uint32_t *__restrict out = xy;
-      unsigned acc = 0;
-      for (int64_t e = a0; e < a1; e++) {
-        acc |= (unsigned)(xs[e] >= sensor_w) | (unsigned)(ys[e] >= sensor_h);
-        out[e] = (uint32_t)xs[e] | ((uint32_t)ys[e] << 16) | ((uint32_t)(ts[e] < t_next_win_beg_ns) << 31);
-      }
-      if (acc) out_of_range = 1;
-    });
-  // (with sub-sampling only the sampled events were looked at: the reference reads nothing else either, but the ABI
-  // promises that every event handed over is inside the sensor)
-  if (!d_raw && (out_of_range.load() || rate != 1)) {
-    rc = check_events(c, n, x, y, t_ns, aos);
-    if (rc) return rc;
+    if (bad.kind) return fail_batch_time(c, bad, sup);
   }
-  if (err_kind.load() == CMX_ERR_TIME_ORDER)
-    return fail(c, CMX_ERR_TIME_ORDER, "batch at event %lld spans a negative time interval", err_at.load());
-  if (err_kind.load() == CMX_ERR_SPLINE_RANGE)
-    return fail(c, CMX_ERR_SPLINE_RANGE, "batch time %lld ns outside the support of %d knots (start %lld, dt %lld)", err_at.load(), K,
-                (long long)start_ns, (long long)dt_ns);
-  const int nb = nbatches;
   c->order = order; c->K = K; c->num_fixed = num_fixed;
   c->batch = B; c->sample_rate = rate; c->measure = contrast_measure;
   c->knots0.resize((size_t)K);
-  for (int i = 0; i < K; i++) c->knots0[i] = Quat{knots_xyzw[4 * i], knots_xyzw[4 * i + 1], knots_xyzw[4 * i + 2], knots_xyzw[4 * i + 3]};
+  for (int i = 0; i < K; i++) c->knots0[i] = Quat{w.knots[4 * i], w.knots[4 * i + 1], w.knots[4 * i + 2], w.knots[4 * i + 3]};
   memset(c->h_spline, 0, sizeof(SplineArgs));
   c->h_spline->order = order;
   c->h_spline->K = K;
-  c->h_spline->start_ns = start_ns;
-  c->h_spline->dt_ns = dt_ns;
+  c->h_spline->start_ns = sup.start_ns;
+  c->h_spline->dt_ns = sup.dt_ns;
   blending_matrix(order, c->h_spline->blend);
 
-  rc = ensure(c, c->d_xy, c->xy_cap, (size_t)n_packed_total);
+  rc = ensure(c, c->d_xy, c->xy_cap, (size_t)p.n_packed);
   if (rc) return rc;
   rc = ensure(c, c->d_batch_t, c->batch_t_cap, (size_t)nb);
   if (rc) return rc;
@@ -159,28 +93,27 @@ int be_set_window_impl(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t 
   if (rc) return rc;
   rc = ensure(c, c->d_poseR, c->poseR_cap, (size_t)nb);
   if (rc) return rc;
-  if (n_packed_total > 0) {
-    if (d_raw)
-      launch_be_pack_from_store(d_raw, reinterpret_cast<const long long *>(d_t), (long long)n, B, rate, per_batch,
-                                (int)n_packed_total, (long long)t_next_win_beg_ns, c->d_xy, c->stream);
+  if (p.n_packed > 0) {
+    if (host)
+      HIP_TRY(c, hipMemcpyAsync(c->d_xy, c->h_xy, (size_t)p.n_packed * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     else
-      HIP_TRY(c, hipMemcpyAsync(c->d_xy, xy, (size_t)n_packed_total * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+      launch_be_pack_from_store(src.d_xy, reinterpret_cast<const long long *>(src.d_t), (long long)n, B, rate, p.per_batch, (int)p.n_packed,
+                                (long long)w.t_next_win_beg_ns, c->d_xy, c->stream);
   }
   // (on the context's stream, not the null stream: a masked stream -- cmx_set_cu_mask -- is a BLOCKING stream, and a null-stream
   //  copy would serialise this hand-over against every other context's null-stream work on the device; `bt` lives until the
   //  synchronisation at the end of this function)
-  if (nb && !d_raw) HIP_TRY(c, hipMemcpyAsync(c->d_batch_t, bt.data(), (size_t)nb * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-  if (nb && d_raw) {  // batch times + their validation on the device; the two error words come back with the final sync
+  if (nb && host) HIP_TRY(c, hipMemcpyAsync(c->d_batch_t, bt.data(), (size_t)nb * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+  if (nb && !host) {  // batch times + their validation on the device; the two error words are read after the final sync
     if (!c->d_batch_err) HIP_TRY(c, hipMalloc((void **)&c->d_batch_err, 2 * sizeof(long long)));
-    long long *d_err = c->d_batch_err;
-    HIP_TRY(c, hipMemsetAsync(d_err, 0, 2 * sizeof(long long), c->stream));
-    launch_be_batch_times(reinterpret_cast<const long long *>(d_t), (long long)n, B, nb, (long long)start_ns, (long long)dt_ns, order,
-                          K, c->d_batch_t, d_err, c->stream);
+    rc = queue_batch_times(c, src.d_t, n, B, nb, sup, c->d_batch_t, c->d_batch_err, true);
+    if (rc) return rc;
   }
   const size_t np = (size_t)c->Wp * c->Hp;
-  if (IG == CMX_KEEP_MAP) {
+  if (w.IG == CMX_KEEP_MAP) {
     c->ig_nonzero = true;  // resident map: contents unknown to the host; the alpha kernel counts the non-zeros itself
-  } else if (IG) {
+  } else if (w.IG) {
+    const float *IG = w.IG;
     HIP_TRY(c, hipMemcpyAsync(c->d_IG, IG, np * sizeof(float), hipMemcpyHostToDevice, c->stream));
     std::atomic<bool> nz(false);
     parallel_ranges((int64_t)np, [&](int64_t a0, int64_t a1) {
@@ -197,17 +130,14 @@ int be_set_window_impl(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t 
   c->first_iter = true;     // setFirstIter(true), pose_graph_optimizer.cpp:293
   comm_reset_xset(c);       // sharded panoramas: the first exchange of a window covers the whole planes
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (nb && d_raw) {
-    long long e[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(e, c->d_batch_err, sizeof(e), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (e[0] == CMX_ERR_TIME_ORDER) return fail(c, CMX_ERR_TIME_ORDER, "batch at event %lld spans a negative time interval", e[1]);
-    if (e[0] == CMX_ERR_SPLINE_RANGE)
-      return fail(c, CMX_ERR_SPLINE_RANGE, "batch time %lld ns outside the support of %d knots (start %lld, dt %lld)", e[1], K,
-                  (long long)start_ns, (long long)dt_ns);
+  if (nb && !host) {
+    BatchTimeError bad;
+    rc = read_batch_errors(c, c->d_batch_err, &bad);
+    if (rc) return rc;
+    if (bad.kind) return fail_batch_time(c, bad, sup);
   }
-  c->n_packed = (int)n_packed_total;
-  c->per_batch = per_batch;
+  c->n_packed = (int)p.n_packed;
+  c->per_batch = p.per_batch;
   c->nb = nb;
   c->have_data = true;
   c->tb_valid = false;
@@ -219,25 +149,22 @@ int cmx_backend_set_window(cmx_ctx *c, int64_t n, const uint16_t *x, const uint1
                            int order, int K, const double *knots_xyzw, int64_t start_ns, int64_t dt_ns,
                            int num_fixed, int64_t t_next_win_beg_ns, int event_batch_size, int event_sample_rate,
                            double blur_sigma, int contrast_measure, const float *IG) {
-  if (is_group(c))
-    return group_set_window(c, nullptr, n, x, y, t_ns, order, K, knots_xyzw, start_ns, dt_ns, num_fixed, t_next_win_beg_ns, event_batch_size,
-                            event_sample_rate, blur_sigma, contrast_measure, IG);
-  return be_set_window_impl(c, n, x, y, t_ns, nullptr, nullptr, order, K, knots_xyzw, start_ns, dt_ns, num_fixed,
-                            t_next_win_beg_ns, event_batch_size, event_sample_rate, blur_sigma, contrast_measure, IG);
+  const EventSource src = EventSource::arrays(n, x, y, t_ns);
+  const WindowSpec w{{order, K, start_ns, dt_ns}, knots_xyzw, num_fixed, t_next_win_beg_ns, event_batch_size, event_sample_rate, blur_sigma,
+                     contrast_measure, IG};
+  return is_group(c) ? group_set_window(c, src, w) : be_set_window_impl(c, src, w);
 }
 
 int cmx_backend_set_window_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout, int order, int K,
                                const double *knots_xyzw, int64_t start_ns, int64_t dt_ns, int num_fixed, int64_t t_next_win_beg_ns,
                                int event_batch_size, int event_sample_rate, double blur_sigma, int contrast_measure, const float *IG) {
   if (!c || c->kind != KIND_BE) return fail(c, CMX_ERR_STATE, "not a back-end context");
-  EvAos aos;
-  const int rc = make_aos(c, n, events, layout, &aos);
+  EventSource src;
+  const int rc = make_aos(c, n, events, layout, &src);
   if (rc) return rc;
-  if (is_group(c))
-    return group_set_window(c, &aos, n, nullptr, nullptr, nullptr, order, K, knots_xyzw, start_ns, dt_ns, num_fixed, t_next_win_beg_ns,
-                            event_batch_size, event_sample_rate, blur_sigma, contrast_measure, IG);
-  return be_set_window_impl(c, n, nullptr, nullptr, nullptr, nullptr, nullptr, order, K, knots_xyzw, start_ns, dt_ns, num_fixed,
-                            t_next_win_beg_ns, event_batch_size, event_sample_rate, blur_sigma, contrast_measure, IG, &aos);
+  const WindowSpec w{{order, K, start_ns, dt_ns}, knots_xyzw, num_fixed, t_next_win_beg_ns, event_batch_size, event_sample_rate, blur_sigma,
+                     contrast_measure, IG};
+  return is_group(c) ? group_set_window(c, src, w) : be_set_window_impl(c, src, w);
 }
 
 // knot_i <- exp(drot_i) * knot_i for the non-fixed knots (CopyAndIncrementalUpdate, trajectory.cpp:240-263)

@@ -22,22 +22,6 @@ int bind_device(cmx_ctx *c) {
   return CMX_OK;
 }
 
-// ---- ros::Time arithmetic (roscpp noetic semantics), needed to reproduce the per-batch pose time:
-//   time_batch = time_first + (time_last - time_first) * 0.5         [Duration*double -> fromSec: floor + round]
-//   reference: local_image_warped_events.cpp:68-75, event_pano_warper.cpp:239-242
-long long time_batch_ns(long long t_first, long long t_last) {
-  const long long d = t_last - t_first;
-  long long ds = d / 1000000000LL, dn = d % 1000000000LL;
-  if (dn < 0) { dn += 1000000000LL; ds -= 1; }
-  const double half = ((double)ds + 1e-9 * (double)dn) * 0.5;
-  const long long hs = (long long)floor(half);
-  const long long hn = (long long)round((half - (double)hs) * 1e9);
-  return t_first + hs * 1000000000LL + hn;
-}
-double time_to_sec(long long t_ns) {  // ros::Time::toSec
-  return (double)(t_ns / 1000000000LL) + 1e-9 * (double)(t_ns % 1000000000LL);
-}
-
 // c1d[q] = (G^T 1)_q for one axis of length L: taps that stay inside + the taps the forward pass reflected back
 // (see adjoint_kernel / image_adjoint_kernel).  1 in the interior; only the outer r pixels differ.
 int upload_gt1(cmx_ctx *c) {
@@ -209,44 +193,54 @@ int create_common(cmx_ctx **out, int kind, int device, int W, int H, const doubl
 
 int ensure_accum(cmx_ctx *c, size_t need);
 
-int check_event_args(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t) {
-  if (n < 0 || n > kMaxEvents) return fail(c, CMX_ERR_INVALID_ARG, "bad event count %lld (limit %lld)", (long long)n, (long long)kMaxEvents);
-  if (n > 0 && (!x || !y || !t)) return fail(c, CMX_ERR_INVALID_ARG, "null event arrays");
+int check_event_args(cmx_ctx *c, const EventSource &src) {
+  const int64_t n = src.n;
+  const bool soa = src.kind == EventSource::SOA;  // (records: make_aos has looked at the pointers; event store: store_source at the range)
+  if (n < 0 || n > kMaxEvents)
+    return soa ? fail(c, CMX_ERR_INVALID_ARG, "bad event count %lld (limit %lld)", (long long)n, (long long)kMaxEvents)
+               : fail(c, CMX_ERR_INVALID_ARG, "bad event count %lld", (long long)n);
+  if (soa && n > 0 && (!src.soa.x || !src.soa.y || !src.soa.t)) return fail(c, CMX_ERR_INVALID_ARG, "null event arrays");
   return CMX_OK;
 }
-int make_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout, EvAos *out) {
+int make_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout, EventSource *out) {
   if (n < 0 || n > kMaxEvents) return fail(c, CMX_ERR_INVALID_ARG, "bad event count %lld (limit %lld)", (long long)n, (long long)kMaxEvents);
   if (!layout || (n > 0 && !events)) return fail(c, CMX_ERR_INVALID_ARG, "null event array / layout");
-  const size_t st = layout->stride;
-  if (st < 12 || layout->off_x + 2 > st || layout->off_y + 2 > st || layout->off_sec + 4 > st || layout->off_nsec + 4 > st)
-    return fail(c, CMX_ERR_INVALID_ARG, "record layout: fields outside the %zu-byte record", st);
-  out->base = static_cast<const unsigned char *>(events);
-  out->stride = st; out->ox = layout->off_x; out->oy = layout->off_y; out->os = layout->off_sec; out->on = layout->off_nsec;
+  *out = EventSource{EventSource::AOS, n};
+  if (!aos_view(events, layout, &out->aos)) return fail(c, CMX_ERR_INVALID_ARG, "record layout: fields outside the %zu-byte record", layout->stride);
   return CMX_OK;
 }
-int check_events(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t, const EvAos *aos) {
-  if (!aos) {
-    int rc0 = check_event_args(c, n, x, y, t);
-    if (rc0) return rc0;
-  }
-  const int W = c->W, H = c->H;
-  std::atomic<int64_t> bad(-1);
-  auto X = [&](int64_t i) { return aos ? aos->X(i) : (unsigned)x[i]; };
-  auto Y = [&](int64_t i) { return aos ? aos->Y(i) : (unsigned)y[i]; };
-  parallel_ranges(n, [&](int64_t a, int64_t b) {
-    unsigned acc = 0;
-    for (int64_t i = a; i < b; i++) acc |= (unsigned)(X(i) >= (unsigned)W) | (unsigned)(Y(i) >= (unsigned)H);
-    if (acc)
-      for (int64_t i = a; i < b; i++)
-        if (X(i) >= (unsigned)W || Y(i) >= (unsigned)H) {
-          int64_t cur = bad.load();
-          while ((cur < 0 || i < cur) && !bad.compare_exchange_weak(cur, i)) {}
-          break;
-        }
+int check_events(cmx_ctx *c, const EventSource &src) {
+  const int rc0 = check_event_args(c, src);
+  if (rc0) return rc0;
+  return src.view([&](const auto &v) {
+    const int64_t i = first_outside(v, src.n, (unsigned)c->W, (unsigned)c->H);
+    if (i >= 0) return fail(c, CMX_ERR_EVENT_RANGE, "event %lld at (%u,%u) outside the %dx%d sensor", (long long)i, v.X(i), v.Y(i), c->W, c->H);
+    return (int)CMX_OK;
   });
-  const int64_t i = bad.load();
-  if (i >= 0)
-    return fail(c, CMX_ERR_EVENT_RANGE, "event %lld at (%u,%u) outside the %dx%d sensor", (long long)i, X(i), Y(i), W, H);
+}
+
+int queue_batch_times(cmx_ctx *c, const int64_t *d_t, int64_t n, int B, int nb, const KnotSupport &sup, long long *d_bt, long long *d_err,
+                      bool clear_err) {
+  if (clear_err) HIP_TRY(c, hipMemsetAsync(d_err, 0, 2 * sizeof(long long), c->stream));
+  launch_be_batch_times(reinterpret_cast<const long long *>(d_t), (long long)n, B, nb, sup.start_ns, sup.dt_ns, sup.order, sup.K, d_bt, d_err,
+                        c->stream);
+  return CMX_OK;
+}
+int read_batch_errors(cmx_ctx *c, const long long *d_err, BatchTimeError *e) {
+  long long w[2] = {0, 0};
+  HIP_TRY(c, hipMemcpyAsync(w, d_err, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  e->kind = (int)w[0];
+  e->at = w[1];
+  return CMX_OK;
+}
+int fail_batch_time(cmx_ctx *c, const BatchTimeError &e, const KnotSupport &sup, bool with_event) {
+  if (e.kind == CMX_ERR_TIME_ORDER)
+    return with_event ? fail(c, CMX_ERR_TIME_ORDER, "batch at event %lld spans a negative time interval", e.at)
+                      : fail(c, CMX_ERR_TIME_ORDER, "a batch spans a negative time interval");
+  if (e.kind == CMX_ERR_SPLINE_RANGE)
+    return fail(c, CMX_ERR_SPLINE_RANGE, "batch time %lld ns outside the support of %d knots (start %lld, dt %lld)", e.at, sup.K, sup.start_ns,
+                sup.dt_ns);
   return CMX_OK;
 }
 

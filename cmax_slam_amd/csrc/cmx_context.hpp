@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "cmx_hostpool.hpp"
+#include "cmx_ingest.hpp"
 #include "cmx_internal.hpp"
 
 using namespace cmx;  // internal header of one library: the parameter blocks of cmx_internal.hpp are used unqualified
@@ -375,30 +376,14 @@ int ensure(cmx_ctx *c, T *&ptr, size_t &cap, size_t need) {
 // ---- cmx_context.cpp
 int bind_device(cmx_ctx *c);
 int comm_probe_exchange(cmx_ctx *c, float *in, float *out, size_t count);  // cmx_comm.cpp
-long long time_batch_ns(long long t_first, long long t_last);
-double time_to_sec(long long t_ns);
 int upload_gt1(cmx_ctx *c);
 int setup_blur(cmx_ctx *c, double sigma);
 hipEvent_t get_event(cmx_ctx *c);
 void collect_spans(cmx_ctx *c);  // call after the stream has been synchronised
 int create_common(cmx_ctx **out, int kind, int device, int W, int H, const double *lut);
-// events as an array of records (cmx_aos_layout): the accessors the packing passes use when a hand-over comes from the *_aos entry points
-struct EvAos {
-  const unsigned char *base = nullptr;
-  size_t stride = 0, ox = 0, oy = 0, os = 0, on = 0;
-  inline unsigned X(int64_t i) const { uint16_t v; memcpy(&v, base + (size_t)i * stride + ox, 2); return v; }
-  inline unsigned Y(int64_t i) const { uint16_t v; memcpy(&v, base + (size_t)i * stride + oy, 2); return v; }
-  inline int64_t T(int64_t i) const {
-    uint32_t sec, nsec;
-    memcpy(&sec, base + (size_t)i * stride + os, 4);
-    memcpy(&nsec, base + (size_t)i * stride + on, 4);
-    return (int64_t)sec * 1000000000LL + (int64_t)nsec;
-  }
-  EvAos from(int64_t first) const { EvAos r = *this; r.base = base + (size_t)first * stride; return r; }
-};
-int make_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout, EvAos *out);  // argument checks
-int check_event_args(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t);
-int check_events(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t, const EvAos *aos = nullptr);
+int make_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout, EventSource *out);  // argument checks of the *_aos entry points
+int check_event_args(cmx_ctx *c, const EventSource &src);  // count, and the arrays of a SoA hand-over
+int check_events(cmx_ctx *c, const EventSource &src);      // ... and every coordinate inside the sensor (host sources)
 int ensure_pinned_xy(cmx_ctx *c, size_t n);
 int ensure_pinned_dts(cmx_ctx *c, size_t n);
 int display_begin(cmx_ctx *c, size_t bytes);                       // device image, pinned copy, range keys reset (queued)
@@ -482,21 +467,18 @@ int group_size(const cmx_ctx *c);
 int group_members(const cmx_ctx *c, cmx_ctx **out, int max);  // the member contexts in rank order (a plain context: itself); returns their number
 int group_all(cmx_ctx *leader, const std::function<int(cmx_ctx *, int)> &fn);  // fn(member, rank) on every member; first failure
 void group_destroy(cmx_ctx *leader);
-int group_set_window(cmx_ctx *leader, const EvAos *aos, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, int order, int K,
-                     const double *knots_xyzw, int64_t start_ns, int64_t dt_ns, int num_fixed, int64_t t_next_win_beg_ns,
-                     int event_batch_size, int event_sample_rate, double blur_sigma, int contrast_measure, const float *IG);
+int group_set_window(cmx_ctx *leader, const EventSource &src, const WindowSpec &w);  // src: host arrays / records, or a range of an event store
 int group_eval(cmx_ctx *leader, const double *drotv, double *contrast, double *grad);
-int group_set_window_from(cmx_ctx *leader, const cmx_events *e, int64_t first, int64_t count, int order, int K, const double *knots_xyzw,
-                          int64_t start_ns, int64_t dt_ns, int num_fixed, int64_t t_next_win_beg_ns, int event_batch_size,
-                          int event_sample_rate, double blur_sigma, int contrast_measure, const float *IG);
+int store_source(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count, EventSource *out);  // cmx_events.cpp: the range on c's device
+int group_member_window_from(cmx_ctx *m, const EventSource &src, const WindowSpec &w);  // cmx_events.cpp: one member's cut
 int be_eval_one(cmx_ctx *c, const double *drotv, double *contrast, double *grad);  // cmx_backend.cpp: one context's evaluation
 #define CMX_NOT_FOR_GROUPS(c, what) \
   do { if ((c) && (c)->group) return fail((c), CMX_ERR_STATE, what " is not available on a group (the group runs its own exchange)"); } while (0)
 
 // ---- cmx_reconstruct.cpp: the bodies behind cmx_backend_recon_add[_aos] and _add_from (events on the host / in the event store)
 int recon_enter(cmx_ctx *c, bool need_begun);  // front door of every cmx_backend_recon_*: plain back-end context, not a group, begun; binds the device
-int recon_add_host(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, const EvAos *aos);
-int recon_add_store(cmx_ctx *c, int64_t n, const uint32_t *d_raw, const int64_t *d_t);
+int recon_add_host(cmx_ctx *c, const EventSource &src);
+int recon_add_store(cmx_ctx *c, const EventSource &src);
 int recon_diag_slice_events(int n);  // CMX_DIAG_RECON_SLICE_EVENTS (cmax_hip_diag.h)
 void recon_release(cmx_ctx *c);  // frees whatever a reconstruction holds (cmx_backend_recon_end, cmx_destroy)
 
@@ -505,12 +487,14 @@ int finish_sharded(cmx_ctx *c, int kind, bool exchange_planes, double *contrast,
 void comm_reset_xset(cmx_ctx *c);  // a new window / packet / panorama: the next exchange covers the whole planes
 void comm_release(cmx_ctx *c);  // destroys an attached communicator (cmx_destroy)
 
-// ---- cmx_frontend.cpp / cmx_backend.cpp: the bodies behind set_packet / set_window and their *_from forms
-// (d_raw != nullptr: the events are already on the device -- event store)
-int fe_set_packet_impl(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns,
-                       const uint32_t *d_raw, int64_t t_ref_ns, double fx, double fy, double cx, double cy,
-                       int event_batch_size, double blur_sigma, int contrast_measure, const EvAos *aos = nullptr);
-int be_set_window_impl(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns,
-                       const uint32_t *d_raw, const int64_t *d_t, int order, int K, const double *knots_xyzw,
-                       int64_t start_ns, int64_t dt_ns, int num_fixed, int64_t t_next_win_beg_ns, int event_batch_size,
-                       int event_sample_rate, double blur_sigma, int contrast_measure, const float *IG, const EvAos *aos = nullptr);
+// ---- cmx_frontend.cpp / cmx_backend.cpp: the bodies behind set_packet / set_window and their *_aos / *_from forms
+int fe_set_packet_impl(cmx_ctx *c, const EventSource &src, int64_t t_ref_ns, double fx, double fy, double cx, double cy,
+                       int event_batch_size, double blur_sigma, int contrast_measure);
+int be_set_window_impl(cmx_ctx *c, const EventSource &src, const WindowSpec &w);
+// batch times of events on the device (event store): queue launch_be_batch_times over the nb batches of n timestamps, its two error
+// words cleared first when asked; read the words back once the stream has run; turn a batch-time error, host's or device's, into
+// the call's failure (with_event = false: `at` of a negative interval is not an index the caller knows)
+int queue_batch_times(cmx_ctx *c, const int64_t *d_t, int64_t n, int B, int nb, const KnotSupport &sup, long long *d_bt, long long *d_err,
+                      bool clear_err);
+int read_batch_errors(cmx_ctx *c, const long long *d_err, BatchTimeError *e);
+int fail_batch_time(cmx_ctx *c, const BatchTimeError &e, const KnotSupport &sup, bool with_event = true);

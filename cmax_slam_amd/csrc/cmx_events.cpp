@@ -64,24 +64,21 @@ int cmx_events_devices(const cmx_events *e, int *devices, int max_devices) {
 
 // append a chunk of the (time-ordered) stream: AngVelEstimator::pushEvent's events_.push_back (ang_vel_estimator.cpp:68-78).
 // One packing pass on the host into pinned staging, then one asynchronous upload per replica (the devices copy side by side).
-static int events_push_impl(cmx_events *e, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, const EvAos *aos);
+static int events_push_impl(cmx_events *e, const EventSource &src);
 int cmx_events_push(cmx_events *e, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns) {
   if (!e || n < 0 || (n > 0 && (!x || !y || !t_ns))) return efail(e, CMX_ERR_INVALID_ARG, "bad arguments");
-  return events_push_impl(e, n, x, y, t_ns, nullptr);
+  return events_push_impl(e, EventSource::arrays(n, x, y, t_ns));
 }
 // the same from the host's own records (dvs_msgs::Event, cmx_aos_layout): pushEvent's loop over msg->events
 // (ang_vel_estimator.cpp:68-78) as ONE call -- x | y << 16 and sec * 1e9 + nsec are formed in the packing pass
 int cmx_events_push_aos(cmx_events *e, int64_t n, const void *events, const cmx_aos_layout *layout) {
   if (!e || n < 0 || !layout || (n > 0 && !events)) return efail(e, CMX_ERR_INVALID_ARG, "bad arguments");
-  const size_t st = layout->stride;
-  if (st < 12 || layout->off_x + 2 > st || layout->off_y + 2 > st || layout->off_sec + 4 > st || layout->off_nsec + 4 > st)
-    return efail(e, CMX_ERR_INVALID_ARG, "record layout: fields outside the record");
-  EvAos aos;
-  aos.base = static_cast<const unsigned char *>(events);
-  aos.stride = st; aos.ox = layout->off_x; aos.oy = layout->off_y; aos.os = layout->off_sec; aos.on = layout->off_nsec;
-  return events_push_impl(e, n, nullptr, nullptr, nullptr, &aos);
+  EventSource src{EventSource::AOS, n};
+  if (!aos_view(events, layout, &src.aos)) return efail(e, CMX_ERR_INVALID_ARG, "record layout: fields outside the record");
+  return events_push_impl(e, src);
 }
-static int events_push_impl(cmx_events *e, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, const EvAos *aos) {
+static int events_push_impl(cmx_events *e, const EventSource &src) {
+  const int64_t n = src.n;
   if (e->size + (size_t)n > e->capacity) return efail(e, CMX_ERR_INVALID_ARG, "event store full: drop old events first");
   if (n == 0) return CMX_OK;
   if ((size_t)n > e->stage_cap) {
@@ -94,32 +91,12 @@ static int events_push_impl(cmx_events *e, int64_t n, const uint16_t *x, const u
       return efail(e, CMX_ERR_HIP, "pinned staging allocation failed");
     e->stage_cap = cap;
   }
-  std::atomic<unsigned> bad(0);
-  const unsigned W = (unsigned)e->W, H = (unsigned)e->H;
   uint32_t *xy = e->h_xy;
   int64_t *tp = e->h_tp;
-  if (aos)
-    parallel_ranges(n, [&](int64_t a0, int64_t a1) {
-      unsigned acc = 0;
-      for (int64_t i = a0; i < a1; i++) {
-        const unsigned ex = aos->X(i), ey = aos->Y(i);
-        acc |= (unsigned)(ex >= W) | (unsigned)(ey >= H);
-        xy[i] = ex | (ey << 16);
-        tp[i] = aos->T(i);
-      }
-      if (acc) bad = 1;
-    });
-  else
-  parallel_ranges(n, [&](int64_t a0, int64_t a1) {
-    unsigned acc = 0;
-    for (int64_t i = a0; i < a1; i++) {
-      acc |= (unsigned)(x[i] >= W) | (unsigned)(y[i] >= H);
-      xy[i] = (uint32_t)x[i] | ((uint32_t)y[i] << 16);
-      tp[i] = t_ns[i];
-    }
-    if (acc) bad = 1;
+  const unsigned outside = src.view([&](const auto &v) {  // every event, as one batch
+    return pack_events<false>(v, n, 1, n, 1, (unsigned)e->W, (unsigned)e->H, 0, xy, tp);
   });
-  if (bad.load()) return efail(e, CMX_ERR_EVENT_RANGE, "event coordinates outside the sensor");
+  if (outside) return efail(e, CMX_ERR_EVENT_RANGE, "event coordinates outside the sensor");
   for (cmx_events::Replica &r : e->rep) {
     if (hipSetDevice(r.device) != hipSuccess) return efail(e, CMX_ERR_HIP, "hipSetDevice failed");
     if (hipMemcpyAsync(r.d_xy[e->cur] + e->size, xy, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, r.stream) != hipSuccess ||
@@ -164,16 +141,19 @@ int cmx_events_drop_before(cmx_events *e, int64_t global_index) {
   return CMX_OK;
 }
 
-static int store_range(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count, size_t *off, const cmx_events::Replica **rep) {
+// events_[first, first + count) of the store, as the replica on c's device holds them
+int store_source(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count, EventSource *out) {
   if (!e) return fail(c, CMX_ERR_INVALID_ARG, "null event store");
   if (!c) return CMX_ERR_INVALID_ARG;
-  *rep = e->on(c->device);
-  if (!*rep || e->W != c->W || e->H != c->H)
+  const cmx_events::Replica *rep = e->on(c->device);
+  if (!rep || e->W != c->W || e->H != c->H)
     return fail(c, CMX_ERR_INVALID_ARG, "event store belongs to another device / sensor");
   if (count < 0 || first < e->first_index || first + count > e->first_index + (int64_t)e->size)
     return fail(c, CMX_ERR_INVALID_ARG, "range [%lld, %lld) is not held by the event store [%lld, %lld)", (long long)first,
                 (long long)(first + count), (long long)e->first_index, (long long)(e->first_index + (int64_t)e->size));
-  *off = (size_t)(first - e->first_index);
+  const size_t off = (size_t)(first - e->first_index);
+  *out = EventSource{EventSource::DEVICE, count, EvSoa{nullptr, nullptr, e->h_t.data() + off}, EvAos{}, e, first,
+                     rep->d_xy[e->cur] + off, rep->d_t[e->cur] + off};
   return CMX_OK;
 }
 
@@ -182,27 +162,23 @@ static int store_range(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t c
 int cmx_frontend_set_packet_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count, int64_t t_ref_ns, double fx,
                                  double fy, double cx, double cy, int event_batch_size, double blur_sigma,
                                  int contrast_measure) {
-  size_t off = 0;
-  const cmx_events::Replica *r = nullptr;
-  int rc = store_range(c, e, first, count, &off, &r);
+  EventSource src;
+  const int rc = store_source(c, e, first, count, &src);
   if (rc) return rc;
-  return fe_set_packet_impl(c, count, nullptr, nullptr, e->h_t.data() + off, r->d_xy[e->cur] + off, t_ref_ns, fx, fy, cx, cy,
-                            event_batch_size, blur_sigma, contrast_measure);
+  return fe_set_packet_impl(c, src, t_ref_ns, fx, fy, cx, cy, event_batch_size, blur_sigma, contrast_measure);
 }
 int cmx_backend_set_window_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count, int order, int K,
                                 const double *knots_xyzw, int64_t start_ns, int64_t dt_ns, int num_fixed,
                                 int64_t t_next_win_beg_ns, int event_batch_size, int event_sample_rate, double blur_sigma,
                                 int contrast_measure, const float *IG) {
-  if (is_group(c))
-    return group_set_window_from(c, e, first, count, order, K, knots_xyzw, start_ns, dt_ns, num_fixed, t_next_win_beg_ns,
-                                 event_batch_size, event_sample_rate, blur_sigma, contrast_measure, IG);
-  size_t off = 0;
-  const cmx_events::Replica *r = nullptr;
-  int rc = store_range(c, e, first, count, &off, &r);
+  const WindowSpec w{{order, K, start_ns, dt_ns}, knots_xyzw, num_fixed, t_next_win_beg_ns, event_batch_size, event_sample_rate, blur_sigma,
+                     contrast_measure, IG};
+  // (a group: every member cuts its range from the replica on its own device, group_member_window_from)
+  if (is_group(c)) return group_set_window(c, EventSource{EventSource::DEVICE, count, EvSoa{}, EvAos{}, e, first}, w);
+  EventSource src;
+  const int rc = store_source(c, e, first, count, &src);
   if (rc) return rc;
-  return be_set_window_impl(c, count, nullptr, nullptr, e->h_t.data() + off, r->d_xy[e->cur] + off, r->d_t[e->cur] + off, order,
-                            K, knots_xyzw, start_ns, dt_ns, num_fixed, t_next_win_beg_ns, event_batch_size,
-                            event_sample_rate, blur_sigma, contrast_measure, IG);
+  return be_set_window_impl(c, src, w);
 }
 
 // cmx_backend_recon_add over events_[first, first+count) of the store: the vote kernel reads the store's own packed events (the
@@ -210,24 +186,18 @@ int cmx_backend_set_window_from(cmx_ctx *c, const cmx_events *e, int64_t first, 
 int cmx_backend_recon_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
   int rc = recon_enter(c, true);
   if (rc) return rc;
-  size_t off = 0;
-  const cmx_events::Replica *r = nullptr;
-  rc = store_range(c, e, first, count, &off, &r);
+  EventSource src;
+  rc = store_source(c, e, first, count, &src);
   if (rc) return rc;
-  return recon_add_store(c, count, r->d_xy[e->cur] + off, r->d_t[e->cur] + off);
+  return recon_add_store(c, src);
 }
 
 // A window cut from a replicated store on a GROUP: member r cuts ITS batch range (the range group_set_window hands it, the
 // one-event rule included) from the replica on its own device -- no event crosses the host or a link at hand-over
 // (pose_graph_optimizer.cpp:131-165 is the copy this replaces; event_pano_warper.cpp:188-196 the loop being sharded).
-int group_member_window_from(cmx_ctx *m, const cmx_events *e, int64_t first, int64_t beg, int64_t end, int order, int K,
-                             const double *knots_xyzw, int64_t start_ns, int64_t dt_ns, int num_fixed, int64_t t_next_win_beg_ns,
-                             int event_batch_size, int event_sample_rate, double blur_sigma, int contrast_measure, const float *IG) {
-  size_t off = 0;
-  const cmx_events::Replica *r = nullptr;
-  int rc = store_range(m, e, first + beg, end - beg, &off, &r);
+int group_member_window_from(cmx_ctx *m, const EventSource &src, const WindowSpec &w) {
+  EventSource mine;
+  const int rc = store_source(m, src.store, src.first, src.n, &mine);
   if (rc) return rc;
-  return be_set_window_impl(m, end - beg, nullptr, nullptr, e->h_t.data() + off, r->d_xy[e->cur] + off, r->d_t[e->cur] + off, order,
-                            K, knots_xyzw, start_ns, dt_ns, num_fixed, t_next_win_beg_ns, event_batch_size, event_sample_rate,
-                            blur_sigma, contrast_measure, IG);
+  return be_set_window_impl(m, mine, w);
 }

@@ -13,11 +13,8 @@ int cmx_frontend_create(cmx_ctx **out, int device, int W, int H, const double *l
   return chain_prealloc(*out);
 }
 
-// d_raw != nullptr: the events are already on the device (event store), x / y are unused and t_ns is the store's
-// host mirror of the timestamps
-int fe_set_packet_impl(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns,
-                              const uint32_t *d_raw, int64_t t_ref_ns, double fx, double fy, double cx, double cy,
-                              int event_batch_size, double blur_sigma, int contrast_measure, const EvAos *aos) {
+int fe_set_packet_impl(cmx_ctx *c, const EventSource &src, int64_t t_ref_ns, double fx, double fy, double cx, double cy,
+                       int event_batch_size, double blur_sigma, int contrast_measure) {
   if (!c || c->kind != KIND_FE) return fail(c, CMX_ERR_STATE, "not a front-end context");
   int rc = bind_device(c);
   if (rc) return rc;
@@ -27,71 +24,43 @@ int fe_set_packet_impl(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t 
   if (event_batch_size <= 0) return fail(c, CMX_ERR_INVALID_ARG, "event_batch_size must be > 0");
   // computeContrast's switch (local_focus_funcs.cpp:98-109): 1 = mean square, 2 = gradient magnitude, default = variance
   if (contrast_measure != CMX_MEAN_SQUARE && contrast_measure != CMX_GRADIENT_MAGNITUDE) contrast_measure = CMX_VARIANCE;
-  if (!d_raw && !aos) {
-    rc = check_event_args(c, n, x, y, t_ns);
-    if (rc) return rc;
-  } else if (n < 0 || n > kMaxEvents) {
-    return fail(c, CMX_ERR_INVALID_ARG, "bad event count %lld", (long long)n);
-  }
+  rc = check_event_args(c, src);
+  if (rc) return rc;
   rc = setup_blur(c, blur_sigma);
   if (rc) return rc;
   c->fx = fx; c->fy = fy; c->cx = cx; c->cy = cy;
   c->batch = event_batch_size;
   c->measure = contrast_measure;
 
-  // SoA packing + per-batch dt = time_batch.toSec() - time_ref.toSec()  (local_image_warped_events.cpp:68-75)
+  // packing + per-batch dt = time_batch.toSec() - time_ref.toSec()  (local_image_warped_events.cpp:68-75); every event is in a
+  // batch here, a trailing single one included
+  const int64_t n = src.n;
   const int nb = (int)((n + event_batch_size - 1) / event_batch_size);
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // the pinned staging buffer may still feed the previous upload
-  uint32_t *xy = nullptr;
-  if (!d_raw) {
+  if (!src.on_device()) {
     rc = ensure_pinned_xy(c, (size_t)n);
     if (rc) return rc;
-    xy = c->h_xy;
-    std::atomic<unsigned> out_of_range(0);
-    const unsigned W = (unsigned)c->W, H = (unsigned)c->H;
-    if (aos)  // straight from the host's records (dvs_msgs::Event): the same words, no x[] / y[] vectors in between
-      parallel_ranges(n, [&](int64_t a, int64_t b) {
-        unsigned acc = 0;
-        for (int64_t i = a; i < b; i++) {
-          const unsigned ex = aos->X(i), ey = aos->Y(i);
-          acc |= (unsigned)(ex >= W) | (unsigned)(ey >= H);
-          xy[i] = ex | (ey << 16);
-        }
-        if (acc) out_of_range = 1;
-      });
-    else
-    parallel_ranges(n, [&](int64_t a, int64_t b) {
-      unsigned acc = 0;
-      for (int64_t i = a; i < b; i++) {
-        acc |= (unsigned)(x[i] >= W) | (unsigned)(y[i] >= H);
-        xy[i] = (uint32_t)x[i] | ((uint32_t)y[i] << 16);
-      }
-      if (acc) out_of_range = 1;
+    const unsigned outside = src.view([&](const auto &v) {
+      return pack_events<false>(v, n, nb, event_batch_size, 1, (unsigned)c->W, (unsigned)c->H, 0, c->h_xy);
     });
-    if (out_of_range.load()) return check_events(c, n, x, y, t_ns, aos);  // locate and report the offender
+    if (outside) return check_events(c, src);  // locate and report the offender
   }
   rc = ensure_pinned_dts(c, (size_t)nb);
   if (rc) return rc;
   double *dts = c->h_dts;  // pinned: uploaded asynchronously below (the synchronisation above protects its reuse)
   const double tref = time_to_sec(t_ref_ns);
-  std::atomic<int> bad_batch(-1);
-  parallel_ranges(nb, [&](int64_t b0, int64_t b1) {
-    for (int64_t b = b0; b < b1; b++) {
-      const int64_t beg = b * event_batch_size;
-      const int64_t end = (beg + event_batch_size < n) ? beg + event_batch_size : n;
-      const int64_t t_first = aos ? aos->T(beg) : t_ns[beg], t_last = aos ? aos->T(end - 1) : t_ns[end - 1];
-      if (t_last < t_first) { bad_batch = (int)b; return; }
-      dts[(size_t)b] = time_to_sec(time_batch_ns(t_first, t_last)) - tref;
-    }
-  }, /*serial_below=*/4096);
-  if (bad_batch.load() >= 0) return fail(c, CMX_ERR_TIME_ORDER, "batch %d spans a negative time interval", bad_batch.load());
+  const BatchTimeError bad = src.view([&](const auto &v) {
+    return batch_times(v, n, event_batch_size, 0, nb, nullptr, [&](int64_t b, long long tb) { dts[b] = time_to_sec(tb) - tref; },
+                       /*serial_below=*/4096);
+  });
+  if (bad.kind) return fail(c, CMX_ERR_TIME_ORDER, "batch %d spans a negative time interval", (int)(bad.at / event_batch_size));
   rc = ensure(c, c->d_xy, c->xy_cap, (size_t)n);
   if (rc) return rc;
   rc = ensure(c, c->d_batch_dt, c->batch_cap, (size_t)nb);
   if (rc) return rc;
   if (n) {
-    if (d_raw) HIP_TRY(c, hipMemcpyAsync(c->d_xy, d_raw, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-    else HIP_TRY(c, hipMemcpyAsync(c->d_xy, xy, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (src.on_device()) HIP_TRY(c, hipMemcpyAsync(c->d_xy, src.d_xy, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    else HIP_TRY(c, hipMemcpyAsync(c->d_xy, c->h_xy, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     // both uploads are stream-ordered in front of everything the evaluations launch; nobody waits for them here (the 4 MB of
     // a 1M-event packet cross PCIe while the caller is already issuing the first evaluation)
     HIP_TRY(c, hipMemcpyAsync(c->d_batch_dt, dts, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -108,17 +77,16 @@ int fe_set_packet_impl(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t 
 int cmx_frontend_set_packet(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns,
                             int64_t t_ref_ns, double fx, double fy, double cx, double cy, int event_batch_size,
                             double blur_sigma, int contrast_measure) {
-  return fe_set_packet_impl(c, n, x, y, t_ns, nullptr, t_ref_ns, fx, fy, cx, cy, event_batch_size, blur_sigma, contrast_measure);
+  return fe_set_packet_impl(c, EventSource::arrays(n, x, y, t_ns), t_ref_ns, fx, fy, cx, cy, event_batch_size, blur_sigma, contrast_measure);
 }
 
 int cmx_frontend_set_packet_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout, int64_t t_ref_ns, double fx,
                                 double fy, double cx, double cy, int event_batch_size, double blur_sigma, int contrast_measure) {
   if (!c || c->kind != KIND_FE) return fail(c, CMX_ERR_STATE, "not a front-end context");
-  EvAos aos;
-  const int rc = make_aos(c, n, events, layout, &aos);
+  EventSource src;
+  const int rc = make_aos(c, n, events, layout, &src);
   if (rc) return rc;
-  return fe_set_packet_impl(c, n, nullptr, nullptr, nullptr, nullptr, t_ref_ns, fx, fy, cx, cy, event_batch_size, blur_sigma,
-                            contrast_measure, &aos);
+  return fe_set_packet_impl(c, src, t_ref_ns, fx, fy, cx, cy, event_batch_size, blur_sigma, contrast_measure);
 }
 
 // CMX_FUSE_TRACE (diagnostics): looked up during the first few hundred evaluations of the process only (tools/fuse_trace.py sets it after its warm-up)

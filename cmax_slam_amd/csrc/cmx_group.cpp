@@ -332,13 +332,6 @@ void publish(cmx_group *g) {
   }
 }
 
-void batch_range(int64_t n, int B, int rank, int world, int64_t *beg, int64_t *end) {  // cmax_slam_amd/dist.py: batch_range
-  const int64_t nb = (n + B - 1) / B, per = (nb + world - 1) / world;
-  const int64_t b0 = std::min<int64_t>((int64_t)rank * per, nb), b1 = std::min<int64_t>(b0 + per, nb);
-  *beg = std::min<int64_t>(b0 * B, n);
-  *end = std::min<int64_t>(b1 * B, n);
-}
-
 }  // namespace
 
 bool is_group(const cmx_ctx *c) { return c && c->group && c->group_rank == 0; }
@@ -597,63 +590,28 @@ int cmx_backend_create_group(cmx_ctx **out, const int *devices, int n_devices, i
 }
 
 // ---- the group forms of the entry points (called from the C ABI functions when the handle is a group's)
-int group_set_window(cmx_ctx *leader, const EvAos *aos, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, int order, int K,
-                     const double *knots_xyzw, int64_t start_ns, int64_t dt_ns, int num_fixed, int64_t t_next_win_beg_ns,
-                     int event_batch_size, int event_sample_rate, double blur_sigma, int contrast_measure, const float *IG) {
+// member r is handed the events of ITS whole batches (member_range, cmx_ingest.hpp): a range of the host's arrays or records, or
+// of the replica of the event store on its own device
+int group_set_window(cmx_ctx *leader, const EventSource &src, const WindowSpec &w) {
   cmx_group *g = leader->group;
-  const int N = g->n;
-  const bool shardable = n > 0 && event_batch_size > 0 && ((x && y && t_ns) || aos);
+  bool have = src.kind == EventSource::AOS || (src.soa.x && src.soa.y && src.soa.t);
+  if (src.on_device()) {
+    if (!src.store) return fail(leader, CMX_ERR_INVALID_ARG, "null event store");
+    for (int r = 0; r < g->n; r++)
+      if (!src.store->on(g->m[r]->device))
+        return fail(leader, CMX_ERR_INVALID_ARG, "the event store holds no replica on device %d (member %d): create it with cmx_events_create_group",
+                    g->m[r]->device, r);
+    have = true;
+  }
+  const bool shardable = src.n > 0 && w.batch > 0 && have;
   const int rc = group_all(leader, [&](cmx_ctx *m, int r) {
-    int64_t beg = 0, end = (r == 0) ? n : 0;  // bad arguments: member 0 gets them as they are and reports the error
-    if (shardable) {
-      batch_range(n, event_batch_size, r, N, &beg, &end);
-      // One event more than the member's batches hold.  The reference's loop `for (beg = 0; beg < n - 1; beg += B)` with
-      // `end = (n - beg > B) ? beg + B : n` (event_pano_warper.cpp:188-196) never opens a batch for a single trailing event;
-      // with the extra event a member's last batch is a whole one (n - beg = B + 1 > B) and the event itself is in no batch of
-      // this member -- the next member owns it.  The last member holding events sees the true tail, quirk included.
-      if (end > beg && end < n) end += 1;
-    }
-    const bool none = !shardable && r != 0;
-    if (aos) {  // the member's range of the host's records (cmx_backend_set_window_aos)
-      const EvAos mine = aos->from(none ? 0 : beg);
-      return be_set_window_impl(m, none ? 0 : end - beg, nullptr, nullptr, nullptr, nullptr, nullptr, order, K, knots_xyzw, start_ns, dt_ns,
-                                num_fixed, t_next_win_beg_ns, event_batch_size, event_sample_rate, blur_sigma, contrast_measure, IG, &mine);
-    }
-    return be_set_window_impl(m, none ? 0 : end - beg, none ? nullptr : x + beg, none ? nullptr : y + beg, none ? nullptr : t_ns + beg,
-                              nullptr, nullptr, order, K, knots_xyzw, start_ns, dt_ns, num_fixed, t_next_win_beg_ns, event_batch_size,
-                              event_sample_rate, blur_sigma, contrast_measure, IG);
+    int64_t beg = 0, end = (r == 0) ? src.n : 0;  // bad arguments: member 0 gets them as they are and reports the error
+    if (shardable) member_range(src.n, w.batch, r, g->n, &beg, &end);
+    const EventSource mine = src.from(beg, end - beg);
+    return src.on_device() ? group_member_window_from(m, mine, w) : be_set_window_impl(m, mine, w);
   });
   if (rc)  // a window one member rejected is no window: no member may walk into a collective its peers will not join
-    for (int r = 0; r < N; r++) g->m[r]->have_data = false;
-  return rc;
-}
-
-int group_member_window_from(cmx_ctx *m, const cmx_events *e, int64_t first, int64_t beg, int64_t end, int order, int K,
-                             const double *knots_xyzw, int64_t start_ns, int64_t dt_ns, int num_fixed, int64_t t_next_win_beg_ns,
-                             int event_batch_size, int event_sample_rate, double blur_sigma, int contrast_measure, const float *IG);  // cmx_events.cpp
-
-int group_set_window_from(cmx_ctx *leader, const cmx_events *e, int64_t first, int64_t count, int order, int K, const double *knots_xyzw,
-                          int64_t start_ns, int64_t dt_ns, int num_fixed, int64_t t_next_win_beg_ns, int event_batch_size,
-                          int event_sample_rate, double blur_sigma, int contrast_measure, const float *IG) {
-  cmx_group *g = leader->group;
-  const int N = g->n;
-  if (!e) return fail(leader, CMX_ERR_INVALID_ARG, "null event store");
-  for (int r = 0; r < N; r++)
-    if (!e->on(g->m[r]->device))
-      return fail(leader, CMX_ERR_INVALID_ARG, "the event store holds no replica on device %d (member %d): create it with cmx_events_create_group",
-                  g->m[r]->device, r);
-  const bool shardable = count > 0 && event_batch_size > 0;
-  const int rc = group_all(leader, [&](cmx_ctx *m, int r) {
-    int64_t beg = 0, end = (r == 0) ? count : 0;
-    if (shardable) {
-      batch_range(count, event_batch_size, r, N, &beg, &end);
-      if (end > beg && end < count) end += 1;  // (group_set_window: the member's last batch is a whole one, the extra event is in none of its batches)
-    }
-    return group_member_window_from(m, e, first, beg, end, order, K, knots_xyzw, start_ns, dt_ns, num_fixed, t_next_win_beg_ns,
-                                    event_batch_size, event_sample_rate, blur_sigma, contrast_measure, IG);
-  });
-  if (rc)
-    for (int r = 0; r < N; r++) g->m[r]->have_data = false;
+    for (int r = 0; r < g->n; r++) g->m[r]->have_data = false;
   return rc;
 }
 

@@ -103,6 +103,4 @@ void parallel_ranges(int64_t n, F fn, int64_t serial_below = 262144) {
   });
 }
 
-// argument checks only; the coordinate range is validated inside the packing pass (one sweep over the events instead
-
 }  // namespace cmx

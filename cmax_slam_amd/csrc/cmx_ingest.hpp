@@ -1,0 +1,245 @@
+// cmx_ingest.hpp -- the host side of every hand-over of events (set_packet, set_window, recon_add, events_push and their
+// _aos / _from / group forms): where the events are, how they are cut into batches, the one packing pass and the one batch-time
+// pass.  Pure host code: no HIP, no context -- tests/ingest_host.cpp builds it alone with a plain C++ compiler.
+#pragma once
+#include <atomic>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+
+#include "../../include/cmax_hip.h"
+#include "cmx_hostpool.hpp"
+
+namespace cmx {
+
+// ---- event views: element i of a range of events, whatever the host keeps them in
+struct EvSoa {
+  const uint16_t *x = nullptr, *y = nullptr;
+  const int64_t *t = nullptr;
+  unsigned X(int64_t i) const { return x[i]; }
+  unsigned Y(int64_t i) const { return y[i]; }
+  int64_t T(int64_t i) const { return t[i]; }
+  EvSoa from(int64_t first) const { return EvSoa{x + first, y + first, t + first}; }
+};
+// an array of records (cmx_aos_layout, e.g. dvs_msgs::Event)
+struct EvAos {
+  const unsigned char *base = nullptr;
+  size_t stride = 0, ox = 0, oy = 0, os = 0, on = 0;
+  unsigned X(int64_t i) const { uint16_t v; memcpy(&v, base + (size_t)i * stride + ox, 2); return v; }
+  unsigned Y(int64_t i) const { uint16_t v; memcpy(&v, base + (size_t)i * stride + oy, 2); return v; }
+  int64_t T(int64_t i) const {
+    uint32_t sec, nsec;
+    memcpy(&sec, base + (size_t)i * stride + os, 4);
+    memcpy(&nsec, base + (size_t)i * stride + on, 4);
+    return (int64_t)sec * 1000000000LL + (int64_t)nsec;
+  }
+  EvAos from(int64_t first) const { EvAos r = *this; r.base = base + (size_t)first * stride; return r; }
+};
+// the one layout check (`layout` is not null); the callers report a failure in their own words
+inline bool aos_view(const void *events, const cmx_aos_layout *layout, EvAos *out) {
+  const size_t st = layout->stride;
+  if (st < 12 || layout->off_x + 2 > st || layout->off_y + 2 > st || layout->off_sec + 4 > st || layout->off_nsec + 4 > st) return false;
+  out->base = static_cast<const unsigned char *>(events);
+  out->stride = st; out->ox = layout->off_x; out->oy = layout->off_y; out->os = layout->off_sec; out->on = layout->off_nsec;
+  return true;
+}
+
+// ---- where the n events of a hand-over are
+struct EventSource {
+  enum Kind { SOA, AOS, DEVICE } kind = SOA;
+  int64_t n = 0;
+  EvSoa soa;  // SOA; DEVICE: soa.t is the store's host mirror of the timestamps
+  EvAos aos;  // AOS
+  // DEVICE: the store and the global index of the first event; once a consumer's device is known (store_source, cmx_events.cpp)
+  // the packed events and timestamps of the replica on that device
+  const cmx_events *store = nullptr;
+  int64_t first = 0;
+  const uint32_t *d_xy = nullptr;
+  const int64_t *d_t = nullptr;
+
+  static EventSource arrays(int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t) { return EventSource{SOA, n, EvSoa{x, y, t}}; }
+  bool on_device() const { return kind == DEVICE; }
+  EventSource from(int64_t beg, int64_t count) const {  // events [beg, beg + count) of this source
+    EventSource r = *this;
+    r.n = count;
+    if (kind == SOA) r.soa = soa.from(beg);
+    if (kind == AOS) r.aos = aos.from(beg);
+    r.first = first + beg;
+    if (d_xy) { r.soa.t = soa.t + beg; r.d_xy = d_xy + beg; r.d_t = d_t + beg; }
+    return r;
+  }
+  template <typename F>
+  auto view(F f) const { return kind == AOS ? f(aos) : f(soa); }  // f(view) on the host-readable view (DEVICE: timestamps only)
+};
+
+// ---- everything of a back-end window that is not its events
+struct KnotSupport {
+  int order = 0, K = 0;
+  long long start_ns = 0, dt_ns = 0;
+};
+struct WindowSpec {
+  KnotSupport sup;
+  const double *knots;
+  int num_fixed;
+  int64_t t_next_win_beg_ns;
+  int batch, rate;
+  double sigma;
+  int measure;
+  const float *IG;
+};
+
+// ---- ros::Time arithmetic (roscpp noetic semantics), needed to reproduce the per-batch pose time:
+//   time_batch = time_first + (time_last - time_first) * 0.5         [Duration*double -> fromSec: floor + round]
+//   reference: local_image_warped_events.cpp:68-75, event_pano_warper.cpp:239-242
+inline long long time_batch_ns(long long t_first, long long t_last) {
+  const long long d = t_last - t_first;
+  long long ds = d / 1000000000LL, dn = d % 1000000000LL;
+  if (dn < 0) { dn += 1000000000LL; ds -= 1; }
+  const double half = ((double)ds + 1e-9 * (double)dn) * 0.5;
+  const long long hs = (long long)floor(half);
+  const long long hn = (long long)round((half - (double)hs) * 1e9);
+  return t_first + hs * 1000000000LL + hn;
+}
+inline double time_to_sec(long long t_ns) {  // ros::Time::toSec
+  return (double)(t_ns / 1000000000LL) + 1e-9 * (double)(t_ns % 1000000000LL);
+}
+
+// ---- the back end's batches: for (beg = 0; beg < n-1; beg += B) { end = (n-beg > B) ? beg+B : n; } -- a trailing batch holding
+// exactly the last single event is never opened (event_pano_warper.cpp:188-196); inside a batch events are taken with stride `rate`
+// restarting at the batch start (:262)
+struct BatchPlan {
+  int B = 1, rate = 1, per_batch = 1, nb = 0;
+  int64_t last_len = 0;  // events of the last batch
+  int64_t n_packed = 0;  // events the sampling selects
+  int64_t packed(int b_lo, int b_hi) const {  // ... in the batches [b_lo, b_hi)
+    const int64_t nbs = b_hi - b_lo;
+    if (nbs <= 0) return 0;
+    return b_hi == nb ? (nbs - 1) * per_batch + (last_len + rate - 1) / rate : nbs * per_batch;
+  }
+};
+inline bool plan_batches(int64_t n, int B, int rate, BatchPlan *p) {  // false: more batches than an int counts
+  *p = BatchPlan{};
+  p->B = B; p->rate = rate; p->per_batch = (B + rate - 1) / rate;
+  const int64_t nb64 = (n > 1) ? (n - 1 + B - 1) / B : 0;
+  if (nb64 > 0x7fffffffLL) return false;
+  p->nb = (int)nb64;
+  if (p->nb > 0) {
+    const int64_t last_beg = (int64_t)(p->nb - 1) * B;
+    p->last_len = (n - last_beg > B) ? B : (n - last_beg);
+    p->n_packed = p->packed(0, p->nb);
+  }
+  return true;
+}
+// the contiguous range of whole batches a group hands member `rank` (cmax_slam_amd/dist.py: batch_range)
+inline void batch_range(int64_t n, int B, int rank, int world, int64_t *beg, int64_t *end) {
+  const int64_t nb = (n + B - 1) / B, per = (nb + world - 1) / world;
+  const int64_t b0 = (int64_t)rank * per < nb ? (int64_t)rank * per : nb, b1 = b0 + per < nb ? b0 + per : nb;
+  *beg = b0 * B < n ? b0 * B : n;
+  *end = b1 * B < n ? b1 * B : n;
+}
+// ... and the events the member is handed: one event more than its batches hold.  With the extra event the member's last batch
+// is a whole one (n - beg = B + 1 > B) and the event itself is in no batch of this member -- the next member owns it.  The last
+// member holding events sees the true tail, the never-opened single-event batch included.
+inline void member_range(int64_t n, int B, int rank, int world, int64_t *beg, int64_t *end) {
+  batch_range(n, B, rank, world, beg, end);
+  if (*end > *beg && *end < n) *end += 1;
+}
+
+// ---- the packing pass.  Batch j of the n events of `v` is [j B, min(j B + B, n)); of the batches [0, nb) every rate-th event
+// from its batch's start becomes the word x | y << 16 [| (t < t_old) << 31] at out[j per_batch ...] (and its timestamp at
+// t_out, when given).  Returns non-zero when a packed event lies outside the W x H sensor.
+template <bool kOldFlag, typename View>
+inline uint32_t pack_word(const View &v, int64_t i, unsigned W, unsigned H, int64_t t_old, unsigned &outside) {
+  const unsigned ex = v.X(i), ey = v.Y(i);
+  outside |= (unsigned)(ex >= W) | (unsigned)(ey >= H);
+  uint32_t w = ex | (ey << 16);
+  if (kOldFlag) w |= (uint32_t)(v.T(i) < t_old) << 31;
+  return w;
+}
+template <bool kOldFlag, typename View>
+unsigned pack_events(const View &v, int64_t n, int64_t nb, int64_t B, int rate, unsigned W, unsigned H, int64_t t_old, uint32_t *out,
+                     int64_t *t_out = nullptr) {
+  std::atomic<unsigned> outside(0);
+  if (rate == 1) {  // flat and vectorisable: packed index == event index
+    const int64_t count = nb * B < n ? nb * B : n;
+    // (the loop's scalars and pointers by value: captured by reference they may alias the words it stores, and the loop loses its shape)
+    parallel_ranges(count, [&, W, H, t_old, out, t_out](int64_t a0, int64_t a1) {
+      unsigned acc = 0;
+      for (int64_t i = a0; i < a1; i++) {
+        out[i] = pack_word<kOldFlag>(v, i, W, H, t_old, acc);
+        if (t_out) t_out[i] = v.T(i);
+      }
+      if (acc) outside = 1;
+    });
+  } else {
+    const int64_t per_batch = (B + rate - 1) / rate;
+    parallel_ranges(nb, [&](int64_t j0, int64_t j1) {
+      unsigned acc = 0;
+      for (int64_t j = j0; j < j1; j++) {
+        const int64_t beg = j * B, end = (n - beg > B) ? beg + B : n;
+        int64_t k = j * per_batch;
+        for (int64_t i = beg; i < end; i += rate, k++) {
+          out[k] = pack_word<kOldFlag>(v, i, W, H, t_old, acc);
+          if (t_out) t_out[k] = v.T(i);
+        }
+      }
+      if (acc) outside = 1;
+    });
+  }
+  return outside.load();
+}
+
+// index of the first event outside the W x H sensor, -1 when there is none
+template <typename View>
+int64_t first_outside(const View &v, int64_t n, unsigned W, unsigned H) {
+  std::atomic<int64_t> bad(-1);
+  parallel_ranges(n, [&](int64_t a, int64_t b) {
+    unsigned acc = 0;
+    for (int64_t i = a; i < b; i++) acc |= (unsigned)(v.X(i) >= W) | (unsigned)(v.Y(i) >= H);
+    if (acc)
+      for (int64_t i = a; i < b; i++)
+        if (v.X(i) >= W || v.Y(i) >= H) {
+          int64_t cur = bad.load();
+          while ((cur < 0 || i < cur) && !bad.compare_exchange_weak(cur, i)) {}
+          break;
+        }
+  });
+  return bad.load();
+}
+
+// ---- the batch-time pass: emit(b, t_b) with t_b the midpoint (time_batch_ns) of the first and last timestamp of batch b, for b in
+// [b_lo, b_hi) of the n events of `v`.  Reports the first batch that spans a negative interval (CMX_ERR_TIME_ORDER, at = its first
+// event) or, with a knot support, whose time lies outside it (CMX_ERR_SPLINE_RANGE, at = the batch time); emits nothing for it.
+struct BatchTimeError {
+  int kind = CMX_OK;
+  long long at = -1;
+};
+template <typename View, typename Emit>
+BatchTimeError batch_times(const View &v, int64_t n, int64_t B, int64_t b_lo, int64_t b_hi, const KnotSupport *sup, Emit emit,
+                           int64_t serial_below = 262144) {
+  auto one = [&](int64_t b, long long *tb) {
+    const int64_t beg = b * B, end = (n - beg > B) ? beg + B : n;
+    const int64_t t_first = v.T(beg), t_last = v.T(end - 1);
+    if (t_last < t_first) return BatchTimeError{CMX_ERR_TIME_ORDER, (long long)beg};
+    *tb = time_batch_ns(t_first, t_last);
+    const long long st = sup ? *tb - sup->start_ns : 0;
+    if (sup && (st < 0 || st / sup->dt_ns + sup->order > sup->K)) return BatchTimeError{CMX_ERR_SPLINE_RANGE, *tb};
+    return BatchTimeError{};
+  };
+  std::atomic<int64_t> bad(-1);
+  parallel_ranges(b_hi - b_lo, [&](int64_t j0, int64_t j1) {
+    for (int64_t b = b_lo + j0; b < b_lo + j1; b++) {
+      long long tb = 0;
+      if (one(b, &tb).kind) {
+        int64_t cur = bad.load();
+        while ((cur < 0 || b < cur) && !bad.compare_exchange_weak(cur, b)) {}
+        return;
+      }
+      emit(b, tb);
+    }
+  }, serial_below);
+  long long tb = 0;
+  return bad.load() < 0 ? BatchTimeError{} : one(bad.load(), &tb);
+}
+
+}  // namespace cmx

@@ -28,9 +28,9 @@ struct ReconSlot {
 };
 
 struct ReconState {
-  int order = 0, K = 0, B = 0, rate = 0, per_batch = 0;
+  KnotSupport sup;
+  int B = 0, rate = 0, per_batch = 0;
   bool deterministic = false;
-  long long start_ns = 0, dt_ns = 0;
   double blend[kMaxOrder * kMaxOrder] = {0};
   Quat *d_knots = nullptr;
   double *d_delta = nullptr;
@@ -78,9 +78,9 @@ int recon_enter(cmx_ctx *c, bool need_begun) {
 static int recon_begin_inner(cmx_ctx *c, int order, int K, const double *knots_xyzw, int64_t start_ns, int64_t dt_ns, int B, int rate) {
   ReconState *r = new ReconState();
   c->recon = r;
-  r->order = order; r->K = K; r->B = B; r->rate = rate;
+  r->sup = KnotSupport{order, K, (long long)start_ns, (long long)dt_ns};
+  r->B = B; r->rate = rate;
   r->per_batch = (B + rate - 1) / rate;
-  r->start_ns = start_ns; r->dt_ns = dt_ns;
   r->deterministic = c->deterministic;
   blending_matrix(order, r->blend);
   const size_t np = (size_t)c->Wp * c->Hp;
@@ -130,38 +130,20 @@ int cmx_backend_recon_end(cmx_ctx *c) {
   return CMX_OK;
 }
 
-// ---- one add: batches of the call, slices of whole batches
-struct ReconCall {
-  int nb = 0;               // batches (a trailing batch holding a single event is skipped, event_pano_warper.cpp:188-196)
-  int64_t last_len = 0;     // events of the last batch
-  int64_t n_packed = 0;     // events the sampling selects
-  int slice_batches = 1;
-};
-static int recon_plan(cmx_ctx *c, const ReconState *r, int64_t n, ReconCall *p) {
-  const int B = r->B, rate = r->rate;
-  const int64_t nb64 = (n > 1) ? (n - 1 + B - 1) / B : 0;
-  if (nb64 > 0x7fffffffLL) return fail(c, CMX_ERR_INVALID_ARG, "too many batches");
-  p->nb = (int)nb64;
-  if (p->nb > 0) {
-    const int64_t last_beg = (int64_t)(p->nb - 1) * B;
-    p->last_len = (n - last_beg > B) ? B : (n - last_beg);
-    p->n_packed = (int64_t)(p->nb - 1) * r->per_batch + (p->last_len + rate - 1) / rate;
-  }
-  const int64_t sb = g_slice_events.load(std::memory_order_relaxed) / B;
-  p->slice_batches = (int)(sb < 1 ? 1 : sb);
+// ---- one add: batches of the call (plan_batches), slices of whole batches
+static int recon_plan(cmx_ctx *c, const ReconState *r, int64_t n, BatchPlan *p, int *slice_batches) {
+  if (!plan_batches(n, r->B, r->rate, p)) return fail(c, CMX_ERR_INVALID_ARG, "too many batches");
+  const int64_t sb = g_slice_events.load(std::memory_order_relaxed) / r->B;
+  *slice_batches = (int)(sb < 1 ? 1 : sb);
   return CMX_OK;
-}
-static int64_t slice_packed(const ReconState *r, const ReconCall &p, int b_lo, int b_hi) {
-  const int64_t nbs = b_hi - b_lo;
-  return b_hi == p.nb ? (nbs - 1) * r->per_batch + (p.last_len + r->rate - 1) / r->rate : nbs * r->per_batch;
 }
 
 static ReconArgs recon_args(const cmx_ctx *c, const ReconState *r) {
   ReconArgs a{};
   a.cam = be_args(c);
   a.cam.xy = nullptr; a.cam.poseR = nullptr; a.cam.poses = nullptr; a.cam.planes = nullptr;
-  a.order = r->order; a.K = r->K;
-  a.start_ns = r->start_ns; a.dt_ns = r->dt_ns;
+  a.order = r->sup.order; a.K = r->sup.K;
+  a.start_ns = r->sup.start_ns; a.dt_ns = r->sup.dt_ns;
   for (int i = 0; i < kMaxOrder * kMaxOrder; i++) a.blend[i] = r->blend[i];
   a.knots = r->d_knots; a.delta = r->d_delta;
   a.B = r->B;
@@ -205,71 +187,40 @@ static int slot_ensure(cmx_ctx *c, ReconSlot &s, size_t n_xy, size_t n_bt, bool 
 
 // host arrays (SoA, or the host's own records): validate EVERYTHING first -- a call that fails adds nothing -- then pack slice
 // i+1 on the host pool and upload it on the copy stream while the vote kernel of slice i runs
-int recon_add_host(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, const EvAos *aos) {
+int recon_add_host(cmx_ctx *c, const EventSource &src) {
   ReconState *r = c->recon;
   // argument checks + EVERY coordinate handed in inside the sensor, those the sampling or the one-event rule skip included: what
   // cmx_backend_set_window checks when it sub-samples, here at every rate (cmax_hip.h)
-  int rc = check_events(c, n, x, y, t_ns, aos);
+  int rc = check_events(c, src);
   if (rc) return rc;
-  ReconCall p;
-  rc = recon_plan(c, r, n, &p);
+  const int64_t n = src.n;
+  BatchPlan p;
+  int slice_batches = 1;
+  rc = recon_plan(c, r, n, &p, &slice_batches);
   if (rc) return rc;
   if (p.nb == 0) return CMX_OK;
-  const int B = r->B, rate = r->rate, per_batch = r->per_batch, order = r->order, K = r->K;
-  const long long start_ns = r->start_ns, dt_ns = r->dt_ns;
-  auto T = [&](int64_t i) { return aos ? aos->T(i) : t_ns[i]; };
-  {
-    std::atomic<int> err_kind(0);
-    std::atomic<long long> err_at(-1);
-    parallel_ranges(p.nb, [&](int64_t b0, int64_t b1) {
-      for (int64_t b = b0; b < b1; b++) {
-        const int64_t beg = b * B, end = (n - beg > B) ? beg + B : n;
-        const int64_t t_first = T(beg), t_last = T(end - 1);
-        if (t_last < t_first) { err_kind = CMX_ERR_TIME_ORDER; err_at = beg; return; }
-        const long long tb = time_batch_ns(t_first, t_last), st = tb - start_ns;
-        if (st < 0 || st / dt_ns + order > K) { err_kind = CMX_ERR_SPLINE_RANGE; err_at = tb; return; }
-      }
-    });
-    if (err_kind.load() == CMX_ERR_TIME_ORDER)
-      return fail(c, CMX_ERR_TIME_ORDER, "batch at event %lld spans a negative time interval", err_at.load());
-    if (err_kind.load() == CMX_ERR_SPLINE_RANGE)
-      return fail(c, CMX_ERR_SPLINE_RANGE, "batch time %lld ns outside the support of %d knots (start %lld, dt %lld)", err_at.load(), K,
-                  start_ns, dt_ns);
-  }
+  const int B = r->B;
+  const BatchTimeError bad = src.view([&](const auto &v) { return batch_times(v, n, B, 0, p.nb, &r->sup, [](int64_t, long long) {}); });
+  if (bad.kind) return fail_batch_time(c, bad, r->sup);
   ReconArgs a = recon_args(c, r);
   // From here on only a runtime error (CMX_ERR_HIP) can end the call, and slices queued before it have voted: "a call that fails
   // adds nothing" is the contract of the validation above.  The slots are left idle either way.
   auto vote_slices = [&]() -> int {
   int k = 0;
-  for (int b_lo = 0; b_lo < p.nb; b_lo += p.slice_batches, k++) {
-    const int b_hi = (p.nb - b_lo > p.slice_batches) ? b_lo + p.slice_batches : p.nb;
+  for (int b_lo = 0; b_lo < p.nb; b_lo += slice_batches, k++) {
+    const int b_hi = (p.nb - b_lo > slice_batches) ? b_lo + slice_batches : p.nb;
     const int nbs = b_hi - b_lo;
-    const int64_t ev_off = (int64_t)b_lo * B, np_s = slice_packed(r, p, b_lo, b_hi);
+    const int64_t ev_off = (int64_t)b_lo * B, np_s = p.packed(b_lo, b_hi);
     ReconSlot &s = r->slot[k & 1];
     if (s.busy) { HIP_TRY(c, hipEventSynchronize(s.done)); s.busy = false; }  // its previous slice has been voted
     rc = slot_ensure(c, s, (size_t)np_s, (size_t)nbs, true);
     if (rc) return rc;
     uint32_t *xy = s.h_xy;
     long long *bt = s.h_bt;
-    parallel_ranges(nbs, [&](int64_t j0, int64_t j1) {
-      for (int64_t j = j0; j < j1; j++) {
-        const int64_t beg = ev_off + j * B, end = (n - beg > B) ? beg + B : n;
-        bt[j] = time_batch_ns(T(beg), T(end - 1));
-        if (rate == 1) continue;  // packed below by a flat loop (packed index == event index)
-        uint32_t *dst = xy + j * per_batch;
-        for (int64_t e = beg; e < end; e += rate) *dst++ = aos ? (aos->X(e) | (aos->Y(e) << 16)) : ((uint32_t)x[e] | ((uint32_t)y[e] << 16));
-      }
+    src.view([&](const auto &v) {  // (validated above: neither pass finds anything)
+      batch_times(v, n, B, b_lo, b_hi, nullptr, [&](int64_t b, long long tb) { bt[b - b_lo] = tb; });
+      return pack_events<false>(v.from(ev_off), n - ev_off, nbs, B, r->rate, (unsigned)c->W, (unsigned)c->H, 0, xy);
     });
-    if (rate == 1)
-      parallel_ranges(np_s, [&](int64_t a0, int64_t a1) {
-        if (aos) {
-          for (int64_t e = a0; e < a1; e++) xy[e] = aos->X(ev_off + e) | (aos->Y(ev_off + e) << 16);
-        } else {
-          const uint16_t *__restrict xs = x + ev_off, *__restrict ys = y + ev_off;
-          uint32_t *__restrict out = xy;
-          for (int64_t e = a0; e < a1; e++) out[e] = (uint32_t)xs[e] | ((uint32_t)ys[e] << 16);
-        }
-      });
     HIP_TRY(c, hipMemcpyAsync(s.d_xy, xy, (size_t)np_s * sizeof(uint32_t), hipMemcpyHostToDevice, r->copy_stream));
     HIP_TRY(c, hipMemcpyAsync(s.d_bt, bt, (size_t)nbs * sizeof(long long), hipMemcpyHostToDevice, r->copy_stream));
     HIP_TRY(c, hipEventRecord(s.up, r->copy_stream));
@@ -295,42 +246,43 @@ int recon_add_host(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, 
 
 // events already on the device (event store): batch times and their validation by launch_be_batch_times, slice by slice into
 // one slice-sized table; the error words are read before the first vote kernel of the call is queued
-int recon_add_store(cmx_ctx *c, int64_t n, const uint32_t *d_raw, const int64_t *d_t) {
+int recon_add_store(cmx_ctx *c, const EventSource &src) {
   ReconState *r = c->recon;
+  const int64_t n = src.n;
   if (n < 0 || n > kMaxEvents) return fail(c, CMX_ERR_INVALID_ARG, "bad event count %lld", (long long)n);
-  ReconCall p;
-  int rc = recon_plan(c, r, n, &p);
+  BatchPlan p;
+  int slice_batches = 1;
+  int rc = recon_plan(c, r, n, &p, &slice_batches);
   if (rc) return rc;
   if (p.nb == 0) return CMX_OK;
   const int B = r->B;
   ReconSlot &s = r->slot[0];
-  rc = slot_ensure(c, s, 0, (size_t)(p.nb < p.slice_batches ? p.nb : p.slice_batches), false);
+  rc = slot_ensure(c, s, 0, (size_t)(p.nb < slice_batches ? p.nb : slice_batches), false);
   if (rc) return rc;
-  const long long *t = reinterpret_cast<const long long *>(d_t);
-  auto batch_times = [&](int b_lo, int b_hi) {
+  auto slice_times = [&](int b_lo, int b_hi, bool clear_err) {
     const int64_t ev_off = (int64_t)b_lo * B;
     const int64_t n_s = b_hi == p.nb ? n - ev_off : (int64_t)(b_hi - b_lo) * B;
-    launch_be_batch_times(t + ev_off, (long long)n_s, B, b_hi - b_lo, r->start_ns, r->dt_ns, r->order, r->K, s.d_bt, r->d_err, c->stream);
+    return queue_batch_times(c, src.d_t + ev_off, n_s, B, b_hi - b_lo, r->sup, s.d_bt, r->d_err, clear_err);
   };
-  HIP_TRY(c, hipMemsetAsync(r->d_err, 0, 2 * sizeof(long long), c->stream));
-  for (int b_lo = 0; b_lo < p.nb; b_lo += p.slice_batches)
-    batch_times(b_lo, (p.nb - b_lo > p.slice_batches) ? b_lo + p.slice_batches : p.nb);
+  for (int b_lo = 0; b_lo < p.nb && !rc; b_lo += slice_batches)
+    rc = slice_times(b_lo, (p.nb - b_lo > slice_batches) ? b_lo + slice_batches : p.nb, b_lo == 0);
+  if (rc) return rc;
   HIP_TRY(c, hipGetLastError());
-  long long e[2] = {0, 0};
-  HIP_TRY(c, hipMemcpyAsync(e, r->d_err, sizeof(e), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (e[0] == CMX_ERR_TIME_ORDER) return fail(c, CMX_ERR_TIME_ORDER, "a batch spans a negative time interval");
-  if (e[0] == CMX_ERR_SPLINE_RANGE)
-    return fail(c, CMX_ERR_SPLINE_RANGE, "batch time %lld ns outside the support of %d knots (start %lld, dt %lld)", e[1], r->K, r->start_ns,
-                r->dt_ns);
+  BatchTimeError bad;
+  rc = read_batch_errors(c, r->d_err, &bad);
+  if (rc) return rc;
+  if (bad.kind) return fail_batch_time(c, bad, r->sup, /*with_event=*/false);  // (its index would be relative to a slice)
   ReconArgs a = recon_args(c, r);
-  const bool one_slice = p.nb <= p.slice_batches;  // (its batch times are those the validation pass has just written)
-  for (int b_lo = 0; b_lo < p.nb; b_lo += p.slice_batches) {
-    const int b_hi = (p.nb - b_lo > p.slice_batches) ? b_lo + p.slice_batches : p.nb;
-    if (!one_slice) batch_times(b_lo, b_hi);
-    a.xy = d_raw + (int64_t)b_lo * B; a.stride = r->rate;
+  const bool one_slice = p.nb <= slice_batches;  // (its batch times are those the validation pass has just written)
+  for (int b_lo = 0; b_lo < p.nb; b_lo += slice_batches) {
+    const int b_hi = (p.nb - b_lo > slice_batches) ? b_lo + slice_batches : p.nb;
+    if (!one_slice) {
+      rc = slice_times(b_lo, b_hi, false);
+      if (rc) return rc;
+    }
+    a.xy = src.d_xy + (int64_t)b_lo * B; a.stride = r->rate;
     a.batch_t = s.d_bt; a.nb = b_hi - b_lo;
-    a.n = (int)slice_packed(r, p, b_lo, b_hi);
+    a.n = (int)p.packed(b_lo, b_hi);
     launch_recon_votes(a, c->stream);
   }
   HIP_TRY(c, hipGetLastError());
@@ -342,16 +294,16 @@ int recon_add_store(cmx_ctx *c, int64_t n, const uint32_t *d_raw, const int64_t 
 int cmx_backend_recon_add(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns) {
   int rc = recon_enter(c, true);
   if (rc) return rc;
-  return recon_add_host(c, n, x, y, t_ns, nullptr);
+  return recon_add_host(c, EventSource::arrays(n, x, y, t_ns));
 }
 
 int cmx_backend_recon_add_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout) {
   int rc = recon_enter(c, true);
   if (rc) return rc;
-  EvAos aos;
-  rc = make_aos(c, n, events, layout, &aos);
+  EventSource src;
+  rc = make_aos(c, n, events, layout, &src);
   if (rc) return rc;
-  return recon_add_host(c, n, nullptr, nullptr, nullptr, &aos);
+  return recon_add_host(c, src);
 }
 
 // the plane as fp32 on the device: in deterministic mode the current fixed-point sums, converted (they stay: votes may follow)
