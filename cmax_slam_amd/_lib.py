@@ -126,6 +126,13 @@ SYMBOLS = {
     "cmx_backend_recon_get": (C.c_int, [ctx_p, c_fp, c_i64p, c_i64p]),
     "cmx_backend_recon_render": (C.c_int, [ctx_p, C.c_double, c_dp, C.POINTER(C.c_uint8)]),
     "cmx_backend_recon_end": (C.c_int, [ctx_p]),
+    "cmx_backend_recon_restart": (C.c_int, [ctx_p, c_dp]),
+    "cmx_backend_recon_contrast": (C.c_int, [ctx_p, C.c_double, C.c_int, C.c_int, c_dp]),
+    "cmx_backend_recon_grad_add": (C.c_int, [ctx_p, C.c_int64, c_u16p, c_u16p, c_i64p]),
+    "cmx_backend_recon_grad_add_aos": (C.c_int, [ctx_p, C.c_int64, C.c_void_p, C.POINTER(AosLayout)]),
+    "cmx_backend_recon_grad_add_from": (C.c_int, [ctx_p, C.c_void_p, C.c_int64, C.c_int64]),
+    "cmx_backend_recon_grad_get": (C.c_int, [ctx_p, c_dp]),
+    "cmx_backend_recon_eval_from": (C.c_int, [ctx_p, C.c_void_p, C.c_int64, C.c_int64, c_dp, C.c_double, C.c_int, c_dp, c_dp]),
     "cmx_traj_temp_start_ns": (C.c_int64, [C.c_double, C.c_int, C.c_double]),
     "cmx_accum_capacity": (C.c_size_t, [ctx_p]),
     "cmx_set_accum_buffer": (C.c_int, [ctx_p, C.c_void_p, C.c_size_t]),

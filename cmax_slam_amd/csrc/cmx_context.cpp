@@ -24,6 +24,23 @@ int bind_device(cmx_ctx *c) {
 
 // c1d[q] = (G^T 1)_q for one axis of length L: taps that stay inside + the taps the forward pass reflected back
 // (see adjoint_kernel / image_adjoint_kernel).  1 in the interior; only the outer r pixels differ.
+void gt1_factors(const float *taps, int r, int L, float *out) {
+  for (int q = 0; q < L; q++) {
+    double s = 0;
+    for (int j = -r; j <= r; j++)
+      if (q - j >= 0 && q - j < L) s += (double)taps[r + j];
+    if (L > 2 * r + 1) {
+      if (1 <= q && q <= r)
+        for (int m = 0; m <= r - q; m++) s += (double)taps[r + q + m];
+      if (L - 1 - r <= q && q <= L - 2) {
+        const int d = L - 1 - q;
+        for (int m = 0; m <= r - d; m++) s += (double)taps[r + d + m];
+      }
+    }
+    out[(size_t)q] = (float)s;
+  }
+}
+
 int upload_gt1(cmx_ctx *c) {
   const int r = c->radius;
   c->Mx_radius = -1;
@@ -32,20 +49,7 @@ int upload_gt1(cmx_ctx *c) {
     const int L = axis == 0 ? c->imgW : c->imgH;
     if (L <= 0) continue;
     std::vector<float> v((size_t)L);
-    for (int q = 0; q < L; q++) {
-      double s = 0;
-      for (int j = -r; j <= r; j++)
-        if (q - j >= 0 && q - j < L) s += (double)c->taps[r + j];
-      if (L > 2 * r + 1) {
-        if (1 <= q && q <= r)
-          for (int m = 0; m <= r - q; m++) s += (double)c->taps[r + q + m];
-        if (L - 1 - r <= q && q <= L - 2) {
-          const int d = L - 1 - q;
-          for (int m = 0; m <= r - d; m++) s += (double)c->taps[r + d + m];
-        }
-      }
-      v[(size_t)q] = (float)s;
-    }
+    gt1_factors(c->taps, r, L, v.data());
     float *&dst = axis == 0 ? c->d_cx : c->d_cy;
     size_t &cap = axis == 0 ? c->cx_cap : c->cy_cap;
     int rc = ensure(c, dst, cap, (size_t)L);
@@ -88,6 +92,22 @@ int upload_gt1(cmx_ctx *c) {
 }
 
 // cv::GaussianBlur(Size(0,0), sigma) on CV_32F: ksize = cvRound(sigma*8+1)|1; fp64 kernel normalised, cast to fp32
+int blur_taps(cmx_ctx *c, double sigma, float *taps, int *radius) {  // sigma > 0
+  const int n = ((int)lrint(sigma * 4 * 2 + 1)) | 1;
+  const int r = n / 2;
+  if (r > kMaxRadius) return fail(c, CMX_ERR_INVALID_ARG, "blur_sigma %.3f needs radius %d > %d", sigma, r, kMaxRadius);
+  double t[2 * kMaxRadius + 1], sum = 0;
+  const double scale2X = -0.5 / (sigma * sigma);
+  for (int i = 0; i < n; i++) {
+    const double x = i - (n - 1) * 0.5;
+    t[i] = exp(scale2X * x * x);
+    sum += t[i];
+  }
+  sum = 1. / sum;
+  for (int i = 0; i < n; i++) taps[i] = (float)(t[i] * sum);
+  *radius = r;
+  return CMX_OK;
+}
 int setup_blur(cmx_ctx *c, double sigma) {
   // same sigma as last time (the image size of a context never changes): taps, G^T 1 factors and operator tables are on the
   // device already -- a packet / window no longer pays four to six synchronous table uploads
@@ -101,18 +121,9 @@ int setup_blur(cmx_ctx *c, double sigma) {
     if (!rc0) c->blur_sigma_built = sigma;
     return rc0;
   }
-  const int n = ((int)lrint(sigma * 4 * 2 + 1)) | 1;
-  const int r = n / 2;
-  if (r > kMaxRadius) return fail(c, CMX_ERR_INVALID_ARG, "blur_sigma %.3f needs radius %d > %d", sigma, r, kMaxRadius);
-  double t[2 * kMaxRadius + 1], sum = 0;
-  const double scale2X = -0.5 / (sigma * sigma);
-  for (int i = 0; i < n; i++) {
-    const double x = i - (n - 1) * 0.5;
-    t[i] = exp(scale2X * x * x);
-    sum += t[i];
-  }
-  sum = 1. / sum;
-  for (int i = 0; i < n; i++) c->taps[i] = (float)(t[i] * sum);
+  int r = 0;
+  const int rcb = blur_taps(c, sigma, c->taps, &r);
+  if (rcb) return rcb;
   c->radius = r;
   const int rc1 = upload_gt1(c);
   if (!rc1) c->blur_sigma_built = sigma;

@@ -377,6 +377,8 @@ int ensure(cmx_ctx *c, T *&ptr, size_t &cap, size_t need) {
 int bind_device(cmx_ctx *c);
 int comm_probe_exchange(cmx_ctx *c, float *in, float *out, size_t count);  // cmx_comm.cpp
 int upload_gt1(cmx_ctx *c);
+void gt1_factors(const float *taps, int r, int L, float *out);  // (G^T 1) of one axis of length L: the factors upload_gt1 uploads
+int blur_taps(cmx_ctx *c, double sigma, float *taps, int *radius);  // the taps setup_blur builds for sigma > 0 (CMX_ERR_INVALID_ARG beyond kMaxRadius)
 int setup_blur(cmx_ctx *c, double sigma);
 hipEvent_t get_event(cmx_ctx *c);
 void collect_spans(cmx_ctx *c);  // call after the stream has been synchronised
@@ -477,8 +479,8 @@ int be_eval_one(cmx_ctx *c, const double *drotv, double *contrast, double *grad)
 
 // ---- cmx_reconstruct.cpp: the bodies behind cmx_backend_recon_add[_aos] and _add_from (events on the host / in the event store)
 int recon_enter(cmx_ctx *c, bool need_begun);  // front door of every cmx_backend_recon_*: plain back-end context, not a group, begun; binds the device
-int recon_add_host(cmx_ctx *c, const EventSource &src);
-int recon_add_store(cmx_ctx *c, const EventSource &src);
+int recon_add_host(cmx_ctx *c, const EventSource &src, bool grad = false);  // grad: the gradient pass (recon_grad_add*) over the same events
+int recon_add_store(cmx_ctx *c, const EventSource &src, bool grad = false);
 int recon_diag_slice_events(int n);  // CMX_DIAG_RECON_SLICE_EVENTS (cmax_hip_diag.h)
 void recon_release(cmx_ctx *c);  // frees whatever a reconstruction holds (cmx_backend_recon_end, cmx_destroy)
 

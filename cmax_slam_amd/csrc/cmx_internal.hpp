@@ -453,6 +453,30 @@ void launch_recon_delta(const Quat *knots, int K, double *delta, hipStream_t s);
 void launch_recon_votes(const ReconArgs &a, hipStream_t s);
 void launch_recon_fixed_to_float(const unsigned long long *fixed, float *plane, size_t n, hipStream_t s);  // non-destructive
 
+// whole-trajectory contrast and gradient (cmx_backend_recon_contrast / _grad_add*): the second pass over the events of a
+// reconstruction.  One launch per slice, the run structure of the vote kernel; per workgroup the batches' V / U sums go through
+// their 3 x 3N spline Jacobians into sums over the knot window [s0, s0 + kReconWindow) the workgroup's batches touch.
+constexpr int kReconWindow = kReconMaxRun + 2 + kMaxOrder;  // knots a workgroup's sums cover (batches beyond it add for themselves)
+struct ReconGatherArgs {
+  ReconArgs ev;              // events, batches, spline: as for the votes (plane / fixed / n_inside are not used)
+  const float *itilde;       // G^T (G I) of the plane
+  const float *cx, *cy;      // G^T 1 factors
+  int r;
+  double *gsum;              // [2][3K]: S1 then S2, added to
+  unsigned long long *n_voted;  // events that passed the vote test in this gradient pass
+  // deterministic mode: workgroup g stores its window (first knot, knots) and its 2 x 3 kReconWindow sums as row g, and
+  // launch_recon_gather_rows adds the rows to gsum workgroup by workgroup; null = fp64 atomics on gsum
+  double *rows;
+  int *row_win;              // [workgroups][2]
+};
+int recon_gather_blocks(const ReconArgs &a);
+void launch_recon_gather(const ReconGatherArgs &g, hipStream_t s);
+void launch_recon_gather_rows(const ReconGatherArgs &g, int blocks, hipStream_t s);
+// contrast and mean of the blurred plane from the image pass's two moment rows ([2][nblk], the first *nvalid entries of each when
+// nvalid is set), summed in index order: out[0] = contrast, out[1] = mu
+void launch_recon_moments_finalize(const double *partials, int nblk, const unsigned *nvalid, double npix, int measure, double *out,
+                                   hipStream_t s);
+
 // global-map upkeep (once per window)
 void launch_update_map(float *IG, const float *IL_old, const unsigned char *visits, int npix, int max_update_times,
                        hipStream_t s);

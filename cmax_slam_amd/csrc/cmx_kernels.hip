@@ -1613,27 +1613,7 @@ void launch_image_adjoint(const ImgAdjArgs &a, hipStream_t s, hipEvent_t t0, hip
 }
 
 // ---------------------------------------------------------------------------------------------- gather passes
-// d(contrast)/d(theta_k) = (2/N) sum_events [ r0_k * dJt/dx(at the event) + r1_k * dJt/dy ] where the
-// bilinear-interpolation derivatives are exactly the signed-weight sums the reference scatters into its derivative
-// images (local_image_warped_events.cpp:163-166, event_pano_warper.cpp:327-330).
-__device__ __forceinline__ void bilinear_grad(const float *it, int W, int xx, int yy, float dx, float dy, float &A, float &B) {
-  const float *q = it + (size_t)yy * W + xx;
-  const float i00 = q[0], i01 = q[1], i10 = q[W], i11 = q[W + 1];
-  A = (1.f - dy) * (i01 - i00) + dy * (i11 - i10);
-  B = (1.f - dx) * (i10 - i00) + dx * (i11 - i01);
-}
-
-// the same two directional derivatives of the separable plane c(x,y) = cx[x]*cy[y] (= G^T 1); zero away from the border
-__device__ __forceinline__ void border_grad(const float *cx, const float *cy, int W, int H, int r, int xx, int yy, float dx,
-                                            float dy, float &A, float &B) {
-  A = 0.f;
-  B = 0.f;
-  if (xx <= r || xx + 1 >= W - 1 - r || yy <= r || yy + 1 >= H - 1 - r) {
-    const float c00 = cx[xx] * cy[yy], c01 = cx[xx + 1] * cy[yy], c10 = cx[xx] * cy[yy + 1], c11 = cx[xx + 1] * cy[yy + 1];
-    A = (1.f - dy) * (c01 - c00) + dy * (c11 - c10);
-    B = (1.f - dx) * (c10 - c00) + dx * (c11 - c01);
-  }
-}
+// (bilinear_grad / border_grad, the two directional derivatives every gather takes at a vote cell: cmx_warp.hpp)
 
 int gather_blocks(int n) {
   int blocks = (n + 255) / 256;

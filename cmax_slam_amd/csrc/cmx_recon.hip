@@ -139,4 +139,333 @@ void launch_recon_fixed_to_float(const unsigned long long *fixed, float *plane, 
   hipLaunchKernelGGL(recon_fixed_to_float_kernel, dim3((unsigned)blocks), dim3(256), 0, s, fixed, plane, n);
 }
 
+// ---------------------------------------------------------------------------------------------- contrast and gradient
+// recon_gather   the SECOND pass over a slice's events (cmx_backend_recon_grad_add*), one launch per slice with the run structure of
+//                recon_votes: batch poses into LDS, then all lanes walk the run's events with be_warp_math<2>, take the two
+//                directional differences of Jt = G^T (G I) (and of G^T 1 next to the border) at the vote cell and reduce
+//                V = (A, B) dpm_ddrot and U per batch -- the segmented shuffle of be_gather_kernel inside the wave, LDS across waves.
+//                After the walk one lane per batch evaluates the batch's 3 x 3N spline Jacobian (So3Spline<N>::evaluate, the
+//                arithmetic of spline_eval<N, true>, rounded to fp32 as Trajectory::evaluate hands it on), multiplies V and U
+//                through it block by block and stores the 2 x 3N columns in LDS; then one lane per knot PARAMETER of the
+//                workgroup's knot window sums the columns that fall on it in batch order -- no atomics inside the workgroup --
+//                and adds its two sums to gsum: one global fp64 atomic per (workgroup, parameter touched), or, in
+//                deterministic mode, one row per workgroup that recon_gather_rows adds workgroup by workgroup.
+//                A batch whose segment lies outside the window (a run spanning more than kReconWindow knot intervals: a gap
+//                in the recording) adds its columns to gsum itself, with atomics in both modes.
+// recon_moments_finalize   contrast and mean from the image pass's moment rows, summed in index order by one workgroup
+
+__device__ __forceinline__ int recon_segment(const ReconArgs &a, long long t_ns) {
+  long long s = (t_ns - a.start_ns) / a.dt_ns;
+  const long long s_max = (long long)a.K - a.order;
+  return (int)(s < 0 ? 0 : (s > s_max ? s_max : s));  // (validated before the launch; the clamp keeps a bad one inside the tables)
+}
+
+// emit(k, J_k): the N blocks d_val_d_knot[s + k] of So3Spline<N>::evaluate at t_ns, in the order spline_eval<N, true> forms them
+template <int N, typename Emit>
+__device__ __forceinline__ void recon_pose_jac(const ReconArgs &a, long long t_ns, int s, Emit emit) {
+  const long long st = t_ns - a.start_ns;
+  const double u = (double)(st % a.dt_ns) / (double)a.dt_ns;
+  double p[N], coeff[N];
+  p[0] = 1.0;
+  double ti = u;
+#pragma unroll
+  for (int j = 1; j < N; j++) { p[j] = 1.0 * ti; ti = ti * u; }
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    double c = 0;
+#pragma unroll
+    for (int j = 0; j < N; j++) c += a.blend[i * N + j] * p[j];
+    coeff[i] = c;
+  }
+  Quat res = a.knots[s];
+  Mat3 Jh;
+#pragma unroll
+  for (int i = 0; i < 9; i++) Jh.m[i] = (i % 4 == 0) ? 1.0 : 0.0;
+#pragma unroll
+  for (int i = 0; i < N - 1; i++) {
+    const Quat p0 = a.knots[s + i];
+    const double *d = a.delta + 3 * (size_t)(s + i);
+    const double k = coeff[i + 1];
+    const double delta[3] = {d[0], d[1], d[2]}, kdelta[3] = {d[0] * k, d[1] * k, d[2] * k};
+    const Mat3 Jinv = left_jacobian_inv(delta);
+    const Mat3 Jk = left_jacobian(kdelta);
+    Mat3 Jb = Jh;
+    Mat3 T = q_to_R(res);
+#pragma unroll
+    for (int c = 0; c < 9; c++) T.m[c] = k * T.m[c];
+    T = m3_mul(T, Jk);
+    T = m3_mul(T, Jinv);
+    Jh = m3_mul(T, q_to_R(q_conj(p0)));
+#pragma unroll
+    for (int c = 0; c < 9; c++) Jb.m[c] -= Jh.m[c];
+    emit(i, Jb);
+    res = q_mul(res, so3_exp(kdelta[0], kdelta[1], kdelta[2]));
+  }
+  emit(N - 1, Jh);
+}
+
+__device__ __forceinline__ void recon_gsum_add(double *p, double v) {
+  if (v != 0.0) __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+constexpr int kReconWinParams = 3 * kReconWindow;
+static_assert(kReconWinParams <= 4 * kReconThreads, "four knot parameters per lane cover a workgroup's window");
+
+template <int N, bool DET>
+__global__ __launch_bounds__(kReconThreads) void recon_gather_kernel(const ReconGatherArgs g) {
+  constexpr int kCols = 3 * N;
+  constexpr int kChunk = 512 / N;  // batches per Jacobian round: their 2 x 3N columns are 24 KB of LDS
+  constexpr int kPoseD = (kReconMaxRun + 2) * 9, kColD = kChunk * 2 * kCols;
+  __shared__ double sh_u[kPoseD > kColD ? kPoseD : kColD];  // batch rotations during the walk, the rounds' columns after it
+  __shared__ double sh_vu[(kReconMaxRun + 2) * 6];          // per batch: V (3), U (3)
+  __shared__ int sh_off[kChunk];                             // per batch of a round: first parameter in the window, or none
+  __shared__ int sh_s0;
+  __shared__ unsigned sh_inside;
+  const ReconArgs &a = g.ev;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int e0 = blockIdx.x * a.run;  // (the grid covers [0, n): e0 < n)
+  const int e1 = (a.n - e0 > a.run) ? e0 + a.run : a.n;
+  const int b0 = e0 / a.per_batch;
+  int nbw = (e1 - 1) / a.per_batch - b0 + 1;
+  if (nbw > kReconMaxRun + 2) nbw = kReconMaxRun + 2;  // (cannot happen with run = recon_run(per_batch))
+  if (tid == 0) { sh_inside = 0; sh_s0 = 0x7fffffff; }
+  __syncthreads();
+  for (int j = tid; j < nbw; j += kReconThreads) {
+    const int b = b0 + j < a.nb ? b0 + j : a.nb - 1;
+    const long long t = a.batch_t[b];
+    recon_pose<N>(a, t, sh_u + 9 * j);
+    atomicMin(&sh_s0, recon_segment(a, t));
+  }
+  for (int j = tid; j < nbw * 6; j += kReconThreads) sh_vu[j] = 0.0;
+  __syncthreads();
+
+  unsigned inside = 0;
+  int cur = -1;
+  double R[9];
+  for (int base = e0; base < e1; base += kReconThreads) {  // (uniform trip count: the deterministic form has barriers)
+    const int i = base + tid;
+    double V0 = 0, V1 = 0, V2 = 0, U0 = 0, U1 = 0, U2 = 0;
+    int j = -1;
+    if (i < e1) {
+      const int b = i / a.per_batch;
+      j = b - b0;
+      j = j < nbw ? j : nbw - 1;
+      if (j != cur) {
+#pragma unroll
+        for (int c = 0; c < 9; c++) R[c] = sh_u[9 * j + c];
+        cur = j;
+      }
+      const size_t src = a.stride ? (size_t)b * a.B + (size_t)(i - b * a.per_batch) * a.stride : (size_t)i;
+      const uint32_t e = a.xy[src] & 0x7fffffffu;
+      const int ex = e & 0xffff, ey = e >> 16;
+      double v0, v1, v2;
+      load_bearing(a.cam, ex, ey, v0, v1, v2);
+      const BeWarp w = be_warp_math<2>(a.cam, e, b, v0, v1, v2, R);
+      if (w.ok) {
+        inside++;
+        float A, B;
+        bilinear_grad(g.itilde, a.cam.Wp, w.xx, w.yy, w.dx, w.dy, A, B);
+        V0 = (double)A * (double)w.m[0] + (double)B * (double)w.m[3];
+        V1 = (double)A * (double)w.m[1] + (double)B * (double)w.m[4];
+        V2 = (double)A * (double)w.m[2] + (double)B * (double)w.m[5];
+        float Ac, Bc;
+        border_grad(g.cx, g.cy, a.cam.Wp, a.cam.Hp, g.r, w.xx, w.yy, w.dx, w.dy, Ac, Bc);
+        if (Ac != 0.f || Bc != 0.f) {  // rare: votes within r of the panorama border
+          U0 = (double)Ac * (double)w.m[0] + (double)Bc * (double)w.m[3];
+          U1 = (double)Ac * (double)w.m[1] + (double)Bc * (double)w.m[4];
+          U2 = (double)Ac * (double)w.m[2] + (double)Bc * (double)w.m[5];
+        }
+      }
+    }
+    const bool any_u = __any(U0 != 0.0 || U1 != 0.0 || U2 != 0.0);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const double t0 = __shfl_down(V0, o, 64), t1 = __shfl_down(V1, o, 64), t2 = __shfl_down(V2, o, 64);
+      const int jo = __shfl_down(j, o, 64);
+      const bool same = lane + o < 64 && jo == j;
+      if (same) { V0 += t0; V1 += t1; V2 += t2; }
+      if (any_u) {  // wave-uniform
+        const double u0 = __shfl_down(U0, o, 64), u1 = __shfl_down(U1, o, 64), u2 = __shfl_down(U2, o, 64);
+        if (same) { U0 += u0; U1 += u1; U2 += u2; }
+      }
+    }
+    const int jprev = __shfl_up(j, 1, 64);
+    const bool head = j >= 0 && (lane == 0 || jprev != j);  // (one head per batch and wave: distinct LDS cells within a wave)
+    double *dst = sh_vu + 6 * (j < 0 ? 0 : j);
+    if (!DET) {
+      if (head) {
+        atomicAdd(dst + 0, V0); atomicAdd(dst + 1, V1); atomicAdd(dst + 2, V2);
+        if (any_u) { atomicAdd(dst + 3, U0); atomicAdd(dst + 4, U1); atomicAdd(dst + 5, U2); }
+      }
+    } else {
+      // deterministic mode: the waves add one after the other, walk step by walk step
+      for (int w = 0; w < kReconThreads / 64; w++) {
+        if (head && wave == w) {
+          dst[0] += V0; dst[1] += V1; dst[2] += V2;
+          dst[3] += U0; dst[4] += U1; dst[5] += U2;
+        }
+        __syncthreads();
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) inside += __shfl_down(inside, off, 64);
+  if (lane == 0 && inside) atomicAdd(&sh_inside, inside);
+
+  // ---- per batch: V, U through the batch's spline Jacobian; per knot parameter of the window: the sum over the batches on it
+  const size_t P = 3 * (size_t)a.K;
+  double acc1[4] = {0, 0, 0, 0}, acc2[4] = {0, 0, 0, 0};
+  for (int c0 = 0; c0 < nbw; c0 += kChunk) {
+    __syncthreads();  // the walk (or the previous round) is done with sh_u; sh_vu and sh_s0 are complete
+    const int s0 = sh_s0;
+    const int j = c0 + tid;
+    if (tid < kChunk) {
+      int off = -(1 << 28);
+      if (j < nbw) {
+        const double *vu = sh_vu + 6 * j;
+        const double V0 = vu[0], V1 = vu[1], V2 = vu[2], U0 = vu[3], U1 = vu[4], U2 = vu[5];
+        const bool has_u = U0 != 0.0 || U1 != 0.0 || U2 != 0.0;
+        if (V0 != 0.0 || V1 != 0.0 || V2 != 0.0 || has_u) {
+          const int b = b0 + j < a.nb ? b0 + j : a.nb - 1;
+          const long long t = a.batch_t[b];
+          const int s = recon_segment(a, t);
+          const bool in_win = s - s0 + N <= kReconWindow;
+          if (in_win) off = 3 * (s - s0);
+          double *col = sh_u + (size_t)tid * 2 * kCols;
+          recon_pose_jac<N>(a, t, s, [&](int k, const Mat3 &Jb) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+              const double j0 = (double)(float)Jb.m[c], j1 = (double)(float)Jb.m[3 + c], j2 = (double)(float)Jb.m[6 + c];
+              const double c1 = V0 * j0 + V1 * j1 + V2 * j2;
+              const double c2 = has_u ? U0 * j0 + U1 * j1 + U2 * j2 : 0.0;
+              if (in_win) {
+                col[3 * k + c] = c1;
+                col[kCols + 3 * k + c] = c2;
+              } else {
+                const size_t q = 3 * (size_t)(s + k) + c;
+                recon_gsum_add(g.gsum + q, c1);
+                recon_gsum_add(g.gsum + P + q, c2);
+              }
+            }
+          });
+        }
+      }
+      sh_off[tid] = off;
+    }
+    __syncthreads();
+    const int nj = nbw - c0 < kChunk ? nbw - c0 : kChunk;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int p = tid + q * kReconThreads;
+      if (p < kReconWinParams) {
+        for (int jj = 0; jj < nj; jj++) {
+          const int d = p - sh_off[jj];
+          if (d >= 0 && d < kCols) {
+            acc1[q] += sh_u[(size_t)jj * 2 * kCols + d];
+            acc2[q] += sh_u[(size_t)jj * 2 * kCols + kCols + d];
+          }
+        }
+      }
+    }
+  }
+  const int s0 = sh_s0;
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int p = tid + q * kReconThreads;
+    if (p < kReconWinParams) {
+      if (DET) {
+        g.rows[((size_t)blockIdx.x * 2 + 0) * kReconWinParams + p] = acc1[q];
+        g.rows[((size_t)blockIdx.x * 2 + 1) * kReconWinParams + p] = acc2[q];
+      } else {
+        const size_t kp = 3 * (size_t)s0 + p;
+        if (kp < P) {
+          recon_gsum_add(g.gsum + kp, acc1[q]);
+          recon_gsum_add(g.gsum + P + kp, acc2[q]);
+        }
+      }
+    }
+  }
+  if (tid == 0) {
+    if (DET) g.row_win[blockIdx.x] = s0;
+    if (sh_inside) atomicAdd(g.n_voted, (unsigned long long)sh_inside);  // (every wave's add precedes the rounds' first barrier)
+  }
+}
+
+int recon_gather_blocks(const ReconArgs &a) {
+  if (a.n <= 0 || a.nb <= 0) return 0;
+  return (int)(((long long)a.n + a.run - 1) / a.run);  // (a.n <= 2^30: cmx_reconstruct.cpp)
+}
+void launch_recon_gather(const ReconGatherArgs &g, hipStream_t s) {
+  const int blocks = recon_gather_blocks(g.ev);
+  if (blocks <= 0) return;
+  const dim3 gr((unsigned)blocks), b(kReconThreads);
+  if (g.ev.order == 2) {
+    if (g.rows) hipLaunchKernelGGL((recon_gather_kernel<2, true>), gr, b, 0, s, g);
+    else hipLaunchKernelGGL((recon_gather_kernel<2, false>), gr, b, 0, s, g);
+  } else {
+    if (g.rows) hipLaunchKernelGGL((recon_gather_kernel<4, true>), gr, b, 0, s, g);
+    else hipLaunchKernelGGL((recon_gather_kernel<4, false>), gr, b, 0, s, g);
+  }
+}
+
+// deterministic mode: gsum[p] += sum over the launch's workgroups, in workgroup order, of the row entries that fall on parameter p.
+// One lane per parameter of the knot range the rows cover (a slice of time-ordered events covers few knots); every lane walks
+// all the rows' windows.
+__global__ __launch_bounds__(256) void recon_gather_rows_kernel(const double *rows, const int *row_win, int blocks, double *gsum, int K) {
+  __shared__ int sh_lo, sh_hi;
+  if (threadIdx.x == 0) { sh_lo = 0x7fffffff; sh_hi = -1; }
+  __syncthreads();
+  int lo = 0x7fffffff, hi = -1;
+  for (int w = threadIdx.x; w < blocks; w += 256) {
+    const int s = row_win[w];
+    lo = s < lo ? s : lo;
+    hi = s > hi ? s : hi;
+  }
+  atomicMin(&sh_lo, lo);
+  atomicMax(&sh_hi, hi);
+  __syncthreads();
+  const long long P = 3LL * K;
+  const long long p_lo = 3LL * sh_lo;
+  long long p_hi = 3LL * sh_hi + kReconWinParams;
+  p_hi = p_hi < P ? p_hi : P;
+  for (long long p = p_lo + (long long)blockIdx.x * 256 + threadIdx.x; p < p_hi; p += (long long)gridDim.x * 256) {
+    double a1 = 0, a2 = 0;
+    for (int w = 0; w < blocks; w++) {
+      const long long d = p - 3LL * row_win[w];
+      if (d >= 0 && d < kReconWinParams) {
+        a1 += rows[((size_t)w * 2 + 0) * kReconWinParams + d];
+        a2 += rows[((size_t)w * 2 + 1) * kReconWinParams + d];
+      }
+    }
+    gsum[p] += a1;
+    gsum[P + p] += a2;
+  }
+}
+void launch_recon_gather_rows(const ReconGatherArgs &g, int blocks, hipStream_t s) {
+  if (blocks <= 0 || !g.rows) return;
+  hipLaunchKernelGGL(recon_gather_rows_kernel, dim3(64), dim3(256), 0, s, g.rows, g.row_win, blocks, g.gsum, g.ev.K);
+}
+
+__global__ __launch_bounds__(256) void recon_moments_finalize_kernel(const double *partials, int nblk, const unsigned *nvalid, double npix,
+                                                                     int measure, double *out) {
+  __shared__ double sh[2][256];
+  const int n = nvalid ? (int)(*nvalid < (unsigned)nblk ? *nvalid : (unsigned)nblk) : nblk;
+  double s0 = 0, s1 = 0;
+  for (int i = threadIdx.x; i < n; i += 256) { s0 += partials[i]; s1 += partials[(size_t)nblk + i]; }
+  sh[0][threadIdx.x] = s0;
+  sh[1][threadIdx.x] = s1;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t0 = 0, t1 = 0;
+    for (int i = 0; i < 256; i++) { t0 += sh[0][i]; t1 += sh[1][i]; }
+    double mu;
+    out[0] = contrast_from_sums(t0, t1, npix, measure, &mu);
+    out[1] = mu;
+  }
+}
+void launch_recon_moments_finalize(const double *partials, int nblk, const unsigned *nvalid, double npix, int measure, double *out,
+                                   hipStream_t s) {
+  hipLaunchKernelGGL(recon_moments_finalize_kernel, dim3(1), dim3(256), 0, s, partials, nblk, nvalid, npix, measure, out);
+}
+
 }  // namespace cmx

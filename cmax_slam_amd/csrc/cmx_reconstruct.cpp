@@ -2,6 +2,10 @@
 // count.  One call of recon_add* is the vote loop of EventWarper::computeImageOfWarpedEvents (event_pano_warper.cpp:188-196,
 // :233-311) over exactly the events handed in, added into a plane that belongs to the reconstruction alone: no old / new split, no
 // alpha, no IG, no blur, and nothing of the window state, the resident evaluation point, the map or the exchange sets is touched.
+// On top of it, the whole-trajectory contrast and its gradient with respect to a left increment of EVERY control pose
+// (recon_contrast, recon_grad_add*, recon_grad_get, recon_eval_from): the image pass over the plane and a second pass over the same
+// events, in the adjoint form of the window path -- per batch one 3-vector through the 3 x 3N spline Jacobian,
+// so nothing grows with the knot count but the 2 x 3K sums.
 // Kernels: cmx_recon.hip.
 #include "cmx_context.hpp"
 
@@ -41,6 +45,25 @@ struct ReconState {
   int64_t n_sampled = 0;
   hipStream_t copy_stream = nullptr;      // uploads of slice i+1 beside the vote kernel of slice i
   ReconSlot slot[2];
+  // ---- contrast and gradient (all of it the reconstruction's own: the context's blur state and image buffers are not touched)
+  double sigma_built = -1.0;              // sigma the taps / G^T 1 factors below were built for (-1: none)
+  int radius = 0;
+  float taps[2 * kMaxRadius + 1] = {1.f};
+  float *d_cx = nullptr, *d_cy = nullptr; // G^T 1 = cx(x) cy(y), Wp and Hp floats
+  unsigned char *d_tflags = nullptr;      // tile occupancy of the plane (launch_tile_flags)
+  unsigned *d_tile_list = nullptr, *d_tile_count = nullptr;  // large panoramas: the image passes' work list, in tile order
+  double *d_partials = nullptr;           // [2][tiles] moment rows of the image pass
+  double *d_cm = nullptr;                 // contrast, mu (recon_moments_finalize)
+  float *d_jt = nullptr;                  // Jt = G^T (G plane), allocated at the first want_grad
+  double *d_gsum = nullptr;               // [2][3K]: S1, S2, allocated at the first want_grad
+  unsigned long long *d_voted = nullptr;  // events that passed the vote test in the gradient pass
+  double *d_rows = nullptr;               // deterministic mode: one row of window sums per gather workgroup of a slice ...
+  int *d_row_win = nullptr;               // ... and the rows' first knots
+  size_t rows_cap = 0;                    // (workgroups)
+  bool grad_open = false;                 // a gradient pass is open: recon_contrast(want_grad) ran and nothing voted since
+  int64_t g_sampled = 0;                  // events the gradient pass has sampled
+  int measure = CMX_VARIANCE;
+  double mu = 0;
 };
 
 void recon_release(cmx_ctx *c) {
@@ -63,6 +86,18 @@ void recon_release(cmx_ctx *c) {
   (void)hipFree(r->d_fixed);
   (void)hipFree(r->d_inside);
   (void)hipFree(r->d_err);
+  (void)hipFree(r->d_cx);
+  (void)hipFree(r->d_cy);
+  (void)hipFree(r->d_tflags);
+  (void)hipFree(r->d_tile_list);
+  (void)hipFree(r->d_tile_count);
+  (void)hipFree(r->d_partials);
+  (void)hipFree(r->d_cm);
+  (void)hipFree(r->d_jt);
+  (void)hipFree(r->d_gsum);
+  (void)hipFree(r->d_voted);
+  (void)hipFree(r->d_rows);
+  (void)hipFree(r->d_row_win);
   delete r;
   c->recon = nullptr;
 }
@@ -155,6 +190,45 @@ static ReconArgs recon_args(const cmx_ctx *c, const ReconState *r) {
   return a;
 }
 
+// the gradient pass's view of the same launch: the events and the spline of recon_args, Jt and the border factors, the sums
+static ReconGatherArgs recon_gather_args(const cmx_ctx *c, const ReconState *r) {
+  ReconGatherArgs g{};
+  g.ev = recon_args(c, r);
+  g.itilde = r->d_jt;
+  g.cx = r->d_cx; g.cy = r->d_cy; g.r = r->radius;
+  g.gsum = r->d_gsum;
+  g.n_voted = r->d_voted;
+  return g;
+}
+
+// first thing of every pass over events: a vote pass closes an open gradient pass, a gradient pass needs one
+static int recon_pass_enter(cmx_ctx *c, ReconState *r, bool grad) {
+  if (!grad) { r->grad_open = false; return CMX_OK; }
+  if (!r->grad_open) return fail(c, CMX_ERR_STATE, "no gradient pass is open (cmx_backend_recon_contrast with want_grad, and no add since)");
+  return CMX_OK;
+}
+
+// one slice of the gradient pass; deterministic mode: the workgroups' rows, then their sum in workgroup order
+static int queue_gather(cmx_ctx *c, ReconState *r, ReconGatherArgs &g) {
+  const int blocks = recon_gather_blocks(g.ev);
+  if (blocks <= 0) return CMX_OK;
+  if (r->deterministic) {
+    if ((size_t)blocks > r->rows_cap) {
+      HIP_TRY(c, hipStreamSynchronize(c->stream));  // (an earlier slice may still be reading the rows)
+      (void)hipFree(r->d_rows); (void)hipFree(r->d_row_win);
+      r->d_rows = nullptr; r->d_row_win = nullptr; r->rows_cap = 0;
+      HIP_TRY(c, hipMalloc((void **)&r->d_rows, (size_t)blocks * 2 * 3 * kReconWindow * sizeof(double)));
+      HIP_TRY(c, hipMalloc((void **)&r->d_row_win, (size_t)blocks * sizeof(int)));
+      r->rows_cap = (size_t)blocks;
+    }
+    g.rows = r->d_rows;
+    g.row_win = r->d_row_win;
+  }
+  launch_recon_gather(g, c->stream);
+  launch_recon_gather_rows(g, blocks, c->stream);
+  return CMX_OK;
+}
+
 // staging of one slot.  The host paths (pinned) hold packed events and batch times in pinned memory and on the device; the store
 // path reads the store's events in place and forms the batch times on the device, so it holds the device table alone.
 static int slot_ensure(cmx_ctx *c, ReconSlot &s, size_t n_xy, size_t n_bt, bool pinned) {
@@ -187,8 +261,9 @@ static int slot_ensure(cmx_ctx *c, ReconSlot &s, size_t n_xy, size_t n_bt, bool 
 
 // host arrays (SoA, or the host's own records): validate EVERYTHING first -- a call that fails adds nothing -- then pack slice
 // i+1 on the host pool and upload it on the copy stream while the vote kernel of slice i runs
-int recon_add_host(cmx_ctx *c, const EventSource &src) {
+int recon_add_host(cmx_ctx *c, const EventSource &src, bool grad) {
   ReconState *r = c->recon;
+  if (int rc0 = recon_pass_enter(c, r, grad)) return rc0;
   // argument checks + EVERY coordinate handed in inside the sensor, those the sampling or the one-event rule skip included: what
   // cmx_backend_set_window checks when it sub-samples, here at every rate (cmax_hip.h)
   int rc = check_events(c, src);
@@ -202,7 +277,8 @@ int recon_add_host(cmx_ctx *c, const EventSource &src) {
   const int B = r->B;
   const BatchTimeError bad = src.view([&](const auto &v) { return batch_times(v, n, B, 0, p.nb, &r->sup, [](int64_t, long long) {}); });
   if (bad.kind) return fail_batch_time(c, bad, r->sup);
-  ReconArgs a = recon_args(c, r);
+  ReconGatherArgs ga = recon_gather_args(c, r);
+  ReconArgs &a = ga.ev;
   // From here on only a runtime error (CMX_ERR_HIP) can end the call, and slices queued before it have voted: "a call that fails
   // adds nothing" is the contract of the validation above.  The slots are left idle either way.
   auto vote_slices = [&]() -> int {
@@ -228,7 +304,9 @@ int recon_add_host(cmx_ctx *c, const EventSource &src) {
     a.xy = s.d_xy; a.stride = 0;
     a.batch_t = s.d_bt; a.nb = nbs;
     a.n = (int)np_s;
-    launch_recon_votes(a, c->stream);
+    if (grad) rc = queue_gather(c, r, ga);
+    else launch_recon_votes(a, c->stream);
+    if (rc) return rc;
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(s.done, c->stream));
     s.busy = true;
@@ -240,14 +318,15 @@ int recon_add_host(cmx_ctx *c, const EventSource &src) {
   if (rc) { (void)hipStreamSynchronize(r->copy_stream); (void)hipStreamSynchronize(c->stream); }
   r->slot[0].busy = r->slot[1].busy = false;
   if (rc) return rc;
-  r->n_sampled += p.n_packed;
+  (grad ? r->g_sampled : r->n_sampled) += p.n_packed;
   return CMX_OK;
 }
 
 // events already on the device (event store): batch times and their validation by launch_be_batch_times, slice by slice into
 // one slice-sized table; the error words are read before the first vote kernel of the call is queued
-int recon_add_store(cmx_ctx *c, const EventSource &src) {
+int recon_add_store(cmx_ctx *c, const EventSource &src, bool grad) {
   ReconState *r = c->recon;
+  if (int rc0 = recon_pass_enter(c, r, grad)) return rc0;
   const int64_t n = src.n;
   if (n < 0 || n > kMaxEvents) return fail(c, CMX_ERR_INVALID_ARG, "bad event count %lld", (long long)n);
   BatchPlan p;
@@ -272,7 +351,8 @@ int recon_add_store(cmx_ctx *c, const EventSource &src) {
   rc = read_batch_errors(c, r->d_err, &bad);
   if (rc) return rc;
   if (bad.kind) return fail_batch_time(c, bad, r->sup, /*with_event=*/false);  // (its index would be relative to a slice)
-  ReconArgs a = recon_args(c, r);
+  ReconGatherArgs ga = recon_gather_args(c, r);
+  ReconArgs &a = ga.ev;
   const bool one_slice = p.nb <= slice_batches;  // (its batch times are those the validation pass has just written)
   for (int b_lo = 0; b_lo < p.nb; b_lo += slice_batches) {
     const int b_hi = (p.nb - b_lo > slice_batches) ? b_lo + slice_batches : p.nb;
@@ -283,18 +363,20 @@ int recon_add_store(cmx_ctx *c, const EventSource &src) {
     a.xy = src.d_xy + (int64_t)b_lo * B; a.stride = r->rate;
     a.batch_t = s.d_bt; a.nb = b_hi - b_lo;
     a.n = (int)p.packed(b_lo, b_hi);
-    launch_recon_votes(a, c->stream);
+    if (grad) rc = queue_gather(c, r, ga);
+    else launch_recon_votes(a, c->stream);
+    if (rc) return rc;
   }
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  r->n_sampled += p.n_packed;
+  (grad ? r->g_sampled : r->n_sampled) += p.n_packed;
   return CMX_OK;
 }
 
 int cmx_backend_recon_add(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns) {
   int rc = recon_enter(c, true);
   if (rc) return rc;
-  return recon_add_host(c, EventSource::arrays(n, x, y, t_ns));
+  return recon_add_host(c, EventSource::arrays(n, x, y, t_ns), false);
 }
 
 int cmx_backend_recon_add_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout) {
@@ -303,7 +385,196 @@ int cmx_backend_recon_add_aos(cmx_ctx *c, int64_t n, const void *events, const c
   EventSource src;
   rc = make_aos(c, n, events, layout, &src);
   if (rc) return rc;
-  return recon_add_host(c, src);
+  return recon_add_host(c, src, false);
+}
+
+int cmx_backend_recon_grad_add(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  return recon_add_host(c, EventSource::arrays(n, x, y, t_ns), true);
+}
+
+int cmx_backend_recon_grad_add_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  EventSource src;
+  rc = make_aos(c, n, events, layout, &src);
+  if (rc) return rc;
+  return recon_add_host(c, src, true);
+}
+
+int cmx_backend_recon_grad_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  EventSource src;
+  rc = store_source(c, e, first, count, &src);
+  if (rc) return rc;
+  return recon_add_store(c, src, true);
+}
+
+// new knot values for the trajectory of begin; plane, counters and gradient state start over.  Nothing is allocated or freed.
+int cmx_backend_recon_restart(cmx_ctx *c, const double *knots_xyzw) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (!knots_xyzw) return fail(c, CMX_ERR_INVALID_ARG, "null knot array");
+  ReconState *r = c->recon;
+  const size_t np = (size_t)c->Wp * c->Hp;
+  r->grad_open = false;
+  r->n_sampled = 0;
+  HIP_TRY(c, hipMemcpyAsync(r->d_knots, knots_xyzw, (size_t)r->sup.K * sizeof(Quat), hipMemcpyHostToDevice, c->stream));
+  launch_recon_delta(r->d_knots, r->sup.K, r->d_delta, c->stream);
+  HIP_TRY(c, hipMemsetAsync(r->d_plane, 0, np * sizeof(float), c->stream));
+  HIP_TRY(c, hipMemsetAsync(r->d_inside, 0, sizeof(unsigned long long), c->stream));
+  if (r->d_fixed) HIP_TRY(c, hipMemsetAsync(r->d_fixed, 0, np * sizeof(unsigned long long), c->stream));
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller's knot array is free again
+  return CMX_OK;
+}
+
+static void recon_refresh_plane(cmx_ctx *c, ReconState *r);
+
+// taps and G^T 1 factors of the reconstruction for this sigma (setup_blur's, in buffers of its own)
+static int recon_setup_blur(cmx_ctx *c, ReconState *r, double sigma) {
+  if (r->sigma_built == sigma && sigma >= 0) return CMX_OK;
+  int radius = 0;
+  float taps[2 * kMaxRadius + 1] = {1.f};
+  if (sigma > 0) {
+    const int rc = blur_taps(c, sigma, taps, &radius);
+    if (rc) return rc;
+  }
+  r->sigma_built = -1.0;
+  r->grad_open = false;  // (an open gradient pass was made for the other sigma's Jt and border factors)
+  r->radius = radius;
+  memcpy(r->taps, taps, sizeof(taps));
+  if (!r->d_cx) HIP_TRY(c, hipMalloc((void **)&r->d_cx, (size_t)c->Wp * sizeof(float)));
+  if (!r->d_cy) HIP_TRY(c, hipMalloc((void **)&r->d_cy, (size_t)c->Hp * sizeof(float)));
+  std::vector<float> vx((size_t)c->Wp), vy((size_t)c->Hp);
+  gt1_factors(taps, radius, c->Wp, vx.data());
+  gt1_factors(taps, radius, c->Hp, vy.data());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // (nothing queued reads the factors any more)
+  HIP_TRY(c, hipMemcpy(r->d_cx, vx.data(), vx.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(r->d_cy, vy.data(), vy.size() * sizeof(float), hipMemcpyHostToDevice));
+  r->sigma_built = sigma;
+  return CMX_OK;
+}
+
+// The image pass over the plane as accumulated so far: contrast of GaussianBlur(plane, sigma), and with want_grad
+// Jt = G^T (G plane) for the gradient pass it opens.  The plane is read only.
+int cmx_backend_recon_contrast(cmx_ctx *c, double blur_sigma, int contrast_measure, int want_grad, double *contrast) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (!contrast) return fail(c, CMX_ERR_INVALID_ARG, "null output");
+  if (!std::isfinite(blur_sigma)) return fail(c, CMX_ERR_INVALID_ARG, "blur_sigma is not finite");
+  ReconState *r = c->recon;
+  rc = recon_setup_blur(c, r, blur_sigma);
+  if (rc) return rc;
+  const int W = c->Wp, H = c->Hp, rad = r->radius;
+  const size_t np = (size_t)W * H;
+  if (want_grad && !(W > 2 * rad + 1 && H > 2 * rad + 1))
+    return fail(c, CMX_ERR_INVALID_ARG, "panorama %d x %d too small for the adjoint gradient at blur radius %d", W, H, rad);
+  ImgAdjArgs ia{};
+  ImgArgs &a = ia.img;
+  a.W = W; a.H = H; a.r = rad;
+  memcpy(a.taps, r->taps, sizeof(a.taps));
+  a.src_a = r->d_plane;
+  a.P = 0;
+  a.tiles_x = (W + kTileX - 1) / kTileX;
+  a.tiles_y = (H + kTileY - 1) / kTileY;
+  a.nblk = a.tiles_x * a.tiles_y;
+  if (!r->d_tflags) HIP_TRY(c, hipMalloc((void **)&r->d_tflags, (size_t)a.nblk));
+  if (!r->d_partials) HIP_TRY(c, hipMalloc((void **)&r->d_partials, 2 * (size_t)a.nblk * sizeof(double)));
+  if (!r->d_cm) HIP_TRY(c, hipMalloc((void **)&r->d_cm, 2 * sizeof(double)));
+  if (a.nblk > kTileListMin && !r->d_tile_list) {
+    HIP_TRY(c, hipMalloc((void **)&r->d_tile_list, (2 * (size_t)a.nblk + 8) * sizeof(unsigned)));  // list + dense scratch (launch_tile_list)
+    HIP_TRY(c, hipMalloc((void **)&r->d_tile_count, 2 * sizeof(unsigned)));
+  }
+  if (want_grad) {
+    if (!r->d_jt) {  // tiles the image pass skips keep whatever they held: finite from the start
+      HIP_TRY(c, hipMalloc((void **)&r->d_jt, np * sizeof(float)));
+      HIP_TRY(c, hipMemsetAsync(r->d_jt, 0, np * sizeof(float), c->stream));
+    }
+    if (!r->d_gsum) HIP_TRY(c, hipMalloc((void **)&r->d_gsum, 2 * 3 * (size_t)r->sup.K * sizeof(double)));
+    if (!r->d_voted) HIP_TRY(c, hipMalloc((void **)&r->d_voted, sizeof(unsigned long long)));
+  }
+  recon_refresh_plane(c, r);
+  HIP_TRY(c, hipMemsetAsync(r->d_tflags, 0, (size_t)a.nblk, c->stream));
+  launch_tile_flags(r->d_plane, W, H, r->d_tflags, c->stream);
+  a.flags_cur = r->d_tflags;
+  a.partials = r->d_partials;
+  if (r->d_tile_list) {  // tile order: the order the moment rows are summed in does not depend on the run
+    launch_tile_list(a, want_grad ? 2 * rad : rad, r->d_tile_list, r->d_tile_count, r->d_tile_count + 1, /*ordered=*/true, c->stream);
+    a.tile_list = r->d_tile_list;
+    a.tile_count = r->d_tile_count;
+  }
+  if (want_grad) {
+    ia.jt = r->d_jt;
+    launch_image_adjoint(ia, c->stream);
+  } else {
+    launch_image_moments(a, c->stream);
+  }
+  launch_recon_moments_finalize(r->d_partials, a.nblk, a.tile_count, (double)np, contrast_measure, r->d_cm, c->stream);
+  double cm[2] = {0, 0};
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(cm, r->d_cm, sizeof(cm), hipMemcpyDeviceToHost, c->stream));
+  if (want_grad) {
+    HIP_TRY(c, hipMemsetAsync(r->d_gsum, 0, 2 * 3 * (size_t)r->sup.K * sizeof(double), c->stream));
+    HIP_TRY(c, hipMemsetAsync(r->d_voted, 0, sizeof(unsigned long long), c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  *contrast = cm[0];
+  if (want_grad) {
+    r->mu = cm[1];
+    r->measure = contrast_measure;
+    r->g_sampled = 0;
+    r->grad_open = true;
+  }
+  return CMX_OK;
+}
+
+// grad = (2/N)(S1 - mu S2) once the gradient pass has seen exactly the plane's events
+int cmx_backend_recon_grad_get(cmx_ctx *c, double *grad) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (!grad) return fail(c, CMX_ERR_INVALID_ARG, "null output");
+  ReconState *r = c->recon;
+  if (!r->grad_open) return fail(c, CMX_ERR_STATE, "no gradient pass is open");
+  unsigned long long cnt[2] = {0, 0};
+  HIP_TRY(c, hipMemcpyAsync(&cnt[0], r->d_inside, sizeof(cnt[0]), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&cnt[1], r->d_voted, sizeof(cnt[1]), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (r->g_sampled != r->n_sampled || cnt[0] != cnt[1])
+    return fail(c, CMX_ERR_STATE, "the gradient pass saw %lld sampled / %llu voting events, the plane holds %lld / %llu: feed it the same events in the same cuts",
+                (long long)r->g_sampled, cnt[1], (long long)r->n_sampled, cnt[0]);
+  const size_t P = 3 * (size_t)r->sup.K;
+  std::vector<double> s(2 * P);
+  HIP_TRY(c, hipMemcpy(s.data(), r->d_gsum, 2 * P * sizeof(double), hipMemcpyDeviceToHost));
+  const double N = (double)c->Wp * (double)c->Hp, mu = r->measure == CMX_MEAN_SQUARE ? 0.0 : r->mu;
+  for (size_t k = 0; k < P; k++) grad[k] = 2.0 * (s[k] - (mu != 0.0 ? mu * s[P + k] : 0.0)) / N;
+  return CMX_OK;
+}
+
+// restart (when knots are given) + add_from + contrast + (grad_add_from + grad_get): the form an optimiser calls per trial point
+int cmx_backend_recon_eval_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count, const double *knots_xyzw, double blur_sigma,
+                                int contrast_measure, double *contrast, double *grad) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (!contrast) return fail(c, CMX_ERR_INVALID_ARG, "null output");
+  ReconState *r = c->recon;
+  if (grad) {  // (before anything is changed: the one argument error the later steps would find)
+    rc = recon_setup_blur(c, r, blur_sigma);
+    if (rc) return rc;
+    if (!(c->Wp > 2 * r->radius + 1 && c->Hp > 2 * r->radius + 1))
+      return fail(c, CMX_ERR_INVALID_ARG, "panorama %d x %d too small for the adjoint gradient at blur radius %d", c->Wp, c->Hp, r->radius);
+  }
+  EventSource src;
+  rc = store_source(c, e, first, count, &src);
+  if (rc) return rc;
+  if (knots_xyzw) rc = cmx_backend_recon_restart(c, knots_xyzw);
+  if (!rc) rc = recon_add_store(c, src, false);
+  if (!rc) rc = cmx_backend_recon_contrast(c, blur_sigma, contrast_measure, grad != nullptr, contrast);
+  if (!rc && grad) rc = recon_add_store(c, src, true);
+  if (!rc && grad) rc = cmx_backend_recon_grad_get(c, grad);
+  return rc;
 }
 
 // the plane as fp32 on the device: in deterministic mode the current fixed-point sums, converted (they stay: votes may follow)

@@ -581,10 +581,13 @@ class BackendEvaluator(_Evaluator):
                                              v.ctypes.data_as(C.POINTER(C.c_uint8)) if v is not None else None))
 
     # --- whole-trajectory reconstruction (cmx_backend_recon_*): all events along the final spline, any knot count
+    _recon_K = 0  # knots of the last reconstruct_begin (0: none yet -- the library reports the state error)
+
     def reconstruct_begin(self, order, knots_xyzw, start_ns, dt_ns, event_batch_size=100, event_sample_rate=1):
         """Start a reconstruction along the spline (order 2 | 4, K >= order knots, no upper bound on K): zeroes a plane that
         belongs to the reconstruction alone and records the current deterministic setting.  A second call starts over."""
         k = _c(knots_xyzw, np.float64).reshape(-1, 4)
+        self._recon_K = k.shape[0]
         self._ck(self._L.cmx_backend_recon_begin(self._ctx, int(order), k.shape[0], _dp(k), int(start_ns), int(dt_ns),
                                                  int(event_batch_size), int(event_sample_rate)))
 
@@ -624,6 +627,85 @@ class BackendEvaluator(_Evaluator):
 
     def reconstruct_end(self):
         self._ck(self._L.cmx_backend_recon_end(self._ctx))
+
+    # --- whole-trajectory contrast and gradient on top of an open reconstruction (cmx_backend_recon_contrast .. _eval_from)
+    def reconstruct_restart(self, knots_xyzw):
+        """New knot values for the spline of reconstruct_begin (same K); plane, counters and gradient state start over."""
+        k = _c(knots_xyzw, np.float64).reshape(-1, 4)
+        if self._recon_K and k.shape[0] != self._recon_K:
+            raise ValueError("restart takes the %d knots of begin, got %d" % (self._recon_K, k.shape[0]))
+        self._ck(self._L.cmx_backend_recon_restart(self._ctx, _dp(k)))
+
+    def reconstruct_contrast(self, sigma=1.0, measure=VARIANCE, want_grad=False):
+        """Contrast of GaussianBlur(plane, sigma) over the plane as accumulated so far; want_grad opens a gradient pass
+        (reconstruct_grad_add* over the same events in the same cuts, then reconstruct_grad_get)."""
+        out = C.c_double()
+        self._ck(self._L.cmx_backend_recon_contrast(self._ctx, float(sigma), int(measure), 1 if want_grad else 0, C.byref(out)))
+        return out.value
+
+    def reconstruct_grad_add(self, x, y, t_ns):
+        x, y, t = _c(x, np.uint16), _c(y, np.uint16), _c(t_ns, np.int64)
+        if not (len(x) == len(y) == len(t)):
+            raise ValueError("x, y, t_ns must have equal length")
+        self._ck(self._L.cmx_backend_recon_grad_add(self._ctx, len(x), x.ctypes.data_as(c_u16p), y.ctypes.data_as(c_u16p),
+                                                    t.ctypes.data_as(c_i64p)))
+
+    def reconstruct_grad_add_aos(self, events):
+        ev = np.ascontiguousarray(events)
+        lay = _lib.aos_layout_of(ev)
+        self._ck(self._L.cmx_backend_recon_grad_add_aos(self._ctx, len(ev), ev.ctypes.data_as(C.c_void_p), C.byref(lay)))
+
+    def reconstruct_grad_add_from(self, store, first, count):
+        self._ck(self._L.cmx_backend_recon_grad_add_from(self._ctx, store._h, int(first), int(count)))
+
+    def reconstruct_grad_get(self):
+        """d(contrast) / d(left increment of every control pose): 3K doubles."""
+        g = np.empty(3 * self._recon_K, np.float64)
+        self._ck(self._L.cmx_backend_recon_grad_get(self._ctx, _dp(g)))
+        return g
+
+    def reconstruct_eval(self, store, first, count, knots=None, sigma=1.0, measure=VARIANCE, want_grad=True):
+        """restart (when knots are given) + add_from + contrast [+ grad_add_from + grad_get] in one call: (contrast, grad | None)."""
+        k = None
+        if knots is not None:
+            k = _c(knots, np.float64).reshape(-1, 4)
+            if self._recon_K and k.shape[0] != self._recon_K:
+                raise ValueError("eval takes the %d knots of begin, got %d" % (self._recon_K, k.shape[0]))
+        out = C.c_double()
+        g = np.empty(3 * self._recon_K, np.float64) if want_grad else None
+        self._ck(self._L.cmx_backend_recon_eval_from(self._ctx, store._h, int(first), int(count), _dp(k) if k is not None else None,
+                                                     float(sigma), int(measure), C.byref(out), _dp(g) if want_grad else None))
+        return out.value, g
+
+    def reconstruct_refine(self, store, first, count, order, knots, start_ns, dt_ns, num_fixed, sigma=1.0, measure=VARIANCE,
+                           event_batch_size=100, event_sample_rate=1, **solver_kw):
+        """One bundle adjustment over the whole recording: FR-CG (the back end's constants unless given) over a left increment
+        of every control pose but the first num_fixed, cost = -contrast of the panorama of events_[first, first+count).
+        Returns (knots, report)."""
+        from . import solver
+        k0 = np.array(_c(knots, np.float64).reshape(-1, 4), copy=True)
+        K = k0.shape[0]
+        nf = int(num_fixed)
+        if not 0 <= nf < K:
+            raise ValueError("num_fixed must be in [0, K)")
+        kw = dict(solver.BACKEND)
+        kw.update(solver_kw)
+
+        def moved(x):
+            k = k0.copy()
+            self._ck(self._L.cmx_traj_incremental_update(K, _dp(k), nf, int(x.size), _dp(_c(x, np.float64))))
+            return k
+
+        def fdf(x, want_grad):
+            c, g = self.reconstruct_eval(store, first, count, moved(x), sigma, measure, want_grad)
+            return -c, (-g[3 * nf:] if want_grad else None)
+
+        self.reconstruct_begin(order, k0, start_ns, dt_ns, event_batch_size, event_sample_rate)
+        try:
+            x, rep = solver.frcg_minimize(fdf, np.zeros(3 * (K - nf)), **kw)
+        finally:
+            self.reconstruct_end()
+        return moved(x), rep
 
     def reconstruct(self, x, y, t_ns, order, knots_xyzw, start_ns, dt_ns, **kw):
         """begin + one add + get + end: the panorama of these events along this spline."""

@@ -73,16 +73,43 @@ def write_display_images(fe, be, ang_vel, pose, prefix, gamma=0.75):
     return paths
 
 
-def reconstruct_panorama(be, traj, x, y, t, prm, store=None):
+def _support_range(traj, t):
+    """[first, last) of the events inside the knot support of the trajectory"""
+    t_hi = traj.t_beg_ns + (traj.size() - traj.order + 1) * traj.dt_ns
+    return int(np.searchsorted(t, traj.t_beg_ns, side="left")), int(np.searchsorted(t, t_hi, side="left"))
+
+
+def refine_trajectory(be, traj, x, y, t, prm, store=None):
+    """One bundle adjustment over the WHOLE recording, the step a rotational event SLAM ends with once the sliding windows have
+    passed: FR-CG over every control pose but the first order - 1 (a common rotation of all of them is a gauge freedom of the
+    contrast), cost = -contrast of the panorama of all events along the trajectory: BackendEvaluator.reconstruct_refine
+    (cmx_backend_recon_eval_from).  Returns (refined knots, report); the report carries contrast_before / contrast_after."""
+    i0, i1 = _support_range(traj, t)
+    own = store is None
+    if own:  # (the evaluation reads its events from a device-resident store)
+        store = evaluator.EventStore(be.W, be.H, max(i1 - i0, 1))
+        store.push(x[i0:i1], y[i0:i1], t[i0:i1])
+        i0, i1 = 0, i1 - i0
+    try:
+        knots, rep = be.reconstruct_refine(store, i0, i1 - i0, traj.order, traj.knots, traj.t_beg_ns, traj.dt_ns, traj.order - 1,
+                                           sigma=prm.backend_blur_sigma, event_batch_size=prm.event_batch_size,
+                                           event_sample_rate=prm.backend_event_sample_rate)
+    finally:
+        if own:
+            store.close()
+    rep = dict(rep, contrast_before=-rep["initial_cost"], contrast_after=-rep["final_cost"], events=i1 - i0)
+    return knots, rep
+
+
+def reconstruct_panorama(be, traj, x, y, t, prm, store=None, knots=None):
     """All events inside the support of the refined trajectory, re-warped along the WHOLE of it (any number of control poses)
     into one panorama: BackendEvaluator.reconstruct_* (cmx_backend_recon_*).  Leaves the evaluator's window and map untouched.
     This function calls reconstruct_begin and adds the events, and returns with the reconstruction OPEN: the caller reads it with
     be.reconstruct_get() and / or be.reconstruct_render(), then closes it with be.reconstruct_end().
+    knots: control poses to warp along instead of the trajectory's own (refine_trajectory's).
     Returns (first event, event count)."""
-    t_hi = traj.t_beg_ns + (traj.size() - traj.order + 1) * traj.dt_ns  # end of the knot support
-    i0 = int(np.searchsorted(t, traj.t_beg_ns, side="left"))
-    i1 = int(np.searchsorted(t, t_hi, side="left"))
-    be.reconstruct_begin(traj.order, traj.knots, traj.t_beg_ns, traj.dt_ns, event_batch_size=prm.event_batch_size,
+    i0, i1 = _support_range(traj, t)
+    be.reconstruct_begin(traj.order, traj.knots if knots is None else knots, traj.t_beg_ns, traj.dt_ns, event_batch_size=prm.event_batch_size,
                          event_sample_rate=prm.backend_event_sample_rate)
     if store is not None:
         be.reconstruct_add_from(store, i0, i1 - i0)
@@ -91,11 +118,13 @@ def reconstruct_panorama(be, traj, x, y, t, prm, store=None):
     return i0, i1 - i0
 
 
-def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefix=None, reconstruct=False):
+def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefix=None, reconstruct=False, refine_global=False):
     """stream: synth.EventStream (or anything with x, y, t_ns, W, H, fx, fy, cx, cy, lut).  Returns a dict.
     display_prefix: write the final panorama with the last pose's FOV and the last packet's local-IWE pair there.
     reconstruct: after the last window, re-warp all events along the whole refined trajectory (res["recon"]; with
-    display_prefix also <prefix>_recon.pgm)."""
+    display_prefix also <prefix>_recon.pgm).
+    refine_global: after the last window, one bundle adjustment over the whole trajectory (res["refined_knots"],
+    res["refine_report"]); the trajectory in res["traj"] stays the sliding windows' -- reconstruct then warps along the refined knots."""
     prm = prm or Params()
     x, y, t = stream.x, stream.y, stream.t_ns
     n_total = len(t)
@@ -248,9 +277,17 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
             log("display images: %s, %s" % paths)
     res = dict(ang_vel_t=av_t, ang_vel=av_w, traj=traj, dead_reckoning=dead_reckoning, IG=be.getIG(),
                reports=reports, fe_ms=fe_ms, be_ms=be_ms, windows=count_window)
+    if refine_global and traj.size() >= traj.order:
+        t0 = time.perf_counter()
+        res["refined_knots"], res["refine_report"] = refine_trajectory(be, traj, x, y, t, prm, store)
+        if log:
+            r = res["refine_report"]
+            log("global refinement: %d events, %d control poses, %d iterations (%d f, %d df) in %.2f ms; contrast %.6g -> %.6g" %
+                (r["events"], traj.size(), r["iterations"], r["n_f"], r["n_df"], (time.perf_counter() - t0) * 1e3,
+                 r["contrast_before"], r["contrast_after"]))
     if reconstruct and traj.size() >= traj.order:
         t0 = time.perf_counter()
-        _, n_rec = reconstruct_panorama(be, traj, x, y, t, prm, store)
+        _, n_rec = reconstruct_panorama(be, traj, x, y, t, prm, store, res.get("refined_knots"))
         res["recon"], n_sampled, n_inside = be.reconstruct_get(with_counts=True)
         if log:
             log("reconstruction: %d events along %d control poses in %.2f ms (%d sampled, %d voted)" %
@@ -317,6 +354,8 @@ def main():
                     help="write PREFIX_pano.ppm (final panorama, last pose's FOV) and PREFIX_local_iwe.pgm (one local-IWE pair)")
     ap.add_argument("--reconstruct", action="store_true",
                     help="after the last window, re-warp ALL events along the whole refined trajectory (with --display: PREFIX_recon.pgm)")
+    ap.add_argument("--refine-global", action="store_true",
+                    help="after the last window, one bundle adjustment over the whole trajectory (--reconstruct then uses its result)")
     a = ap.parse_args()
     stream = synth.event_stream(a.rate, a.seconds, 240, 180, 200.0, 200.0, 119.5, 89.5, omega_mean=(0.2, 1.8, 0.3),
                                 omega_amp=(1.0, 0.8, 1.0))
@@ -324,7 +363,8 @@ def main():
     prm.spline_degree = a.degree
     prm.deterministic = a.deterministic
     t0 = time.perf_counter()
-    res = run_pipeline(stream, prm, use_event_store=not a.host_events, log=print, display_prefix=a.display, reconstruct=a.reconstruct)
+    res = run_pipeline(stream, prm, use_event_store=not a.host_events, log=print, display_prefix=a.display, reconstruct=a.reconstruct,
+                       refine_global=a.refine_global)
     wall = time.perf_counter() - t0
     m = evaluate_against_truth(stream, res)
     print("%.2f s of events (%d) processed in %.2f s wall" % (a.seconds, len(stream.x), wall))
@@ -333,6 +373,12 @@ def main():
     print("refined trajectory orientation error: rms %.3f deg, max %.3f deg" % (m["ba_err_deg_rms"], m["ba_err_deg_max"]))
     print("map: %d x %d, %.0f%% of pixels touched" % (res["IG"].shape[1], res["IG"].shape[0],
                                                        100.0 * float((res["IG"] > 0).mean())))
+    if "refined_knots" in res:
+        r = res["refine_report"]
+        res["traj"].knots = res["refined_knots"]
+        m2 = evaluate_against_truth(stream, res)
+        print("global refinement: contrast %.6g -> %.6g; orientation error rms %.3f deg -> %.3f deg" %
+              (r["contrast_before"], r["contrast_after"], m["ba_err_deg_rms"], m2["ba_err_deg_rms"]))
     if "recon" in res:
         print("reconstruction along the whole trajectory: %.0f votes, %.0f%% of pixels touched" %
               (float(res["recon"].sum(dtype=np.float64)), 100.0 * float((res["recon"] > 0).mean())))

@@ -344,6 +344,44 @@ int cmx_backend_recon_add_from(cmx_ctx *ctx, const cmx_events *ev, int64_t first
 int cmx_backend_recon_get(cmx_ctx *ctx, float *pano /* Hp*Wp or NULL */, int64_t *n_sampled, int64_t *n_inside /* either may be NULL */);
 int cmx_backend_recon_render(cmx_ctx *ctx, double gamma, const double fov_quat_xyzw[4] /* or NULL */, unsigned char *out);
 int cmx_backend_recon_end(cmx_ctx *ctx);
+/* Whole-trajectory contrast and its gradient with respect to a LEFT increment of every control pose, on top of an open
+ * reconstruction -- the evaluation one bundle adjustment over the whole recording needs, for a spline of any knot count:
+ *     recon_begin   recon_add*(events) ...   recon_contrast(want_grad)   recon_grad_add*(the same events) ...   recon_grad_get
+ * With the plane holding one vote loop over events E along knots q, contrast is the contrast of GaussianBlur(plane, blur_sigma) and
+ * grad[3k + c] what the back end's global_contrast_fdf returns for num_fixed = 0, zero increments, an all-zero map (alpha = 0) and
+ * every event on one side of the old / new split: cmx_backend_set_window(num_fixed = 0, IG = NULL) + cmx_backend_eval(0), without
+ * the 64-knot limit.  contrast_measure: CMX_VARIANCE, CMX_MEAN_SQUARE, anything else = variance; N = Wp * Hp.  The gradient is
+ * formed the adjoint way: Jt = G^T (G plane), per event the two directional differences of Jt at its vote cell times
+ * d(pixel)/d(rotation), summed per batch, through the batch's 3 x 3N spline Jacobian onto the N knots it touches;
+ * grad = (2/N)(S1 - mu S2) with the border term S2 accumulated apart.
+ *   restart    new knot values (K x 4, xyzw) for the spline description, batch size, sample rate and deterministic setting of begin;
+ *              zeroes the plane, both counters and any gradient state; allocates and frees nothing (once per trial point).
+ *   contrast   the image pass over the plane as accumulated so far; never changes the plane (add* may follow).  Every panorama size
+ *              and every blur_sigma cmx_backend_set_window accepts (CMX_ERR_INVALID_ARG beyond radius 12).  want_grad != 0: Jt stays
+ *              resident, the gradient sums are zeroed and a gradient pass is OPEN; CMX_ERR_INVALID_ARG when Wp <= 2r+1 or Hp <= 2r+1
+ *              (r = blur radius: the folded G^T needs single reflections; there is no derivative-plane fallback for 3K planes).
+ *              Taps, G^T 1 factors, Jt and the moment rows belong to the reconstruction: the window's blur state and image buffers
+ *              are not touched.  A cost-only call leaves an open pass open unless it changes blur_sigma.
+ *   grad_add*  the SECOND pass over the same events, in the same calls and cuts as the add* calls (batches start at each call's
+ *              first event).  Validation and status codes of add*; a call that fails validation adds nothing.  Same internal slices
+ *              and staging.  CMX_ERR_STATE without an open pass; begin, restart and every add* close it.
+ *   grad_get   grad = 3K doubles.  CMX_ERR_STATE unless the pass's sampled count and voted count both equal the plane's n_sampled /
+ *              n_inside (other events or other cuts were fed).  May be called repeatedly.
+ *   eval_from  restart (knots_xyzw != NULL) + add_from + contrast + (grad != NULL: grad_add_from + grad_get) in one call.
+ *   end        also frees Jt, the image-pass scratch and the 2 x 3K gradient sums (allocated at the first want_grad).
+ * All of them return CMX_ERR_STATE before begin and on a group handle.
+ * CMX_OPT_DETERMINISTIC = 1 at begin: contrast and gradient are bitwise identical from run to run for the same sequence of calls
+ * (every floating-point sum has a fixed order; a workgroup whose 2048 events span more than 262 knot intervals -- a gap in the
+ * recording -- adds its out-of-window batches with atomics) and agree across slicings to summation order. */
+int cmx_backend_recon_restart(cmx_ctx *ctx, const double *knots_xyzw);
+int cmx_backend_recon_contrast(cmx_ctx *ctx, double blur_sigma, int contrast_measure, int want_grad, double *contrast);
+int cmx_backend_recon_grad_add(cmx_ctx *ctx, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns);
+int cmx_backend_recon_grad_add_aos(cmx_ctx *ctx, int64_t n, const void *events, const cmx_aos_layout *layout);
+int cmx_backend_recon_grad_add_from(cmx_ctx *ctx, const cmx_events *ev, int64_t first, int64_t count);
+int cmx_backend_recon_grad_get(cmx_ctx *ctx, double *grad /* 3K */);
+int cmx_backend_recon_eval_from(cmx_ctx *ctx, const cmx_events *ev, int64_t first, int64_t count,
+                                const double *knots_xyzw /* K x 4, or NULL = keep */, double blur_sigma,
+                                int contrast_measure, double *contrast, double *grad /* 3K or NULL */);
 
 /* ------------------------------------------------------------------ split-phase (multi-GPU) ------------
  * The IWE is a sum over events, the contrast a non-linear function of the SUMMED image, so ranks exchange
@@ -557,7 +595,8 @@ int cmx_get_stats(cmx_ctx *ctx, double *stats, int n_stats); /* writes min(n_sta
  *     rejected (before: accepted as non-zero);
  *  6: named cmx_get_stats indices, five more of them (the buffer length is the caller's: old callers keep reading what they asked for); cmx_group_transport_info; the *_aos entry points; cmx_set_stream_priority /
  *     cmx_set_cu_mask moved to cmax_hip_diag.h;
- *     added without a bump (no signature or buffer layout changed): the seven cmx_backend_recon_* entry points) */
+ *     added without a bump (no signature or buffer layout changed): the seven cmx_backend_recon_* entry points, then
+ *     recon_restart / _contrast / _grad_add[_aos|_from] / _grad_get / _eval_from) */
 #define CMX_ABI_VERSION 6
 int cmx_abi_version(void);
 int cmx_timing_enable(cmx_ctx *ctx, int on);

@@ -1,0 +1,203 @@
+#!/usr/bin/env python3
+"""Whole-trajectory contrast and gradient (cmx_backend_recon_restart / _contrast / _grad_add_from / _grad_get / _eval_from), phase by
+phase, in one run on one GPU.
+
+  (large)   tools/time_recon.py's configuration: 20M events from the event store, 1280x720 sensor, 4096x2048 panorama, linear spline
+            with 401 knots, batch 100.  Median of --reps runs per phase after --warmup warm-up runs, host clock around synchronous
+            calls: restart, add_from (the vote pass: the kernel profiles/recon_timing.txt records), contrast cost-only, contrast with
+            gradient, grad_add_from (the gather pass), grad_get, and the whole eval_from with and without the gradient.
+  (window)  config 3 (5M events, cubic K = 10, 1024 x 1024): reconstruct_eval with the gradient against the window path's
+            set_window_from + one eval with the gradient (num_fixed = 0, no map).
+  (pmc)     the large configuration once under rocprofv3 --pmc, one counter group per run: VALU instructions of the gather kernel
+            per event, and the atomic requests that reach the L2.
+
+No threshold is fixed: the file states the ratios.  Every step runs in a child process of its own, in a process group of its own,
+under a time limit; a child that ends with a non-zero status or at its limit is the LAST thing this tool starts on the GPU.
+Writes profiles/recon_grad_timing.txt (--out).  Needs a GPU; there is no fallback."""
+import argparse
+import json
+import os
+import shutil
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import numpy as np  # noqa: E402
+
+import time_recon as tr  # noqa: E402  (the stream of the large configuration, the child runner, the CSV reader)
+
+
+def med(v):
+    return statistics.median(v) if v else float("nan")
+
+
+def timed(fn, *a, **k):
+    t0 = time.perf_counter()
+    r = fn(*a, **k)
+    return time.perf_counter() - t0, r
+
+
+def step_large(a):
+    from cmax_slam_amd import evaluator
+    x, y, t, knots, start_ns, dt_ns, lut = tr.make_inputs(a)
+    be = evaluator.BackendEvaluator(a.sensor[0], a.sensor[1], lut, a.pano[0], a.pano[1])
+    store = evaluator.EventStore(a.sensor[0], a.sensor[1], len(x))
+    store.push(x, y, t)
+    n = len(x)
+    ph = {k: [] for k in ("restart", "add_from", "contrast_cost", "contrast_grad", "grad_add_from", "grad_get", "eval_cost", "eval_grad")}
+    be.reconstruct_begin(2, knots, start_ns, dt_ns, a.batch, 1)
+    c = g = None
+    for i in range(a.warmup + a.reps):
+        s = {}
+        s["restart"], _ = timed(be.reconstruct_restart, knots)
+        s["add_from"], _ = timed(be.reconstruct_add_from, store, 0, n)
+        s["contrast_cost"], _ = timed(be.reconstruct_contrast, a.sigma, 0, False)
+        s["contrast_grad"], c = timed(be.reconstruct_contrast, a.sigma, 0, True)
+        s["grad_add_from"], _ = timed(be.reconstruct_grad_add_from, store, 0, n)
+        s["grad_get"], g = timed(be.reconstruct_grad_get)
+        s["eval_cost"], _ = timed(be.reconstruct_eval, store, 0, n, knots, a.sigma, 0, False)
+        s["eval_grad"], (c2, g2) = timed(be.reconstruct_eval, store, 0, n, knots, a.sigma, 0, True)
+        if i >= a.warmup:
+            for k, v in s.items():
+                ph[k].append(v)
+    _, ns, ni = be.reconstruct_get(with_counts=True)
+    be.reconstruct_end()
+    out = {"events": n, "K": len(knots), "sampled": ns, "inside": ni, "contrast": c, "gmax": float(np.abs(g).max()),
+           "eval_vs_phases": float(np.abs(g2 - g).max()), "phases": {k: med(v) for k, v in ph.items()}}
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+def step_window(a):
+    from cmax_slam_amd import evaluator, synth
+    w = synth.config3()
+    be = evaluator.BackendEvaluator(w.W, w.H, w.lut, w.Wp, w.Hp)
+    n = len(w.x)
+    store = evaluator.EventStore(w.W, w.H, n)
+    store.push(w.x, w.y, w.t_ns)
+    t_all = int(w.t_ns[-1]) + 1
+    win_set, win_eval, rec = [], [], []
+    zero = np.zeros(3 * len(w.knots_init))
+    be.reconstruct_begin(w.order, w.knots_init, w.start_ns, w.dt_ns, 100, 1)
+    for i in range(a.warmup + a.reps):
+        t0, _ = timed(be.set_window_from, store, 0, n, w.order, w.knots_init, w.start_ns, w.dt_ns, 0, t_all, 100, 1, blur_sigma=a.sigma)
+        t1, (cw, gw) = timed(be.eval, zero, True)
+        t2, (cr, gr) = timed(be.reconstruct_eval, store, 0, n, w.knots_init, a.sigma, 0, True)
+        if i >= a.warmup:
+            win_set.append(t0); win_eval.append(t1); rec.append(t2)
+    be.reconstruct_end()
+    out = {"events": n, "set_window_from": med(win_set), "eval": med(win_eval), "reconstruct_eval": med(rec),
+           "contrast_rel": abs(cr - cw) / abs(cw), "grad_rel": float(np.abs(np.array(gr) - gw).max() / np.abs(gw).max())}
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--step", default=None, choices=(None, "large", "window"))
+    ap.add_argument("--events", type=int, default=20_000_000)
+    ap.add_argument("--seconds", type=float, default=20.0)
+    ap.add_argument("--sensor", type=int, nargs=2, default=(1280, 720))
+    ap.add_argument("--pano", type=int, nargs=2, default=(4096, 2048))
+    ap.add_argument("--batch", type=int, default=100)
+    ap.add_argument("--sigma", type=float, default=1.0)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--no-profile", action="store_true", help="skip the rocprofv3 counter runs")
+    ap.add_argument("--commit", default=None)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "recon_grad_timing.txt"))
+    a = ap.parse_args()
+    if a.step == "large":
+        return step_large(a)
+    if a.step == "window":
+        return step_window(a)
+
+    from cmax_slam_amd import _lib
+    assert _lib.lib().cmx_device_count() > 0, "no GPU visible: this tool measures on the device only"
+    commit = a.commit
+    if not commit:
+        try:
+            commit = subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], stderr=subprocess.DEVNULL).decode().strip()
+        except Exception:
+            commit = "unknown"
+
+    def child(step, extra=(), wrap=(), limit=420):
+        # (time_recon's runner starts its own file: point it at this one)
+        saved = tr.__file__
+        tr.__file__ = os.path.abspath(__file__)
+        try:
+            return tr.child(a, step, ["--sigma", str(a.sigma)] + list(extra), wrap, limit)
+        finally:
+            tr.__file__ = saved
+
+    big = child("large")  # (a timing child that dies ends the run: ChildDied propagates, nothing further is started)
+    win = child("window")
+    n, p = big["events"], big["phases"]
+    L = ["whole-trajectory contrast and gradient: cmx_backend_recon_restart / _contrast / _grad_add_from / _grad_get / _eval_from",
+         "commit: %s    %d events from the event store, %dx%d sensor, %dx%d panorama, linear spline with %d knots, batch %d, rate 1, sigma %g" %
+         (commit, n, a.sensor[0], a.sensor[1], a.pano[0], a.pano[1], big["K"], a.batch, a.sigma),
+         "median of %d runs after %d warm-up runs; host clock around synchronous calls" % (a.reps, a.warmup),
+         "sampled %d, voted %d; contrast %.6g, |grad|max %.4g; eval_from against the phase-by-phase gradient: max |diff| %.2e" %
+         (big["sampled"], big["inside"], big["contrast"], big["gmax"], big["eval_vs_phases"]),
+         "",
+         "%-58s %10s %14s" % ("phase", "ms", "events/s")]
+    for k, label in (("restart", "restart (knots, zero the plane)"), ("add_from", "add_from (vote pass)"),
+                     ("contrast_cost", "contrast, cost only (tile flags, list, moments)"),
+                     ("contrast_grad", "contrast with gradient (tile flags, list, adjoint pass)"),
+                     ("grad_add_from", "grad_add_from (gather pass)"), ("grad_get", "grad_get (2 x 3K sums to the host)"),
+                     ("eval_cost", "eval_from, cost only"), ("eval_grad", "eval_from, with gradient")):
+        L.append("%-58s %10.3f %14.3e" % (label, 1e3 * p[k], n / p[k]))
+    L += ["",
+          "gather pass / vote pass of the same run: %.2f x" % (p["grad_add_from"] / p["add_from"]),
+          "eval_from with gradient / cost only: %.2f x" % (p["eval_grad"] / p["eval_cost"]),
+          "",
+          "config 3 (%d events, cubic K = 10, 1024 x 1024), num_fixed = 0, no map:" % win["events"],
+          "  window path: set_window_from %.3f ms + eval with gradient %.3f ms = %.3f ms" %
+          (1e3 * win["set_window_from"], 1e3 * win["eval"], 1e3 * (win["set_window_from"] + win["eval"])),
+          "  reconstruct_eval with gradient (restart + add_from + contrast + grad_add_from + grad_get): %.3f ms" % (1e3 * win["reconstruct_eval"]),
+          "  reconstruct_eval / (set_window_from + eval): %.2f x;  / eval alone: %.2f x" %
+          (win["reconstruct_eval"] / (win["set_window_from"] + win["eval"]), win["reconstruct_eval"] / win["eval"]),
+          "  agreement of the two: contrast %.2e, gradient %.2e (relative, max-norm)" % (win["contrast_rel"], win["grad_rel"])]
+    died = None
+    if not a.no_profile and not shutil.which("rocprofv3"):
+        L += ["", "rocprofv3 is not installed: no counters"]
+    elif not a.no_profile:
+        one = ["--reps", "1", "--warmup", "0"]
+        evs = 2.0 * big["sampled"]  # the phase-by-phase gather and eval_from's: two gather passes in a profiled run
+        for grp in ("SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES", "TCC_ATOMIC_sum TCC_READ_sum TCC_WRITE_sum"):
+            if died:
+                break
+            with tempfile.TemporaryDirectory(prefix="recon_grad_pmc_") as d:
+                try:
+                    child("large", one, ["rocprofv3", "--pmc"] + grp.split() + ["--output-format", "csv", "-d", d, "-o", "rg", "--"], limit=300)
+                    for kern in ("recon_gather", "recon_votes"):
+                        acc = {}
+                        for r in tr.rows_of(d, "counter_collection.csv"):
+                            if kern in r.get("Kernel_Name", "") and "rows" not in r.get("Kernel_Name", ""):
+                                acc[r["Counter_Name"]] = acc.get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])
+                        L.append("PMC (a run of its own), %s launches summed: " % kern + ", ".join("%s %.4g" % kv for kv in sorted(acc.items())))
+                        per = evs if kern == "recon_gather" else 3.0 * big["sampled"]  # (add_from + two eval_from vote passes)
+                        if acc.get("SQ_INSTS_VALU"):
+                            L.append("    %s: %.1f VALU instructions per event (wave instructions x 64 lanes / events)" %
+                                     (kern, 64.0 * acc["SQ_INSTS_VALU"] / per))
+                        if acc.get("TCC_ATOMIC_sum") is not None and "TCC_ATOMIC_sum" in acc:
+                            L.append("    %s: %.4g atomic requests at the L2 = %.4f per event" % (kern, acc["TCC_ATOMIC_sum"], acc["TCC_ATOMIC_sum"] / per))
+                except tr.ChildDied as e:
+                    died = str(e).splitlines()[0]
+                except Exception as e:
+                    L.append("PMC %s: not readable (%s)" % (grp, str(e).splitlines()[0]))
+        if died:
+            L += ["", "PROFILING STOPPED, nothing further was started on the GPU: " + died]
+    text = "\n".join(L) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+    print(text)
+    return 1 if died else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
