@@ -302,7 +302,7 @@ int chain_run_frontend(cmx_ctx *c, FrcgSM &hs, bool *completed) {
     (void)hipMemcpy(&c->d_chain->done, &one, sizeof(int), hipMemcpyHostToDevice);  // (null stream: overtakes the queued slots)
     (void)hipStreamSynchronize(c->stream);
     if (c->d_tail_counters) (void)hipMemsetAsync(c->d_tail_counters, 0, kTailCounterWords * sizeof(unsigned), c->stream);
-    if (c->d_gacc) (void)hipMemsetAsync(c->d_gacc, 0, (size_t)kTailShards * kGaccStride * sizeof(double), c->stream);
+    if (c->d_gacc) (void)hipMemsetAsync(c->d_gacc, 0, kGaccDoubles * sizeof(double), c->stream);
     // The stop word lands in the middle of whatever slot is running: of a fused slot, some chunk workgroups may have arrived on tile
     // counters whose tile workgroups then left at once (counts never taken back), or tile workgroups may be waiting for chunks that left
     // (they give up after kFuseTimeoutTicks and flag the fallback word nobody reads any more).  Counters and word start from zero again.

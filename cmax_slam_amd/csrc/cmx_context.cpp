@@ -196,8 +196,8 @@ int create_common(cmx_ctx **out, int kind, int device, int W, int H, const doubl
   HIP_TRY(c, hipMemset(c->d_gate, 0, sizeof(int)));
   HIP_TRY(c, hipMalloc((void **)&c->d_tail_counters, kTailCounterWords * sizeof(unsigned)));
   HIP_TRY(c, hipMemset(c->d_tail_counters, 0, kTailCounterWords * sizeof(unsigned)));
-  HIP_TRY(c, hipMalloc((void **)&c->d_gacc, (size_t)kTailShards * kGaccStride * sizeof(double)));
-  HIP_TRY(c, hipMemset(c->d_gacc, 0, (size_t)kTailShards * kGaccStride * sizeof(double)));
+  HIP_TRY(c, hipMalloc((void **)&c->d_gacc, kGaccDoubles * sizeof(double)));
+  HIP_TRY(c, hipMemset(c->d_gacc, 0, kGaccDoubles * sizeof(double)));
   HIP_TRY(c, hipDeviceSynchronize());  // null-stream clears / copies above vs the context's non-blocking stream
   return CMX_OK;
 }
@@ -437,7 +437,8 @@ static int set_option_one(cmx_ctx *c, int key, int value) {
       return CMX_OK;
     case CMX_OPT_TAIL_FINALIZE:
       c->tail_poll = value == 3;  // 3: the tail as 1, with the polling form on the front-end gather (A/B: measured, no gain)
-      c->tail_finalize = value == 3 ? 1 : (value < 0 ? 0 : (value > 2 ? 2 : value));
+      c->tail_host = value == 4;  // 4: the tail as 1, front-end gradient evaluations finalized on the host from per-shard records
+      c->tail_finalize = (value == 3 || value == 4) ? 1 : (value < 0 ? 0 : (value > 2 ? 2 : value));
       return CMX_OK;
     case CMX_OPT_GATED_DF:
       c->gated_df = value != 0;
@@ -623,6 +624,7 @@ int cmx_get_stats(cmx_ctx *c, double *out, int n_stats) {
   stats[CMX_STAT_ONE_LAUNCH_EVALS] = (double)c->fused_full_evals;
   stats[CMX_STAT_FUSED_TIMEOUTS] = (double)c->fused_timeouts;
   stats[CMX_STAT_SELF_SERVE_EVALS] = (double)c->fused_self_evals;
+  stats[CMX_STAT_HOST_FINALIZE_EVALS] = (double)c->hostfin_evals;
   for (int i = 0; i < n_stats && i < CMX_N_STATS; i++) out[i] = stats[i];
   return CMX_OK;
 }

@@ -266,8 +266,16 @@ struct cmx_ctx {
   int64_t chain_solves = 0, chain_slots = 0, chain_takeovers = 0, chain_warm_starts = 0;
   int tail_finalize = 1;              // CMX_OPT_TAIL_FINALIZE: 0 off, 1 on (back end: cost-only evaluations), 2 on everywhere
   bool tail_poll = false;             // ... 3: as 1 with the POLLING tail on the front-end gather (measured: no gain, profiles/r06_tail_poll.txt)
+  int tail_host = -1;                 // ... 4: as 1 with the HOST finalize of front-end gradient evaluations (cmx_hostfin.hpp; arm_tail);
+                                      // -1: never set -- the build's default (kTailHostDefault, cmx_pipeline.cpp), 0: any other value was set
+  int host_shards = 0;                // S of that form (8 / 16 / 32); 0: the build's default (kHostShardsDefault)
+  // the pending evaluation ends in host records instead of a device finalize when hostfin_ticket == ticket_issued
+  unsigned long long hostfin_ticket = 0;
+  int hostfin_G = 0, hostfin_S = 0, hostfin_gP = 0, hostfin_mu_free = 0, hostfin_measure = 0;
+  double hostfin_npix = 0;
+  int64_t hostfin_evals = 0;
   unsigned *d_tail_counters = nullptr;  // kTailCounterWords words, all-zero between launches
-  double *d_gacc = nullptr;             // kTailShards x kGaccStride gradient accumulators of the tail finalize, all-zero between launches
+  double *d_gacc = nullptr;             // kGaccDoubles gradient accumulators of the tail finalize (rows of kGaccStride), all-zero between launches
 
   // native RCCL exchange (cmx_comm_attach): every evaluation all-reduces its partial planes / gradient sums in place
   ncclComm_t comm = nullptr;

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "cmx_frcg_sm.hpp"
+#include "cmx_hostfin.hpp"
 #include "cmx_so3.hpp"
 
 namespace cmx {
@@ -125,17 +126,7 @@ struct FinalizeArgs {
   double *macc_clear;
   int nout_pad;
 };
-// contrast from the two image moments: the one expression shared by the finalize step and by the workgroups of a self-gating
-// gradient pass (they must take the machine's decision from bitwise the same number)
-static inline __host__ __device__ double contrast_from_sums(double s0, double s1, double N, int measure, double *mu_out) {
-  const double mu = s0 / N;
-  *mu_out = mu;
-  if (measure == 1) return s1 / N;
-  double var = s1 / N - mu * mu;
-  if (var < 0) var = 0;
-  const double sd = sqrt(var);
-  return sd * sd;
-}
+// (contrast_from_sums, the one expression for the contrast on the device and on the host: cmx_hostfin.hpp)
 // the condition of the gate, the same expression on the device (finalize) and on the host (which result to expect)
 static inline __host__ __device__ int gate_condition(double contrast, double thr, int mode) {
   const double f = -contrast;
@@ -149,20 +140,28 @@ constexpr int kAlphaSlot = 4095;     // alpha mirror (back end)
 constexpr int kXsetSlot = 4088;      // sharded panoramas (xset_kernel): [0] tiles in the next evaluation's exchange set, [1] flagged tiles
                                      // this evaluation's exchange did not cover, [2] flagged tiles, [3] = stamp:
                                      // bits[0] ^ bits[1] ^ bits[2] ^ (launch sequence number * kTicketMix)
-constexpr unsigned long long kTicketMix = 0x9E3779B97F4A7C15ull;
+// (kTicketMix: cmx_hostfin.hpp)
 
 
 // Tail finalize (cmx_kernels.hip, tail_arrive): the LAST kernel of an evaluation -- image_moments / image_adjoint2 (cost-only),
 // fe_gather / be_gather4 with the per-batch pass folded in / be_gather_batch (adjoint gradient) -- runs the finalize step in
 // its last-arriving workgroup, so an evaluation ends without the one-workgroup finalize launch and the boundary in front of it.
-constexpr int kTailCounterWords = (kTailShards + 1) * kTailStride;
+// (the allocations hold kHostShardsMax rows / shard counters: the host-finalize form below shards by up to that many)
+constexpr int kTailCounterWords = (kHostShardsMax + 1) * kTailStride;
 constexpr int kGaccStride = 2 * 3 * kMaxKnots + 2;  // doubles per accumulator row: S1 | S2 columns (+ spare), see FinalizeArgs::gacc
+constexpr size_t kGaccDoubles = (size_t)kHostShardsMax * kGaccStride;  // the accumulator allocation
 struct TailArgs {
   unsigned *counters;  // all-zero between launches (the last arrivers reset what they completed); null = no tail finalize
   FinalizeArgs fin;
   int poll;            // 1 (front-end plain gather, round 6): workgroup 0 finalizes once every other workgroup has ARRIVED -- fire-and-forget
                        // arrival atomics on counters[0], one polling lane -- instead of the last arriver found through two levels of
                        // returning ticket atomics (two dependent memory trips less at the end of every gradient evaluation)
+  // host finalize (front-end plain gather, CMX_OPT_TAIL_FINALIZE 4; cmx_hostfin.hpp): host_shards = S > 0 -- the workgroups add to row
+  // blockIdx % S, the last arriver of every shard stores the shard's sums as one record to host_rec (mapped host memory, record q at
+  // q * kHostRecWords) and nobody looks for the overall last arriver; the launch carries ONE more workgroup, which stores the
+  // moments record (image moments, fallback word).  fin.ticket stamps the records; the host forms contrast and gradient.
+  int host_shards;
+  unsigned long long *host_rec;
 };
 
 struct ImgArgs {

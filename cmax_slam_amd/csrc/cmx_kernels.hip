@@ -531,10 +531,38 @@ __device__ __forceinline__ void chain_step(const FinalizeArgs &a, ChainMachine &
   }
 }
 
+// the two image moments from the image pass's per-tile rows (FinalizeArgs::direct), by the whole workgroup: sm.sh[0], sm.sh[1],
+// written by threads 0 and 1 (a barrier away from their readers).  One order of additions for the device finalize and for the
+// moments record of the host finalize (host_moments_record).
+template <int NT>
+__device__ __forceinline__ void direct_moment_sums(const FinalizeArgs &a, FinSmem &sm) {
+  constexpr int NW = NT / 64, HALF = NW / 2;  // waves; waves per image-moment row
+  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  // this is ONE workgroup reading tables other CUs just wrote (L2-remote): keep many independent loads in flight
+  const int row = wave & 1, part = wave >> 1;
+  double p = 0;
+  const double *src = a.partials + (size_t)row * a.nblk;
+  const int nvalid = a.nvalid ? (int)(*a.nvalid) : a.nblk;  // list path: only the first *nvalid entries were written
+  int b = part * 64 + lane;
+  for (; b + 3 * HALF * 64 < nvalid; b += 4 * HALF * 64) {
+    const double v0 = ld_sc1(src + b), v1 = ld_sc1(src + b + HALF * 64), v2 = ld_sc1(src + b + 2 * HALF * 64),
+                 v3 = ld_sc1(src + b + 3 * HALF * 64);
+    p += (v0 + v1) + (v2 + v3);
+  }
+  for (; b < nvalid; b += HALF * 64) p += ld_sc1(src + b);
+  p = wave_sum(p);
+  if (lane == 0) sm.shp[wave] = p;
+  __syncthreads();
+  if (t < 2) {
+    double s = 0;
+    for (int w = 0; w < HALF; w++) s += sm.shp[2 * w + t];
+    sm.sh[t] = s;
+  }
+}
+
 template <int NT, bool CHAIN = false>  // CHAIN: the device-driven solve's variant (the machine's step is compiled in)
 __device__ __forceinline__ void finalize_body(const FinalizeArgs &a, FinSmem &sm) {
-  constexpr int NW = NT / 64;   // waves
-  constexpr int HALF = NW / 2;  // waves per image-moment row
+  constexpr int NW = NT / 64;   // waves (direct_moment_sums: half of them per image-moment row)
   static_assert(NW >= 2 && NW <= 16 && 2 + 3 * kMaxKnots < NT, "finalize geometry");
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
   if (t == 0) sm.shchk = 0ull;
@@ -624,26 +652,7 @@ __device__ __forceinline__ void finalize_body(const FinalizeArgs &a, FinSmem &sm
     if (t == 0) chain_moment_sums(a.macc, sm.sh[0], sm.sh[1]);
     if (t < 2 * kTailShards) a.macc_clear[(size_t)(t >> 1) * 16 + (t & 1)] = 0.0;  // the NEXT slot's buffer (nobody reads it now)
   } else if (a.direct) {  // few tiles: sum the image kernel's per-tile moments here instead of a separate launch
-    // this is ONE workgroup reading tables other CUs just wrote (L2-remote): keep many independent loads in flight
-    const int row = wave & 1, part = wave >> 1;
-    double p = 0;
-    const double *src = a.partials + (size_t)row * a.nblk;
-    const int nvalid = a.nvalid ? (int)(*a.nvalid) : a.nblk;  // list path: only the first *nvalid entries were written
-    int b = part * 64 + lane;
-    for (; b + 3 * HALF * 64 < nvalid; b += 4 * HALF * 64) {
-      const double v0 = ld_sc1(src + b), v1 = ld_sc1(src + b + HALF * 64), v2 = ld_sc1(src + b + 2 * HALF * 64),
-                   v3 = ld_sc1(src + b + 3 * HALF * 64);
-      p += (v0 + v1) + (v2 + v3);
-    }
-    for (; b < nvalid; b += HALF * 64) p += ld_sc1(src + b);
-    p = wave_sum(p);
-    if (lane == 0) sm.shp[wave] = p;
-    __syncthreads();
-    if (t < 2) {
-      double s = 0;
-      for (int w = 0; w < HALF; w++) s += sm.shp[2 * w + t];
-      sm.sh[t] = s;
-    }
+    direct_moment_sums<NT>(a, sm);
   } else if (t < 2) {
     sm.sh[t] = a.sums[t];
   }
@@ -777,6 +786,63 @@ __device__ __forceinline__ bool tail_arrive(const TailArgs &tl, int nblocks, int
   }
   __syncthreads();
   return sm.is_last != 0;
+}
+
+// ---- host finalize (TailArgs::host_shards, cmx_hostfin.hpp): the launch's tail ends one level earlier.  Every workgroup drains its
+// accumulator atomics and takes its shard's ticket as in tail_arrive; the workgroup that completes a shard resets the counter, loads
+// the shard's own row in one round of sc1 loads, stores the zeros the next launch expects, and sends the row as ONE record -- eight
+// contiguous lanes of one wave, 64 bytes -- to mapped host memory.  No top counter, no gathering of the rows in one workgroup, no
+// moment sums behind the last arriver: the waiting host adds the records up.  Call from every thread of an event workgroup once.
+__device__ __forceinline__ void host_record_store(unsigned long long *rec, unsigned long long payload, unsigned long long ticket, int lane) {
+  // lanes 0..5 hold the payload words (unused ones 0); lane 6 the ticket; lane 7 the checksum.  Plain stores, no fence: the host
+  // accepts the record only when ticket and checksum match the words it read.
+  unsigned long long x = lane < kHostRecCols ? payload : 0ull;
+#pragma unroll
+  for (int o = 4; o >= 1; o >>= 1) x ^= __shfl_xor(x, o, 64);  // (lanes 0..7: the xor of the payload)
+  const unsigned long long w = lane < kHostRecCols ? payload : (lane == kHostRecTicket ? ticket : (x ^ (ticket * kTicketMix)));
+  if (lane < 8) rec[lane] = w;
+}
+__device__ __forceinline__ void host_shard_arrive(const TailArgs &tl, int nblocks, int block, int ncol) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's accumulator atomics have left
+  __syncthreads();
+  if (threadIdx.x >= 64) return;
+  const int lane = threadIdx.x, S = tl.host_shards, shard = block % S;
+  int last = 0;
+  if (lane == 0) {
+    const unsigned shard_size = (unsigned)((nblocks - shard + S - 1) / S);
+    unsigned *cs = tl.counters + shard * kTailStride;
+    if (atomicAdd(cs, 1u) == shard_size - 1u) {
+      __hip_atomic_store(cs, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // nobody else touches it in this launch
+      last = 1;
+    }
+  }
+  if (!__shfl(last, 0, 64)) return;
+  // (no acquire fence: the row was written by agent-scope atomics and is read with sc1 loads, as in finalize_body)
+  double *row = tl.fin.gacc + (size_t)shard * tl.fin.gacc_stride;
+  unsigned long long bits = 0ull;
+  if (lane < ncol) {
+    bits = (unsigned long long)__double_as_longlong(ld_sc1(row + lane));
+    st_sc1(row + lane, 0.0);
+  }
+  host_record_store(tl.host_rec + (size_t)shard * kHostRecWords, bits, tl.fin.ticket, lane);
+}
+// ... and the launch's one extra workgroup (no events, no ticket): the image moments -- rows of an EARLIER launch, summed exactly as
+// the device finalize sums them -- and the splat's fallback word (read and reset) as the moments record.  It waits for nothing.
+template <int NT>
+__device__ __forceinline__ void host_moments_record(const TailArgs &tl, FinSmem &sm) {
+  const FinalizeArgs &a = tl.fin;
+  const int t = threadIdx.x;
+  unsigned fb_count = 0u;
+  if (t == 0 && a.fallback) {
+    fb_count = *a.fallback;
+    *a.fallback = 0u;
+  }
+  direct_moment_sums<NT>(a, sm);
+  __syncthreads();
+  if (t >= 64) return;
+  const double fb = (double)__shfl(fb_count, 0, 64);
+  const double v = t == 0 ? sm.sh[0] : (t == 1 ? sm.sh[1] : (t == 2 ? fb : 0.0));
+  host_record_store(tl.host_rec + (size_t)kHostRecMoments * kHostRecWords, (unsigned long long)__double_as_longlong(v), a.ticket, t);
 }
 
 // Sharded panoramas: the EXCHANGE SET.  The ranks' votes cover a few per cent of a panorama's tiles, so only those tiles
@@ -1744,11 +1810,18 @@ __global__ __launch_bounds__(kFeGatherNT) void fe_gather_kernel(FeGatherArgs g) 
     }
   }
   if (CHAIN) fe_resolve_omega(g.ev);
+  // host finalize (plain gather only): the launch's last workgroup has no events -- it sends the moments record and leaves
+  const bool hostfin = CHAIN == 0 && g.tail.host_shards > 0;
+  const int nblocks = hostfin ? (int)gridDim.x - 1 : (int)gridDim.x;  // event workgroups
+  if (hostfin && (int)blockIdx.x == nblocks) {
+    host_moments_record<kFeGatherNT>(g.tail, fin_sm);
+    return;
+  }
   const FeSplatArgs &a = g.ev;
   double acc[3] = {0, 0, 0}, acc2[3] = {0, 0, 0};
   constexpr int U = 2;  // events in flight per thread (swept on MI355X: 2 -> 11.9 us, 1 -> 12.2, 4 -> 12.9, 8 -> 14.9 per 1M events)
   // every workgroup walks ONE contiguous slice of the event list (in tile order that keeps its LUT / Itilde reads local)
-  const int per_block = ((a.n + (int)gridDim.x - 1) / (int)gridDim.x + kFeGatherNT - 1) / kFeGatherNT * kFeGatherNT;
+  const int per_block = ((a.n + nblocks - 1) / nblocks + kFeGatherNT - 1) / kFeGatherNT * kFeGatherNT;
   const int blk_beg = blockIdx.x * per_block, blk_end = min(a.n, blk_beg + per_block);
   const int stride = kFeGatherNT;
   // (the device-driven solve's variants keep the generic loop: with the finalize and the machine's step inlined, four events in
@@ -1840,11 +1913,16 @@ __global__ __launch_bounds__(kFeGatherNT) void fe_gather_kernel(FeGatherArgs g) 
 #pragma unroll
     for (int wv = 4; wv < kFeGatherNT / 64; wv++) v += red[6 * wv + k];
     if (g.tail.fin.gacc) {  // accumulator rows instead of the table (see FinalizeArgs::gacc); with or without the tail
+      const int nrows = hostfin ? g.tail.host_shards : kTailShards;
       if (v != 0.0)
-        __hip_atomic_fetch_add(g.tail.fin.gacc + (size_t)(blockIdx.x % kTailShards) * g.tail.fin.gacc_stride + k, v, __ATOMIC_RELAXED,
+        __hip_atomic_fetch_add(g.tail.fin.gacc + (size_t)((int)blockIdx.x % nrows) * g.tail.fin.gacc_stride + k, v, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
     } else if (tail) st_sc1(g.gpartials + (size_t)k * gridDim.x + blockIdx.x, v);  // write-through: read by the last arriver
     else g.gpartials[(size_t)k * gridDim.x + blockIdx.x] = v;
+  }
+  if (hostfin) {  // one record per shard to the host, which finalizes (always with the accumulator rows and the counters)
+    host_shard_arrive(g.tail, nblocks, (int)blockIdx.x, g.cx ? 6 : 3);
+    return;
   }
   if (CHAIN == 0 && tail && g.tail.poll) {
     // Polling tail: the sums above are on their way as agent-scope atomics; drain them, then everybody but workgroup 0 ARRIVES
@@ -1890,7 +1968,13 @@ int launch_fe_gather(const FeGatherArgs &a, hipStream_t s, hipEvent_t t0, hipEve
   const int blocks = fe_gather_blocks(a.ev.n);
   if (a.tail.fin.chain.sm && a.tail.fin.chain.stage == 2) CMX_LAUNCH(fe_gather_kernel<2>, dim3(blocks), dim3(kFeGatherNT), 0, s, t0, t1, a);
   else if (a.tail.fin.chain.sm || a.ev.w_dev) CMX_LAUNCH(fe_gather_kernel<1>, dim3(blocks), dim3(kFeGatherNT), 0, s, t0, t1, a);
-  else CMX_LAUNCH(fe_gather_kernel<0>, dim3(blocks), dim3(kFeGatherNT), 0, s, t0, t1, a);
+  else {
+    // host finalize: one more workgroup behind the event workgroups (the moments record)
+    const bool hostfin = a.tail.host_shards > 0 && a.tail.counters && a.tail.fin.gacc && a.tail.host_rec && a.tail.fin.direct;
+    FeGatherArgs b = a;
+    if (!hostfin) b.tail.host_shards = 0;
+    CMX_LAUNCH(fe_gather_kernel<0>, dim3(blocks + (hostfin ? 1 : 0)), dim3(kFeGatherNT), 0, s, t0, t1, b);
+  }
   return blocks;
 }
 

@@ -3,13 +3,26 @@
 #include <cstdlib>
 #include "cmx_context.hpp"
 
+// the host finalize of front-end gradient evaluations (arm_tail): on while CMX_OPT_TAIL_FINALIZE has not been set (an explicit 1
+// means the device tail), and its shard count -- 8 / 16 / 32 measured a tie, and 8 sums the rows the device tail sums, in its order
+// (profiles/tail_host_finalize.txt; A/B builds: tools/build_variant.sh recompiles this file with other values)
+#ifndef CMX_TAIL_HOST_DEFAULT
+#define CMX_TAIL_HOST_DEFAULT 1
+#endif
+#ifndef CMX_HOSTFIN_SHARDS
+#define CMX_HOSTFIN_SHARDS 8
+#endif
+static constexpr bool kTailHostDefault = CMX_TAIL_HOST_DEFAULT != 0;
+static constexpr int kHostShardsDefault = CMX_HOSTFIN_SHARDS;
+static_assert(kHostShardsDefault >= 1 && kHostShardsDefault <= cmx::kHostShardsMax, "shard count of the host finalize");
+
 // Fast path: swap to the partner buffer if it is known clean, otherwise clear the current one.  After this call
 // c->d_accum is all-zero over `nplanes` planes and c->pingpong_planes tells the image pass to clear the partner.
 int begin_accum(cmx_ctx *c, int nplanes, size_t np, bool fast) {
   c->pingpong_planes = 0;
   if (c->acc_dirty) {  // a split evaluation added to the accumulator rows and never reached its finalize (an error between the
                        // two phases): every later gradient would carry those sums -- the buffers are all-zero between launches
-    if (c->d_gacc) HIP_TRY(c, hipMemsetAsync(c->d_gacc, 0, (size_t)kTailShards * kGaccStride * sizeof(double), c->stream));
+    if (c->d_gacc) HIP_TRY(c, hipMemsetAsync(c->d_gacc, 0, kGaccDoubles * sizeof(double), c->stream));
     if (c->d_tail_counters) HIP_TRY(c, hipMemsetAsync(c->d_tail_counters, 0, kTailCounterWords * sizeof(unsigned), c->stream));
     c->acc_dirty = false;
   }
@@ -319,6 +332,25 @@ bool arm_tail(cmx_ctx *c, FinalizeArgs &f, TailArgs &tail, bool gated) {
   // CMX_OPT_TAIL_FINALIZE 3 (A/B, measured without gain): front-end gradient evaluations through accumulator rows let workgroup 0 poll
   // sharded arrival counts instead of finding the last arriver through two levels of returning tickets
   tail.poll = (c->kind == KIND_FE && f.gP > 0 && f.gacc && c->tail_poll && !f.chain.sm) ? 1 : 0;
+  // CMX_OPT_TAIL_FINALIZE 4 (cmx_hostfin.hpp): the same evaluations -- host-driven, one result block, variance or mean square -- end
+  // in one record per accumulator-row shard and a moments record; sync_and_collect forms contrast and gradient from them.  Gated
+  // passes, the slots of a device-driven solve, eval_many's blocks and sharded or deterministic contexts keep the device finalize.
+  tail.host_shards = 0;
+  tail.host_rec = nullptr;
+  const bool host = c->tail_host >= 0 ? c->tail_host != 0 : kTailHostDefault;
+  if (host && c->kind == KIND_FE && f.gP > 0 && 2 * f.gP <= kHostRecCols && f.gacc && f.mu_free && !tail.poll && !gated && !f.chain.sm &&
+      !c->chain_active && !c->result_override && !c->sharded() && (f.measure == 0 || f.measure == 1) && !f.macc) {
+    const int S = c->host_shards > 0 ? c->host_shards : kHostShardsDefault;
+    tail.host_shards = S;
+    tail.host_rec = reinterpret_cast<unsigned long long *>(c->d_result + kHostRecBase);
+    c->hostfin_ticket = f.ticket;
+    c->hostfin_G = fe_gather_blocks(c->n_packed);
+    c->hostfin_S = S;
+    c->hostfin_gP = f.gP;
+    c->hostfin_mu_free = f.mu_free;
+    c->hostfin_measure = f.measure;
+    c->hostfin_npix = f.npix;
+  }
   return true;
 }
 
@@ -734,14 +766,75 @@ bool spin_for_ticket(const double *h_block, unsigned long long want, int nout, i
   return done;
 }
 
+// the same wait for an evaluation that ends in host records (arm_tail: host finalize); the accepted payloads stay in `r`
+static bool spin_for_records(const double *h_block, unsigned long long want, uint64_t expected, int budget_us, HostFinRecords &r) {
+  const volatile unsigned long long *recs = reinterpret_cast<const volatile unsigned long long *>(h_block + kHostRecBase);
+  const auto t0 = std::chrono::steady_clock::now();
+  bool done = false;
+  const double limit_ms = budget_us >= 0 ? budget_us * 1e-3 : 20.0;
+  const unsigned check = budget_us >= 0 ? 63u : 1023u;
+  for (unsigned spins = 0;; spins++) {
+    if (hostfin_poll(recs, want, expected, r)) { done = true; break; }
+    __builtin_ia32_pause();
+    if ((spins & check) == check &&
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > limit_ms)
+      break;
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return done;
+}
+
+// contrast, mean, gradient and fallback word of such an evaluation into the result block, where the device finalize puts them
+static void hostfin_deliver(cmx_ctx *c, const HostFinRecords &r) {
+  const HostFinResult o = hostfin_combine(r, c->hostfin_S, c->hostfin_gP, c->hostfin_mu_free, c->hostfin_measure, c->hostfin_npix);
+  c->h_result[0] = o.contrast;
+  c->h_result[1] = o.mu;
+  for (int k = 0; k < c->hostfin_gP; k++) c->h_result[2 + k] = o.grad[k];
+  c->h_result[kFallbackSlot] = o.fallback;
+  // (ticket and checksum as the device finalize leaves them: the block stays a consistent snapshot of the last evaluation)
+  unsigned long long *w = reinterpret_cast<unsigned long long *>(c->h_result);
+  unsigned long long x = w[kFallbackSlot];
+  for (int k = 0; k < c->ticket_nout; k++) x ^= w[k];
+  w[kChecksumSlot] = x ^ (c->hostfin_ticket * kTicketMix);
+  w[kTicketSlot] = c->hostfin_ticket;
+  c->hostfin_evals++;
+}
+
+// the wait of an evaluation whose last launch hands over per-shard sums and the image moments: the finalize step runs here
+static int wait_hostfin(cmx_ctx *c, bool *spun) {
+  HostFinRecords r;
+  const uint64_t expected = hostfin_expected(c->hostfin_G, c->hostfin_S);
+  const bool done = c->ticket_wait && spin_for_records(c->h_result, c->ticket_issued, expected, c->spin_eval_us, r);
+  *spun = done;
+  if (!done) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // the stream is idle: every record must be there
+    const volatile unsigned long long *recs = reinterpret_cast<const volatile unsigned long long *>(c->h_result + kHostRecBase);
+    if (!hostfin_poll(recs, c->ticket_issued, expected, r)) {
+      if (c->d_tail_counters) (void)hipMemsetAsync(c->d_tail_counters, 0, kTailCounterWords * sizeof(unsigned), c->stream);
+      if (c->d_gacc) (void)hipMemsetAsync(c->d_gacc, 0, kGaccDoubles * sizeof(double), c->stream);
+      c->hostfin_ticket = 0;
+      return fail(c, CMX_ERR_HIP, "evaluation ended without its records (ticket %llu, records 0x%llx of 0x%llx)",
+                  (unsigned long long)c->ticket_issued, (unsigned long long)r.have, (unsigned long long)expected);
+    }
+  }
+  hostfin_deliver(c, r);
+  c->hostfin_ticket = 0;
+  return CMX_OK;
+}
+
 int sync_and_collect(cmx_ctx *c, bool ends_in_finalize) {
   // ends_in_finalize: the last thing queued on the stream is an evaluation's finalize kernel.  Wait for it through
   // its completion ticket in mapped host memory (a few microseconds earlier than the runtime reports the stream idle);
   // anything slower than the spin budget, and every caller that queued copies or other kernels after the finalize,
   // takes the ordinary stream synchronisation.
   bool done = false;
-  if (ends_in_finalize && c->ticket_wait && c->ticket_issued) done = spin_for_ticket(c->h_result, c->ticket_issued, c->ticket_nout, c->spin_eval_us);
-  if (!done) {
+  const bool hostfin = ends_in_finalize && c->ticket_issued && c->hostfin_ticket == c->ticket_issued;
+  if (hostfin) {
+    const int rc = wait_hostfin(c, &done);
+    if (rc) return rc;
+  } else if (ends_in_finalize && c->ticket_wait && c->ticket_issued) done = spin_for_ticket(c->h_result, c->ticket_issued, c->ticket_nout, c->spin_eval_us);
+  if (!done && !hostfin) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (ends_in_finalize && c->ticket_issued) {
       // the stream is idle: the finalize (its own launch, or the tail of the last kernel) must have delivered its ticket
@@ -749,7 +842,7 @@ int sync_and_collect(cmx_ctx *c, bool ends_in_finalize) {
       if (w[kTicketSlot] != c->ticket_issued) {
         const unsigned long long got = w[kTicketSlot];
         if (c->d_tail_counters) (void)hipMemsetAsync(c->d_tail_counters, 0, kTailCounterWords * sizeof(unsigned), c->stream);
-        if (c->d_gacc) (void)hipMemsetAsync(c->d_gacc, 0, (size_t)kTailShards * kGaccStride * sizeof(double), c->stream);
+        if (c->d_gacc) (void)hipMemsetAsync(c->d_gacc, 0, kGaccDoubles * sizeof(double), c->stream);
         return fail(c, CMX_ERR_HIP, "evaluation ended without its finalize step (ticket %llu, expected %llu)", got,
                     (unsigned long long)c->ticket_issued);
       }

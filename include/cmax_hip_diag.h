@@ -15,7 +15,7 @@ enum {
                              df at every accepted point; the reference recomputes everything, :58-70).  A cost-only
                              evaluation then also runs the adjoint image pass (Jt) instead of the moments-only pass, so the
                              df that follows launches its gather at once: +3..4 us per f, -12 us per df */
-  CMX_OPT_TAIL_FINALIZE = 6, /* 1 (default): the last kernel of an evaluation (cost-only: the blur + moments pass; adjoint gradient:
+  CMX_OPT_TAIL_FINALIZE = 6, /* 1: the last kernel of an evaluation (cost-only: the blur + moments pass; adjoint gradient:
                              the gather pass / the back end's per-batch pass) runs the finalize step -- contrast, gradient,
                              result hand-off -- in its last-arriving workgroup (write-through partial sums, tickets sharded
                              by XCD, sc1 loads) instead of a separate one-workgroup launch behind a kernel boundary.  The
@@ -27,6 +27,14 @@ enum {
                              3: as 1, with a POLLING tail on the front-end gather (workgroup 0 polls sharded fire-and-forget
                                 arrival counts and finalizes; round 6 A/B: 14.2 vs 14.1 us, no gain -- and 21.6 us with ONE
                                 counter: ~1000 atomics on one memory-side address serialise at ~12 ns each).
+                             4 (what a context does until this option is set; an explicit 1 is the device tail everywhere):
+                                as 1, with the HOST finalize on the front-end gather of host-driven gradient evaluations (variance /
+                                mean square, not deterministic, no communicator, not cmx_*_eval_many, not the gated pass or a
+                                device-driven solve): the last arriver of each accumulator-row shard stores the shard's column
+                                sums as one 64-byte record to mapped host memory, one extra workgroup stores the image moments and
+                                the fallback word, and the waiting host forms contrast and gradient with the device finalize's
+                                expressions -- no top ticket, no one-workgroup finalize at the end of the launch
+                                (profiles/tail_host_finalize.txt).
                              0: separate finalize launch (the round-1 flow) */
   /* 7: retired (round 2's opt-in fused gradient pass: measured slower, removed; profiles/r02_pmc_fe_fused_gather.txt) */
   CMX_OPT_COMPOSITE_IMAGE = 8, /* 1 (default): the image pass of the adjoint gradient applies G^T G as one banded operator per

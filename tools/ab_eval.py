@@ -1,6 +1,7 @@
 """A/B timing of one evaluation in a tight host loop (no oracle, no torch): fdf and cost-only, front end (config 2) and
 back end (config 3), for a list of option settings.  Usage on the GPU box:
-    python tools/ab_eval.py [fe|be|both] [key=value ...]     keys: tail, spin, reuse (ints); events=N; reps=N
+    python tools/ab_eval.py [fe|be|both] [key=value ...]     keys: tail, spin, reuse (ints); events=N; reps=N;
+                                                             tailhost=1: CMX_OPT_TAIL_FINALIZE 1 against 4, three times each
 Prints one line per variant: ms per fdf, ms per cost-only evaluation, kernel-class times (HIP events, separate pass)."""
 import os
 import sys
@@ -90,6 +91,8 @@ def main():
                     ("composite=0", {_lib.OPT_COMPOSITE_IMAGE: 0}), ("composite=1", {_lib.OPT_COMPOSITE_IMAGE: 1})]
     if "tailpoll" in kv:
         variants = [("tail tickets", {_lib.OPT_TAIL_FINALIZE: 1}), ("tail polling", {_lib.OPT_TAIL_FINALIZE: 3})] * 3
+    if "tailhost" in kv:
+        variants = [("tail device", {_lib.OPT_TAIL_FINALIZE: 1}), ("tail host", {_lib.OPT_TAIL_FINALIZE: 4})] * 3
     if "fused" in kv:
         variants = [("fused=0", {_lib.OPT_FUSED_IMAGE: 0}), ("fused=1", {_lib.OPT_FUSED_IMAGE: 1}), ("fused=3", {_lib.OPT_FUSED_IMAGE: 3})] * 2
     if "fold" in kv:
