@@ -433,17 +433,8 @@ void launch_build_chunks(const int *tile_start, int ntiles, int planes_per_tile,
 // (193 G lane-atomics/s for any address pattern) while ds_add_u64 runs at 1.7 T/s (tools/microbench/lds_atomics.hip).
 // Integer adds also commute, so a window's sum does not depend on the order the votes arrive in; the quantisation
 // (<= 2^-31 per vote) is far below fp32's own rounding of the reference's accumulators.
-// (fix_t, to_fix and the two global vote forms live in cmx_fixed.hpp: the whole-trajectory reconstruction votes the same way)
-__device__ __forceinline__ void lds_add_fix(fix_t *p, fix_t v) {
-  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void vote4_lds(fix_t *win, int lx, int ly, float dx, float dy) {
-  fix_t *q = win + ly * kBinStride + lx;
-  lds_add_fix(q, to_fix((1.f - dx) * (1.f - dy)));
-  lds_add_fix(q + 1, to_fix(dx * (1.f - dy)));
-  lds_add_fix(q + kBinStride, to_fix((1.f - dx) * dy));
-  lds_add_fix(q + kBinStride + 1, to_fix(dx * dy));
-}
+// (fix_t, to_fix, the LDS vote and the two global vote forms live in cmx_fixed.hpp: the whole-trajectory reconstruction votes the
+//  same way)
 
 // deterministic mode (CMX_OPT_DETERMINISTIC): everything that reaches global memory is a 64-bit INTEGER add into a
 // fixed-point plane -- integer adds commute, so the planes (and everything computed from them) are the same bits on every

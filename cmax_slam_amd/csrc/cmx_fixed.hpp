@@ -1,6 +1,6 @@
-// cmx_fixed.hpp -- the 2^-30 fixed-point vote representation (CMX_OPT_DETERMINISTIC) and the two forms of a bilinear vote
-// that reaches global memory, shared by the LDS splats (cmx_binning.hip) and the whole-trajectory reconstruction
-// (cmx_recon.hip).  Device inline only.
+// cmx_fixed.hpp -- the 2^-30 fixed-point vote representation (CMX_OPT_DETERMINISTIC), the two forms of a bilinear vote
+// that reaches global memory and the vote into an LDS window, shared by the LDS splats (cmx_binning.hip) and the
+// whole-trajectory reconstruction (cmx_recon.hip).  Device inline only.
 #pragma once
 #include "cmx_warp.hpp"
 
@@ -25,6 +25,21 @@ __device__ __forceinline__ void vote4_global_fix(fix_t *img, int W, int xx, int 
   atomicAdd(q + 1, to_fix(dx * (1.f - dy)));
   atomicAdd(q + W, to_fix((1.f - dx) * dy));
   atomicAdd(q + W + 1, to_fix(dx * dy));
+}
+
+// The same vote into a workgroup's LDS window (kBinWindow^2 cells, row stride kBinStride).  LDS accumulators are 64-bit fixed point
+// (2^-30 units), not fp32: on gfx950 ds_add_f32 retires ONE lane at a time (193 G lane-atomics/s for any address pattern) while
+// ds_add_u64 runs at 1.7 T/s (tools/microbench/lds_atomics.hip).  Integer adds also commute, so a window's sum does not depend on
+// the order the votes arrive in; the quantisation (<= 2^-31 per vote) is far below fp32's own rounding of the reference's accumulators.
+__device__ __forceinline__ void lds_add_fix(fix_t *p, fix_t v) {
+  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void vote4_lds(fix_t *win, int lx, int ly, float dx, float dy) {
+  fix_t *q = win + ly * kBinStride + lx;
+  lds_add_fix(q, to_fix((1.f - dx) * (1.f - dy)));
+  lds_add_fix(q + 1, to_fix(dx * (1.f - dy)));
+  lds_add_fix(q + kBinStride, to_fix((1.f - dx) * dy));
+  lds_add_fix(q + kBinStride + 1, to_fix(dx * dy));
 }
 
 }  // namespace cmx

@@ -130,6 +130,37 @@ inline bool plan_batches(int64_t n, int B, int rate, BatchPlan *p) {  // false: 
   }
   return true;
 }
+// ---- events bound to a reconstruction (cmx_backend_recon_bind_from): the sizes that follow from counts alone.
+// chunk_events: events of a full chunk of the tile-sorted vote pass -- n / 768 (three 256-thread workgroups per compute unit fill
+// the chip in one round), at least 1536 and at most 32768, a multiple of 256.  max_chunks: an upper bound of the chunk table's
+// length for ANY distribution of the n events over `keys` sort tiles and the no-window tile, whose events go in chunks of 256:
+// every tile adds floor(len / M) full chunks and at most one remainder.
+struct BoundPlan {
+  int chunk_events = 0;
+  int64_t max_chunks = 0;
+};
+inline BoundPlan plan_bound(int64_t n_packed, int64_t keys) {
+  BoundPlan b;
+  int64_t M = n_packed / 768;
+  M = M < 1536 ? 1536 : (M > 32768 ? 32768 : M);
+  b.chunk_events = (int)((M + 255) / 256 * 256);
+  b.max_chunks = n_packed / b.chunk_events + keys + 2 + n_packed / 256;
+  return b;
+}
+// a pass over the bound, time-ordered packed events in slices of whole batches: the slice that starts at batch b_lo
+struct BoundSlice {
+  int b_hi = 0;        // its batches are [b_lo, b_hi)
+  int64_t first = 0;   // its first packed event
+  int64_t n = 0;       // its packed events
+};
+inline BoundSlice bound_slice(const BatchPlan &p, int b_lo, int slice_batches) {
+  BoundSlice s;
+  s.b_hi = (p.nb - b_lo > slice_batches) ? b_lo + slice_batches : p.nb;
+  s.first = (int64_t)b_lo * p.per_batch;
+  s.n = p.packed(b_lo, s.b_hi);
+  return s;
+}
+
 // the contiguous range of whole batches a group hands member `rank` (cmax_slam_amd/dist.py: batch_range)
 inline void batch_range(int64_t n, int B, int rank, int world, int64_t *beg, int64_t *end) {
   const int64_t nb = (n + B - 1) / B, per = (nb + world - 1) / world;

@@ -451,6 +451,20 @@ int recon_run(int per_batch);
 void launch_recon_delta(const Quat *knots, int K, double *delta, hipStream_t s);
 void launch_recon_votes(const ReconArgs &a, hipStream_t s);
 void launch_recon_fixed_to_float(const unsigned long long *fixed, float *plane, size_t n, hipStream_t s);  // non-destructive
+// bound events (cmx_backend_recon_bind_from / _eval_bound): the batch poses of a spline of any knot count as a table in global
+// memory (recon_pose<N>, one thread per batch: a.batch_t, a.nb) -- what the tile sort (launch_count_sort with poseR = the table)
+// and the vote kernel below read -- and the vote pass over the tile-sorted events: one workgroup per chunk, votes into a
+// 64 x 64 LDS window of 64-bit fixed-point cells, one flush add per touched cell into the ONE plane; a vote that misses the
+// window goes to global memory as in recon_votes.  n_inside counts the events that voted, ev.fallback those of them that left
+// their window.
+struct ReconLdsArgs {
+  BeSplatArgs cam;           // as ReconArgs::cam, with poseR = the table
+  BinnedEvents ev;           // sxy, sbatch, chunks, nchunks (launch bound), nchunks_dev, fallback; fixed (deterministic mode) or null
+  float *plane;
+  unsigned long long *n_inside;
+};
+void launch_recon_pose_table(const ReconArgs &a, PoseR *out, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+void launch_recon_votes_lds(const ReconLdsArgs &g, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 
 // whole-trajectory contrast and gradient (cmx_backend_recon_contrast / _grad_add*): the second pass over the events of a
 // reconstruction.  One launch per slice, the run structure of the vote kernel; per workgroup the batches' V / U sums go through

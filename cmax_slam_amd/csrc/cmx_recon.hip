@@ -128,6 +128,127 @@ void launch_recon_votes(const ReconArgs &a, hipStream_t s) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------- bound events
+// recon_pose_table       the batch poses of an evaluation as a table in global memory: recon_pose<N> once per batch, the value the
+//                        votes kernel above forms in LDS, bit for bit (72 B per batch)
+// recon_votes_lds        the vote pass over events sorted by the destination tile of their vote (launch_count_sort /
+//                        launch_build_chunks with poseR = the table): be_splat_lds_kernel's structure with ONE plane and the
+//                        count of voting events.  load_bearing + be_warp_math<0> on the table's R is the arithmetic of
+//                        recon_votes_kernel, so vote cell and weights are the same bits, and to_fix of them the same integers.
+//                        Windows that hang over the plane's edge are safe for two reasons: a vote is only made when w.ok (all
+//                        four cells inside the plane), and the flush only writes cells that are non-zero.
+template <int N>
+__global__ __launch_bounds__(256) void recon_pose_table_kernel(const ReconArgs a, PoseR *out) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= a.nb) return;
+  double R[9];
+  recon_pose<N>(a, a.batch_t[b], R);
+#pragma unroll
+  for (int c = 0; c < 9; c++) out[b].R[c] = R[c];
+}
+void launch_recon_pose_table(const ReconArgs &a, PoseR *out, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {
+  if (a.nb <= 0) return;
+  const dim3 g((unsigned)((a.nb + 255) / 256)), b(256);
+  auto k = a.order == 2 ? recon_pose_table_kernel<2> : recon_pose_table_kernel<4>;
+  if (t0 || t1) hipExtLaunchKernelGGL(k, g, b, 0, s, t0, t1, 0, a, out);
+  else hipLaunchKernelGGL(k, g, b, 0, s, a, out);
+}
+
+static_assert(kBinWindow * kBinWindow % kReconThreads == 0, "window cells per thread");
+template <bool FIXED>
+__global__ __launch_bounds__(kReconThreads) void recon_votes_lds_kernel(const ReconLdsArgs g) {
+  __shared__ fix_t win[kBinWindow * kBinStride];
+  __shared__ unsigned sh_inside, sh_fall;
+  const BeSplatArgs &a = g.cam;
+  const BinnedEvents &b = g.ev;
+  // (the launch is sized by an upper bound of the table's length, and so is the table's allocation: be_splat_lds_kernel)
+  const Chunk c = b.chunks[blockIdx.x];
+  if ((int)blockIdx.x >= *b.nchunks_dev) return;
+  const bool has_win = c.wx0 > -100000000;
+  const int tid = threadIdx.x;
+  if (tid == 0) { sh_inside = 0; sh_fall = 0; }
+  if (has_win)
+    for (int p = tid; p < kBinWindow * kBinStride; p += kReconThreads) win[p] = 0ull;
+  __syncthreads();
+  unsigned inside = 0, nfall = 0;
+  constexpr int U = 2;  // events in flight per thread, as in be_splat_lds_kernel
+  for (int j0 = c.beg + tid; j0 < c.end; j0 += kReconThreads * U) {
+    uint32_t e[U], bi[U];
+    bool act[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int j = j0 + u * kReconThreads;
+      act[u] = j < c.end;
+      e[u] = act[u] ? b.sxy[j] & 0x7fffffffu : 0u;
+      bi[u] = act[u] ? b.sbatch[j] : 0u;
+    }
+    double v0[U], v1[U], v2[U], R[U][9];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const double *Rp = a.poseR[bi[u]].R;
+#pragma unroll
+      for (int k = 0; k < 9; k++) R[u][k] = Rp[k];
+      load_bearing(a, (int)(e[u] & 0xffff), (int)(e[u] >> 16), v0[u], v1[u], v2[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const BeWarp w = be_warp_math<0>(a, e[u], (int)bi[u], v0[u], v1[u], v2[u], R[u]);
+      if (act[u] && w.ok) {  // 1 <= xx < Wp - 2 && 1 <= yy < Hp - 2: the four cells are inside the plane
+        inside++;
+        const int lx = w.xx - c.wx0, ly = w.yy - c.wy0;
+        if (has_win && lx >= 0 && lx < kBinWindow - 1 && ly >= 0 && ly < kBinWindow - 1) {
+          vote4_lds(win, lx, ly, w.dx, w.dy);
+        } else {
+          if (FIXED) vote4_global_fix(b.fixed, a.Wp, w.xx, w.yy, w.dx, w.dy);
+          else vote4_global(g.plane, a.Wp, w.xx, w.yy, w.dx, w.dy);
+          nfall++;
+        }
+      }
+    }
+  }
+  // events that voted, and those of them on the global path: one wave reduction, one LDS add per wave, one atomic per workgroup
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    inside += __shfl_down(inside, off, 64);
+    nfall += __shfl_down(nfall, off, 64);
+  }
+  if ((tid & 63) == 0) {
+    if (inside) atomicAdd(&sh_inside, inside);
+    if (nfall) atomicAdd(&sh_fall, nfall);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    if (sh_inside) atomicAdd(g.n_inside, (unsigned long long)sh_inside);
+    if (sh_fall) atomicAdd(b.fallback, sh_fall);
+  }
+  if (has_win) {
+    constexpr int kCells = kBinWindow * kBinWindow / kReconThreads;  // (reads first, then the flush: be_splat_lds_kernel)
+    fix_t cell[kCells];
+#pragma unroll
+    for (int k = 0; k < kCells; k++) {
+      const int p = tid + kReconThreads * k, ly = p / kBinWindow, lx = p - ly * kBinWindow;
+      cell[k] = win[ly * kBinStride + lx];
+    }
+#pragma unroll
+    for (int k = 0; k < kCells; k++) {
+      const fix_t v = cell[k];
+      if (v != 0ull) {  // (a cell outside the plane never received a vote)
+        const int p = tid + kReconThreads * k, ly = p / kBinWindow, lx = p - ly * kBinWindow;
+        const size_t at = (size_t)(c.wy0 + ly) * a.Wp + (c.wx0 + lx);
+        if (FIXED) atomicAdd(b.fixed + at, v);
+        else atomic_add_f32(g.plane + at, (float)((double)v * kFixInv));
+      }
+    }
+  }
+}
+void launch_recon_votes_lds(const ReconLdsArgs &g, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {
+  if (g.ev.nchunks <= 0) return;
+  const dim3 gr((unsigned)g.ev.nchunks), b(kReconThreads);
+  auto k = g.ev.fixed ? recon_votes_lds_kernel<true> : recon_votes_lds_kernel<false>;
+  if (t0 || t1) hipExtLaunchKernelGGL(k, gr, b, 0, s, t0, t1, 0, g);
+  else hipLaunchKernelGGL(k, gr, b, 0, s, g);
+}
+
 __global__ __launch_bounds__(256) void recon_fixed_to_float_kernel(const fix_t *fixed, float *plane, size_t n) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
     plane[i] = (float)((double)fixed[i] * kFixInv);

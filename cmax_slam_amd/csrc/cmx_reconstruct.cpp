@@ -5,8 +5,12 @@
 // On top of it, the whole-trajectory contrast and its gradient with respect to a left increment of EVERY control pose
 // (recon_contrast, recon_grad_add*, recon_grad_get, recon_eval_from): the image pass over the plane and a second pass over the same
 // events, in the adjoint form of the window path -- per batch one 3-vector through the 3 x 3N spline Jacobian,
-// so nothing grows with the knot count but the 2 x 3K sums.
+// so nothing grows with the knot count but the 2 x 3K sums.  And for an optimiser that evaluates the SAME events many times: events
+// bound once (recon_bind_from), evaluated through a batch-pose table, a tile sort of the reconstruction's own and LDS votes
+// (recon_eval_bound).
 // Kernels: cmx_recon.hip.
+#include <limits>
+
 #include "cmx_context.hpp"
 
 // Raw events per internal slice (a whole number of batches).  Staging -- two slots of pinned + device memory for the packed events
@@ -29,6 +33,41 @@ struct ReconSlot {
   size_t xy_cap = 0, bt_cap = 0, h_bt_cap = 0;  // (h_bt: host paths only)
   hipEvent_t up = nullptr, done = nullptr;  // upload complete (copy stream) / vote kernel complete (context stream)
   bool busy = false;
+};
+
+// Events bound to the reconstruction (cmx_backend_recon_bind_from): the sampled events of the range in time order, their batch
+// times, and what the tile-sorted vote pass of cmx_backend_recon_eval_bound needs -- all of it the reconstruction's own, nothing of
+// the context's binning state (d_sxy, d_chunks, bin_valid, ...) is used: the window's sort survives a whole-trajectory evaluation.
+// Resident bytes per sampled event: 4 (xy) + 4 (keys) + 4 (sxy) + 4 (sbatch) = 16, plus 80 per batch (time, PoseR); the counting
+// sort's histogram table and the chunk table depend on the panorama, not on the events.
+struct ReconBound {
+  int64_t n_events = 0;                 // events of the bound range
+  BatchPlan plan;                       // its batches; plan.n_packed = events the sampling selects
+  uint32_t *d_xy = nullptr;             // [n_packed] packed, time order, per_batch slots per batch
+  long long *d_bt = nullptr;            // [nb] batch pose times
+  PoseR *d_poseR = nullptr;             // [nb] batch poses of the current evaluation
+  uint32_t *d_keys = nullptr, *d_sxy = nullptr, *d_sbatch = nullptr;  // [n_packed] sort keys; events and batch indices in tile order
+  uint32_t *d_keys_s = nullptr, *d_idx = nullptr, *d_idx_s = nullptr; // radix-sort fallback (key spaces above count_sort_ok) ...
+  void *d_sort_temp = nullptr;                                        // ... allocated by the first sort that needs them
+  size_t sort_temp_cap = 0;
+  int *d_hist = nullptr, *d_tile_start = nullptr, *d_nchunks = nullptr;
+  Chunk *d_chunks = nullptr;
+  // the table's allocation and every vote launch's size: an upper bound known on the host (workgroups beyond the table's true
+  // length return at once; launching that length instead was measured and gained nothing: 0.453 -> 0.452 ms at 20M events);
+  // events per full chunk
+  int max_chunks = 0, chunk_events = 0;
+  unsigned *d_fallback = nullptr;       // votes of the last evaluation that left their LDS window
+  unsigned long long *h_stat = nullptr; // pinned: [0] = n_inside, [1] = fallback word of the last evaluation
+  bool sorted = false;
+  int64_t sorts = 0;
+  double fallback_frac = 0;
+  void release() {
+    void *dev[] = {d_xy, d_bt, d_poseR, d_keys, d_sxy, d_sbatch, d_keys_s, d_idx, d_idx_s, d_sort_temp, d_hist, d_tile_start, d_nchunks,
+                   d_chunks, d_fallback};
+    for (void *p : dev) (void)hipFree(p);
+    if (h_stat) (void)hipHostFree(h_stat);
+    *this = ReconBound{};
+  }
 };
 
 struct ReconState {
@@ -64,6 +103,9 @@ struct ReconState {
   int64_t g_sampled = 0;                  // events the gradient pass has sampled
   int measure = CMX_VARIANCE;
   double mu = 0;
+  // ---- bound events (recon_bind_from .. recon_unbind): survive restart, dropped by begin and end
+  bool bound = false;
+  ReconBound bnd;
 };
 
 void recon_release(cmx_ctx *c) {
@@ -98,6 +140,7 @@ void recon_release(cmx_ctx *c) {
   (void)hipFree(r->d_voted);
   (void)hipFree(r->d_rows);
   (void)hipFree(r->d_row_win);
+  r->bnd.release();
   delete r;
   c->recon = nullptr;
 }
@@ -413,22 +456,27 @@ int cmx_backend_recon_grad_add_from(cmx_ctx *c, const cmx_events *e, int64_t fir
 }
 
 // new knot values for the trajectory of begin; plane, counters and gradient state start over.  Nothing is allocated or freed.
-int cmx_backend_recon_restart(cmx_ctx *c, const double *knots_xyzw) {
-  int rc = recon_enter(c, true);
-  if (rc) return rc;
-  if (!knots_xyzw) return fail(c, CMX_ERR_INVALID_ARG, "null knot array");
-  ReconState *r = c->recon;
+// (knots_xyzw == NULL, eval_bound only: the current knots stay, and nothing of the caller's is read -- no wait)
+static int recon_start_over(cmx_ctx *c, ReconState *r, const double *knots_xyzw) {
   const size_t np = (size_t)c->Wp * c->Hp;
   r->grad_open = false;
   r->n_sampled = 0;
-  HIP_TRY(c, hipMemcpyAsync(r->d_knots, knots_xyzw, (size_t)r->sup.K * sizeof(Quat), hipMemcpyHostToDevice, c->stream));
-  launch_recon_delta(r->d_knots, r->sup.K, r->d_delta, c->stream);
+  if (knots_xyzw) {
+    HIP_TRY(c, hipMemcpyAsync(r->d_knots, knots_xyzw, (size_t)r->sup.K * sizeof(Quat), hipMemcpyHostToDevice, c->stream));
+    launch_recon_delta(r->d_knots, r->sup.K, r->d_delta, c->stream);
+  }
   HIP_TRY(c, hipMemsetAsync(r->d_plane, 0, np * sizeof(float), c->stream));
   HIP_TRY(c, hipMemsetAsync(r->d_inside, 0, sizeof(unsigned long long), c->stream));
   if (r->d_fixed) HIP_TRY(c, hipMemsetAsync(r->d_fixed, 0, np * sizeof(unsigned long long), c->stream));
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller's knot array is free again
+  if (knots_xyzw) HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller's knot array is free again
   return CMX_OK;
+}
+int cmx_backend_recon_restart(cmx_ctx *c, const double *knots_xyzw) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (!knots_xyzw) return fail(c, CMX_ERR_INVALID_ARG, "null knot array");
+  return recon_start_over(c, c->recon, knots_xyzw);
 }
 
 static void recon_refresh_plane(cmx_ctx *c, ReconState *r);
@@ -573,6 +621,230 @@ int cmx_backend_recon_eval_from(cmx_ctx *c, const cmx_events *e, int64_t first, 
   if (!rc) rc = recon_add_store(c, src, false);
   if (!rc) rc = cmx_backend_recon_contrast(c, blur_sigma, contrast_measure, grad != nullptr, contrast);
   if (!rc && grad) rc = recon_add_store(c, src, true);
+  if (!rc && grad) rc = cmx_backend_recon_grad_get(c, grad);
+  return rc;
+}
+
+// ---- bound events: hand the events over ONCE, evaluate them many times (an optimiser's trial points) with the votes made through LDS
+// bind_from   validation of recon_add_from, then the sampled events of the range, packed in time order, and their batch times into
+//             memory of the reconstruction's own, with the buffers of the tile sort; everything is built beside an earlier binding,
+//             which is replaced only once nothing can fail any more
+// eval_bound  restart + eval_from over the bound events: batch-pose table behind recon_delta, tile sort at the first evaluation and
+//             again after one whose votes left their windows (kRebinFallbackFrac), recon_votes_lds, the image pass, and the gather
+//             pass over the time-ordered copy in recon_add_store's slices
+constexpr int64_t kMaxBoundSampled = 1LL << 30;  // (sorted positions, chunk bounds and keys are 32-bit)
+
+static int bound_build(cmx_ctx *c, ReconState *r, const EventSource &src, const BatchPlan &p, ReconBound *b) {
+  b->n_events = src.n;
+  b->plan = p;
+  HIP_TRY(c, hipHostMalloc((void **)&b->h_stat, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+  b->h_stat[0] = b->h_stat[1] = 0ull;
+  if (p.nb == 0) return CMX_OK;  // (0 or 1 events: nothing to vote)
+  HIP_TRY(c, hipMalloc((void **)&b->d_bt, (size_t)p.nb * sizeof(long long)));
+  int rc = queue_batch_times(c, src.d_t, src.n, r->B, p.nb, r->sup, b->d_bt, r->d_err, true);
+  if (rc) return rc;
+  HIP_TRY(c, hipGetLastError());
+  BatchTimeError bad;
+  rc = read_batch_errors(c, r->d_err, &bad);
+  if (rc) return rc;
+  if (bad.kind) return fail_batch_time(c, bad, r->sup, /*with_event=*/false);
+  // ---- valid: the copy, and the sort's buffers
+  const size_t n = (size_t)p.n_packed;
+  const int tiles = ((c->Wp + kBinTile - 1) / kBinTile) * ((c->Hp + kBinTile - 1) / kBinTile);
+  const int ntiles = 2 * tiles;  // (the back end's sort keys carry the old / new bit: no bound event sets it, half of the bins stay empty)
+  HIP_TRY(c, hipMalloc((void **)&b->d_xy, n * sizeof(uint32_t)));
+  HIP_TRY(c, hipMalloc((void **)&b->d_poseR, (size_t)p.nb * sizeof(PoseR)));
+  HIP_TRY(c, hipMalloc((void **)&b->d_keys, n * sizeof(uint32_t)));
+  HIP_TRY(c, hipMalloc((void **)&b->d_sxy, n * sizeof(uint32_t)));
+  HIP_TRY(c, hipMalloc((void **)&b->d_sbatch, n * sizeof(uint32_t)));
+  if (count_sort_ok(ntiles + 1))
+    HIP_TRY(c, hipMalloc((void **)&b->d_hist, count_sort_scratch_ints((int)n, ntiles + 1) * sizeof(int)));
+  HIP_TRY(c, hipMalloc((void **)&b->d_tile_start, ((size_t)ntiles + 2) * sizeof(int)));
+  // chunk size and the table's bound: do_binning's rule for the back end (plan_bound, cmx_ingest.hpp)
+  const BoundPlan bp = plan_bound(p.n_packed, ntiles);
+  b->chunk_events = bp.chunk_events;
+  b->max_chunks = (int)bp.max_chunks;  // (n <= 2^30, at most 2^20 tiles: below 2^23)
+  HIP_TRY(c, hipMalloc((void **)&b->d_chunks, (size_t)b->max_chunks * sizeof(Chunk)));
+  HIP_TRY(c, hipMalloc((void **)&b->d_nchunks, sizeof(int)));
+  HIP_TRY(c, hipMalloc((void **)&b->d_fallback, sizeof(unsigned)));
+  HIP_TRY(c, hipMemsetAsync(b->d_nchunks, 0, sizeof(int), c->stream));
+  HIP_TRY(c, hipMemsetAsync(b->d_fallback, 0, sizeof(unsigned), c->stream));
+  // (t_next = the smallest time: no event carries the old flag)
+  launch_be_pack_from_store(src.d_xy, reinterpret_cast<const long long *>(src.d_t), (long long)src.n, r->B, r->rate, p.per_batch, (int)n,
+                            std::numeric_limits<long long>::min(), b->d_xy, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the store may be pushed to, compacted or closed from here on
+  return CMX_OK;
+}
+
+int cmx_backend_recon_bind_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  EventSource src;
+  rc = store_source(c, e, first, count, &src);
+  if (rc) return rc;
+  ReconState *r = c->recon;
+  (void)recon_pass_enter(c, r, false);  // as every add: an open gradient pass is closed
+  if (src.n < 0 || src.n > kMaxEvents) return fail(c, CMX_ERR_INVALID_ARG, "bad event count %lld", (long long)src.n);
+  BatchPlan p;
+  int slice_batches = 1;
+  rc = recon_plan(c, r, src.n, &p, &slice_batches);
+  if (rc) return rc;
+  if (p.n_packed > kMaxBoundSampled)
+    return fail(c, CMX_ERR_INVALID_ARG, "%lld sampled events above the limit of a binding (2^30)", (long long)p.n_packed);
+  ReconBound b;
+  rc = bound_build(c, r, src, p, &b);
+  if (rc) {  // (an earlier binding is intact: nothing of it was touched)
+    (void)hipStreamSynchronize(c->stream);
+    b.release();
+    return rc;
+  }
+  r->bnd.release();
+  r->bnd = b;
+  r->bound = true;
+  return CMX_OK;
+}
+
+int cmx_backend_recon_unbind(cmx_ctx *c) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  ReconState *r = c->recon;
+  if (!r->bound) return CMX_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  r->bnd.release();
+  r->bound = false;
+  return CMX_OK;
+}
+
+int cmx_backend_recon_bound_info(cmx_ctx *c, int64_t *n_events, int64_t *n_sampled, int64_t *sorts, double *fallback_frac) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  const ReconState *r = c->recon;  // (without a binding: all zero)
+  if (n_events) *n_events = r->bound ? r->bnd.n_events : 0;
+  if (n_sampled) *n_sampled = r->bound ? r->bnd.plan.n_packed : 0;
+  if (sorts) *sorts = r->bound ? r->bnd.sorts : 0;
+  if (fallback_frac) *fallback_frac = r->bound ? r->bnd.fallback_frac : 0.0;
+  return CMX_OK;
+}
+
+// the bound events by the destination tile of their vote under the pose table as it stands, and the chunk table
+static int bound_sort(cmx_ctx *c, ReconBound &b, const BeSplatArgs &be) {
+  const int n = (int)b.plan.n_packed;
+  const int tiles_x = (c->Wp + kBinTile - 1) / kBinTile, tiles = tiles_x * ((c->Hp + kBinTile - 1) / kBinTile), ntiles = 2 * tiles;
+  if (b.d_hist) {
+    launch_count_sort(nullptr, &be, tiles_x, tiles, b.d_xy, b.plan.per_batch, n, b.d_keys, b.d_hist, b.d_tile_start, b.d_sxy, b.d_sbatch,
+                      nullptr, nullptr, c->stream);
+  } else {  // more destination tiles than an LDS histogram holds: (key, index) radix sort, as do_binning
+    if (!b.d_keys_s) {
+      uint32_t **ptrs[3] = {&b.d_keys_s, &b.d_idx, &b.d_idx_s};
+      for (auto p : ptrs) HIP_TRY(c, hipMalloc((void **)p, (size_t)n * sizeof(uint32_t)));
+    }
+    launch_be_bin_keys(be, tiles_x, tiles, b.d_keys, b.d_idx, c->stream);
+    int end_bit = 1;
+    while ((1 << end_bit) <= ntiles) end_bit++;
+    size_t tb = 0;
+    if (sort_pairs_u32(nullptr, &tb, b.d_keys, b.d_keys_s, b.d_idx, b.d_idx_s, (unsigned)n, end_bit, c->stream) != 0)
+      return fail(c, CMX_ERR_HIP, "rocprim radix sort (size query) failed");
+    if (tb > b.sort_temp_cap || !b.d_sort_temp) {
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      (void)hipFree(b.d_sort_temp);
+      b.d_sort_temp = nullptr;
+      b.sort_temp_cap = 0;
+      HIP_TRY(c, hipMalloc(&b.d_sort_temp, tb ? tb : 1));
+      b.sort_temp_cap = tb;
+    }
+    if (sort_pairs_u32(b.d_sort_temp, &tb, b.d_keys, b.d_keys_s, b.d_idx, b.d_idx_s, (unsigned)n, end_bit, c->stream) != 0)
+      return fail(c, CMX_ERR_HIP, "rocprim radix sort failed");
+    launch_apply_perm(b.d_xy, b.d_idx_s, b.plan.per_batch, n, b.d_sxy, b.d_sbatch, c->stream);
+    launch_tile_lower_bound(b.d_keys_s, n, ntiles + 2, b.d_tile_start, c->stream);
+  }
+  launch_build_chunks(b.d_tile_start, ntiles, 2, tiles_x, kBinMargin, b.chunk_events, b.d_chunks, b.d_nchunks, nullptr, 0, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  b.sorted = true;
+  b.sorts++;
+  return CMX_OK;
+}
+
+// the gradient pass over the bound time-ordered copy: recon_add_store's slices, runs and launches, with stride 0
+static int bound_gather(cmx_ctx *c, ReconState *r) {
+  if (int rc0 = recon_pass_enter(c, r, true)) return rc0;
+  const ReconBound &b = r->bnd;
+  const BatchPlan &p = b.plan;
+  const int64_t sb = g_slice_events.load(std::memory_order_relaxed) / r->B;
+  const int slice_batches = (int)(sb < 1 ? 1 : sb);
+  ReconGatherArgs ga = recon_gather_args(c, r);
+  ReconArgs &a = ga.ev;
+  for (int b_lo = 0; b_lo < p.nb; b_lo += slice_batches) {
+    const BoundSlice sl = bound_slice(p, b_lo, slice_batches);
+    a.xy = b.d_xy + sl.first; a.stride = 0;
+    a.batch_t = b.d_bt + b_lo; a.nb = sl.b_hi - b_lo;
+    a.n = (int)sl.n;
+    const int rc = queue_gather(c, r, ga);
+    if (rc) return rc;
+  }
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  r->g_sampled += p.n_packed;
+  return CMX_OK;
+}
+
+int cmx_backend_recon_eval_bound(cmx_ctx *c, const double *knots_xyzw, double blur_sigma, int contrast_measure, double *contrast,
+                                 double *grad) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  ReconState *r = c->recon;
+  if (!r->bound) return fail(c, CMX_ERR_STATE, "no events are bound (cmx_backend_recon_bind_from)");
+  if (!contrast) return fail(c, CMX_ERR_INVALID_ARG, "null output");
+  if (grad) {  // (before anything is changed, as in eval_from)
+    rc = recon_setup_blur(c, r, blur_sigma);
+    if (rc) return rc;
+    if (!(c->Wp > 2 * r->radius + 1 && c->Hp > 2 * r->radius + 1))
+      return fail(c, CMX_ERR_INVALID_ARG, "panorama %d x %d too small for the adjoint gradient at blur radius %d", c->Wp, c->Hp, r->radius);
+  }
+  ReconBound &b = r->bnd;
+  rc = recon_start_over(c, r, knots_xyzw);
+  if (rc) return rc;
+  if (b.plan.n_packed > 0) {
+    ReconArgs a = recon_args(c, r);
+    a.batch_t = b.d_bt; a.nb = b.plan.nb;
+    {
+      Span sp(c, CMX_T_POSE, /*exact=*/true);
+      launch_recon_pose_table(a, b.d_poseR, c->stream, sp.t0(), sp.t1());
+    }
+    ReconLdsArgs g{};
+    g.cam = a.cam;
+    g.cam.poseR = b.d_poseR;
+    g.cam.xy = b.d_xy;
+    g.cam.per_batch = b.plan.per_batch;
+    g.cam.n = (int)b.plan.n_packed;
+    g.cam.order = r->sup.order;
+    if (!b.sorted || b.fallback_frac > kRebinFallbackFrac) {
+      Span sp(c, CMX_T_BATCH);
+      rc = bound_sort(c, b, g.cam);
+      if (rc) return rc;
+    }
+    g.ev.sxy = b.d_sxy; g.ev.sbatch = b.d_sbatch;
+    g.ev.chunks = b.d_chunks; g.ev.nchunks = b.max_chunks; g.ev.nchunks_dev = b.d_nchunks;
+    g.ev.fallback = b.d_fallback;
+    g.ev.fixed = r->deterministic ? r->d_fixed : nullptr;
+    g.plane = r->d_plane;
+    g.n_inside = r->d_inside;
+    HIP_TRY(c, hipMemsetAsync(b.d_fallback, 0, sizeof(unsigned), c->stream));
+    {
+      Span sp(c, CMX_T_SPLAT, /*exact=*/true);
+      launch_recon_votes_lds(g, c->stream, sp.t0(), sp.t1());
+    }
+    HIP_TRY(c, hipGetLastError());
+    // (into pinned memory of the binding's own; complete once the image pass below has waited for the stream)
+    b.h_stat[1] = 0ull;
+    HIP_TRY(c, hipMemcpyAsync(&b.h_stat[0], r->d_inside, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&b.h_stat[1], b.d_fallback, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    r->n_sampled += b.plan.n_packed;
+  }
+  rc = cmx_backend_recon_contrast(c, blur_sigma, contrast_measure, grad != nullptr, contrast);
+  if (rc && hipStreamSynchronize(c->stream) != hipSuccess) return rc;  // (the two words below are not known to have arrived)
+  if (b.plan.n_packed > 0) b.fallback_frac = b.h_stat[0] ? (double)(unsigned)b.h_stat[1] / (double)b.h_stat[0] : 0.0;
+  if (!rc && grad) rc = bound_gather(c, r);
   if (!rc && grad) rc = cmx_backend_recon_grad_get(c, grad);
   return rc;
 }

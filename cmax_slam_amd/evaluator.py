@@ -678,11 +678,41 @@ class BackendEvaluator(_Evaluator):
                                                      float(sigma), int(measure), C.byref(out), _dp(g) if want_grad else None))
         return out.value, g
 
+    # --- bound events (cmx_backend_recon_bind_from .. _bound_info): hand the events over once, evaluate them many times
+    def reconstruct_bind(self, store, first, count):
+        """Copy events_[first, first+count) of an EventStore -- those the sampling selects, and their batch times -- into the open
+        reconstruction; the store may change or be closed afterwards.  A second call replaces the binding."""
+        self._ck(self._L.cmx_backend_recon_bind_from(self._ctx, store._h, int(first), int(count)))
+
+    def reconstruct_unbind(self):
+        self._ck(self._L.cmx_backend_recon_unbind(self._ctx))
+
+    def reconstruct_eval_bound(self, knots=None, sigma=1.0, measure=VARIANCE, want_grad=True):
+        """reconstruct_eval over the bound events, always from a zeroed plane (knots None: the current ones), with the votes made
+        through LDS over a tile sort kept from one evaluation to the next: (contrast, grad | None)."""
+        k = None
+        if knots is not None:
+            k = _c(knots, np.float64).reshape(-1, 4)
+            if self._recon_K and k.shape[0] != self._recon_K:
+                raise ValueError("eval takes the %d knots of begin, got %d" % (self._recon_K, k.shape[0]))
+        out = C.c_double()
+        g = np.empty(3 * self._recon_K, np.float64) if want_grad else None
+        self._ck(self._L.cmx_backend_recon_eval_bound(self._ctx, _dp(k) if k is not None else None, float(sigma), int(measure),
+                                                      C.byref(out), _dp(g) if want_grad else None))
+        return out.value, g
+
+    def reconstruct_bound_info(self):
+        """{'n_events', 'n_sampled', 'sorts' (tile sorts since the bind), 'fallback_frac' (share of the last evaluation's voting
+        events that left their LDS window)}; all zero without a binding."""
+        ne, ns, so, ff = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
+        self._ck(self._L.cmx_backend_recon_bound_info(self._ctx, C.byref(ne), C.byref(ns), C.byref(so), C.byref(ff)))
+        return {"n_events": ne.value, "n_sampled": ns.value, "sorts": so.value, "fallback_frac": ff.value}
+
     def reconstruct_refine(self, store, first, count, order, knots, start_ns, dt_ns, num_fixed, sigma=1.0, measure=VARIANCE,
-                           event_batch_size=100, event_sample_rate=1, **solver_kw):
+                           event_batch_size=100, event_sample_rate=1, bind=False, **solver_kw):
         """One bundle adjustment over the whole recording: FR-CG (the back end's constants unless given) over a left increment
         of every control pose but the first num_fixed, cost = -contrast of the panorama of events_[first, first+count).
-        Returns (knots, report)."""
+        bind=True: the events are bound once and every trial point is a reconstruct_eval_bound.  Returns (knots, report)."""
         from . import solver
         k0 = np.array(_c(knots, np.float64).reshape(-1, 4), copy=True)
         K = k0.shape[0]
@@ -698,11 +728,16 @@ class BackendEvaluator(_Evaluator):
             return k
 
         def fdf(x, want_grad):
-            c, g = self.reconstruct_eval(store, first, count, moved(x), sigma, measure, want_grad)
+            if bind:
+                c, g = self.reconstruct_eval_bound(moved(x), sigma, measure, want_grad)
+            else:
+                c, g = self.reconstruct_eval(store, first, count, moved(x), sigma, measure, want_grad)
             return -c, (-g[3 * nf:] if want_grad else None)
 
         self.reconstruct_begin(order, k0, start_ns, dt_ns, event_batch_size, event_sample_rate)
         try:
+            if bind:
+                self.reconstruct_bind(store, first, count)
             x, rep = solver.frcg_minimize(fdf, np.zeros(3 * (K - nf)), **kw)
         finally:
             self.reconstruct_end()

@@ -79,11 +79,13 @@ def _support_range(traj, t):
     return int(np.searchsorted(t, traj.t_beg_ns, side="left")), int(np.searchsorted(t, t_hi, side="left"))
 
 
-def refine_trajectory(be, traj, x, y, t, prm, store=None):
+def refine_trajectory(be, traj, x, y, t, prm, store=None, bind=False):
     """One bundle adjustment over the WHOLE recording, the step a rotational event SLAM ends with once the sliding windows have
     passed: FR-CG over every control pose but the first order - 1 (a common rotation of all of them is a gauge freedom of the
     contrast), cost = -contrast of the panorama of all events along the trajectory: BackendEvaluator.reconstruct_refine
-    (cmx_backend_recon_eval_from).  Returns (refined knots, report); the report carries contrast_before / contrast_after."""
+    (cmx_backend_recon_eval_from; bind=True: the events are bound once and every trial point is a cmx_backend_recon_eval_bound, votes
+    through LDS over a tile sort kept between evaluations).  Returns (refined knots, report); the report carries contrast_before /
+    contrast_after."""
     i0, i1 = _support_range(traj, t)
     own = store is None
     if own:  # (the evaluation reads its events from a device-resident store)
@@ -93,7 +95,7 @@ def refine_trajectory(be, traj, x, y, t, prm, store=None):
     try:
         knots, rep = be.reconstruct_refine(store, i0, i1 - i0, traj.order, traj.knots, traj.t_beg_ns, traj.dt_ns, traj.order - 1,
                                            sigma=prm.backend_blur_sigma, event_batch_size=prm.event_batch_size,
-                                           event_sample_rate=prm.backend_event_sample_rate)
+                                           event_sample_rate=prm.backend_event_sample_rate, bind=bind)
     finally:
         if own:
             store.close()
@@ -118,13 +120,15 @@ def reconstruct_panorama(be, traj, x, y, t, prm, store=None, knots=None):
     return i0, i1 - i0
 
 
-def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefix=None, reconstruct=False, refine_global=False):
+def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefix=None, reconstruct=False, refine_global=False,
+                 refine_bound=False):
     """stream: synth.EventStream (or anything with x, y, t_ns, W, H, fx, fy, cx, cy, lut).  Returns a dict.
     display_prefix: write the final panorama with the last pose's FOV and the last packet's local-IWE pair there.
     reconstruct: after the last window, re-warp all events along the whole refined trajectory (res["recon"]; with
     display_prefix also <prefix>_recon.pgm).
     refine_global: after the last window, one bundle adjustment over the whole trajectory (res["refined_knots"],
-    res["refine_report"]); the trajectory in res["traj"] stays the sliding windows' -- reconstruct then warps along the refined knots."""
+    res["refine_report"]); the trajectory in res["traj"] stays the sliding windows' -- reconstruct then warps along the refined knots.
+    refine_bound: that bundle adjustment binds the events once (reconstruct_refine(bind=True))."""
     prm = prm or Params()
     x, y, t = stream.x, stream.y, stream.t_ns
     n_total = len(t)
@@ -279,7 +283,7 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
                reports=reports, fe_ms=fe_ms, be_ms=be_ms, windows=count_window)
     if refine_global and traj.size() >= traj.order:
         t0 = time.perf_counter()
-        res["refined_knots"], res["refine_report"] = refine_trajectory(be, traj, x, y, t, prm, store)
+        res["refined_knots"], res["refine_report"] = refine_trajectory(be, traj, x, y, t, prm, store, bind=refine_bound)
         if log:
             r = res["refine_report"]
             log("global refinement: %d events, %d control poses, %d iterations (%d f, %d df) in %.2f ms; contrast %.6g -> %.6g" %
@@ -356,6 +360,8 @@ def main():
                     help="after the last window, re-warp ALL events along the whole refined trajectory (with --display: PREFIX_recon.pgm)")
     ap.add_argument("--refine-global", action="store_true",
                     help="after the last window, one bundle adjustment over the whole trajectory (--reconstruct then uses its result)")
+    ap.add_argument("--refine-bound", action="store_true",
+                    help="with --refine-global: bind the events once and evaluate every trial point over the bound copy")
     a = ap.parse_args()
     stream = synth.event_stream(a.rate, a.seconds, 240, 180, 200.0, 200.0, 119.5, 89.5, omega_mean=(0.2, 1.8, 0.3),
                                 omega_amp=(1.0, 0.8, 1.0))
@@ -364,7 +370,7 @@ def main():
     prm.deterministic = a.deterministic
     t0 = time.perf_counter()
     res = run_pipeline(stream, prm, use_event_store=not a.host_events, log=print, display_prefix=a.display, reconstruct=a.reconstruct,
-                       refine_global=a.refine_global)
+                       refine_global=a.refine_global, refine_bound=a.refine_bound)
     wall = time.perf_counter() - t0
     m = evaluate_against_truth(stream, res)
     print("%.2f s of events (%d) processed in %.2f s wall" % (a.seconds, len(stream.x), wall))

@@ -382,6 +382,42 @@ int cmx_backend_recon_grad_get(cmx_ctx *ctx, double *grad /* 3K */);
 int cmx_backend_recon_eval_from(cmx_ctx *ctx, const cmx_events *ev, int64_t first, int64_t count,
                                 const double *knots_xyzw /* K x 4, or NULL = keep */, double blur_sigma,
                                 int contrast_measure, double *contrast, double *grad /* 3K or NULL */);
+/* Bound events: an optimiser over the whole trajectory evaluates the SAME events hundreds of times along slightly moved knots.
+ * eval_from reads the event store again every time and votes with one global atomic per bilinear corner; these calls hand the
+ * events over once and vote through LDS:
+ *     recon_begin   recon_bind_from(events)   recon_eval_bound(knots) ...   recon_unbind / recon_end
+ *   bind_from   validation and status codes of add_from, all of it before any device state changes.  Copies what the evaluations
+ *               need into memory the reconstruction owns -- the events of the range the sampling selects, packed in time order, and
+ *               the batch pose times -- so the store may be pushed to, compacted or closed afterwards.  Votes nothing; the plane, the
+ *               counters and the knots stay as they are; an open gradient pass is closed.  A second bind replaces the first; a call
+ *               that fails validation leaves an earlier binding intact.  count of 0 or 1 is valid and binds nothing to vote.
+ *               Limit: at most 2^30 sampled events (CMX_ERR_INVALID_ARG above: sorted positions are 32-bit).  Resident memory: 16
+ *               bytes per sampled event and 80 per batch, plus the sort's tables (a function of the panorama: 34 MB at 4096 x 2048).
+ *   unbind      frees the bound buffers; CMX_OK without a binding.  begin and end drop a binding too; restart keeps it.
+ *   eval_bound  by definition restart(knots_xyzw, or the current knots when NULL) followed by eval_from over the bound events: it
+ *               always starts from a zeroed plane, and leaves the reconstruction as eval_from would -- the plane readable by get /
+ *               render, n_sampled and n_inside exact, the gradient repeatable by grad_get, later add* calls accumulating on top.
+ *               blur_sigma, contrast_measure and the size rule of grad != NULL as in contrast.  CMX_ERR_STATE without a binding.
+ *               How: a batch-pose table (72 bytes per batch) behind the knots' logarithms; the bound events sorted by the 32 x 32
+ *               destination tile of their vote -- in front of the first evaluation after a bind, and again in front of an evaluation
+ *               when more than 3 % of the previous one's voting events left their LDS window (the rule of the window path); one
+ *               workgroup per chunk of a tile's events votes into a 64 x 64 window of 64-bit 2^-30 fixed-point cells in LDS and
+ *               adds every touched cell to the plane once; a vote outside the window goes to the plane directly, so the result is
+ *               exact wherever the knots move.  The sort, the chunk table and the counters belong to the reconstruction: the
+ *               window's sort and cmx_get_stats' re-sort count are not touched.  The gradient pass runs over the time-ordered copy
+ *               in eval_from's slices.  Under cmx_timing_enable: CMX_T_POSE = the pose table, CMX_T_SPLAT = the vote kernel,
+ *               CMX_T_BATCH = the tile sort (bracketed on the stream), when one ran.
+ *   bound_info  any pointer may be NULL; all zero without a binding.  *n_events = events bound, *n_sampled = those the sampling
+ *               selects, *sorts = tile sorts run since the bind, *fallback_frac = the share of the last evaluation's voting events
+ *               that left their LDS window.
+ * CMX_OPT_DETERMINISTIC = 1 at begin: plane, counters and contrast are bitwise those of eval_from over the same events at the same
+ * knots (the same integers are added, in another order); the gradient is bitwise identical from run to run and agrees with
+ * eval_from's to summation order.  Otherwise every window's sum is rounded to fp32 once, when it is added to the plane. */
+int cmx_backend_recon_bind_from(cmx_ctx *ctx, const cmx_events *ev, int64_t first, int64_t count);
+int cmx_backend_recon_unbind(cmx_ctx *ctx);
+int cmx_backend_recon_eval_bound(cmx_ctx *ctx, const double *knots_xyzw /* K x 4, or NULL = keep */, double blur_sigma,
+                                 int contrast_measure, double *contrast, double *grad /* 3K or NULL */);
+int cmx_backend_recon_bound_info(cmx_ctx *ctx, int64_t *n_events, int64_t *n_sampled, int64_t *sorts, double *fallback_frac);
 
 /* ------------------------------------------------------------------ split-phase (multi-GPU) ------------
  * The IWE is a sum over events, the contrast a non-linear function of the SUMMED image, so ranks exchange
@@ -597,7 +633,8 @@ int cmx_get_stats(cmx_ctx *ctx, double *stats, int n_stats); /* writes min(n_sta
  *  6: named cmx_get_stats indices, five more of them (the buffer length is the caller's: old callers keep reading what they asked for); cmx_group_transport_info; the *_aos entry points; cmx_set_stream_priority /
  *     cmx_set_cu_mask moved to cmax_hip_diag.h;
  *     added without a bump (no signature or buffer layout changed): the seven cmx_backend_recon_* entry points, then
- *     recon_restart / _contrast / _grad_add[_aos|_from] / _grad_get / _eval_from) */
+ *     recon_restart / _contrast / _grad_add[_aos|_from] / _grad_get / _eval_from, then recon_bind_from / _unbind / _eval_bound /
+ *     _bound_info) */
 #define CMX_ABI_VERSION 6
 int cmx_abi_version(void);
 int cmx_timing_enable(cmx_ctx *ctx, int on);

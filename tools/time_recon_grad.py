@@ -1,19 +1,23 @@
 #!/usr/bin/env python3
 """Whole-trajectory contrast and gradient (cmx_backend_recon_restart / _contrast / _grad_add_from / _grad_get / _eval_from), phase by
-phase, in one run on one GPU.
+phase, and the same evaluation over events bound once (cmx_backend_recon_bind_from / _eval_bound), in one run on one GPU.
 
   (large)   tools/time_recon.py's configuration: 20M events from the event store, 1280x720 sensor, 4096x2048 panorama, linear spline
             with 401 knots, batch 100.  Median of --reps runs per phase after --warmup warm-up runs, host clock around synchronous
             calls: restart, add_from (the vote pass: the kernel profiles/recon_timing.txt records), contrast cost-only, contrast with
-            gradient, grad_add_from (the gather pass), grad_get, and the whole eval_from with and without the gradient.
+            gradient, grad_add_from (the gather pass), grad_get, and the whole eval_from with and without the gradient.  Then, in the
+            same process on the same events: bind_from, the first eval_bound (the one that sorts), steady-state eval_bound cost-only
+            and with the gradient, eval_bound at knots moved by N(0, 1 mrad) with the share of votes that left their windows, the
+            pose-table, tile-sort and vote kernels by their own events (cmx_timing_enable), and the break-even number of
+            evaluations (bind + sort) / (eval_from - eval_bound).
   (window)  config 3 (5M events, cubic K = 10, 1024 x 1024): reconstruct_eval with the gradient against the window path's
-            set_window_from + one eval with the gradient (num_fixed = 0, no map).
-  (pmc)     the large configuration once under rocprofv3 --pmc, one counter group per run: VALU instructions of the gather kernel
-            per event, and the atomic requests that reach the L2.
+            set_window_from + one eval with the gradient (num_fixed = 0, no map), and against eval_bound on the same events.
+  (pmc)     the large configuration once under rocprofv3 --pmc, one counter group per run: VALU instructions of the gather and
+            vote kernels per event, and the atomic requests that reach the L2.
 
 No threshold is fixed: the file states the ratios.  Every step runs in a child process of its own, in a process group of its own,
 under a time limit; a child that ends with a non-zero status or at its limit is the LAST thing this tool starts on the GPU.
-Writes profiles/recon_grad_timing.txt (--out).  Needs a GPU; there is no fallback."""
+Writes profiles/recon_bound_timing.txt (--out).  Needs a GPU; there is no fallback."""
 import argparse
 import json
 import os
@@ -66,9 +70,41 @@ def step_large(a):
             for k, v in s.items():
                 ph[k].append(v)
     _, ns, ni = be.reconstruct_get(with_counts=True)
+    # ---- the same events bound once, evaluated through the tile sort and LDS votes
+    from scipy.spatial.transform import Rotation as Rot
+    moved = (Rot.from_rotvec(np.random.default_rng(5).normal(0, 1e-3, (len(knots), 3))) * Rot.from_quat(knots)).as_quat()
+    bp = {k: [] for k in ("bind", "first_eval", "bound_cost", "bound_grad", "bound_moved")}
+    frac_moved = 0.0
+    rounds = a.warmup + a.reps
+    for i in range(rounds):
+        s = {}
+        s["bind"], _ = timed(be.reconstruct_bind, store, 0, n)
+        s["first_eval"], _ = timed(be.reconstruct_eval_bound, knots, a.sigma, 0, True)
+        s["bound_cost"], _ = timed(be.reconstruct_eval_bound, knots, a.sigma, 0, False)
+        s["bound_grad"], (cb, gb) = timed(be.reconstruct_eval_bound, knots, a.sigma, 0, True)
+        s["bound_moved"], _ = timed(be.reconstruct_eval_bound, moved, a.sigma, 0, True)
+        frac_moved = be.reconstruct_bound_info()["fallback_frac"]
+        if i >= a.warmup:
+            for k, v in s.items():
+                bp[k].append(v)
+    extra = max(a.reps, 1)
+    be.timing_enable(["pose", "batch", "splat"])  # the bound path's kernels by their own events, in evaluations of their own
+    be.reconstruct_bind(store, 0, n)
+    for i in range(extra):
+        be.reconstruct_eval_bound(knots, a.sigma, 0, True)
+    tm = be.timing_get()
+    be.timing_enable(False)
+    info = be.reconstruct_bound_info()
+    _, nsb, nib = be.reconstruct_get(with_counts=True)
     be.reconstruct_end()
+    bound = {"phases": {k: med(v) for k, v in bp.items()}, "contrast_rel": abs(cb - c2) / abs(c2),
+             "grad_rel": float(np.abs(gb - g2).max() / np.abs(g2).max()), "sampled": nsb, "inside": nib, "sorts": info["sorts"],
+             "fallback_frac": info["fallback_frac"], "fallback_frac_moved": frac_moved,
+             "kernels": {k: [tm[k][0], tm[k][1]] for k in ("pose", "batch", "splat")},
+             # passes over the sampled events this process made, per kernel (the per-event figures of a profiled run)
+             "passes": {"recon_votes_kernel": 3 * rounds, "recon_votes_lds": 4 * rounds + extra, "recon_gather": 5 * rounds + extra}}
     out = {"events": n, "K": len(knots), "sampled": ns, "inside": ni, "contrast": c, "gmax": float(np.abs(g).max()),
-           "eval_vs_phases": float(np.abs(g2 - g).max()), "phases": {k: med(v) for k, v in ph.items()}}
+           "eval_vs_phases": float(np.abs(g2 - g).max()), "phases": {k: med(v) for k, v in ph.items()}, "bound": bound}
     print("RESULT " + json.dumps(out), flush=True)
 
 
@@ -89,8 +125,17 @@ def step_window(a):
         t2, (cr, gr) = timed(be.reconstruct_eval, store, 0, n, w.knots_init, a.sigma, 0, True)
         if i >= a.warmup:
             win_set.append(t0); win_eval.append(t1); rec.append(t2)
+    bnd = []
+    t_bind, _ = timed(be.reconstruct_bind, store, 0, n)
+    t_first, _ = timed(be.reconstruct_eval_bound, w.knots_init, a.sigma, 0, True)
+    for i in range(a.warmup + a.reps):
+        t3, (cb, gb) = timed(be.reconstruct_eval_bound, w.knots_init, a.sigma, 0, True)
+        if i >= a.warmup:
+            bnd.append(t3)
     be.reconstruct_end()
     out = {"events": n, "set_window_from": med(win_set), "eval": med(win_eval), "reconstruct_eval": med(rec),
+           "bind": t_bind, "first_eval_bound": t_first, "eval_bound": med(bnd),
+           "bound_grad_rel": float(np.abs(np.array(gb) - gw).max() / np.abs(gw).max()),
            "contrast_rel": abs(cr - cw) / abs(cw), "grad_rel": float(np.abs(np.array(gr) - gw).max() / np.abs(gw).max())}
     print("RESULT " + json.dumps(out), flush=True)
 
@@ -108,7 +153,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-profile", action="store_true", help="skip the rocprofv3 counter runs")
     ap.add_argument("--commit", default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "recon_grad_timing.txt"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "recon_bound_timing.txt"))
     a = ap.parse_args()
     if a.step == "large":
         return step_large(a)
@@ -136,7 +181,8 @@ def main():
     big = child("large")  # (a timing child that dies ends the run: ChildDied propagates, nothing further is started)
     win = child("window")
     n, p = big["events"], big["phases"]
-    L = ["whole-trajectory contrast and gradient: cmx_backend_recon_restart / _contrast / _grad_add_from / _grad_get / _eval_from",
+    L = ["whole-trajectory contrast and gradient: cmx_backend_recon_restart / _contrast / _grad_add_from / _grad_get / _eval_from, and "
+         "the same over bound events: _bind_from / _eval_bound",
          "commit: %s    %d events from the event store, %dx%d sensor, %dx%d panorama, linear spline with %d knots, batch %d, rate 1, sigma %g" %
          (commit, n, a.sensor[0], a.sensor[1], a.pano[0], a.pano[1], big["K"], a.batch, a.sigma),
          "median of %d runs after %d warm-up runs; host clock around synchronous calls" % (a.reps, a.warmup),
@@ -150,7 +196,30 @@ def main():
                      ("grad_add_from", "grad_add_from (gather pass)"), ("grad_get", "grad_get (2 x 3K sums to the host)"),
                      ("eval_cost", "eval_from, cost only"), ("eval_grad", "eval_from, with gradient")):
         L.append("%-58s %10.3f %14.3e" % (label, 1e3 * p[k], n / p[k]))
+    bd = big["bound"]
+    q, kt = bd["phases"], bd["kernels"]
+    for k, label in (("bind", "bind_from (batch times, packed copy, the sort's buffers)"),
+                     ("first_eval", "eval_bound with gradient, the first (tile sort included)"),
+                     ("bound_cost", "eval_bound, cost only, steady state"), ("bound_grad", "eval_bound, with gradient, steady state"),
+                     ("bound_moved", "eval_bound, with gradient, knots moved by N(0, 1 mrad)")):
+        L.append("%-58s %10.3f %14.3e" % (label, 1e3 * q[k], n / q[k]))
+
+    def each(v):
+        return v[0] / v[1] if v[1] else float("nan")
+    sort_ms = 1e3 * (q["first_eval"] - q["bound_grad"])
+    gain_ms = 1e3 * (p["eval_grad"] - q["bound_grad"])
     L += ["",
+          "bound path, kernels by their own events (%d evaluations of their own): pose table %.3f ms, tile sort + chunk table %.3f ms "
+          "(%d run), vote kernel %.3f ms" % (kt["splat"][1], each(kt["pose"]), each(kt["batch"]), kt["batch"][1], each(kt["splat"])),
+          "bound path: sampled %d, voted %d, tile sorts since the last bind %d; votes outside their window: %.4f at the sort's knots, "
+          "%.4f with the knots moved by 1 mrad" % (bd["sampled"], bd["inside"], bd["sorts"], bd["fallback_frac"], bd["fallback_frac_moved"]),
+          "eval_bound against eval_from at the same knots: contrast %.2e, gradient %.2e (relative, max-norm)" %
+          (bd["contrast_rel"], bd["grad_rel"]),
+          "eval_from with gradient / eval_bound with gradient, steady state: %.2f x" % (p["eval_grad"] / q["bound_grad"]),
+          "break-even: (bind %.3f ms + sort %.3f ms) / (eval_from %.3f ms - eval_bound %.3f ms) = %s" %
+          (1e3 * q["bind"], sort_ms, 1e3 * p["eval_grad"], 1e3 * q["bound_grad"],
+           "%.1f evaluations" % ((1e3 * q["bind"] + sort_ms) / gain_ms) if gain_ms > 0 else "never: eval_bound is not faster"),
+          "",
           "gather pass / vote pass of the same run: %.2f x" % (p["grad_add_from"] / p["add_from"]),
           "eval_from with gradient / cost only: %.2f x" % (p["eval_grad"] / p["eval_cost"]),
           "",
@@ -160,26 +229,31 @@ def main():
           "  reconstruct_eval with gradient (restart + add_from + contrast + grad_add_from + grad_get): %.3f ms" % (1e3 * win["reconstruct_eval"]),
           "  reconstruct_eval / (set_window_from + eval): %.2f x;  / eval alone: %.2f x" %
           (win["reconstruct_eval"] / (win["set_window_from"] + win["eval"]), win["reconstruct_eval"] / win["eval"]),
-          "  agreement of the two: contrast %.2e, gradient %.2e (relative, max-norm)" % (win["contrast_rel"], win["grad_rel"])]
+          "  agreement of the two: contrast %.2e, gradient %.2e (relative, max-norm)" % (win["contrast_rel"], win["grad_rel"]),
+          "  bound: bind_from %.3f ms, first eval_bound (sort included) %.3f ms, eval_bound with gradient, steady state %.3f ms" %
+          (1e3 * win["bind"], 1e3 * win["first_eval_bound"], 1e3 * win["eval_bound"]),
+          "  eval_bound / (set_window_from + eval): %.2f x;  / eval alone: %.2f x;  its gradient against the window path's: %.2e" %
+          (win["eval_bound"] / (win["set_window_from"] + win["eval"]), win["eval_bound"] / win["eval"], win["bound_grad_rel"])]
     died = None
     if not a.no_profile and not shutil.which("rocprofv3"):
         L += ["", "rocprofv3 is not installed: no counters"]
     elif not a.no_profile:
         one = ["--reps", "1", "--warmup", "0"]
-        evs = 2.0 * big["sampled"]  # the phase-by-phase gather and eval_from's: two gather passes in a profiled run
         for grp in ("SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES", "TCC_ATOMIC_sum TCC_READ_sum TCC_WRITE_sum"):
             if died:
                 break
             with tempfile.TemporaryDirectory(prefix="recon_grad_pmc_") as d:
                 try:
-                    child("large", one, ["rocprofv3", "--pmc"] + grp.split() + ["--output-format", "csv", "-d", d, "-o", "rg", "--"], limit=300)
-                    for kern in ("recon_gather", "recon_votes"):
+                    prof = child("large", one, ["rocprofv3", "--pmc"] + grp.split() + ["--output-format", "csv", "-d", d, "-o", "rg", "--"],
+                                 limit=300)
+                    passes = prof["bound"]["passes"]  # (of the profiled run itself)
+                    for kern in ("recon_gather", "recon_votes_kernel", "recon_votes_lds"):
                         acc = {}
                         for r in tr.rows_of(d, "counter_collection.csv"):
                             if kern in r.get("Kernel_Name", "") and "rows" not in r.get("Kernel_Name", ""):
                                 acc[r["Counter_Name"]] = acc.get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])
                         L.append("PMC (a run of its own), %s launches summed: " % kern + ", ".join("%s %.4g" % kv for kv in sorted(acc.items())))
-                        per = evs if kern == "recon_gather" else 3.0 * big["sampled"]  # (add_from + two eval_from vote passes)
+                        per = float(passes[kern]) * big["sampled"]  # (every pass of the profiled run is over the sampled events)
                         if acc.get("SQ_INSTS_VALU"):
                             L.append("    %s: %.1f VALU instructions per event (wave instructions x 64 lanes / events)" %
                                      (kern, 64.0 * acc["SQ_INSTS_VALU"] / per))
