@@ -122,7 +122,7 @@ int queue_slot_self_gating(cmx_ctx *c, int slot, SlotTickets *t) {
   g.itilde = c->d_itilde;
   g.gpartials = nullptr;
   g.cx = c->d_cx; g.cy = c->d_cy; g.r = c->radius;
-  g.sxy = c->d_sxy; g.sbatch = c->d_sbatch; g.sb = c->d_sb; g.sdt = c->d_sdt;
+  g.sxy = c->sort.d_sxy; g.sbatch = c->sort.d_sbatch; g.sb = c->d_sb; g.sdt = c->d_sdt;
   FinalizeArgs &f = g.tail.fin;
   f.P = 0;
   f.nblk = a.nblk;
@@ -134,7 +134,7 @@ int queue_slot_self_gating(cmx_ctx *c, int slot, SlotTickets *t) {
   f.direct = 1;
   f.gacc = c->d_gacc;
   f.gacc_stride = kGaccStride;
-  f.fallback = c->d_fallback;
+  f.fallback = c->sort.d_fallback;
   f.macc = a.macc;
   f.macc_clear = &c->d_chain->macc[par ^ 1u][0][0];
   f.nout_pad = 2 + 3;
@@ -308,7 +308,7 @@ int chain_run_frontend(cmx_ctx *c, FrcgSM &hs, bool *completed) {
     // (they give up after kFuseTimeoutTicks and flag the fallback word nobody reads any more).  Counters and word start from zero again.
     (void)fuse_incomplete;
     if (c->d_fnbr_cnt) (void)hipMemsetAsync(c->d_fnbr_cnt, 0, c->fcnt_cap * sizeof(unsigned), c->stream);
-    if (c->d_fallback) (void)hipMemsetAsync(c->d_fallback, 0, sizeof(unsigned), c->stream);
+    if (c->sort.d_fallback) (void)hipMemsetAsync(c->sort.d_fallback, 0, sizeof(unsigned), c->stream);
     if (diverged) c->chain_takeovers++;
   }
   c->x_valid = false;

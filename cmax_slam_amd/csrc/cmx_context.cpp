@@ -341,7 +341,7 @@ void cmx_destroy(cmx_ctx *c) {
   for (auto e : c->event_pool) hipEventDestroy(e);
   hipFree(c->d_lut);
   hipFree(c->d_lut2);
-  hipFree(c->d_nchunks);
+  c->sort.release();
   if (c->h_nchunks) hipHostFree(c->h_nchunks);
   hipFree(c->d_batch_err);
   hipFree(c->d_xy);
@@ -364,16 +364,10 @@ void cmx_destroy(cmx_ctx *c) {
   if (c->h_disp) hipHostFree(c->h_disp);
   hipFree(c->d_partials);
   hipFree(c->d_sums);
-  hipFree(c->d_keys); hipFree(c->d_keys_s); hipFree(c->d_idx); hipFree(c->d_idx_s); hipFree(c->d_sxy); hipFree(c->d_sbatch);
-  hipFree(c->d_sort_temp);
-  hipFree(c->d_hist);
   hipFree(c->d_sb);
   hipFree(c->d_tb);
   hipFree(c->d_sdt);
   hipFree(c->d_fixed);
-  hipFree(c->d_tile_start);
-  hipFree(c->d_chunks);
-  hipFree(c->d_fallback);
   hipFree(c->d_fnbr_expected); hipFree(c->d_fnbr_cnt); hipFree(c->d_fpartials); hipFree(c->d_fuse_trace);
   hipFree(c->d_ftile_done); hipFree(c->d_ftiles_done); hipFree(c->d_fn_active);
   hipFree(c->d_itilde);
@@ -601,8 +595,8 @@ int cmx_get_stats(cmx_ctx *c, double *out, int n_stats) {
   stats[1] = c->last_fallback_frac;
   {  // true length of the chunk table (device-resident until the first evaluation after a binning has been collected)
     int nch = c->nchunks;
-    if (!c->nchunks_exact && c->d_nchunks && c->bin_valid && bind_device(c) == CMX_OK && hipStreamSynchronize(c->stream) == hipSuccess)
-      (void)hipMemcpy(&nch, c->d_nchunks, sizeof(int), hipMemcpyDeviceToHost);
+    if (!c->nchunks_exact && c->sort.d_nchunks && c->bin_valid && bind_device(c) == CMX_OK && hipStreamSynchronize(c->stream) == hipSuccess)
+      (void)hipMemcpy(&nch, c->sort.d_nchunks, sizeof(int), hipMemcpyDeviceToHost);
     stats[2] = (double)nch;
   }
   stats[3] = (double)c->n_packed;

@@ -1,7 +1,8 @@
 // cmx_context.hpp -- the evaluator context behind include/cmax_hip.h's opaque cmx_ctx / cmx_events, and the helpers
 // the translation units of the C ABI share:
 //   cmx_context.cpp   context life cycle, options, timing, error text, event validation
-//   cmx_pipeline.cpp  one evaluation on the stream: accumulate buffers, tile sort, image passes, gather, finalize, ticket
+//   cmx_pipeline.cpp  one evaluation on the stream: accumulate buffers, tile sort (do_binning), image passes, gather, finalize, ticket
+//   cmx_tilesort.cpp  TileSort: the destination-tile sort, its chunk table and their device buffers, for every caller
 //   cmx_frontend.cpp  cmx_frontend_*      cmx_backend.cpp  cmx_backend_*      cmx_events.cpp  cmx_events_*
 //   cmx_comm.cpp      RCCL communicator inside the evaluator (sharded evaluations)
 // Internal to libcmaxhip.so; gfx950 only.  There is NO CPU fallback: every entry point fails loudly without HIP.
@@ -25,6 +26,7 @@
 #include "cmx_hostpool.hpp"
 #include "cmx_ingest.hpp"
 #include "cmx_internal.hpp"
+#include "cmx_tilesort.hpp"
 
 using namespace cmx;  // internal header of one library: the parameter blocks of cmx_internal.hpp are used unqualified
 
@@ -157,8 +159,7 @@ struct cmx_ctx {
 
   // LDS-privatised splat (CMX_OPT_SPLAT_MODE = 1): events sorted by destination tile, chunk table
   bool bin_valid = false;
-  uint32_t *d_keys = nullptr, *d_keys_s = nullptr, *d_idx = nullptr, *d_idx_s = nullptr, *d_sxy = nullptr, *d_sbatch = nullptr;
-  size_t bin_cap = 0;
+  TileSort sort;  // the sorted events, the chunk table and the sort's scratch (cmx_tilesort.hpp)
   bool deterministic = false;            // CMX_OPT_DETERMINISTIC
   unsigned long long *d_fixed = nullptr;  // its fixed-point vote planes (all-zero between evaluations)
   size_t fixed_cap = 0;
@@ -168,22 +169,12 @@ struct cmx_ctx {
   double *d_tb = nullptr;  // back end: bearing (x, y) of every event in time order (gather stream)
   size_t tb_cap = 0;
   bool tb_valid = false;
-  int *d_hist = nullptr;  // counting sort scratch: [bin totals | slices x bins prefix table]
-  size_t hist_cap = 0;
-  void *d_sort_temp = nullptr;
-  size_t sort_temp_cap = 0;
-  int *d_tile_start = nullptr;
-  size_t tile_start_cap = 0;
-  Chunk *d_chunks = nullptr;
-  size_t chunks_cap = 0;
-  int nchunks = 0;          // launch bound of the chunk table (its true length lives in d_nchunks)
-  int *d_nchunks = nullptr;
+  int nchunks = 0;          // launch bound of the chunk table (its true length lives in sort.d_nchunks)
   // mapped host copy of the table's true length, written by build_chunks as (binning id << 32 | length): a count is only
   // accepted with the id of the latest binning, so a stale store of an earlier, uncollected binning cannot be mistaken for it
   unsigned long long *h_nchunks = nullptr, *d_nchunks_host = nullptr;
   unsigned binning_id = 0;
   bool nchunks_exact = false;  // nchunks has been replaced by the table's true length (read back after the first evaluation)
-  unsigned *d_fallback = nullptr;
   // tile-dataflow fusion of the adjoint image pass into the front-end LDS splat (FusedArgs, cmx_internal.hpp; CMX_OPT_FUSED_IMAGE)
   bool fused_image = true;
   int *d_fnbr_expected = nullptr;     // per sort tile: chunk arrivals that complete its 3 x 3 neighbourhood (built with the chunk table)
@@ -485,10 +476,7 @@ int be_eval_one(cmx_ctx *c, const double *drotv, double *contrast, double *grad)
 #define CMX_NOT_FOR_GROUPS(c, what) \
   do { if ((c) && (c)->group) return fail((c), CMX_ERR_STATE, what " is not available on a group (the group runs its own exchange)"); } while (0)
 
-// ---- cmx_reconstruct.cpp: the bodies behind cmx_backend_recon_add[_aos] and _add_from (events on the host / in the event store)
-int recon_enter(cmx_ctx *c, bool need_begun);  // front door of every cmx_backend_recon_*: plain back-end context, not a group, begun; binds the device
-int recon_add_host(cmx_ctx *c, const EventSource &src, bool grad = false);  // grad: the gradient pass (recon_grad_add*) over the same events
-int recon_add_store(cmx_ctx *c, const EventSource &src, bool grad = false);
+// ---- cmx_reconstruct.cpp
 int recon_diag_slice_events(int n);  // CMX_DIAG_RECON_SLICE_EVENTS (cmax_hip_diag.h)
 void recon_release(cmx_ctx *c);  // frees whatever a reconstruction holds (cmx_backend_recon_end, cmx_destroy)
 

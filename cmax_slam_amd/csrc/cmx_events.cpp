@@ -181,17 +181,6 @@ int cmx_backend_set_window_from(cmx_ctx *c, const cmx_events *e, int64_t first, 
   return be_set_window_impl(c, src, w);
 }
 
-// cmx_backend_recon_add over events_[first, first+count) of the store: the vote kernel reads the store's own packed events (the
-// per-batch sampling is an index map, nothing is copied) and launch_be_batch_times forms and validates the batch times
-int cmx_backend_recon_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
-  int rc = recon_enter(c, true);
-  if (rc) return rc;
-  EventSource src;
-  rc = store_source(c, e, first, count, &src);
-  if (rc) return rc;
-  return recon_add_store(c, src);
-}
-
 // A window cut from a replicated store on a GROUP: member r cuts ITS batch range (the range group_set_window hands it, the
 // one-event rule included) from the replica on its own device -- no event crosses the host or a link at hand-over
 // (pose_graph_optimizer.cpp:131-165 is the copy this replaces; event_pano_warper.cpp:188-196 the loop being sharded).

@@ -130,32 +130,50 @@ inline bool plan_batches(int64_t n, int B, int rate, BatchPlan *p) {  // false: 
   }
   return true;
 }
-// ---- events bound to a reconstruction (cmx_backend_recon_bind_from): the sizes that follow from counts alone.
-// chunk_events: events of a full chunk of the tile-sorted vote pass -- n / 768 (three 256-thread workgroups per compute unit fill
-// the chip in one round), at least 1536 and at most 32768, a multiple of 256.  max_chunks: an upper bound of the chunk table's
-// length for ANY distribution of the n events over `keys` sort tiles and the no-window tile, whose events go in chunks of 256:
-// every tile adds floor(len / M) full chunks and at most one remainder.
-struct BoundPlan {
+// ---- the chunk table of a tile sort (window path: do_binning; bound whole-trajectory events: bound_build): the sizes that follow
+// from counts alone.  chunk_events: events of a full chunk -- hot tiles are split so that the chunks fill the chip in ONE resident
+// round; big chunks amortise the window zeroing and flush.  So n / div, at least 1536 (floor swept on MI355X, 1M events:
+// 1536 -> 11.8 us, 1024 -> 15.3) and at most 32768, a multiple of 256.  The divisor is the caller's:
+//   back end (kBackEndChunkDiv): 135 VGPRs = 3 workgroups of 256 threads per CU (swept at 5M events, splat us: 512 -> 50, 640 -> 51,
+//     768 -> 44, 1152 -> 50, 1536 -> 48, 3072 -> 53: anything that needs a second round loses more than it gains in latency hiding;
+//     128 VGPRs + 4 per CU and one event per thread + 4 per CU: no gain, 72 vs 81 us per cost evaluation);
+//   front end (CMX_FE_CHUNK_DIV, cmx_pipeline.cpp; 50 VGPRs, LDS-bound): with 256-thread workgroups n / 512 (1M events, splat us:
+//     256 -> 10.0, 384 -> 8.4, 512 -> 8.2, 640 -> 8.5, 768 -> 8.8); round 5: 512-thread workgroups x chunks of n / 256
+//     (profiles/r05_fe_shape.txt: 7.9 us; 1024 x n / 256: 7.7 but no better as an evaluation).
+// max_chunks: an upper bound of the table's length, known on the host, for ANY distribution of the n events over `keys` sort
+// tiles and the no-window tile, whose events go in chunks of 256 (the bound for 'all events rejected'): every tile adds
+// floor(len / M) full chunks and at most one remainder.
+constexpr int kBackEndChunkDiv = 768;
+struct ChunkPlan {
   int chunk_events = 0;
   int64_t max_chunks = 0;
 };
-inline BoundPlan plan_bound(int64_t n_packed, int64_t keys) {
-  BoundPlan b;
-  int64_t M = n_packed / 768;
+inline ChunkPlan plan_chunks(int64_t n, int64_t keys, int div) {
+  ChunkPlan p;
+  int64_t M = n / div;
   M = M < 1536 ? 1536 : (M > 32768 ? 32768 : M);
-  b.chunk_events = (int)((M + 255) / 256 * 256);
-  b.max_chunks = n_packed / b.chunk_events + keys + 2 + n_packed / 256;
-  return b;
+  p.chunk_events = (int)((M + 255) / 256 * 256);
+  p.max_chunks = n / p.chunk_events + keys + 2 + n / 256;
+  return p;
 }
-// a pass over the bound, time-ordered packed events in slices of whole batches: the slice that starts at batch b_lo
-struct BoundSlice {
-  int b_hi = 0;        // its batches are [b_lo, b_hi)
-  int64_t first = 0;   // its first packed event
-  int64_t n = 0;       // its packed events
+// ---- a pass over events in slices of whole batches (every recon_add*, the bound gather pass): batches per slice, and the slice
+// that starts at batch b_lo of the plan of n_events events
+inline int slice_batches_of(int64_t slice_events, int B) {
+  const int64_t sb = slice_events / B;
+  return (int)(sb < 1 ? 1 : sb);
+}
+struct Slice {
+  int b_hi = 0;          // its batches are [b_lo, b_hi)
+  int64_t ev_first = 0;  // its first event as handed in ...
+  int64_t ev_n = 0;      // ... and how many of those it spans (the last slice: up to the end, a never-opened single-event tail included)
+  int64_t first = 0;     // its first packed event
+  int64_t n = 0;         // its packed events
 };
-inline BoundSlice bound_slice(const BatchPlan &p, int b_lo, int slice_batches) {
-  BoundSlice s;
+inline Slice slice_at(const BatchPlan &p, int64_t n_events, int b_lo, int slice_batches) {
+  Slice s;
   s.b_hi = (p.nb - b_lo > slice_batches) ? b_lo + slice_batches : p.nb;
+  s.ev_first = (int64_t)b_lo * p.B;
+  s.ev_n = s.b_hi == p.nb ? n_events - s.ev_first : (int64_t)(s.b_hi - b_lo) * p.B;
   s.first = (int64_t)b_lo * p.per_batch;
   s.n = p.packed(b_lo, s.b_hi);
   return s;

@@ -76,54 +76,26 @@ int ensure_accum(cmx_ctx *c, size_t need) {
   return ensure(c, c->d_accum, c->accum_cap, need);
 }
 
-// ---- sort the events by destination tile under the CURRENT parameters and build the chunk table
-int do_binning(cmx_ctx *c, const FeSplatArgs *fe, const BeSplatArgs *be) {
-  const int n = c->n_packed;
-  const int W = c->imgW, H = c->imgH;
-  const int tiles_x = (W + kBinTile - 1) / kBinTile, tiles_y = (H + kBinTile - 1) / kBinTile;
-  const int planes_per_tile = fe ? 1 : 2;  // back end: key = 2*tile + (IL_new ? 1 : 0)
-  const int ntiles = tiles_x * tiles_y * planes_per_tile;
-  int rc;
-  const bool counting = count_sort_ok(ntiles + 1);
-  if ((size_t)n > c->bin_cap || !c->d_keys) {
-    uint32_t **ptrs[6] = {&c->d_keys, &c->d_sxy, &c->d_sbatch, &c->d_keys_s, &c->d_idx, &c->d_idx_s};
-    for (int k = 0; k < 6; k++) {
-      uint32_t **p = ptrs[k];
-      if (*p) HIP_TRY(c, hipFree(*p));
-      *p = nullptr;
-      if (k >= 3 && counting) continue;  // the (key, index) pair buffers belong to the radix-sort fallback only
-      HIP_TRY(c, hipMalloc((void **)p, (size_t)(n > 0 ? n : 1) * sizeof(uint32_t)));
-    }
-    c->bin_cap = (size_t)(n > 0 ? n : 1);
-  }
-  if (!counting && !c->d_keys_s) {  // a context that switched to a huge panorama after small ones
-    uint32_t **ptrs[3] = {&c->d_keys_s, &c->d_idx, &c->d_idx_s};
-    for (auto p : ptrs) HIP_TRY(c, hipMalloc((void **)p, c->bin_cap * sizeof(uint32_t)));
-  }
-  if (!c->d_fallback) {
-    HIP_TRY(c, hipMalloc((void **)&c->d_fallback, sizeof(unsigned)));
-    HIP_TRY(c, hipMemsetAsync(c->d_fallback, 0, sizeof(unsigned), c->stream));
-  }
-  rc = ensure(c, c->d_tile_start, c->tile_start_cap, (size_t)ntiles + 2);
-  if (rc) return rc;
-  // chunk size: hot tiles are split so that the chunks fill the chip in ONE resident round; big chunks amortise the window
-  // zeroing and flush.  Back end: 135 VGPRs = 3 workgroups per CU, so n / 768 (swept at 5M events, splat us: 512 -> 50,
-  // 640 -> 51, 768 -> 44, 1152 -> 50, 1536 -> 48, 3072 -> 53: anything that needs a second round loses more than it gains in
-  // latency hiding; 128 VGPRs + 4 per CU and one event per thread + 4 per CU: no gain, 72 vs 81 us per cost evaluation).
-  // Front end (50 VGPRs, LDS-bound): with 256-thread workgroups n / 512 (1M events, splat us: 256 -> 10.0, 384 -> 8.4, 512 -> 8.2,
-  // 640 -> 8.5, 768 -> 8.8); round 5: 512-thread workgroups x chunks of n / 256 (profiles/r05_fe_shape.txt: 7.9 us; 1024 x n / 256: 7.7
-  // but no better as an evaluation).
+// ---- sort the events by destination tile under the CURRENT parameters and build the chunk table (TileSort, cmx_tilesort.cpp).
+// What is the window path's own stays here: the chunk divisor, the bearing / dt streams that ride along with the counting sort,
+// the fused tables, and the state of the binning (id, launch bound, validity, re-sort statistics).
 #ifndef CMX_FE_CHUNK_DIV
 #define CMX_FE_CHUNK_DIV 256
 #endif
-  int M = n / (fe ? CMX_FE_CHUNK_DIV : 768);
-  M = M < 1536 ? 1536 : (M > 32768 ? 32768 : M);  // floor swept on MI355X (1M events: 1536 -> 11.8 us, 1024 -> 15.3)
-  M = (M + 255) / 256 * 256;
-  // every tile contributes floor(len/M) full chunks and at most one remainder: an upper bound known on the host
-  const int max_chunks = (n / M) + ntiles + 2 + n / 256;  // (+ the sentinel's events in chunks of 256: bound for 'all events rejected')
-  rc = ensure(c, c->d_chunks, c->chunks_cap, (size_t)max_chunks);
+int do_binning(cmx_ctx *c, const FeSplatArgs *fe, const BeSplatArgs *be) {
+  const int n = c->n_packed;
+  const int W = c->imgW, H = c->imgH;
+  TileSortJob job;
+  job.fe = fe; job.be = be;
+  job.tiles_x = (W + kBinTile - 1) / kBinTile;
+  const int tiles_y = (H + kBinTile - 1) / kBinTile;
+  job.tiles = job.tiles_x * tiles_y;
+  job.planes_per_tile = fe ? 1 : 2;  // back end: key = 2*tile + (IL_new ? 1 : 0)
+  const int ntiles = job.tiles * job.planes_per_tile;
+  const ChunkPlan cp = plan_chunks(n, ntiles, fe ? CMX_FE_CHUNK_DIV : kBackEndChunkDiv);
+  const int max_chunks = (int)cp.max_chunks;
+  int rc = c->sort.reserve(c, n, ntiles, max_chunks);
   if (rc) return rc;
-  if (!c->d_nchunks) HIP_TRY(c, hipMalloc((void **)&c->d_nchunks, sizeof(int)));
   if (!c->h_nchunks) {
     HIP_TRY(c, hipHostMalloc((void **)&c->h_nchunks, sizeof(unsigned long long), hipHostMallocMapped));
     *c->h_nchunks = 0ull;
@@ -132,47 +104,19 @@ int do_binning(cmx_ctx *c, const FeSplatArgs *fe, const BeSplatArgs *be) {
   c->binning_id++;  // a build_chunks of an earlier binning that was never collected may still store its (id, count): ignored
   if (c->binning_id == 0) c->binning_id = 1;
   if (n > 0) {
-    if (counting) {
-      // counting sort: keys + per-slice histograms, column prefixes, bin scan, scatter (cmx_binning.hip)
-      rc = ensure(c, c->d_hist, c->hist_cap, count_sort_scratch_ints(n, ntiles + 1));
+    c->streams_valid = false;
+    if (c->sort.counting && c->d_lut2) {  // the sorted order also carries every event's bearing (front end: and its dt)
+      rc = ensure(c, c->d_sb, c->sb_cap, (size_t)2 * n);
       if (rc) return rc;
-      c->streams_valid = false;
-      if (c->d_lut2) {  // the sorted order also carries every event's bearing (front end: and its dt)
-        rc = ensure(c, c->d_sb, c->sb_cap, (size_t)2 * n);
+      if (fe) {
+        rc = ensure(c, c->d_sdt, c->sdt_cap, (size_t)n);
         if (rc) return rc;
-        if (fe) {
-          rc = ensure(c, c->d_sdt, c->sdt_cap, (size_t)n);
-          if (rc) return rc;
-        }
-        c->streams_valid = true;
       }
-      launch_count_sort(fe, be, tiles_x, ntiles / planes_per_tile, c->d_xy, c->per_batch, n, c->d_keys, c->d_hist,
-                        c->d_tile_start, c->d_sxy, c->d_sbatch, c->streams_valid ? c->d_sb : nullptr,
-                        c->streams_valid ? c->d_sdt : nullptr, c->stream);
-    } else {
-      c->streams_valid = false;
-      if (fe) launch_fe_bin_keys(*fe, tiles_x, ntiles, c->d_keys, c->d_idx, c->stream);
-      else launch_be_bin_keys(*be, tiles_x, ntiles / 2, c->d_keys, c->d_idx, c->stream);
-      int end_bit = 1;
-      while ((1 << end_bit) <= ntiles) end_bit++;
-      size_t tb = 0;
-      if (sort_pairs_u32(nullptr, &tb, c->d_keys, c->d_keys_s, c->d_idx, c->d_idx_s, (unsigned)n, end_bit, c->stream) != 0)
-        return fail(c, CMX_ERR_HIP, "rocprim radix sort (size query) failed");
-      if (tb > c->sort_temp_cap) {
-        if (c->d_sort_temp) HIP_TRY(c, hipFree(c->d_sort_temp));
-        c->d_sort_temp = nullptr;
-        HIP_TRY(c, hipMalloc(&c->d_sort_temp, tb));
-        c->sort_temp_cap = tb;
-      }
-      if (sort_pairs_u32(c->d_sort_temp, &tb, c->d_keys, c->d_keys_s, c->d_idx, c->d_idx_s, (unsigned)n, end_bit, c->stream) != 0)
-        return fail(c, CMX_ERR_HIP, "rocprim radix sort failed");
-      launch_apply_perm(c->d_xy, c->d_idx_s, c->per_batch, n, c->d_sxy, c->d_sbatch, c->stream);
-      launch_tile_lower_bound(c->d_keys_s, n, ntiles + 2, c->d_tile_start, c->stream);
+      c->streams_valid = true;
     }
-    // the chunk table is built where the offsets are: no read-back, no host loop, no synchronisation
     FusedTables ft{};
     c->fused_bin_id = 0;
-    if (fe && c->fused_image && fused_tables_ok(ntiles, planes_per_tile)) {  // tables of the fused splat + image pass (FusedArgs)
+    if (fe && c->fused_image && fused_tables_ok(ntiles, job.planes_per_tile)) {  // tables of the fused splat + image pass (FusedArgs)
       rc = ensure(c, c->d_fnbr_expected, c->fnbr_cap, (size_t)ntiles * kFuseStrips);
       if (rc) return rc;
       rc = ensure(c, c->d_fnbr_cnt, c->fcnt_cap, (size_t)ntiles * kFuseStrips * kFuseCntStride);
@@ -194,17 +138,21 @@ int do_binning(cmx_ctx *c, const FeSplatArgs *fe, const BeSplatArgs *be) {
       ft.nbr_expected = c->d_fnbr_expected;
       ft.nbr_cnt = c->d_fnbr_cnt;
       ft.partials = c->d_fpartials;
+      job.fused = &ft;
       c->fused_bin_id = c->binning_id;
-      c->fused_tiles_x = tiles_x;
+      c->fused_tiles_x = job.tiles_x;
       c->fused_tiles_y = tiles_y;
     }
-    launch_build_chunks(c->d_tile_start, ntiles, planes_per_tile, tiles_x, kBinMargin, M, c->d_chunks, c->d_nchunks, c->d_nchunks_host,
-                        c->binning_id, c->stream, ft.nbr_expected ? &ft : nullptr);
-    HIP_TRY(c, hipGetLastError());
+    job.xy = c->d_xy; job.per_batch = c->per_batch; job.n = n;
+    job.chunk_events = cp.chunk_events;
+    if (c->streams_valid) { job.sb = c->d_sb; job.sdt = c->d_sdt; }
+    job.count_host = c->d_nchunks_host; job.binning_id = c->binning_id;
+    rc = c->sort.run(c, job);
+    if (rc) return rc;
     c->nchunks = max_chunks;
     c->nchunks_exact = false;
   } else {
-    HIP_TRY(c, hipMemsetAsync(c->d_nchunks, 0, sizeof(int), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->sort.d_nchunks, 0, sizeof(int), c->stream));
     c->nchunks = 0;
     c->nchunks_exact = true;
   }
@@ -225,12 +173,12 @@ int ensure_fixed(cmx_ctx *c, size_t n) {
 
 BinnedEvents binned(const cmx_ctx *c) {
   BinnedEvents b{};
-  b.sxy = c->d_sxy;
-  b.sbatch = c->d_sbatch;
-  b.chunks = c->d_chunks;
+  b.sxy = c->sort.d_sxy;
+  b.sbatch = c->sort.d_sbatch;
+  b.chunks = c->sort.d_chunks;
   b.nchunks = c->nchunks;
-  b.nchunks_dev = c->d_nchunks;
-  b.fallback = c->d_fallback;
+  b.nchunks_dev = c->sort.d_nchunks;
+  b.fallback = c->sort.d_fallback;
   b.sort_tiles_x = (c->imgW + kBinTile - 1) / kBinTile;
   b.sort_tiles_y = (c->imgH + kBinTile - 1) / kBinTile;
   if (c->streams_valid) { b.sb = c->d_sb; b.sdt = c->kind == KIND_FE ? c->d_sdt : nullptr; }
@@ -467,7 +415,7 @@ int run_image_and_finalize(cmx_ctx *c, int P, float *out_blur0, float *out_blurd
     f.partials = c->d_partials; f.sums = c->d_sums; f.result = result_ptr(c);
     f.direct = 1;
     f.gpartials = c->d_gpartials; f.gblocks = sa.nblk; f.gP = P;
-    f.fallback = c->d_fallback;
+    f.fallback = c->sort.d_fallback;
     issue_finalize(c, f, false);
     HIP_TRY(c, hipGetLastError());
     return CMX_OK;
@@ -480,7 +428,7 @@ int run_image_and_finalize(cmx_ctx *c, int P, float *out_blur0, float *out_blurd
   f.partials = c->d_partials;
   f.sums = c->d_sums;
   f.result = result_ptr(c);
-  f.fallback = c->d_fallback;
+  f.fallback = c->sort.d_fallback;
   bool tailed = false;
   {
     Span sp(c, CMX_T_IMAGE, /*exact=*/true);
@@ -621,7 +569,7 @@ int run_adjoint(cmx_ctx *c, int P, int phase) {
     f.gblocks = 1;
   }
   f.gP = P;
-  f.fallback = c->d_fallback;
+  f.fallback = c->sort.d_fallback;
   if (phase == 2) {
     issue_finalize(c, f, false);
     HIP_TRY(c, hipGetLastError());
@@ -670,8 +618,8 @@ int run_adjoint(cmx_ctx *c, int P, int phase) {
       g.cx = c->d_cx; g.cy = c->d_cy; g.r = c->radius;
       if (c->splat_mode == 1 && c->bin_valid && !c->deterministic) {  // tile order: the sorted arrays the LDS splat consumes
         // (deterministic mode: time order -- the order inside a tile depends on the scatter's atomics)
-        g.sxy = c->d_sxy;
-        g.sbatch = c->d_sbatch;
+        g.sxy = c->sort.d_sxy;
+        g.sbatch = c->sort.d_sbatch;
         if (c->streams_valid) { g.sb = c->d_sb; g.sdt = c->d_sdt; }
       }
       if (!g.sxy && c->d_lut2 && c->n_packed > 0) {  // time-ordered gather: the events' bearings as a stream, once per packet
@@ -848,7 +796,7 @@ int sync_and_collect(cmx_ctx *c, bool ends_in_finalize) {
       }
     }
   }
-  if (!c->nchunks_exact && c->bin_valid && c->d_nchunks) {  // once per binning: launch exactly the chunks that exist
+  if (!c->nchunks_exact && c->bin_valid && c->sort.d_nchunks) {  // once per binning: launch exactly the chunks that exist
     // the kernel that built the table also stored its length in mapped host memory; a kernel queued behind it has delivered
     // its completion ticket by now, so that store has landed (no synchronous read-back: ~10 us per packet)
     int nch = -1;
@@ -856,7 +804,7 @@ int sync_and_collect(cmx_ctx *c, bool ends_in_finalize) {
       const unsigned long long w = *reinterpret_cast<volatile unsigned long long *>(c->h_nchunks);
       if ((unsigned)(w >> 32) == c->binning_id) nch = (int)(unsigned)(w & 0xffffffffull);
     }
-    if (nch < 0 && hipMemcpy(&nch, c->d_nchunks, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) nch = -1;
+    if (nch < 0 && hipMemcpy(&nch, c->sort.d_nchunks, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) nch = -1;
     if (nch >= 0 && nch <= c->nchunks) c->nchunks = nch;
     c->nchunks_exact = true;
   }

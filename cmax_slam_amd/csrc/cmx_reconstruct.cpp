@@ -36,8 +36,8 @@ struct ReconSlot {
 };
 
 // Events bound to the reconstruction (cmx_backend_recon_bind_from): the sampled events of the range in time order, their batch
-// times, and what the tile-sorted vote pass of cmx_backend_recon_eval_bound needs -- all of it the reconstruction's own, nothing of
-// the context's binning state (d_sxy, d_chunks, bin_valid, ...) is used: the window's sort survives a whole-trajectory evaluation.
+// times, and what the tile-sorted vote pass of cmx_backend_recon_eval_bound needs -- all of it the reconstruction's own, a TileSort
+// beside the context's (cmx_ctx::sort, bin_valid, ...), which is not used: the window's sort survives a whole-trajectory evaluation.
 // Resident bytes per sampled event: 4 (xy) + 4 (keys) + 4 (sxy) + 4 (sbatch) = 16, plus 80 per batch (time, PoseR); the counting
 // sort's histogram table and the chunk table depend on the panorama, not on the events.
 struct ReconBound {
@@ -46,25 +46,19 @@ struct ReconBound {
   uint32_t *d_xy = nullptr;             // [n_packed] packed, time order, per_batch slots per batch
   long long *d_bt = nullptr;            // [nb] batch pose times
   PoseR *d_poseR = nullptr;             // [nb] batch poses of the current evaluation
-  uint32_t *d_keys = nullptr, *d_sxy = nullptr, *d_sbatch = nullptr;  // [n_packed] sort keys; events and batch indices in tile order
-  uint32_t *d_keys_s = nullptr, *d_idx = nullptr, *d_idx_s = nullptr; // radix-sort fallback (key spaces above count_sort_ok) ...
-  void *d_sort_temp = nullptr;                                        // ... allocated by the first sort that needs them
-  size_t sort_temp_cap = 0;
-  int *d_hist = nullptr, *d_tile_start = nullptr, *d_nchunks = nullptr;
-  Chunk *d_chunks = nullptr;
+  TileSort ts;                          // the events in tile order, the chunk table; ts.d_fallback: votes of the last evaluation that left their LDS window
   // the table's allocation and every vote launch's size: an upper bound known on the host (workgroups beyond the table's true
   // length return at once; launching that length instead was measured and gained nothing: 0.453 -> 0.452 ms at 20M events);
   // events per full chunk
   int max_chunks = 0, chunk_events = 0;
-  unsigned *d_fallback = nullptr;       // votes of the last evaluation that left their LDS window
   unsigned long long *h_stat = nullptr; // pinned: [0] = n_inside, [1] = fallback word of the last evaluation
   bool sorted = false;
   int64_t sorts = 0;
   double fallback_frac = 0;
   void release() {
-    void *dev[] = {d_xy, d_bt, d_poseR, d_keys, d_sxy, d_sbatch, d_keys_s, d_idx, d_idx_s, d_sort_temp, d_hist, d_tile_start, d_nchunks,
-                   d_chunks, d_fallback};
+    void *dev[] = {d_xy, d_bt, d_poseR};
     for (void *p : dev) (void)hipFree(p);
+    ts.release();
     if (h_stat) (void)hipHostFree(h_stat);
     *this = ReconBound{};
   }
@@ -122,35 +116,40 @@ void recon_release(cmx_ctx *c) {
     if (s.up) (void)hipEventDestroy(s.up);
     if (s.done) (void)hipEventDestroy(s.done);
   }
-  (void)hipFree(r->d_knots);
-  (void)hipFree(r->d_delta);
-  (void)hipFree(r->d_plane);
-  (void)hipFree(r->d_fixed);
-  (void)hipFree(r->d_inside);
-  (void)hipFree(r->d_err);
-  (void)hipFree(r->d_cx);
-  (void)hipFree(r->d_cy);
-  (void)hipFree(r->d_tflags);
-  (void)hipFree(r->d_tile_list);
-  (void)hipFree(r->d_tile_count);
-  (void)hipFree(r->d_partials);
-  (void)hipFree(r->d_cm);
-  (void)hipFree(r->d_jt);
-  (void)hipFree(r->d_gsum);
-  (void)hipFree(r->d_voted);
-  (void)hipFree(r->d_rows);
-  (void)hipFree(r->d_row_win);
+  void *dev[] = {r->d_knots, r->d_delta, r->d_plane, r->d_fixed, r->d_inside, r->d_err, r->d_cx, r->d_cy, r->d_tflags, r->d_tile_list,
+                 r->d_tile_count, r->d_partials, r->d_cm, r->d_jt, r->d_gsum, r->d_voted, r->d_rows, r->d_row_win};
+  for (void *p : dev) (void)hipFree(p);
   r->bnd.release();
   delete r;
   c->recon = nullptr;
 }
 
 // common front door: a plain back-end context (a group's handle has no reconstruction: CMX_ERR_STATE), bound to its device
-int recon_enter(cmx_ctx *c, bool need_begun) {
+static int recon_enter(cmx_ctx *c, bool need_begun) {
   if (!c || c->kind != KIND_BE) return fail(c, CMX_ERR_STATE, "not a back-end context");
   if (c->group) return fail(c, CMX_ERR_STATE, "reconstruction is not available on a group handle");
   if (need_begun && !c->recon) return fail(c, CMX_ERR_STATE, "cmx_backend_recon_begin has not succeeded");
   return bind_device(c);
+}
+
+// knot values for the trajectory of begin (begin itself, restart, eval_bound); plane, counters and gradient state start over.
+// Nothing is allocated or freed.
+// (knots_xyzw == NULL, eval_bound only: the current knots stay, and nothing of the caller's is read -- no wait)
+static int recon_start_over(cmx_ctx *c, ReconState *r, const double *knots_xyzw) {
+  const size_t np = (size_t)c->Wp * c->Hp;
+  r->grad_open = false;
+  r->n_sampled = 0;
+  if (knots_xyzw) {
+    static_assert(sizeof(Quat) == 4 * sizeof(double), "knots travel as (x, y, z, w) doubles");
+    HIP_TRY(c, hipMemcpyAsync(r->d_knots, knots_xyzw, (size_t)r->sup.K * sizeof(Quat), hipMemcpyHostToDevice, c->stream));
+    launch_recon_delta(r->d_knots, r->sup.K, r->d_delta, c->stream);
+  }
+  HIP_TRY(c, hipMemsetAsync(r->d_plane, 0, np * sizeof(float), c->stream));
+  HIP_TRY(c, hipMemsetAsync(r->d_inside, 0, sizeof(unsigned long long), c->stream));
+  if (r->d_fixed) HIP_TRY(c, hipMemsetAsync(r->d_fixed, 0, np * sizeof(unsigned long long), c->stream));
+  HIP_TRY(c, hipGetLastError());
+  if (knots_xyzw) HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller's knot array is free again
+  return CMX_OK;
 }
 
 static int recon_begin_inner(cmx_ctx *c, int order, int K, const double *knots_xyzw, int64_t start_ns, int64_t dt_ns, int B, int rate) {
@@ -172,18 +171,8 @@ static int recon_begin_inner(cmx_ctx *c, int order, int K, const double *knots_x
   HIP_TRY(c, hipMalloc((void **)&r->d_plane, np * sizeof(float)));
   HIP_TRY(c, hipMalloc((void **)&r->d_inside, sizeof(unsigned long long)));
   HIP_TRY(c, hipMalloc((void **)&r->d_err, 2 * sizeof(long long)));
-  HIP_TRY(c, hipMemsetAsync(r->d_plane, 0, np * sizeof(float), c->stream));
-  HIP_TRY(c, hipMemsetAsync(r->d_inside, 0, sizeof(unsigned long long), c->stream));
-  if (r->deterministic) {
-    HIP_TRY(c, hipMalloc((void **)&r->d_fixed, np * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMemsetAsync(r->d_fixed, 0, np * sizeof(unsigned long long), c->stream));
-  }
-  static_assert(sizeof(Quat) == 4 * sizeof(double), "knots travel as (x, y, z, w) doubles");
-  HIP_TRY(c, hipMemcpyAsync(r->d_knots, knots_xyzw, (size_t)K * sizeof(Quat), hipMemcpyHostToDevice, c->stream));
-  launch_recon_delta(r->d_knots, K, r->d_delta, c->stream);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller's knot array is free again
-  return CMX_OK;
+  if (r->deterministic) HIP_TRY(c, hipMalloc((void **)&r->d_fixed, np * sizeof(unsigned long long)));
+  return recon_start_over(c, r, knots_xyzw);
 }
 
 int cmx_backend_recon_begin(cmx_ctx *c, int order, int K, const double *knots_xyzw, int64_t start_ns, int64_t dt_ns,
@@ -209,10 +198,10 @@ int cmx_backend_recon_end(cmx_ctx *c) {
 }
 
 // ---- one add: batches of the call (plan_batches), slices of whole batches
+static int recon_slice_batches(const ReconState *r) { return slice_batches_of(g_slice_events.load(std::memory_order_relaxed), r->B); }
 static int recon_plan(cmx_ctx *c, const ReconState *r, int64_t n, BatchPlan *p, int *slice_batches) {
   if (!plan_batches(n, r->B, r->rate, p)) return fail(c, CMX_ERR_INVALID_ARG, "too many batches");
-  const int64_t sb = g_slice_events.load(std::memory_order_relaxed) / r->B;
-  *slice_batches = (int)(sb < 1 ? 1 : sb);
+  *slice_batches = recon_slice_batches(r);
   return CMX_OK;
 }
 
@@ -271,6 +260,12 @@ static int queue_gather(cmx_ctx *c, ReconState *r, ReconGatherArgs &g) {
   launch_recon_gather_rows(g, blocks, c->stream);
   return CMX_OK;
 }
+// one slice of a pass over events, as g.ev describes it: its votes, or its share of the gradient sums
+static int queue_slice(cmx_ctx *c, ReconState *r, ReconGatherArgs &g, bool grad) {
+  if (grad) return queue_gather(c, r, g);
+  launch_recon_votes(g.ev, c->stream);
+  return CMX_OK;
+}
 
 // staging of one slot.  The host paths (pinned) hold packed events and batch times in pinned memory and on the device; the store
 // path reads the store's events in place and forms the batch times on the device, so it holds the device table alone.
@@ -304,7 +299,7 @@ static int slot_ensure(cmx_ctx *c, ReconSlot &s, size_t n_xy, size_t n_bt, bool 
 
 // host arrays (SoA, or the host's own records): validate EVERYTHING first -- a call that fails adds nothing -- then pack slice
 // i+1 on the host pool and upload it on the copy stream while the vote kernel of slice i runs
-int recon_add_host(cmx_ctx *c, const EventSource &src, bool grad) {
+static int recon_add_host(cmx_ctx *c, const EventSource &src, bool grad) {
   ReconState *r = c->recon;
   if (int rc0 = recon_pass_enter(c, r, grad)) return rc0;
   // argument checks + EVERY coordinate handed in inside the sensor, those the sampling or the one-event rule skip included: what
@@ -327,9 +322,9 @@ int recon_add_host(cmx_ctx *c, const EventSource &src, bool grad) {
   auto vote_slices = [&]() -> int {
   int k = 0;
   for (int b_lo = 0; b_lo < p.nb; b_lo += slice_batches, k++) {
-    const int b_hi = (p.nb - b_lo > slice_batches) ? b_lo + slice_batches : p.nb;
-    const int nbs = b_hi - b_lo;
-    const int64_t ev_off = (int64_t)b_lo * B, np_s = p.packed(b_lo, b_hi);
+    const Slice sl = slice_at(p, n, b_lo, slice_batches);
+    const int b_hi = sl.b_hi, nbs = b_hi - b_lo;
+    const int64_t ev_off = sl.ev_first, np_s = sl.n;
     ReconSlot &s = r->slot[k & 1];
     if (s.busy) { HIP_TRY(c, hipEventSynchronize(s.done)); s.busy = false; }  // its previous slice has been voted
     rc = slot_ensure(c, s, (size_t)np_s, (size_t)nbs, true);
@@ -347,8 +342,7 @@ int recon_add_host(cmx_ctx *c, const EventSource &src, bool grad) {
     a.xy = s.d_xy; a.stride = 0;
     a.batch_t = s.d_bt; a.nb = nbs;
     a.n = (int)np_s;
-    if (grad) rc = queue_gather(c, r, ga);
-    else launch_recon_votes(a, c->stream);
+    rc = queue_slice(c, r, ga, grad);
     if (rc) return rc;
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(s.done, c->stream));
@@ -367,7 +361,7 @@ int recon_add_host(cmx_ctx *c, const EventSource &src, bool grad) {
 
 // events already on the device (event store): batch times and their validation by launch_be_batch_times, slice by slice into
 // one slice-sized table; the error words are read before the first vote kernel of the call is queued
-int recon_add_store(cmx_ctx *c, const EventSource &src, bool grad) {
+static int recon_add_store(cmx_ctx *c, const EventSource &src, bool grad) {
   ReconState *r = c->recon;
   if (int rc0 = recon_pass_enter(c, r, grad)) return rc0;
   const int64_t n = src.n;
@@ -381,13 +375,10 @@ int recon_add_store(cmx_ctx *c, const EventSource &src, bool grad) {
   ReconSlot &s = r->slot[0];
   rc = slot_ensure(c, s, 0, (size_t)(p.nb < slice_batches ? p.nb : slice_batches), false);
   if (rc) return rc;
-  auto slice_times = [&](int b_lo, int b_hi, bool clear_err) {
-    const int64_t ev_off = (int64_t)b_lo * B;
-    const int64_t n_s = b_hi == p.nb ? n - ev_off : (int64_t)(b_hi - b_lo) * B;
-    return queue_batch_times(c, src.d_t + ev_off, n_s, B, b_hi - b_lo, r->sup, s.d_bt, r->d_err, clear_err);
+  auto slice_times = [&](int b_lo, const Slice &sl, bool clear_err) {
+    return queue_batch_times(c, src.d_t + sl.ev_first, sl.ev_n, B, sl.b_hi - b_lo, r->sup, s.d_bt, r->d_err, clear_err);
   };
-  for (int b_lo = 0; b_lo < p.nb && !rc; b_lo += slice_batches)
-    rc = slice_times(b_lo, (p.nb - b_lo > slice_batches) ? b_lo + slice_batches : p.nb, b_lo == 0);
+  for (int b_lo = 0; b_lo < p.nb && !rc; b_lo += slice_batches) rc = slice_times(b_lo, slice_at(p, n, b_lo, slice_batches), b_lo == 0);
   if (rc) return rc;
   HIP_TRY(c, hipGetLastError());
   BatchTimeError bad;
@@ -398,16 +389,15 @@ int recon_add_store(cmx_ctx *c, const EventSource &src, bool grad) {
   ReconArgs &a = ga.ev;
   const bool one_slice = p.nb <= slice_batches;  // (its batch times are those the validation pass has just written)
   for (int b_lo = 0; b_lo < p.nb; b_lo += slice_batches) {
-    const int b_hi = (p.nb - b_lo > slice_batches) ? b_lo + slice_batches : p.nb;
+    const Slice sl = slice_at(p, n, b_lo, slice_batches);
     if (!one_slice) {
-      rc = slice_times(b_lo, b_hi, false);
+      rc = slice_times(b_lo, sl, false);
       if (rc) return rc;
     }
-    a.xy = src.d_xy + (int64_t)b_lo * B; a.stride = r->rate;
-    a.batch_t = s.d_bt; a.nb = b_hi - b_lo;
-    a.n = (int)p.packed(b_lo, b_hi);
-    if (grad) rc = queue_gather(c, r, ga);
-    else launch_recon_votes(a, c->stream);
+    a.xy = src.d_xy + sl.ev_first; a.stride = r->rate;
+    a.batch_t = s.d_bt; a.nb = sl.b_hi - b_lo;
+    a.n = (int)sl.n;
+    rc = queue_slice(c, r, ga, grad);
     if (rc) return rc;
   }
   HIP_TRY(c, hipGetLastError());
@@ -416,62 +406,47 @@ int recon_add_store(cmx_ctx *c, const EventSource &src, bool grad) {
   return CMX_OK;
 }
 
+// the six entry points that hand events over: the front door, the call's own way to its source (host arrays, the host's records,
+// a range of an event store -- with that form's argument checks), then the vote pass or the gradient pass over it
+template <typename MakeSource>
+static int recon_add_entry(cmx_ctx *c, bool grad, MakeSource make) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  EventSource src;
+  rc = make(&src);
+  if (rc) return rc;
+  return src.on_device() ? recon_add_store(c, src, grad) : recon_add_host(c, src, grad);
+}
+static int recon_add_arrays(cmx_ctx *c, bool grad, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns) {
+  return recon_add_entry(c, grad, [&](EventSource *src) { *src = EventSource::arrays(n, x, y, t_ns); return (int)CMX_OK; });
+}
+static int recon_add_records(cmx_ctx *c, bool grad, int64_t n, const void *events, const cmx_aos_layout *layout) {
+  return recon_add_entry(c, grad, [&](EventSource *src) { return make_aos(c, n, events, layout, src); });
+}
+// (the vote kernel reads the store's own packed events -- the per-batch sampling is an index map, nothing is copied -- and
+// launch_be_batch_times forms and validates the batch times)
+static int recon_add_range(cmx_ctx *c, bool grad, const cmx_events *e, int64_t first, int64_t count) {
+  return recon_add_entry(c, grad, [&](EventSource *src) { return store_source(c, e, first, count, src); });
+}
 int cmx_backend_recon_add(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns) {
-  int rc = recon_enter(c, true);
-  if (rc) return rc;
-  return recon_add_host(c, EventSource::arrays(n, x, y, t_ns), false);
+  return recon_add_arrays(c, false, n, x, y, t_ns);
 }
-
-int cmx_backend_recon_add_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout) {
-  int rc = recon_enter(c, true);
-  if (rc) return rc;
-  EventSource src;
-  rc = make_aos(c, n, events, layout, &src);
-  if (rc) return rc;
-  return recon_add_host(c, src, false);
-}
-
 int cmx_backend_recon_grad_add(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns) {
-  int rc = recon_enter(c, true);
-  if (rc) return rc;
-  return recon_add_host(c, EventSource::arrays(n, x, y, t_ns), true);
+  return recon_add_arrays(c, true, n, x, y, t_ns);
 }
-
+int cmx_backend_recon_add_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout) {
+  return recon_add_records(c, false, n, events, layout);
+}
 int cmx_backend_recon_grad_add_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout) {
-  int rc = recon_enter(c, true);
-  if (rc) return rc;
-  EventSource src;
-  rc = make_aos(c, n, events, layout, &src);
-  if (rc) return rc;
-  return recon_add_host(c, src, true);
+  return recon_add_records(c, true, n, events, layout);
 }
-
+int cmx_backend_recon_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
+  return recon_add_range(c, false, e, first, count);
+}
 int cmx_backend_recon_grad_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
-  int rc = recon_enter(c, true);
-  if (rc) return rc;
-  EventSource src;
-  rc = store_source(c, e, first, count, &src);
-  if (rc) return rc;
-  return recon_add_store(c, src, true);
+  return recon_add_range(c, true, e, first, count);
 }
 
-// new knot values for the trajectory of begin; plane, counters and gradient state start over.  Nothing is allocated or freed.
-// (knots_xyzw == NULL, eval_bound only: the current knots stay, and nothing of the caller's is read -- no wait)
-static int recon_start_over(cmx_ctx *c, ReconState *r, const double *knots_xyzw) {
-  const size_t np = (size_t)c->Wp * c->Hp;
-  r->grad_open = false;
-  r->n_sampled = 0;
-  if (knots_xyzw) {
-    HIP_TRY(c, hipMemcpyAsync(r->d_knots, knots_xyzw, (size_t)r->sup.K * sizeof(Quat), hipMemcpyHostToDevice, c->stream));
-    launch_recon_delta(r->d_knots, r->sup.K, r->d_delta, c->stream);
-  }
-  HIP_TRY(c, hipMemsetAsync(r->d_plane, 0, np * sizeof(float), c->stream));
-  HIP_TRY(c, hipMemsetAsync(r->d_inside, 0, sizeof(unsigned long long), c->stream));
-  if (r->d_fixed) HIP_TRY(c, hipMemsetAsync(r->d_fixed, 0, np * sizeof(unsigned long long), c->stream));
-  HIP_TRY(c, hipGetLastError());
-  if (knots_xyzw) HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller's knot array is free again
-  return CMX_OK;
-}
 int cmx_backend_recon_restart(cmx_ctx *c, const double *knots_xyzw) {
   int rc = recon_enter(c, true);
   if (rc) return rc;
@@ -505,6 +480,14 @@ static int recon_setup_blur(cmx_ctx *c, ReconState *r, double sigma) {
   r->sigma_built = sigma;
   return CMX_OK;
 }
+// ... and what a gradient at this sigma needs on top of it: G^T folds single reflections, so the panorama is larger than the kernel
+static int recon_grad_precheck(cmx_ctx *c, ReconState *r, double sigma) {
+  const int rc = recon_setup_blur(c, r, sigma);
+  if (rc) return rc;
+  if (!(c->Wp > 2 * r->radius + 1 && c->Hp > 2 * r->radius + 1))
+    return fail(c, CMX_ERR_INVALID_ARG, "panorama %d x %d too small for the adjoint gradient at blur radius %d", c->Wp, c->Hp, r->radius);
+  return CMX_OK;
+}
 
 // The image pass over the plane as accumulated so far: contrast of GaussianBlur(plane, sigma), and with want_grad
 // Jt = G^T (G plane) for the gradient pass it opens.  The plane is read only.
@@ -514,12 +497,10 @@ int cmx_backend_recon_contrast(cmx_ctx *c, double blur_sigma, int contrast_measu
   if (!contrast) return fail(c, CMX_ERR_INVALID_ARG, "null output");
   if (!std::isfinite(blur_sigma)) return fail(c, CMX_ERR_INVALID_ARG, "blur_sigma is not finite");
   ReconState *r = c->recon;
-  rc = recon_setup_blur(c, r, blur_sigma);
+  rc = want_grad ? recon_grad_precheck(c, r, blur_sigma) : recon_setup_blur(c, r, blur_sigma);
   if (rc) return rc;
   const int W = c->Wp, H = c->Hp, rad = r->radius;
   const size_t np = (size_t)W * H;
-  if (want_grad && !(W > 2 * rad + 1 && H > 2 * rad + 1))
-    return fail(c, CMX_ERR_INVALID_ARG, "panorama %d x %d too small for the adjoint gradient at blur radius %d", W, H, rad);
   ImgAdjArgs ia{};
   ImgArgs &a = ia.img;
   a.W = W; a.H = H; a.r = rad;
@@ -609,10 +590,8 @@ int cmx_backend_recon_eval_from(cmx_ctx *c, const cmx_events *e, int64_t first, 
   if (!contrast) return fail(c, CMX_ERR_INVALID_ARG, "null output");
   ReconState *r = c->recon;
   if (grad) {  // (before anything is changed: the one argument error the later steps would find)
-    rc = recon_setup_blur(c, r, blur_sigma);
+    rc = recon_grad_precheck(c, r, blur_sigma);
     if (rc) return rc;
-    if (!(c->Wp > 2 * r->radius + 1 && c->Hp > 2 * r->radius + 1))
-      return fail(c, CMX_ERR_INVALID_ARG, "panorama %d x %d too small for the adjoint gradient at blur radius %d", c->Wp, c->Hp, r->radius);
   }
   EventSource src;
   rc = store_source(c, e, first, count, &src);
@@ -627,11 +606,11 @@ int cmx_backend_recon_eval_from(cmx_ctx *c, const cmx_events *e, int64_t first, 
 
 // ---- bound events: hand the events over ONCE, evaluate them many times (an optimiser's trial points) with the votes made through LDS
 // bind_from   validation of recon_add_from, then the sampled events of the range, packed in time order, and their batch times into
-//             memory of the reconstruction's own, with the buffers of the tile sort; everything is built beside an earlier binding,
+//             memory of the reconstruction's own, with a TileSort reserved for them; everything is built beside an earlier binding,
 //             which is replaced only once nothing can fail any more
 // eval_bound  restart + eval_from over the bound events: batch-pose table behind recon_delta, tile sort at the first evaluation and
 //             again after one whose votes left their windows (kRebinFallbackFrac), recon_votes_lds, the image pass, and the gather
-//             pass over the time-ordered copy in recon_add_store's slices
+//             pass over the time-ordered copy in the slices of every add (slice_at)
 constexpr int64_t kMaxBoundSampled = 1LL << 30;  // (sorted positions, chunk bounds and keys are 32-bit)
 
 static int bound_build(cmx_ctx *c, ReconState *r, const EventSource &src, const BatchPlan &p, ReconBound *b) {
@@ -648,27 +627,17 @@ static int bound_build(cmx_ctx *c, ReconState *r, const EventSource &src, const 
   rc = read_batch_errors(c, r->d_err, &bad);
   if (rc) return rc;
   if (bad.kind) return fail_batch_time(c, bad, r->sup, /*with_event=*/false);
-  // ---- valid: the copy, and the sort's buffers
+  // ---- valid: the copy, the pose table, and the sort's buffers with the chunk table at the back end's chunk size
   const size_t n = (size_t)p.n_packed;
   const int tiles = ((c->Wp + kBinTile - 1) / kBinTile) * ((c->Hp + kBinTile - 1) / kBinTile);
   const int ntiles = 2 * tiles;  // (the back end's sort keys carry the old / new bit: no bound event sets it, half of the bins stay empty)
   HIP_TRY(c, hipMalloc((void **)&b->d_xy, n * sizeof(uint32_t)));
   HIP_TRY(c, hipMalloc((void **)&b->d_poseR, (size_t)p.nb * sizeof(PoseR)));
-  HIP_TRY(c, hipMalloc((void **)&b->d_keys, n * sizeof(uint32_t)));
-  HIP_TRY(c, hipMalloc((void **)&b->d_sxy, n * sizeof(uint32_t)));
-  HIP_TRY(c, hipMalloc((void **)&b->d_sbatch, n * sizeof(uint32_t)));
-  if (count_sort_ok(ntiles + 1))
-    HIP_TRY(c, hipMalloc((void **)&b->d_hist, count_sort_scratch_ints((int)n, ntiles + 1) * sizeof(int)));
-  HIP_TRY(c, hipMalloc((void **)&b->d_tile_start, ((size_t)ntiles + 2) * sizeof(int)));
-  // chunk size and the table's bound: do_binning's rule for the back end (plan_bound, cmx_ingest.hpp)
-  const BoundPlan bp = plan_bound(p.n_packed, ntiles);
-  b->chunk_events = bp.chunk_events;
-  b->max_chunks = (int)bp.max_chunks;  // (n <= 2^30, at most 2^20 tiles: below 2^23)
-  HIP_TRY(c, hipMalloc((void **)&b->d_chunks, (size_t)b->max_chunks * sizeof(Chunk)));
-  HIP_TRY(c, hipMalloc((void **)&b->d_nchunks, sizeof(int)));
-  HIP_TRY(c, hipMalloc((void **)&b->d_fallback, sizeof(unsigned)));
-  HIP_TRY(c, hipMemsetAsync(b->d_nchunks, 0, sizeof(int), c->stream));
-  HIP_TRY(c, hipMemsetAsync(b->d_fallback, 0, sizeof(unsigned), c->stream));
+  const ChunkPlan cp = plan_chunks(p.n_packed, ntiles, kBackEndChunkDiv);
+  b->chunk_events = cp.chunk_events;
+  b->max_chunks = (int)cp.max_chunks;  // (n <= 2^30, at most 2^20 tiles: below 2^23)
+  rc = b->ts.reserve(c, p.n_packed, ntiles, cp.max_chunks);
+  if (rc) return rc;
   // (t_next = the smallest time: no event carries the old flag)
   launch_be_pack_from_store(src.d_xy, reinterpret_cast<const long long *>(src.d_t), (long long)src.n, r->B, r->rate, p.per_batch, (int)n,
                             std::numeric_limits<long long>::min(), b->d_xy, c->stream);
@@ -729,57 +698,34 @@ int cmx_backend_recon_bound_info(cmx_ctx *c, int64_t *n_events, int64_t *n_sampl
 
 // the bound events by the destination tile of their vote under the pose table as it stands, and the chunk table
 static int bound_sort(cmx_ctx *c, ReconBound &b, const BeSplatArgs &be) {
-  const int n = (int)b.plan.n_packed;
-  const int tiles_x = (c->Wp + kBinTile - 1) / kBinTile, tiles = tiles_x * ((c->Hp + kBinTile - 1) / kBinTile), ntiles = 2 * tiles;
-  if (b.d_hist) {
-    launch_count_sort(nullptr, &be, tiles_x, tiles, b.d_xy, b.plan.per_batch, n, b.d_keys, b.d_hist, b.d_tile_start, b.d_sxy, b.d_sbatch,
-                      nullptr, nullptr, c->stream);
-  } else {  // more destination tiles than an LDS histogram holds: (key, index) radix sort, as do_binning
-    if (!b.d_keys_s) {
-      uint32_t **ptrs[3] = {&b.d_keys_s, &b.d_idx, &b.d_idx_s};
-      for (auto p : ptrs) HIP_TRY(c, hipMalloc((void **)p, (size_t)n * sizeof(uint32_t)));
-    }
-    launch_be_bin_keys(be, tiles_x, tiles, b.d_keys, b.d_idx, c->stream);
-    int end_bit = 1;
-    while ((1 << end_bit) <= ntiles) end_bit++;
-    size_t tb = 0;
-    if (sort_pairs_u32(nullptr, &tb, b.d_keys, b.d_keys_s, b.d_idx, b.d_idx_s, (unsigned)n, end_bit, c->stream) != 0)
-      return fail(c, CMX_ERR_HIP, "rocprim radix sort (size query) failed");
-    if (tb > b.sort_temp_cap || !b.d_sort_temp) {
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      (void)hipFree(b.d_sort_temp);
-      b.d_sort_temp = nullptr;
-      b.sort_temp_cap = 0;
-      HIP_TRY(c, hipMalloc(&b.d_sort_temp, tb ? tb : 1));
-      b.sort_temp_cap = tb;
-    }
-    if (sort_pairs_u32(b.d_sort_temp, &tb, b.d_keys, b.d_keys_s, b.d_idx, b.d_idx_s, (unsigned)n, end_bit, c->stream) != 0)
-      return fail(c, CMX_ERR_HIP, "rocprim radix sort failed");
-    launch_apply_perm(b.d_xy, b.d_idx_s, b.plan.per_batch, n, b.d_sxy, b.d_sbatch, c->stream);
-    launch_tile_lower_bound(b.d_keys_s, n, ntiles + 2, b.d_tile_start, c->stream);
-  }
-  launch_build_chunks(b.d_tile_start, ntiles, 2, tiles_x, kBinMargin, b.chunk_events, b.d_chunks, b.d_nchunks, nullptr, 0, c->stream);
-  HIP_TRY(c, hipGetLastError());
+  TileSortJob job;
+  job.be = &be;
+  job.tiles_x = (c->Wp + kBinTile - 1) / kBinTile;
+  job.tiles = job.tiles_x * ((c->Hp + kBinTile - 1) / kBinTile);
+  job.planes_per_tile = 2;
+  job.xy = b.d_xy; job.per_batch = b.plan.per_batch; job.n = (int)b.plan.n_packed;
+  job.chunk_events = b.chunk_events;
+  const int rc = b.ts.run(c, job);
+  if (rc) return rc;
   b.sorted = true;
   b.sorts++;
   return CMX_OK;
 }
 
-// the gradient pass over the bound time-ordered copy: recon_add_store's slices, runs and launches, with stride 0
+// the gradient pass over the bound time-ordered copy: the slices, runs and launches of recon_add_store, with stride 0
 static int bound_gather(cmx_ctx *c, ReconState *r) {
   if (int rc0 = recon_pass_enter(c, r, true)) return rc0;
   const ReconBound &b = r->bnd;
   const BatchPlan &p = b.plan;
-  const int64_t sb = g_slice_events.load(std::memory_order_relaxed) / r->B;
-  const int slice_batches = (int)(sb < 1 ? 1 : sb);
+  const int slice_batches = recon_slice_batches(r);
   ReconGatherArgs ga = recon_gather_args(c, r);
   ReconArgs &a = ga.ev;
   for (int b_lo = 0; b_lo < p.nb; b_lo += slice_batches) {
-    const BoundSlice sl = bound_slice(p, b_lo, slice_batches);
+    const Slice sl = slice_at(p, b.n_events, b_lo, slice_batches);
     a.xy = b.d_xy + sl.first; a.stride = 0;
     a.batch_t = b.d_bt + b_lo; a.nb = sl.b_hi - b_lo;
     a.n = (int)sl.n;
-    const int rc = queue_gather(c, r, ga);
+    const int rc = queue_slice(c, r, ga, true);
     if (rc) return rc;
   }
   HIP_TRY(c, hipGetLastError());
@@ -796,10 +742,8 @@ int cmx_backend_recon_eval_bound(cmx_ctx *c, const double *knots_xyzw, double bl
   if (!r->bound) return fail(c, CMX_ERR_STATE, "no events are bound (cmx_backend_recon_bind_from)");
   if (!contrast) return fail(c, CMX_ERR_INVALID_ARG, "null output");
   if (grad) {  // (before anything is changed, as in eval_from)
-    rc = recon_setup_blur(c, r, blur_sigma);
+    rc = recon_grad_precheck(c, r, blur_sigma);
     if (rc) return rc;
-    if (!(c->Wp > 2 * r->radius + 1 && c->Hp > 2 * r->radius + 1))
-      return fail(c, CMX_ERR_INVALID_ARG, "panorama %d x %d too small for the adjoint gradient at blur radius %d", c->Wp, c->Hp, r->radius);
   }
   ReconBound &b = r->bnd;
   rc = recon_start_over(c, r, knots_xyzw);
@@ -823,13 +767,13 @@ int cmx_backend_recon_eval_bound(cmx_ctx *c, const double *knots_xyzw, double bl
       rc = bound_sort(c, b, g.cam);
       if (rc) return rc;
     }
-    g.ev.sxy = b.d_sxy; g.ev.sbatch = b.d_sbatch;
-    g.ev.chunks = b.d_chunks; g.ev.nchunks = b.max_chunks; g.ev.nchunks_dev = b.d_nchunks;
-    g.ev.fallback = b.d_fallback;
+    g.ev.sxy = b.ts.d_sxy; g.ev.sbatch = b.ts.d_sbatch;
+    g.ev.chunks = b.ts.d_chunks; g.ev.nchunks = b.max_chunks; g.ev.nchunks_dev = b.ts.d_nchunks;
+    g.ev.fallback = b.ts.d_fallback;
     g.ev.fixed = r->deterministic ? r->d_fixed : nullptr;
     g.plane = r->d_plane;
     g.n_inside = r->d_inside;
-    HIP_TRY(c, hipMemsetAsync(b.d_fallback, 0, sizeof(unsigned), c->stream));
+    HIP_TRY(c, hipMemsetAsync(b.ts.d_fallback, 0, sizeof(unsigned), c->stream));
     {
       Span sp(c, CMX_T_SPLAT, /*exact=*/true);
       launch_recon_votes_lds(g, c->stream, sp.t0(), sp.t1());
@@ -838,7 +782,7 @@ int cmx_backend_recon_eval_bound(cmx_ctx *c, const double *knots_xyzw, double bl
     // (into pinned memory of the binding's own; complete once the image pass below has waited for the stream)
     b.h_stat[1] = 0ull;
     HIP_TRY(c, hipMemcpyAsync(&b.h_stat[0], r->d_inside, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(&b.h_stat[1], b.d_fallback, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&b.h_stat[1], b.ts.d_fallback, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     r->n_sampled += b.plan.n_packed;
   }
   rc = cmx_backend_recon_contrast(c, blur_sigma, contrast_measure, grad != nullptr, contrast);

@@ -78,9 +78,9 @@ def test_evaluator_has_the_methods():
 
 
 def test_host_arithmetic_of_a_binding(tmp_path):
-    """plan_bound / bound_slice (cmx_ingest.hpp) alone, under the address and undefined-behaviour sanitizers: the slices of a pass
-    tile the packed events, the chunk table's bound holds for every distribution build_chunks can meet, nothing overflows an int
-    at the limits (tests/bound_plan_host.cpp)."""
+    """plan_chunks / slice_at (cmx_ingest.hpp) alone, under the address and undefined-behaviour sanitizers: the slices of a pass
+    tile the packed events and the events handed in, the chunk table's bound holds for every distribution build_chunks can meet,
+    the front end's divisor gives the window path's formula, nothing overflows an int at the limits (tests/bound_plan_host.cpp)."""
     exe = str(tmp_path / "bound_plan_host")
     cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++")
     assert cxx, "no host C++ compiler"
