@@ -137,6 +137,11 @@ SYMBOLS = {
     "cmx_backend_recon_unbind": (C.c_int, [ctx_p]),
     "cmx_backend_recon_eval_bound": (C.c_int, [ctx_p, c_dp, C.c_double, C.c_int, c_dp, c_dp]),
     "cmx_backend_recon_bound_info": (C.c_int, [ctx_p, c_i64p, c_i64p, c_i64p, c_dp]),
+    "cmx_backend_recon_freeze_head": (C.c_int, [ctx_p, C.c_int]),
+    "cmx_backend_recon_frozen_info": (C.c_int, [ctx_p, C.POINTER(C.c_int), c_i64p, c_i64p]),
+    "cmx_backend_recon_solve": (C.c_int, [ctx_p, c_dp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double,
+                                          C.c_double, C.c_int, C.c_void_p]),
+    "cmx_diag_recon_solve_counts": (C.c_int, [ctx_p, c_i64p, c_i64p]),
     "cmx_traj_temp_start_ns": (C.c_int64, [C.c_double, C.c_int, C.c_double]),
     "cmx_accum_capacity": (C.c_size_t, [ctx_p]),
     "cmx_set_accum_buffer": (C.c_int, [ctx_p, C.c_void_p, C.c_size_t]),

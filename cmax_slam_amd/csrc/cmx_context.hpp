@@ -479,6 +479,14 @@ int be_eval_one(cmx_ctx *c, const double *drotv, double *contrast, double *grad)
 // ---- cmx_reconstruct.cpp
 int recon_diag_slice_events(int n);  // CMX_DIAG_RECON_SLICE_EVENTS (cmax_hip_diag.h)
 void recon_release(cmx_ctx *c);  // frees whatever a reconstruction holds (cmx_backend_recon_end, cmx_destroy)
+// cmx_backend_recon_solve (cmx_solver.cpp) around the bound evaluation: begin validates everything before anything changes, sets
+// up staging and (freeze_head) the frozen head at the start knots, *n_params = 3 (K - num_fixed); eval is one trial point at
+// increment x (grad_free: the 3 (K - num_fixed) free entries, or NULL); end evaluates x once more only if the last trial point was
+// another one, and writes the knots of x to knots_out (cmx_diag_recon_solve_counts reads the solve's evaluations and host waits)
+int recon_solve_begin(cmx_ctx *c, const double *knots_xyzw, int num_fixed, int freeze_head, double blur_sigma, int contrast_measure,
+                      int *n_params);
+int recon_solve_eval(cmx_ctx *c, const double *x, double *contrast, double *grad_free);
+int recon_solve_end(cmx_ctx *c, const double *x, double *knots_out);
 
 // ---- cmx_comm.cpp
 int finish_sharded(cmx_ctx *c, int kind, bool exchange_planes, double *contrast, double *grad);

@@ -179,6 +179,25 @@ inline Slice slice_at(const BatchPlan &p, int64_t n_events, int b_lo, int slice_
   return s;
 }
 
+// ---- the frozen head of a bound whole-trajectory evaluation (cmx_backend_recon_freeze_head): the batches whose pose no free knot
+// can move.  A batch at pose time t lies in segment s = (t - start) / dt, clamped to [0, K - order] as the kernels clamp it
+// (recon_pose, recon_segment), and its pose reads the knots s .. s + order - 1: it is frozen when all of them are among the first
+// num_fixed, s + order - 1 < num_fixed.  Returns b_act, the number of LEADING frozen batches: the frozen head is [0, b_act), the
+// active batches are [b_act, nb).  Batch times of a time-ordered recording do not decrease, so no batch behind b_act is frozen;
+// were one out of order, it would merely be evaluated again every time, which is exact too.  The order is sup.order.
+inline bool batch_is_frozen(const KnotSupport &sup, int num_fixed, long long t_ns) {
+  long long s = (t_ns - sup.start_ns) / sup.dt_ns;
+  const long long s_max = (long long)sup.K - sup.order;
+  s = s < 0 ? 0 : (s > s_max ? s_max : s);
+  return s + sup.order - 1 < (long long)num_fixed;
+}
+inline int frozen_prefix(const KnotSupport &sup, int num_fixed, const long long *batch_t, int nb) {
+  if (num_fixed <= 0 || !batch_t) return 0;
+  int b = 0;
+  while (b < nb && batch_is_frozen(sup, num_fixed, batch_t[b])) b++;
+  return b;
+}
+
 // the contiguous range of whole batches a group hands member `rank` (cmax_slam_amd/dist.py: batch_range)
 inline void batch_range(int64_t n, int B, int rank, int world, int64_t *beg, int64_t *end) {
   const int64_t nb = (n + B - 1) / B, per = (nb + world - 1) / world;

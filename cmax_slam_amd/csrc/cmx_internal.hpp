@@ -489,6 +489,10 @@ void launch_recon_gather_rows(const ReconGatherArgs &g, int blocks, hipStream_t 
 // nvalid is set), summed in index order: out[0] = contrast, out[1] = mu
 void launch_recon_moments_finalize(const double *partials, int nblk, const unsigned *nvalid, double npix, int measure, double *out,
                                    hipStream_t s);
+// the free gradient entries on the device: out[k - first] = (2/N)(gsum[k] - mu gsum[P + k]), k in [first, P), mu = cm[1] (0 for the
+// mean-square measure) -- cmx_backend_recon_grad_get's expression; out may be mapped host memory
+void launch_recon_grad_finalize(const double *gsum, const double *cm, long long P, long long first, double npix, bool mean_square,
+                                double *out, hipStream_t s);
 
 // global-map upkeep (once per window)
 void launch_update_map(float *IG, const float *IL_old, const unsigned char *visits, int npix, int max_update_times,

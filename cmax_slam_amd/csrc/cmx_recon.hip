@@ -589,4 +589,25 @@ void launch_recon_moments_finalize(const double *partials, int nblk, const unsig
   hipLaunchKernelGGL(recon_moments_finalize_kernel, dim3(1), dim3(256), 0, s, partials, nblk, nvalid, npix, measure, out);
 }
 
+// recon_grad_finalize   the gradient of the FREE parameters from the two sums, where the sums are: out[k - first] =
+//                       (2/N)(S1[k] - mu S2[k]) for k in [first, P), the expression of cmx_backend_recon_grad_get term by term --
+//                       the product, the difference, the doubling and the division are four roundings (the build does not contract,
+//                       and the pragma says so for this function alone), so the same sums give the same bits as the host loop.  mu
+//                       is the image pass's own (cm[1], what the host reads back as r->mu), zero for the mean-square measure.
+//                       One lane per parameter; out is host memory mapped into the device, read by the solve after its one wait.
+__global__ __launch_bounds__(256) void recon_grad_finalize_kernel(const double *gsum, const double *cm, long long P, long long first,
+                                                                  double npix, int mean_square, double *out) {
+#pragma clang fp contract(off)
+  const long long k = first + (long long)blockIdx.x * 256 + threadIdx.x;
+  if (k >= P) return;
+  const double mu = mean_square ? 0.0 : cm[1];
+  out[k - first] = 2.0 * (gsum[k] - (mu != 0.0 ? mu * gsum[P + k] : 0.0)) / npix;
+}
+void launch_recon_grad_finalize(const double *gsum, const double *cm, long long P, long long first, double npix, bool mean_square,
+                                double *out, hipStream_t s) {
+  if (first >= P) return;
+  const long long blocks = (P - first + 255) / 256;  // (P <= 3 x 2^28)
+  hipLaunchKernelGGL(recon_grad_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, s, gsum, cm, P, first, npix, mean_square ? 1 : 0, out);
+}
+
 }  // namespace cmx

@@ -7,7 +7,9 @@
 // events, in the adjoint form of the window path -- per batch one 3-vector through the 3 x 3N spline Jacobian,
 // so nothing grows with the knot count but the 2 x 3K sums.  And for an optimiser that evaluates the SAME events many times: events
 // bound once (recon_bind_from), evaluated through a batch-pose table, a tile sort of the reconstruction's own and LDS votes
-// (recon_eval_bound).
+// (recon_eval_bound).  And for the online case -- a settled head, a free tail: the batches under fixed knots voted once
+// into a base plane (recon_freeze_head), and the evaluation side of the native bundle adjustment (recon_solve_*, driven by
+// cmx_solver.cpp's FR-CG machine).
 // Kernels: cmx_recon.hip.
 #include <limits>
 
@@ -64,6 +66,47 @@ struct ReconBound {
   }
 };
 
+// A frozen head of the binding (cmx_backend_recon_freeze_head): the batches [0, b_act) whose pose only the first
+// num_fixed knots can move (frozen_prefix, cmx_ingest.hpp), voted ONCE at the knots of the freeze into a base plane of the
+// reconstruction's own -- fp32 in default mode, the 2^-30 fixed-point plane in deterministic mode -- with the count of its voting
+// events beside it.  An evaluation of the binding then starts from the base and walks the active batches [b_act, nb) alone: their
+// events, a tile sort of their own in the binding's TileSort, a chunk table at the chunk rule of their count.
+struct ReconFrozen {
+  int num_fixed = 0;                      // 0: no frozen head
+  int b_act = 0;                          // first active batch
+  int64_t sampled = 0;                    // sampled events of the frozen batches
+  unsigned long long inside = 0;          // ... of which voted
+  void *d_base = nullptr;                 // [Wp * Hp] float, or fix_t in deterministic mode
+  unsigned long long *d_inside = nullptr; // `inside` on the device, what an evaluation's counter starts from
+  std::vector<double> knots;              // the first num_fixed knots as they were at the freeze (x, y, z, w)
+  int max_chunks = 0, chunk_events = 0;   // the active part's chunk table (plan_chunks of its count)
+  void release() {
+    (void)hipFree(d_base);
+    (void)hipFree(d_inside);
+    *this = ReconFrozen{};
+  }
+};
+
+// What cmx_backend_recon_solve keeps between its trial points: the start knots, pinned staging for the moved knots, and host memory
+// the device writes an evaluation's results into (contrast and mean, the two counters, the free gradient entries).
+struct ReconSolve {
+  std::vector<double> k0, last_x;
+  int num_fixed = 0, measure = CMX_VARIANCE;
+  double sigma = 1.0;
+  double *h_knots = nullptr;              // pinned [K][4]
+  double *h_cm = nullptr;                 // pinned: contrast, mu
+  unsigned long long *h_cnt = nullptr;    // pinned: n_inside, n_voted
+  double *h_grad = nullptr, *d_grad = nullptr;  // mapped [3K]
+  bool have_last = false;
+  int64_t evals = 0, waits = 0;           // of the last solve: evaluations, and host waits inside them
+  void release() {
+    void *host[] = {h_knots, h_cm, h_cnt, h_grad};
+    for (void *p : host)
+      if (p) (void)hipHostFree(p);
+    *this = ReconSolve{};
+  }
+};
+
 struct ReconState {
   KnotSupport sup;
   int B = 0, rate = 0, per_batch = 0;
@@ -100,7 +143,24 @@ struct ReconState {
   // ---- bound events (recon_bind_from .. recon_unbind): survive restart, dropped by begin and end
   bool bound = false;
   ReconBound bnd;
+  ReconFrozen frozen;                     // of the binding: dropped with it, and by restart
+  int g_num_fixed = 0;                    // the open gradient pass is a frozen evaluation's: grad[0, 3 g_num_fixed) is zero by definition
+  ReconSolve solve;
+  int64_t host_waits = 0;                 // times a host thread has waited for the device in this reconstruction's calls
 };
+// every place one of these calls blocks on the stream goes through here (cmx_backend_recon_solve reports the count per evaluation)
+static hipError_t recon_wait(cmx_ctx *c, ReconState *r) {
+  r->host_waits++;
+  return hipStreamSynchronize(c->stream);
+}
+// the binding changes, goes, or the knots are set anew: no frozen head any more, and the next evaluation sorts all events again
+static void frozen_drop(cmx_ctx *c, ReconState *r) {
+  if (!r->frozen.num_fixed && !r->frozen.d_base) return;
+  (void)hipStreamSynchronize(c->stream);  // (an evaluation queued earlier may still read the base)
+  r->frozen.release();
+  r->bnd.sorted = false;
+  r->g_num_fixed = 0;
+}
 
 void recon_release(cmx_ctx *c) {
   ReconState *r = c ? c->recon : nullptr;
@@ -120,6 +180,8 @@ void recon_release(cmx_ctx *c) {
                  r->d_tile_count, r->d_partials, r->d_cm, r->d_jt, r->d_gsum, r->d_voted, r->d_rows, r->d_row_win};
   for (void *p : dev) (void)hipFree(p);
   r->bnd.release();
+  r->frozen.release();
+  r->solve.release();
   delete r;
   c->recon = nullptr;
 }
@@ -135,20 +197,35 @@ static int recon_enter(cmx_ctx *c, bool need_begun) {
 // knot values for the trajectory of begin (begin itself, restart, eval_bound); plane, counters and gradient state start over.
 // Nothing is allocated or freed.
 // (knots_xyzw == NULL, eval_bound only: the current knots stay, and nothing of the caller's is read -- no wait)
-static int recon_start_over(cmx_ctx *c, ReconState *r, const double *knots_xyzw) {
+// from_base (eval_bound with a frozen head): plane and counters start from the frozen batches' votes instead of zero.
+// staged (cmx_backend_recon_solve): the knots are in pinned memory that stays untouched until the evaluation's own wait -- none here.
+static int recon_start_over(cmx_ctx *c, ReconState *r, const double *knots_xyzw, bool from_base = false, bool staged = false) {
   const size_t np = (size_t)c->Wp * c->Hp;
+  const ReconFrozen &fz = r->frozen;
+  const bool base = from_base && fz.num_fixed > 0;
   r->grad_open = false;
-  r->n_sampled = 0;
+  r->g_num_fixed = 0;
+  r->n_sampled = base ? fz.sampled : 0;
   if (knots_xyzw) {
     static_assert(sizeof(Quat) == 4 * sizeof(double), "knots travel as (x, y, z, w) doubles");
     HIP_TRY(c, hipMemcpyAsync(r->d_knots, knots_xyzw, (size_t)r->sup.K * sizeof(Quat), hipMemcpyHostToDevice, c->stream));
     launch_recon_delta(r->d_knots, r->sup.K, r->d_delta, c->stream);
   }
-  HIP_TRY(c, hipMemsetAsync(r->d_plane, 0, np * sizeof(float), c->stream));
-  HIP_TRY(c, hipMemsetAsync(r->d_inside, 0, sizeof(unsigned long long), c->stream));
-  if (r->d_fixed) HIP_TRY(c, hipMemsetAsync(r->d_fixed, 0, np * sizeof(unsigned long long), c->stream));
+  if (base) {  // the base restore: one device-to-device copy in the plane's own format, and the counter's start value
+    if (r->d_fixed) {
+      HIP_TRY(c, hipMemsetAsync(r->d_plane, 0, np * sizeof(float), c->stream));
+      HIP_TRY(c, hipMemcpyAsync(r->d_fixed, fz.d_base, np * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
+    } else {
+      HIP_TRY(c, hipMemcpyAsync(r->d_plane, fz.d_base, np * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(r->d_inside, fz.d_inside, sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
+  } else {
+    HIP_TRY(c, hipMemsetAsync(r->d_plane, 0, np * sizeof(float), c->stream));
+    HIP_TRY(c, hipMemsetAsync(r->d_inside, 0, sizeof(unsigned long long), c->stream));
+    if (r->d_fixed) HIP_TRY(c, hipMemsetAsync(r->d_fixed, 0, np * sizeof(unsigned long long), c->stream));
+  }
   HIP_TRY(c, hipGetLastError());
-  if (knots_xyzw) HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller's knot array is free again
+  if (knots_xyzw && !staged) HIP_TRY(c, recon_wait(c, r));  // the caller's knot array is free again
   return CMX_OK;
 }
 
@@ -451,6 +528,7 @@ int cmx_backend_recon_restart(cmx_ctx *c, const double *knots_xyzw) {
   int rc = recon_enter(c, true);
   if (rc) return rc;
   if (!knots_xyzw) return fail(c, CMX_ERR_INVALID_ARG, "null knot array");
+  frozen_drop(c, c->recon);  // (new knots: what the frozen batches voted no longer holds)
   return recon_start_over(c, c->recon, knots_xyzw);
 }
 
@@ -491,13 +569,12 @@ static int recon_grad_precheck(cmx_ctx *c, ReconState *r, double sigma) {
 
 // The image pass over the plane as accumulated so far: contrast of GaussianBlur(plane, sigma), and with want_grad
 // Jt = G^T (G plane) for the gradient pass it opens.  The plane is read only.
-int cmx_backend_recon_contrast(cmx_ctx *c, double blur_sigma, int contrast_measure, int want_grad, double *contrast) {
-  int rc = recon_enter(c, true);
-  if (rc) return rc;
-  if (!contrast) return fail(c, CMX_ERR_INVALID_ARG, "null output");
+// Everything of it up to the wait: queued on the stream, contrast and mean on their way into cm[2] (host memory that stays valid
+// until the caller has waited for the stream); with want_grad the gradient pass is open from here on, and r->mu is the caller's to
+// set from cm[1] after its wait.
+static int recon_contrast_queue(cmx_ctx *c, ReconState *r, double blur_sigma, int contrast_measure, int want_grad, double *cm) {
   if (!std::isfinite(blur_sigma)) return fail(c, CMX_ERR_INVALID_ARG, "blur_sigma is not finite");
-  ReconState *r = c->recon;
-  rc = want_grad ? recon_grad_precheck(c, r, blur_sigma) : recon_setup_blur(c, r, blur_sigma);
+  int rc = want_grad ? recon_grad_precheck(c, r, blur_sigma) : recon_setup_blur(c, r, blur_sigma);
   if (rc) return rc;
   const int W = c->Wp, H = c->Hp, rad = r->radius;
   const size_t np = (size_t)W * H;
@@ -542,21 +619,29 @@ int cmx_backend_recon_contrast(cmx_ctx *c, double blur_sigma, int contrast_measu
     launch_image_moments(a, c->stream);
   }
   launch_recon_moments_finalize(r->d_partials, a.nblk, a.tile_count, (double)np, contrast_measure, r->d_cm, c->stream);
-  double cm[2] = {0, 0};
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(cm, r->d_cm, sizeof(cm), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(cm, r->d_cm, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (want_grad) {
     HIP_TRY(c, hipMemsetAsync(r->d_gsum, 0, 2 * 3 * (size_t)r->sup.K * sizeof(double), c->stream));
     HIP_TRY(c, hipMemsetAsync(r->d_voted, 0, sizeof(unsigned long long), c->stream));
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  *contrast = cm[0];
-  if (want_grad) {
-    r->mu = cm[1];
     r->measure = contrast_measure;
     r->g_sampled = 0;
+    r->g_num_fixed = 0;
     r->grad_open = true;
   }
+  return CMX_OK;
+}
+int cmx_backend_recon_contrast(cmx_ctx *c, double blur_sigma, int contrast_measure, int want_grad, double *contrast) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (!contrast) return fail(c, CMX_ERR_INVALID_ARG, "null output");
+  ReconState *r = c->recon;
+  double cm[2] = {0, 0};
+  rc = recon_contrast_queue(c, r, blur_sigma, contrast_measure, want_grad, cm);
+  if (rc) return rc;
+  HIP_TRY(c, recon_wait(c, r));
+  *contrast = cm[0];
+  if (want_grad) r->mu = cm[1];
   return CMX_OK;
 }
 
@@ -570,15 +655,19 @@ int cmx_backend_recon_grad_get(cmx_ctx *c, double *grad) {
   unsigned long long cnt[2] = {0, 0};
   HIP_TRY(c, hipMemcpyAsync(&cnt[0], r->d_inside, sizeof(cnt[0]), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(&cnt[1], r->d_voted, sizeof(cnt[1]), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, recon_wait(c, r));
+  // (a frozen evaluation's pass starts both of its counts from the frozen head's -- bound_eval -- so the test below reads
+  //  "base plus active against the plane" there)
   if (r->g_sampled != r->n_sampled || cnt[0] != cnt[1])
     return fail(c, CMX_ERR_STATE, "the gradient pass saw %lld sampled / %llu voting events, the plane holds %lld / %llu: feed it the same events in the same cuts",
                 (long long)r->g_sampled, cnt[1], (long long)r->n_sampled, cnt[0]);
   const size_t P = 3 * (size_t)r->sup.K;
   std::vector<double> s(2 * P);
+  r->host_waits++;
   HIP_TRY(c, hipMemcpy(s.data(), r->d_gsum, 2 * P * sizeof(double), hipMemcpyDeviceToHost));
   const double N = (double)c->Wp * (double)c->Hp, mu = r->measure == CMX_MEAN_SQUARE ? 0.0 : r->mu;
   for (size_t k = 0; k < P; k++) grad[k] = 2.0 * (s[k] - (mu != 0.0 ? mu * s[P + k] : 0.0)) / N;
+  for (size_t k = 0; k < 3 * (size_t)r->g_num_fixed; k++) grad[k] = 0.0;  // (active batches next to the cut do reach fixed knots)
   return CMX_OK;
 }
 
@@ -668,6 +757,7 @@ int cmx_backend_recon_bind_from(cmx_ctx *c, const cmx_events *e, int64_t first, 
     b.release();
     return rc;
   }
+  frozen_drop(c, r);  // (a frozen head is a property of the binding it was cut from)
   r->bnd.release();
   r->bnd = b;
   r->bound = true;
@@ -680,6 +770,7 @@ int cmx_backend_recon_unbind(cmx_ctx *c) {
   ReconState *r = c->recon;
   if (!r->bound) return CMX_OK;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  frozen_drop(c, r);
   r->bnd.release();
   r->bound = false;
   return CMX_OK;
@@ -697,14 +788,16 @@ int cmx_backend_recon_bound_info(cmx_ctx *c, int64_t *n_events, int64_t *n_sampl
 }
 
 // the bound events by the destination tile of their vote under the pose table as it stands, and the chunk table
-static int bound_sort(cmx_ctx *c, ReconBound &b, const BeSplatArgs &be) {
+// (be.xy / be.n / be.poseR: all bound events, or with a frozen head the active ones and the pose table from their first batch on --
+//  the sort numbers batches from the first event it is given)
+static int bound_sort(cmx_ctx *c, ReconBound &b, const BeSplatArgs &be, int chunk_events) {
   TileSortJob job;
   job.be = &be;
   job.tiles_x = (c->Wp + kBinTile - 1) / kBinTile;
   job.tiles = job.tiles_x * ((c->Hp + kBinTile - 1) / kBinTile);
   job.planes_per_tile = 2;
-  job.xy = b.d_xy; job.per_batch = b.plan.per_batch; job.n = (int)b.plan.n_packed;
-  job.chunk_events = b.chunk_events;
+  job.xy = be.xy; job.per_batch = b.plan.per_batch; job.n = be.n;
+  job.chunk_events = chunk_events;
   const int rc = b.ts.run(c, job);
   if (rc) return rc;
   b.sorted = true;
@@ -713,62 +806,67 @@ static int bound_sort(cmx_ctx *c, ReconBound &b, const BeSplatArgs &be) {
 }
 
 // the gradient pass over the bound time-ordered copy: the slices, runs and launches of recon_add_store, with stride 0
-static int bound_gather(cmx_ctx *c, ReconState *r) {
+// From batch b_first on (0, or a frozen head's first active batch: the slices then start there, so with b_first = 0 they are
+// the unbound pass's).  wait = false: queued only, the caller waits.
+static int bound_gather(cmx_ctx *c, ReconState *r, int b_first, bool wait) {
   if (int rc0 = recon_pass_enter(c, r, true)) return rc0;
   const ReconBound &b = r->bnd;
   const BatchPlan &p = b.plan;
   const int slice_batches = recon_slice_batches(r);
   ReconGatherArgs ga = recon_gather_args(c, r);
   ReconArgs &a = ga.ev;
-  for (int b_lo = 0; b_lo < p.nb; b_lo += slice_batches) {
+  for (int b_lo = b_first; b_lo < p.nb; b_lo += slice_batches) {
     const Slice sl = slice_at(p, b.n_events, b_lo, slice_batches);
     a.xy = b.d_xy + sl.first; a.stride = 0;
     a.batch_t = b.d_bt + b_lo; a.nb = sl.b_hi - b_lo;
     a.n = (int)sl.n;
+    Span sp(c, CMX_T_GATHER);
     const int rc = queue_slice(c, r, ga, true);
     if (rc) return rc;
   }
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  r->g_sampled += p.n_packed;
+  if (wait) HIP_TRY(c, recon_wait(c, r));
+  r->g_sampled += p.packed(b_first, p.nb);
   return CMX_OK;
 }
 
-int cmx_backend_recon_eval_bound(cmx_ctx *c, const double *knots_xyzw, double blur_sigma, int contrast_measure, double *contrast,
-                                 double *grad) {
-  int rc = recon_enter(c, true);
-  if (rc) return rc;
-  ReconState *r = c->recon;
-  if (!r->bound) return fail(c, CMX_ERR_STATE, "no events are bound (cmx_backend_recon_bind_from)");
-  if (!contrast) return fail(c, CMX_ERR_INVALID_ARG, "null output");
-  if (grad) {  // (before anything is changed, as in eval_from)
-    rc = recon_grad_precheck(c, r, blur_sigma);
-    if (rc) return rc;
-  }
+// One evaluation of the binding: cmx_backend_recon_eval_bound's body, and -- with sv set -- a trial point of
+// cmx_backend_recon_solve: the same launches in the same order, but the knots come from pinned staging, nothing waits in between,
+// the free gradient entries are formed on the device (recon_grad_finalize) and ONE wait at the end delivers contrast, mean, both
+// counters and that slice.  With a frozen head the plane starts from the base and every pass walks the active batches alone.
+static int bound_eval(cmx_ctx *c, ReconState *r, const double *knots_xyzw, double blur_sigma, int contrast_measure, double *contrast,
+                      double *grad, ReconSolve *sv) {
   ReconBound &b = r->bnd;
-  rc = recon_start_over(c, r, knots_xyzw);
+  const ReconFrozen &fz = r->frozen;
+  const bool frozen = fz.num_fixed > 0;
+  if (frozen && knots_xyzw && memcmp(knots_xyzw, fz.knots.data(), (size_t)fz.num_fixed * sizeof(Quat)) != 0)
+    return fail(c, CMX_ERR_INVALID_ARG, "the first %d knots differ from those the head was frozen at (cmx_backend_recon_freeze_head)",
+                fz.num_fixed);
+  int rc = recon_start_over(c, r, knots_xyzw, /*from_base=*/true, /*staged=*/sv != nullptr);
   if (rc) return rc;
-  if (b.plan.n_packed > 0) {
+  const int b0 = frozen ? fz.b_act : 0;
+  const int64_t first = frozen ? fz.sampled : 0, n_act = b.plan.n_packed - first;
+  if (n_act > 0) {
     ReconArgs a = recon_args(c, r);
-    a.batch_t = b.d_bt; a.nb = b.plan.nb;
+    a.batch_t = b.d_bt + b0; a.nb = b.plan.nb - b0;
     {
       Span sp(c, CMX_T_POSE, /*exact=*/true);
-      launch_recon_pose_table(a, b.d_poseR, c->stream, sp.t0(), sp.t1());
+      launch_recon_pose_table(a, b.d_poseR + b0, c->stream, sp.t0(), sp.t1());
     }
     ReconLdsArgs g{};
     g.cam = a.cam;
-    g.cam.poseR = b.d_poseR;
-    g.cam.xy = b.d_xy;
+    g.cam.poseR = b.d_poseR + b0;
+    g.cam.xy = b.d_xy + first;
     g.cam.per_batch = b.plan.per_batch;
-    g.cam.n = (int)b.plan.n_packed;
+    g.cam.n = (int)n_act;
     g.cam.order = r->sup.order;
     if (!b.sorted || b.fallback_frac > kRebinFallbackFrac) {
       Span sp(c, CMX_T_BATCH);
-      rc = bound_sort(c, b, g.cam);
+      rc = bound_sort(c, b, g.cam, frozen ? fz.chunk_events : b.chunk_events);
       if (rc) return rc;
     }
     g.ev.sxy = b.ts.d_sxy; g.ev.sbatch = b.ts.d_sbatch;
-    g.ev.chunks = b.ts.d_chunks; g.ev.nchunks = b.max_chunks; g.ev.nchunks_dev = b.ts.d_nchunks;
+    g.ev.chunks = b.ts.d_chunks; g.ev.nchunks = frozen ? fz.max_chunks : b.max_chunks; g.ev.nchunks_dev = b.ts.d_nchunks;
     g.ev.fallback = b.ts.d_fallback;
     g.ev.fixed = r->deterministic ? r->d_fixed : nullptr;
     g.plane = r->d_plane;
@@ -783,14 +881,249 @@ int cmx_backend_recon_eval_bound(cmx_ctx *c, const double *knots_xyzw, double bl
     b.h_stat[1] = 0ull;
     HIP_TRY(c, hipMemcpyAsync(&b.h_stat[0], r->d_inside, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(&b.h_stat[1], b.ts.d_fallback, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-    r->n_sampled += b.plan.n_packed;
+    r->n_sampled += n_act;
   }
-  rc = cmx_backend_recon_contrast(c, blur_sigma, contrast_measure, grad != nullptr, contrast);
-  if (rc && hipStreamSynchronize(c->stream) != hipSuccess) return rc;  // (the two words below are not known to have arrived)
-  if (b.plan.n_packed > 0) b.fallback_frac = b.h_stat[0] ? (double)(unsigned)b.h_stat[1] / (double)b.h_stat[0] : 0.0;
-  if (!rc && grad) rc = bound_gather(c, r);
-  if (!rc && grad) rc = cmx_backend_recon_grad_get(c, grad);
+  // the share of the ACTIVE events' votes that left their windows: the frozen head's votes are in the counter, not in the sort
+  auto note_fallback = [&]() {
+    if (n_act <= 0) { if (frozen) b.fallback_frac = 0.0; return; }
+    const unsigned long long act = b.h_stat[0] - (frozen ? fz.inside : 0ull);
+    b.fallback_frac = act ? (double)(unsigned)b.h_stat[1] / (double)act : 0.0;
+  };
+  // a frozen evaluation's gradient pass: both of its counts start from the frozen head's, so that grad_get's test -- sampled and
+  // voted counts against the plane's -- holds for base plus active, and the fixed entries are zero by definition
+  auto open_frozen_pass = [&]() -> int {
+    if (!frozen) return CMX_OK;
+    r->g_sampled = fz.sampled;
+    r->g_num_fixed = fz.num_fixed;
+    HIP_TRY(c, hipMemcpyAsync(r->d_voted, fz.d_inside, sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
+    return CMX_OK;
+  };
+  if (!sv) {
+    rc = cmx_backend_recon_contrast(c, blur_sigma, contrast_measure, grad != nullptr, contrast);
+    if (rc && hipStreamSynchronize(c->stream) != hipSuccess) return rc;  // (the two words below are not known to have arrived)
+    note_fallback();
+    if (!rc && grad) rc = open_frozen_pass();
+    if (!rc && grad) rc = bound_gather(c, r, b0, /*wait=*/true);
+    if (!rc && grad) rc = cmx_backend_recon_grad_get(c, grad);
+    return rc;
+  }
+  rc = recon_contrast_queue(c, r, blur_sigma, contrast_measure, grad != nullptr, sv->h_cm);
+  const size_t P = 3 * (size_t)r->sup.K, p0 = 3 * (size_t)sv->num_fixed;
+  if (!rc && grad) rc = open_frozen_pass();
+  if (!rc && grad) rc = bound_gather(c, r, b0, /*wait=*/false);
+  if (!rc && grad) {
+    launch_recon_grad_finalize(r->d_gsum, r->d_cm, (long long)P, (long long)p0, (double)c->Wp * (double)c->Hp,
+                               contrast_measure == CMX_MEAN_SQUARE, sv->d_grad, c->stream);
+    rc = hipGetLastError() == hipSuccess ? CMX_OK : fail(c, CMX_ERR_HIP, "the gradient finalize could not be queued");
+    if (!rc) {
+      HIP_TRY(c, hipMemcpyAsync(&sv->h_cnt[0], r->d_inside, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(&sv->h_cnt[1], r->d_voted, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    }
+  }
+  const hipError_t waited = recon_wait(c, r);  // the evaluation's one wait (a queueing error above: so that nothing is left in flight)
+  if (!rc && waited != hipSuccess) rc = fail(c, CMX_ERR_HIP, "the evaluation failed: %s", hipGetErrorString(waited));
+  if (rc) return rc;
+  note_fallback();
+  *contrast = sv->h_cm[0];
+  if (grad) {
+    r->mu = sv->h_cm[1];
+    if (r->g_sampled != r->n_sampled || sv->h_cnt[0] != sv->h_cnt[1])  // (grad_get's test)
+      return fail(c, CMX_ERR_STATE, "the gradient pass saw %lld sampled / %llu voting events, the plane holds %lld / %llu",
+                  (long long)r->g_sampled, sv->h_cnt[1], (long long)r->n_sampled, sv->h_cnt[0]);
+    memcpy(grad, sv->h_grad, (P - p0) * sizeof(double));
+  }
+  return CMX_OK;
+}
+
+int cmx_backend_recon_eval_bound(cmx_ctx *c, const double *knots_xyzw, double blur_sigma, int contrast_measure, double *contrast,
+                                 double *grad) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  ReconState *r = c->recon;
+  if (!r->bound) return fail(c, CMX_ERR_STATE, "no events are bound (cmx_backend_recon_bind_from)");
+  if (!contrast) return fail(c, CMX_ERR_INVALID_ARG, "null output");
+  if (grad) {  // (before anything is changed, as in eval_from)
+    rc = recon_grad_precheck(c, r, blur_sigma);
+    if (rc) return rc;
+  }
+  return bound_eval(c, r, knots_xyzw, blur_sigma, contrast_measure, contrast, grad, nullptr);
+}
+
+// ---- frozen head
+int cmx_backend_recon_freeze_head(cmx_ctx *c, int num_fixed) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  ReconState *r = c->recon;
+  if (!r->bound) return fail(c, CMX_ERR_STATE, "no events are bound (cmx_backend_recon_bind_from)");
+  if (num_fixed < 0 || num_fixed >= r->sup.K) return fail(c, CMX_ERR_INVALID_ARG, "num_fixed=%d outside [0, %d)", num_fixed, r->sup.K);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  (void)recon_pass_enter(c, r, false);  // as a bind: an open gradient pass is closed
+  frozen_drop(c, r);
+  if (num_fixed == 0) return CMX_OK;
+  ReconBound &b = r->bnd;
+  const BatchPlan &p = b.plan;
+  ReconFrozen fz;
+  auto build = [&]() -> int {
+    // the prefix rule on the host, over the binding's batch times read back once
+    std::vector<long long> bt((size_t)p.nb);
+    if (p.nb > 0) HIP_TRY(c, hipMemcpy(bt.data(), b.d_bt, (size_t)p.nb * sizeof(long long), hipMemcpyDeviceToHost));
+    fz.b_act = frozen_prefix(r->sup, num_fixed, bt.data(), p.nb);
+    fz.sampled = p.packed(0, fz.b_act);
+    fz.knots.resize(4 * (size_t)num_fixed);
+    HIP_TRY(c, hipMemcpy(fz.knots.data(), r->d_knots, (size_t)num_fixed * sizeof(Quat), hipMemcpyDeviceToHost));
+    // the base: the frozen batches' votes at the current knots
+    const size_t np = (size_t)c->Wp * c->Hp, cell = r->deterministic ? sizeof(unsigned long long) : sizeof(float);
+    HIP_TRY(c, hipMalloc(&fz.d_base, np * cell));
+    HIP_TRY(c, hipMalloc((void **)&fz.d_inside, sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemsetAsync(fz.d_base, 0, np * cell, c->stream));
+    HIP_TRY(c, hipMemsetAsync(fz.d_inside, 0, sizeof(unsigned long long), c->stream));
+    const int tiles = ((c->Wp + kBinTile - 1) / kBinTile) * ((c->Hp + kBinTile - 1) / kBinTile);
+    if (fz.sampled > 0) {
+      // eval_bound's own vote pass over the range [0, b_act): pose table, the binding's TileSort filled with the FROZEN events (the
+      // next evaluation sorts the active ones into it, as it would anyway), LDS votes -- into the base instead of the plane
+      ReconArgs a = recon_args(c, r);
+      a.batch_t = b.d_bt; a.nb = fz.b_act;
+      launch_recon_pose_table(a, b.d_poseR, c->stream);
+      ReconLdsArgs g{};
+      g.cam = a.cam;
+      g.cam.poseR = b.d_poseR;
+      g.cam.xy = b.d_xy;
+      g.cam.per_batch = p.per_batch;
+      g.cam.n = (int)fz.sampled;
+      g.cam.order = r->sup.order;
+      const ChunkPlan cp = plan_chunks(fz.sampled, 2 * tiles, kBackEndChunkDiv);
+      int rc2 = b.ts.reserve(c, fz.sampled, 2 * tiles, cp.max_chunks);
+      if (!rc2) rc2 = bound_sort(c, b, g.cam, cp.chunk_events);
+      if (rc2) return rc2;
+      b.sorted = false;
+      g.ev.sxy = b.ts.d_sxy; g.ev.sbatch = b.ts.d_sbatch;
+      g.ev.chunks = b.ts.d_chunks; g.ev.nchunks = (int)cp.max_chunks; g.ev.nchunks_dev = b.ts.d_nchunks;
+      g.ev.fallback = b.ts.d_fallback;
+      g.ev.fixed = r->deterministic ? static_cast<unsigned long long *>(fz.d_base) : nullptr;
+      g.plane = r->deterministic ? nullptr : static_cast<float *>(fz.d_base);
+      g.n_inside = fz.d_inside;
+      HIP_TRY(c, hipMemsetAsync(b.ts.d_fallback, 0, sizeof(unsigned), c->stream));
+      launch_recon_votes_lds(g, c->stream);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&fz.inside, fz.d_inside, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // the active part's chunk table: the chunk rule at ITS count (the table may be longer than the one the bind reserved)
+    const int64_t n_act = p.n_packed - fz.sampled;
+    if (n_act > 0) {
+      const ChunkPlan cp = plan_chunks(n_act, 2 * tiles, kBackEndChunkDiv);
+      fz.chunk_events = cp.chunk_events;
+      fz.max_chunks = (int)cp.max_chunks;
+      const int rc2 = b.ts.reserve(c, n_act, 2 * tiles, cp.max_chunks);
+      if (rc2) return rc2;
+    }
+    fz.num_fixed = num_fixed;
+    return CMX_OK;
+  };
+  rc = build();
+  if (rc) {
+    (void)hipStreamSynchronize(c->stream);
+    fz.release();
+    return rc;
+  }
+  r->frozen = fz;
+  r->bnd.sorted = false;  // (the sort holds the active events alone from the next evaluation on)
+  return CMX_OK;
+}
+
+int cmx_backend_recon_frozen_info(cmx_ctx *c, int *num_fixed, int64_t *frozen_batches, int64_t *frozen_sampled) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  const ReconFrozen &fz = c->recon->frozen;  // (without a frozen head: all zero)
+  if (num_fixed) *num_fixed = fz.num_fixed;
+  if (frozen_batches) *frozen_batches = fz.num_fixed ? fz.b_act : 0;
+  if (frozen_sampled) *frozen_sampled = fz.num_fixed ? fz.sampled : 0;
+  return CMX_OK;
+}
+
+// ---- cmx_backend_recon_solve's three hooks (the FR-CG loop itself is cmx_solver.cpp's)
+// begin: every argument error, before anything changes; then the staging, the start knots on the device and -- asked for -- the
+// frozen head at them
+int recon_solve_begin(cmx_ctx *c, const double *knots_xyzw, int num_fixed, int freeze_head, double blur_sigma, int contrast_measure,
+                      int *n_params) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  ReconState *r = c->recon;
+  if (!r->bound) return fail(c, CMX_ERR_STATE, "no events are bound (cmx_backend_recon_bind_from)");
+  if (!knots_xyzw) return fail(c, CMX_ERR_INVALID_ARG, "null knot array");
+  const int K = r->sup.K;
+  if (num_fixed < 0 || num_fixed >= K) return fail(c, CMX_ERR_INVALID_ARG, "num_fixed=%d outside [0, %d)", num_fixed, K);
+  if (!std::isfinite(blur_sigma)) return fail(c, CMX_ERR_INVALID_ARG, "blur_sigma is not finite");
+  rc = recon_grad_precheck(c, r, blur_sigma);
+  if (rc) return rc;
+  ReconSolve &sv = r->solve;
+  if (!sv.h_knots) {
+    HIP_TRY(c, hipHostMalloc((void **)&sv.h_knots, (size_t)K * sizeof(Quat), hipHostMallocDefault));
+    HIP_TRY(c, hipHostMalloc((void **)&sv.h_cm, 2 * sizeof(double), hipHostMallocDefault));
+    HIP_TRY(c, hipHostMalloc((void **)&sv.h_cnt, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+    HIP_TRY(c, hipHostMalloc((void **)&sv.h_grad, 3 * (size_t)K * sizeof(double), hipHostMallocMapped));
+    HIP_TRY(c, hipHostGetDevicePointer((void **)&sv.d_grad, sv.h_grad, 0));
+  }
+  sv.k0.assign(knots_xyzw, knots_xyzw + 4 * (size_t)K);
+  sv.num_fixed = num_fixed;
+  sv.sigma = blur_sigma;
+  sv.measure = contrast_measure;
+  sv.have_last = false;
+  sv.evals = 0;
+  sv.waits = 0;
+  if (freeze_head) {  // at the start knots: they go to the device first (restart, which also drops an earlier head)
+    rc = cmx_backend_recon_restart(c, knots_xyzw);
+    if (!rc) rc = cmx_backend_recon_freeze_head(c, num_fixed);
+  } else {  // every event, every time
+    rc = cmx_backend_recon_freeze_head(c, 0);
+  }
+  if (rc) return rc;
+  *n_params = 3 * (K - num_fixed);
+  return CMX_OK;
+}
+
+// the knots of increment x: the start knots moved by cmx_traj_incremental_update itself, into the pinned staging
+static void solve_moved(const ReconState *r, const ReconSolve &sv, const double *x, double *knots) {
+  const int K = r->sup.K;
+  memcpy(knots, sv.k0.data(), (size_t)K * sizeof(Quat));
+  (void)cmx_traj_incremental_update(K, knots, sv.num_fixed, 3 * (K - sv.num_fixed), x);
+}
+
+int recon_solve_eval(cmx_ctx *c, const double *x, double *contrast, double *grad_free) {
+  ReconState *r = c->recon;
+  ReconSolve &sv = r->solve;
+  solve_moved(r, sv, x, sv.h_knots);
+  const int64_t w0 = r->host_waits;
+  const int rc = bound_eval(c, r, sv.h_knots, sv.sigma, sv.measure, contrast, grad_free, &sv);
+  sv.evals++;
+  sv.waits += r->host_waits - w0;
+  const size_t n = 3 * (size_t)(r->sup.K - sv.num_fixed);
+  sv.last_x.assign(x, x + n);
+  sv.have_last = rc == CMX_OK;
   return rc;
+}
+
+// end: the refined knots to the caller, and the reconstruction at their evaluation -- one more cost-only evaluation when the last
+// trial point was another one
+int recon_solve_end(cmx_ctx *c, const double *x, double *knots_out) {
+  ReconState *r = c->recon;
+  ReconSolve &sv = r->solve;
+  const size_t n = 3 * (size_t)(r->sup.K - sv.num_fixed);
+  int rc = CMX_OK;
+  if (!sv.have_last || memcmp(sv.last_x.data(), x, n * sizeof(double)) != 0) {
+    double con = 0;
+    rc = recon_solve_eval(c, x, &con, nullptr);
+  }
+  solve_moved(r, sv, x, knots_out);
+  return rc;
+}
+
+int cmx_diag_recon_solve_counts(cmx_ctx *c, int64_t *evaluations, int64_t *host_waits) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (evaluations) *evaluations = c->recon->solve.evals;
+  if (host_waits) *host_waits = c->recon->solve.waits;
+  return CMX_OK;
 }
 
 // the plane as fp32 on the device: in deterministic mode the current fixed-point sums, converted (they stay: votes may follow)

@@ -114,9 +114,59 @@ int solve(cmx_ctx *ctx, bool backend, int n, double *x_inout, double tol, double
   return st.err;
 }
 
+// ---- cmx_backend_recon_solve: the same machine over the bound whole-trajectory evaluation (cmx_reconstruct.cpp: recon_solve_*).
+// f = -contrast, df = -(the free gradient entries): BackendEvaluator.reconstruct_refine(bind=True)'s functor, call for call.
+struct ReconSolveState {
+  cmx_ctx *ctx;
+  int n;
+  int err = CMX_OK;
+};
+void recon_fdf(const double *x, void *p, double *f, double *df) {
+  ReconSolveState *s = static_cast<ReconSolveState *>(p);
+  double c = 0;
+  const int rc = recon_solve_eval(s->ctx, x, &c, df);
+  if (rc != CMX_OK) {
+    if (s->err == CMX_OK) s->err = rc;
+    *f = NAN;
+    if (df) for (int i = 0; i < s->n; i++) df[i] = NAN;
+    return;
+  }
+  *f = -c;
+  if (df) for (int i = 0; i < s->n; i++) df[i] = -df[i];
+}
+double recon_f(const double *x, void *p) {
+  double cost;
+  recon_fdf(x, p, &cost, nullptr);
+  return cost;
+}
+void recon_df(const double *x, void *p, double *df) {
+  double cost;
+  recon_fdf(x, p, &cost, df);
+}
+
 }  // namespace
 
 extern "C" {
+
+int cmx_backend_recon_solve(cmx_ctx *ctx, double *knots_xyzw, int num_fixed, int freeze_head, double blur_sigma, int contrast_measure,
+                            double step_size, double tol, double epsabs_grad, double tolfun, int max_iterations,
+                            cmx_solve_report *report) {
+  if (ctx && (!std::isfinite(step_size) || !std::isfinite(tol) || !std::isfinite(epsabs_grad) || !std::isfinite(tolfun) || max_iterations < 0))
+    return fail(ctx, CMX_ERR_INVALID_ARG, "solver constants must be finite and max_iterations >= 0");
+  int n = 0;
+  int rc = recon_solve_begin(ctx, knots_xyzw, num_fixed, freeze_head, blur_sigma, contrast_measure, &n);
+  if (rc != CMX_OK) return rc;
+  UrgentScope urgent(ctx);  // the whole solve is one burst
+  ReconSolveState st{ctx, n};
+  cmx::FunctionFdf fn{recon_f, recon_df, recon_fdf, (size_t)n, &st};
+  std::vector<double> x0((size_t)n, 0.0);
+  Machine m(n, x0.data(), step_size, tol, epsabs_grad, tolfun, max_iterations);
+  m.run_host(fn, &st.err);
+  m.report(x0.data(), report);
+  if (st.err != CMX_OK) return st.err;  // (knots_xyzw is untouched: the reconstruction is at the last point that evaluated)
+  return recon_solve_end(ctx, x0.data(), knots_xyzw);
+}
+
 
 int cmx_frontend_solve(cmx_ctx *ctx, double ang_vel[3], cmx_solve_report *report) {
   if (!ctx || !ang_vel) return CMX_ERR_INVALID_ARG;

@@ -743,6 +743,40 @@ class BackendEvaluator(_Evaluator):
             self.reconstruct_end()
         return moved(x), rep
 
+    # --- frozen head and the native solve (cmx_backend_recon_freeze_head / _frozen_info / _solve)
+    def reconstruct_freeze_head(self, num_fixed):
+        """Vote the batches whose pose reads only the first num_fixed knots ONCE, at the current knots, into a base plane; every
+        later reconstruct_eval_bound starts from it and walks the other batches alone.  0 removes the frozen head."""
+        self._ck(self._L.cmx_backend_recon_freeze_head(self._ctx, int(num_fixed)))
+
+    def reconstruct_frozen_info(self):
+        """{'num_fixed', 'frozen_batches', 'frozen_sampled'}; all zero without a frozen head."""
+        nf, fb, fs = C.c_int(), C.c_int64(), C.c_int64()
+        self._ck(self._L.cmx_backend_recon_frozen_info(self._ctx, C.byref(nf), C.byref(fb), C.byref(fs)))
+        return {"num_fixed": nf.value, "frozen_batches": fb.value, "frozen_sampled": fs.value}
+
+    def reconstruct_solve(self, knots, num_fixed, sigma=1.0, measure=VARIANCE, freeze_head=False, **solver_kw):
+        """reconstruct_refine(bind=True)'s bundle adjustment over the events bound to the open reconstruction as ONE native call
+        (FR-CG, the back end's constants unless given; freeze_head: the batches under the fixed knots are voted once).  The
+        reconstruction is left at the refined knots' evaluation.  Returns (knots, report)."""
+        from . import solver
+        k = np.array(_c(knots, np.float64).reshape(-1, 4), copy=True)
+        if self._recon_K and k.shape[0] != self._recon_K:
+            raise ValueError("solve takes the %d knots of begin, got %d" % (self._recon_K, k.shape[0]))
+        kw = dict(solver.BACKEND)
+        kw.update(solver_kw)
+        rep = _lib.SolveReport()
+        self._ck(self._L.cmx_backend_recon_solve(self._ctx, _dp(k), int(num_fixed), 1 if freeze_head else 0, float(sigma), int(measure),
+                                                 float(kw["step_size"]), float(kw["tol"]), float(kw["epsabs_grad"]),
+                                                 float(kw["tolfun"]), int(kw["max_iterations"]), C.byref(rep)))
+        return k, {f: getattr(rep, f) for f, _ in rep._fields_}
+
+    def reconstruct_solve_counts(self):
+        """(evaluations, host waits inside them) of the last reconstruct_solve (cmx_diag_recon_solve_counts)."""
+        ev, hw = C.c_int64(), C.c_int64()
+        self._ck(self._L.cmx_diag_recon_solve_counts(self._ctx, C.byref(ev), C.byref(hw)))
+        return ev.value, hw.value
+
     def reconstruct(self, x, y, t_ns, order, knots_xyzw, start_ns, dt_ns, **kw):
         """begin + one add + get + end: the panorama of these events along this spline."""
         self.reconstruct_begin(order, knots_xyzw, start_ns, dt_ns, **kw)

@@ -79,13 +79,15 @@ def _support_range(traj, t):
     return int(np.searchsorted(t, traj.t_beg_ns, side="left")), int(np.searchsorted(t, t_hi, side="left"))
 
 
-def refine_trajectory(be, traj, x, y, t, prm, store=None, bind=False):
+def refine_trajectory(be, traj, x, y, t, prm, store=None, bind=False, native=False, freeze_head=None):
     """One bundle adjustment over the WHOLE recording, the step a rotational event SLAM ends with once the sliding windows have
     passed: FR-CG over every control pose but the first order - 1 (a common rotation of all of them is a gauge freedom of the
     contrast), cost = -contrast of the panorama of all events along the trajectory: BackendEvaluator.reconstruct_refine
     (cmx_backend_recon_eval_from; bind=True: the events are bound once and every trial point is a cmx_backend_recon_eval_bound, votes
-    through LDS over a tile sort kept between evaluations).  Returns (refined knots, report); the report carries contrast_before /
-    contrast_after."""
+    through LDS over a tile sort kept between evaluations).  native=True: the same problem as ONE call, BackendEvaluator.reconstruct_solve
+    (cmx_backend_recon_solve) over the bound events; freeze_head=N then fixes the first N control poses (N > order - 1: a settled head
+    of the trajectory) and votes the event batches under them once.  Returns (refined knots, report); the report carries
+    contrast_before / contrast_after."""
     i0, i1 = _support_range(traj, t)
     own = store is None
     if own:  # (the evaluation reads its events from a device-resident store)
@@ -93,9 +95,20 @@ def refine_trajectory(be, traj, x, y, t, prm, store=None, bind=False):
         store.push(x[i0:i1], y[i0:i1], t[i0:i1])
         i0, i1 = 0, i1 - i0
     try:
-        knots, rep = be.reconstruct_refine(store, i0, i1 - i0, traj.order, traj.knots, traj.t_beg_ns, traj.dt_ns, traj.order - 1,
-                                           sigma=prm.backend_blur_sigma, event_batch_size=prm.event_batch_size,
-                                           event_sample_rate=prm.backend_event_sample_rate, bind=bind)
+        if native:
+            be.reconstruct_begin(traj.order, traj.knots, traj.t_beg_ns, traj.dt_ns, prm.event_batch_size, prm.backend_event_sample_rate)
+            try:
+                be.reconstruct_bind(store, i0, i1 - i0)
+                knots, rep = be.reconstruct_solve(traj.knots, traj.order - 1 if freeze_head is None else int(freeze_head),
+                                                  sigma=prm.backend_blur_sigma, freeze_head=freeze_head is not None)
+                if freeze_head is not None:
+                    rep = dict(rep, **be.reconstruct_frozen_info())
+            finally:
+                be.reconstruct_end()
+        else:
+            knots, rep = be.reconstruct_refine(store, i0, i1 - i0, traj.order, traj.knots, traj.t_beg_ns, traj.dt_ns, traj.order - 1,
+                                               sigma=prm.backend_blur_sigma, event_batch_size=prm.event_batch_size,
+                                               event_sample_rate=prm.backend_event_sample_rate, bind=bind)
     finally:
         if own:
             store.close()
@@ -121,14 +134,16 @@ def reconstruct_panorama(be, traj, x, y, t, prm, store=None, knots=None):
 
 
 def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefix=None, reconstruct=False, refine_global=False,
-                 refine_bound=False):
+                 refine_bound=False, refine_native=False, freeze_head=None):
     """stream: synth.EventStream (or anything with x, y, t_ns, W, H, fx, fy, cx, cy, lut).  Returns a dict.
     display_prefix: write the final panorama with the last pose's FOV and the last packet's local-IWE pair there.
     reconstruct: after the last window, re-warp all events along the whole refined trajectory (res["recon"]; with
     display_prefix also <prefix>_recon.pgm).
     refine_global: after the last window, one bundle adjustment over the whole trajectory (res["refined_knots"],
     res["refine_report"]); the trajectory in res["traj"] stays the sliding windows' -- reconstruct then warps along the refined knots.
-    refine_bound: that bundle adjustment binds the events once (reconstruct_refine(bind=True))."""
+    refine_bound: that bundle adjustment binds the events once (reconstruct_refine(bind=True)).
+    refine_native: it runs as one native call over the bound events (reconstruct_solve); freeze_head = N: with the first N control
+    poses fixed and the batches under them voted once."""
     prm = prm or Params()
     x, y, t = stream.x, stream.y, stream.t_ns
     n_total = len(t)
@@ -283,7 +298,8 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
                reports=reports, fe_ms=fe_ms, be_ms=be_ms, windows=count_window)
     if refine_global and traj.size() >= traj.order:
         t0 = time.perf_counter()
-        res["refined_knots"], res["refine_report"] = refine_trajectory(be, traj, x, y, t, prm, store, bind=refine_bound)
+        res["refined_knots"], res["refine_report"] = refine_trajectory(be, traj, x, y, t, prm, store, bind=refine_bound,
+                                                                       native=refine_native, freeze_head=freeze_head)
         if log:
             r = res["refine_report"]
             log("global refinement: %d events, %d control poses, %d iterations (%d f, %d df) in %.2f ms; contrast %.6g -> %.6g" %
@@ -362,7 +378,13 @@ def main():
                     help="after the last window, one bundle adjustment over the whole trajectory (--reconstruct then uses its result)")
     ap.add_argument("--refine-bound", action="store_true",
                     help="with --refine-global: bind the events once and evaluate every trial point over the bound copy")
+    ap.add_argument("--refine-native", action="store_true",
+                    help="with --refine-global: the bundle adjustment as one native call over the bound events (cmx_backend_recon_solve)")
+    ap.add_argument("--freeze-head", type=int, metavar="N", default=None,
+                    help="with --refine-native: fix the first N control poses and vote the event batches under them once")
     a = ap.parse_args()
+    if a.freeze_head is not None and not a.refine_native:
+        ap.error("--freeze-head needs --refine-native")
     stream = synth.event_stream(a.rate, a.seconds, 240, 180, 200.0, 200.0, 119.5, 89.5, omega_mean=(0.2, 1.8, 0.3),
                                 omega_amp=(1.0, 0.8, 1.0))
     prm = Params()
@@ -370,7 +392,8 @@ def main():
     prm.deterministic = a.deterministic
     t0 = time.perf_counter()
     res = run_pipeline(stream, prm, use_event_store=not a.host_events, log=print, display_prefix=a.display, reconstruct=a.reconstruct,
-                       refine_global=a.refine_global, refine_bound=a.refine_bound)
+                       refine_global=a.refine_global or a.refine_native, refine_bound=a.refine_bound, refine_native=a.refine_native,
+                       freeze_head=a.freeze_head)
     wall = time.perf_counter() - t0
     m = evaluate_against_truth(stream, res)
     print("%.2f s of events (%d) processed in %.2f s wall" % (a.seconds, len(stream.x), wall))

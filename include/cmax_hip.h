@@ -418,6 +418,43 @@ int cmx_backend_recon_unbind(cmx_ctx *ctx);
 int cmx_backend_recon_eval_bound(cmx_ctx *ctx, const double *knots_xyzw /* K x 4, or NULL = keep */, double blur_sigma,
                                  int contrast_measure, double *contrast, double *grad /* 3K or NULL */);
 int cmx_backend_recon_bound_info(cmx_ctx *ctx, int64_t *n_events, int64_t *n_sampled, int64_t *sorts, double *fallback_frac);
+/* A frozen head, and the whole bundle adjustment as one call.  Online, the recording grows, the head of the trajectory is settled
+ * and only its tail -- of any knot count -- is free.  An event batch whose pose reads fixed knots alone votes the same cells at every
+ * trial point: with s the knot segment of its pose time it is FROZEN when s + order - 1 < num_fixed, and since batch times do not
+ * decrease the frozen batches are a prefix of the binding's.
+ *     recon_begin   recon_bind_from(events)   [recon_freeze_head(num_fixed)]   recon_eval_bound(knots) ... | recon_solve(...)
+ *   freeze_head   needs a binding (CMX_ERR_STATE) and 0 <= num_fixed < K (CMX_ERR_INVALID_ARG).  Votes the frozen batches ONCE, at the
+ *                 knots the reconstruction holds (those of begin, restart or the last evaluation), into a base plane of the
+ *                 reconstruction's own -- fp32, or the 2^-30 fixed-point plane under CMX_OPT_DETERMINISTIC -- and records how many of
+ *                 their events voted.  The plane, its counters and the knots stay as they are; an open gradient pass is closed.
+ *                 num_fixed = 0 removes the frozen head and frees the base.  A second call replaces the first.
+ *   dropped by    begin, end, bind_from, unbind and restart (so also by eval_from with knots); kept by eval_bound.
+ *   eval_bound    with a frozen head: knots_xyzw (when given) must carry the first num_fixed quaternions bytewise as they were at the
+ *                 freeze, CMX_ERR_INVALID_ARG otherwise and nothing changes.  The plane starts from the base; the pose table, the tile
+ *                 sort (of the active events alone, with a chunk table at the chunk rule of their count, re-sorted by the 3 % rule on
+ *                 THEIR votes), the LDS vote pass and the gather pass run over the active batches only.  What it leaves is what
+ *                 eval_bound leaves without one: the full plane for get / render, exact n_sampled / n_inside (base plus active), a
+ *                 gradient grad_get repeats -- grad[0 .. 3 num_fixed) is zero by definition, the other entries are the full
+ *                 gradient's (frozen batches reach no free knot; Jt is built from the full plane).  grad_get's test reads base plus
+ *                 active counts against the plane's.  Deterministic mode: plane, counters and contrast bitwise those of the unfrozen
+ *                 evaluation; the free gradient to summation order (the gather's runs start at the first active batch), and bitwise
+ *                 when no batch is frozen.
+ *   frozen_info   any pointer may be NULL; all zero without a frozen head.  *frozen_batches = b_act, the number of frozen batches,
+ *                 *frozen_sampled = the sampled events in them.
+ *   solve         FR-CG (the machine of cmx_backend_solve / cmx_frcg_minimize) over a left increment of every control pose but the
+ *                 first num_fixed, cost = -contrast of the bound events' panorama; constants as in cmx_frcg_minimize.  Per trial point
+ *                 the start knots are moved by cmx_traj_incremental_update's own code on the host, uploaded from pinned staging, and
+ *                 evaluated by eval_bound's sequence of launches with ONE host wait at the end; with a gradient the device forms
+ *                 (2/N)(S1 - mu S2) for the free parameters and writes them to host memory (no read-back of the 2 x 3K sums).
+ *                 freeze_head != 0: freezes at the start knots, solves, and leaves the frozen head in place; 0: any frozen head is
+ *                 removed and every event is evaluated every time.  Errors before anything changes: CMX_ERR_STATE without a binding;
+ *                 CMX_ERR_INVALID_ARG for num_fixed outside [0, K), a panorama too small for the adjoint gradient at blur_sigma, or a
+ *                 non-finite constant.  On return knots_xyzw holds the refined knots and the reconstruction their evaluation -- plane,
+ *                 counters, contrast -- at the price of one more cost-only evaluation only if the last trial point was another one;
+ *                 report as filled by cmx_backend_solve (n_f / n_df do not count that one). */
+int cmx_backend_recon_freeze_head(cmx_ctx *ctx, int num_fixed);
+int cmx_backend_recon_frozen_info(cmx_ctx *ctx, int *num_fixed, int64_t *frozen_batches, int64_t *frozen_sampled);
+/* (cmx_backend_recon_solve is declared with the other solves, below cmx_solve_report) */
 
 /* ------------------------------------------------------------------ split-phase (multi-GPU) ------------
  * The IWE is a sum over events, the contrast a non-linear function of the SUMMED image, so ranks exchange
@@ -535,6 +572,10 @@ typedef struct {
 int cmx_frontend_solve(cmx_ctx *ctx, double ang_vel[3], cmx_solve_report *report);
 /* drotv: in = start (the reference uses 0), out = optimal incremental rotation vectors, n_params = 3*(K-num_fixed) */
 int cmx_backend_solve(cmx_ctx *ctx, int n_params, double *drotv, cmx_solve_report *report);
+/* the bundle adjustment over the bound events of a whole-trajectory reconstruction (see cmx_backend_recon_freeze_head above) */
+int cmx_backend_recon_solve(cmx_ctx *ctx, double *knots_xyzw /* K x 4, in: start, out: refined */, int num_fixed, int freeze_head,
+                            double blur_sigma, int contrast_measure, double step_size, double tol, double epsabs_grad, double tolfun,
+                            int max_iterations, cmx_solve_report *report);
 /* the same driver loop over an arbitrary functor triple (the shape of gsl_multimin_function_fdf); lets a host or a
  * test run the identical optimiser over any other implementation of the cost */
 typedef double (*cmx_f_fn)(const double *x, void *params);
@@ -634,7 +675,7 @@ int cmx_get_stats(cmx_ctx *ctx, double *stats, int n_stats); /* writes min(n_sta
  *     cmx_set_cu_mask moved to cmax_hip_diag.h;
  *     added without a bump (no signature or buffer layout changed): the seven cmx_backend_recon_* entry points, then
  *     recon_restart / _contrast / _grad_add[_aos|_from] / _grad_get / _eval_from, then recon_bind_from / _unbind / _eval_bound /
- *     _bound_info) */
+ *     _bound_info, then recon_freeze_head / _frozen_info / _solve) */
 #define CMX_ABI_VERSION 6
 int cmx_abi_version(void);
 int cmx_timing_enable(cmx_ctx *ctx, int on);

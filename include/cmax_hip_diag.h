@@ -115,6 +115,11 @@ int cmx_set_cu_mask(cmx_ctx *ctx, const uint32_t *mask, int n_words);
 enum { CMX_DIAG_FORCE_CROSS_DEVICE = 1, CMX_DIAG_RECON_SLICE_EVENTS = 2 };
 int cmx_diag_set(int key, int value);
 
+/* Of the last cmx_backend_recon_solve on this context: the evaluations it made (the closing cost-only one included) and the times a
+ * host thread waited for the device inside them -- a counter at every such wait of the reconstruction's code, not a model
+ * (tools/time_recon_grad.py reports the quotient).  Either pointer may be NULL; zero before the first solve. */
+int cmx_diag_recon_solve_counts(cmx_ctx *ctx, int64_t *evaluations, int64_t *host_waits);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -14,6 +14,11 @@ phase, and the same evaluation over events bound once (cmx_backend_recon_bind_fr
             set_window_from + one eval with the gradient (num_fixed = 0, no map), and against eval_bound on the same events.
   (pmc)     the large configuration once under rocprofv3 --pmc, one counter group per run: VALU instructions of the gather and
             vote kernels per event, and the atomic requests that reach the L2.
+  (solve)   the large configuration again, all rows in one process (--only-solve: this step alone): reconstruct_refine(bind=True)
+            against reconstruct_solve from the same start, whole and per evaluation, in default and in deterministic mode, with
+            the host waits per evaluation the library counted; eval_bound with the gradient under frozen heads of num_fixed = 0,
+            K/2, 3K/4 and K - 8 with the vote and gather passes by their own events, the one-off cost of the freeze and its
+            break-even.  Written to profiles/recon_solve_timing.txt (--solve-out).
 
 No threshold is fixed: the file states the ratios.  Every step runs in a child process of its own, in a process group of its own,
 under a time limit; a child that ends with a non-zero status or at its limit is the LAST thing this tool starts on the GPU.
@@ -140,9 +145,130 @@ def step_window(a):
     print("RESULT " + json.dumps(out), flush=True)
 
 
+def step_solve(a):
+    """The bundle adjustment over the large configuration, all rows in this one process: (a) reconstruct_refine(bind=True), the Python
+    loop around cmx_frcg_minimize; (b) reconstruct_solve(freeze_head=False), the native call, from the same start; (c) eval_bound with
+    the gradient under frozen heads of several lengths, with the vote and gather passes by their own events and the one-off cost of
+    the freeze; (d) the host waits per evaluation of (b), as the library counted them."""
+    from cmax_slam_amd import evaluator
+    x, y, t, knots, start_ns, dt_ns, lut = tr.make_inputs(a)
+    n, K = len(x), len(knots)
+    from scipy.spatial.transform import Rotation as Rot
+    start = np.ascontiguousarray((Rot.from_rotvec(np.random.default_rng(5).normal(0, 1e-3, (K, 3))) * Rot.from_quat(knots)).as_quat())
+    store = evaluator.EventStore(a.sensor[0], a.sensor[1], n)
+    store.push(x, y, t)
+    out = {"events": n, "K": K, "modes": {}}
+    for det in (False, True):
+        be = evaluator.BackendEvaluator(a.sensor[0], a.sensor[1], lut, a.pano[0], a.pano[1])
+        if det:
+            be.set_deterministic(True)
+        py, nat, nat_call, waits = [], [], [], None
+        rp = rn = kp = kn = None
+        for i in range(a.warmup + a.reps):  # alternating: a Python-route solve, then a native one
+            dt_py, (kp, rp) = timed(be.reconstruct_refine, store, 0, n, 2, start, start_ns, dt_ns, 1, a.sigma, 0, a.batch, 1, True)
+            t0 = time.perf_counter()
+            be.reconstruct_begin(2, start, start_ns, dt_ns, a.batch, 1)
+            be.reconstruct_bind(store, 0, n)
+            dt_call, (kn, rn) = timed(be.reconstruct_solve, start, 1, a.sigma, 0, False)
+            waits = be.reconstruct_solve_counts()
+            be.reconstruct_end()
+            dt_nat = time.perf_counter() - t0
+            if i >= a.warmup:
+                py.append(dt_py); nat.append(dt_nat); nat_call.append(dt_call)
+        out["modes"]["deterministic" if det else "default"] = {
+            "python_s": med(py), "native_s": med(nat), "native_call_s": med(nat_call), "python_report": rp, "native_report": rn,
+            "same_knots": bool(kp.tobytes() == kn.tobytes()), "max_dq": float(np.abs(kp - kn).max()), "evals_waits": list(waits)}
+        be.close()
+    # ---- (c) frozen heads, default mode
+    be = evaluator.BackendEvaluator(a.sensor[0], a.sensor[1], lut, a.pano[0], a.pano[1])
+    be.reconstruct_begin(2, knots, start_ns, dt_ns, a.batch, 1)
+    be.reconstruct_bind(store, 0, n)
+    rows = []
+    g0 = None
+    for nf in (0, K // 2, 3 * K // 4, K - 8):
+        fr = []
+        for i in range(3):  # (the freeze is paid once per solve: three calls, their median)
+            be.reconstruct_freeze_head(0)
+            be.reconstruct_restart(knots)
+            dt_f, _ = timed(be.reconstruct_freeze_head, nf)
+            fr.append(dt_f)
+        info = be.reconstruct_frozen_info()
+        cost, grad = [], []
+        for i in range(a.warmup + a.reps):
+            t_c, _ = timed(be.reconstruct_eval_bound, knots, a.sigma, 0, False)
+            t_g, (c, g) = timed(be.reconstruct_eval_bound, knots, a.sigma, 0, True)
+            if i >= a.warmup:
+                cost.append(t_c); grad.append(t_g)
+        if nf == 0:
+            g0 = g
+        be.timing_enable(["pose", "batch", "splat", "gather"])
+        for i in range(max(a.reps, 1)):
+            be.reconstruct_eval_bound(knots, a.sigma, 0, True)
+        tm = be.timing_get()
+        be.timing_enable(False)
+        rows.append({"num_fixed": nf, "freeze_s": med(fr), "frozen_batches": info["frozen_batches"], "frozen_sampled": info["frozen_sampled"],
+                     "cost_s": med(cost), "grad_s": med(grad), "evals": max(a.reps, 1),
+                     "kernels": {k: [tm[k][0], tm[k][1]] for k in ("pose", "batch", "splat", "gather")},
+                     "grad_rel": float(np.abs(g[3 * nf:] - g0[3 * nf:]).max() / np.abs(g0).max()), "fixed_zero": bool(not g[:3 * nf].any())})
+    out["sampled"] = be.reconstruct_bound_info()["n_sampled"]
+    be.reconstruct_end()
+    out["frozen"] = rows
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+def write_solve(a, commit, sv):
+    n, K = sv["events"], sv["K"]
+    L = ["whole-trajectory bundle adjustment as one native call, and the frozen head: cmx_backend_recon_solve / _freeze_head",
+         "commit: %s    %d events from the event store, %dx%d sensor, %dx%d panorama, linear spline with %d knots, batch %d, rate 1, sigma %g" %
+         (commit, n, a.sensor[0], a.sensor[1], a.pano[0], a.pano[1], K, a.batch, a.sigma),
+         "median of %d runs after %d warm-up runs, all rows in one process; host clock around synchronous calls" % (a.reps, a.warmup),
+         "start: the stream's knots moved by N(0, 1 mrad) per component, num_fixed = 1, the back end's solver constants", ""]
+    for mode, m in sv["modes"].items():
+        rp, rn = m["python_report"], m["native_report"]
+        ep, en = rp["n_f"] + rp["n_df"], rn["n_f"] + rn["n_df"]
+        L += ["%s mode:" % mode,
+              "  (a) reconstruct_refine(bind=True): begin + bind + solve + end %10.3f ms; %d iterations, %d evaluations: %.3f ms per evaluation" %
+              (1e3 * m["python_s"], rp["iterations"], ep, 1e3 * m["python_s"] / max(ep, 1)),
+              "  (b) begin + bind + reconstruct_solve(freeze_head=False) + end %10.3f ms; %d iterations, %d evaluations: %.3f ms per evaluation"
+              % (1e3 * m["native_s"], rn["iterations"], en, 1e3 * m["native_s"] / max(en, 1)),
+              "      of which the solve call alone %.3f ms: %.3f ms per evaluation" % (1e3 * m["native_call_s"], 1e3 * m["native_call_s"] / max(en, 1)),
+              "      (b) / (a), whole: %.3f; per evaluation: %.3f; same knots byte for byte: %s (max |dq| %.2e)" %
+              (m["native_s"] / m["python_s"], (m["native_s"] / max(en, 1)) / (m["python_s"] / max(ep, 1)), m["same_knots"], m["max_dq"]),
+              "  (d) host waits inside the evaluations of (b), counted by the library: %d waits in %d evaluations = %.3f per evaluation" %
+              (m["evals_waits"][1], m["evals_waits"][0], m["evals_waits"][1] / max(m["evals_waits"][0], 1)), ""]
+    L += ["(c) eval_bound under a frozen head, default mode, at the knots of the freeze; kernels by their own events over %d evaluations of "
+          "their own (vote: the dispatch's timestamps; gather: events on the stream around each slice's launches); %d sampled events" %
+          (sv["frozen"][0]["evals"], sv["sampled"]),
+          "%-10s %10s %12s %10s %10s %10s %10s %10s %10s" % ("num_fixed", "batches", "active share", "freeze ms", "cost ms", "grad ms", "vote ms",
+                                                           "gather ms", "pose ms")]
+    base = sv["frozen"][0]
+
+    def per(r, k):
+        return r["kernels"][k][0] / r["evals"]
+    for r in sv["frozen"]:
+        L.append("%-10d %10d %12.4f %10.3f %10.3f %10.3f %10.3f %10.3f %10.3f" %
+                 (r["num_fixed"], r["frozen_batches"], 1.0 - r["frozen_sampled"] / sv["sampled"], 1e3 * r["freeze_s"], 1e3 * r["cost_s"],
+                  1e3 * r["grad_s"], per(r, "splat"), per(r, "gather"), per(r, "pose")))
+    L.append("")
+    for r in sv["frozen"][1:]:
+        gain = base["grad_s"] - r["grad_s"]
+        L.append("num_fixed %d against num_fixed 0 of this run: vote %.3f x, gather %.3f x, eval_bound with gradient %.3f x, cost only %.3f x; "
+                 "break-even of the freeze: %s; free gradient against the unfrozen one %.2e (max-norm), fixed entries zero: %s" %
+                 (r["num_fixed"], per(r, "splat") / per(base, "splat"), per(r, "gather") / per(base, "gather"), r["grad_s"] / base["grad_s"],
+                  r["cost_s"] / base["cost_s"], "%.1f evaluations with gradient" % (r["freeze_s"] / gain) if gain > 0 else
+                  "never: the frozen evaluation is not faster", r["grad_rel"], r["fixed_zero"]))
+    text = "\n".join(L) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(a.solve_out)), exist_ok=True)
+    with open(a.solve_out, "w") as f:
+        f.write(text)
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--step", default=None, choices=(None, "large", "window"))
+    ap.add_argument("--step", default=None, choices=(None, "large", "window", "solve"))
+    ap.add_argument("--only-solve", action="store_true", help="the solve / frozen-head rows alone (profiles/recon_solve_timing.txt)")
+    ap.add_argument("--solve-out", default=os.path.join(ROOT, "profiles", "recon_solve_timing.txt"))
     ap.add_argument("--events", type=int, default=20_000_000)
     ap.add_argument("--seconds", type=float, default=20.0)
     ap.add_argument("--sensor", type=int, nargs=2, default=(1280, 720))
@@ -159,6 +285,8 @@ def main():
         return step_large(a)
     if a.step == "window":
         return step_window(a)
+    if a.step == "solve":
+        return step_solve(a)
 
     from cmax_slam_amd import _lib
     assert _lib.lib().cmx_device_count() > 0, "no GPU visible: this tool measures on the device only"
@@ -178,8 +306,12 @@ def main():
         finally:
             tr.__file__ = saved
 
+    if a.only_solve:
+        write_solve(a, commit, child("solve", limit=900))
+        return 0
     big = child("large")  # (a timing child that dies ends the run: ChildDied propagates, nothing further is started)
     win = child("window")
+    write_solve(a, commit, child("solve", limit=900))
     n, p = big["events"], big["phases"]
     L = ["whole-trajectory contrast and gradient: cmx_backend_recon_restart / _contrast / _grad_add_from / _grad_get / _eval_from, and "
          "the same over bound events: _bind_from / _eval_bound",
