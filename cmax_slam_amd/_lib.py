@@ -13,6 +13,7 @@ SO_PATH = os.environ.get("CMAX_HIP_SO") or os.path.join(_HERE, "libcmaxhip.so") 
 OK, ERR_INVALID_ARG, ERR_EVENT_RANGE, ERR_HIP, ERR_SPLINE_RANGE, ERR_STATE, ERR_TIME_ORDER = range(7)
 VARIANCE, MEAN_SQUARE, GRADIENT_MAGNITUDE = 0, 1, 2
 GRAD_PLANES, GRAD_ADJOINT = 0, 1
+RECON_KEEP_HEAD = 2  # cmx_backend_recon_solve's freeze_head: solve under the frozen head as it stands
 DT_U8, DT_F32, DT_F64 = 0, 1, 2
 OP_SUM, OP_MAX = 0, 1
 GROUP_AUTO, GROUP_RCCL, GROUP_DIRECT = 0, 1, 2
@@ -139,6 +140,11 @@ SYMBOLS = {
     "cmx_backend_recon_bound_info": (C.c_int, [ctx_p, c_i64p, c_i64p, c_i64p, c_dp]),
     "cmx_backend_recon_freeze_head": (C.c_int, [ctx_p, C.c_int]),
     "cmx_backend_recon_frozen_info": (C.c_int, [ctx_p, C.POINTER(C.c_int), c_i64p, c_i64p]),
+    "cmx_backend_recon_extend": (C.c_int, [ctx_p, C.c_int, c_dp]),
+    "cmx_backend_recon_bind_append_from": (C.c_int, [ctx_p, C.c_void_p, C.c_int64, C.c_int64]),
+    "cmx_backend_recon_advance_head": (C.c_int, [ctx_p, C.c_int]),
+    "cmx_backend_recon_release_head": (C.c_int, [ctx_p]),
+    "cmx_backend_recon_online_info": (C.c_int, [ctx_p, c_i64p, c_i64p, c_i64p, c_i64p]),
     "cmx_backend_recon_solve": (C.c_int, [ctx_p, c_dp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double,
                                           C.c_double, C.c_int, C.c_void_p]),
     "cmx_diag_recon_solve_counts": (C.c_int, [ctx_p, c_i64p, c_i64p]),

@@ -198,6 +198,34 @@ inline int frozen_prefix(const KnotSupport &sup, int num_fixed, const long long 
   return b;
 }
 
+// ---- appending to a binding (cmx_backend_recon_bind_append_from): `count` events behind n_old bound ones.  A batch that holds B
+// events is closed: plan_batches over any longer stream cuts it the same.  Everything behind the closed batches is OPEN -- a last
+// batch of fewer than B events, or the lone trailing event no batch has opened (with B = 1: always) -- and is cut again together
+// with the new events: the scratch stream is "the open tail ++ the new range", its own plan_batches is the plan of the batches
+// [b_recut, nb), and its packed events land at packed_at.  The plan of the whole is plan_batches(n_old + count), nothing else.
+struct AppendPlan {
+  int b_recut = 0;         // first batch that is cut (again): every batch in front of it stays as it is
+  int64_t keep_from = 0;   // its first event, b_recut * B: the events [keep_from, n_old) are the open tail
+  int64_t tail_n = 0;      // n_old - keep_from, at most B
+  int64_t packed_at = 0;   // packed index of the scratch plan's first event, b_recut * per_batch
+  BatchPlan scratch;       // plan_batches(tail_n + count)
+  BatchPlan plan;          // plan_batches(n_old + count)
+};
+inline int64_t open_tail_from(int64_t n, const BatchPlan &p) {  // first event behind the closed batches of n events
+  const int64_t full = n / p.B;
+  return (full < p.nb ? full : (int64_t)p.nb) * p.B;
+}
+inline bool plan_append(int64_t n_old, int64_t count, int B, int rate, AppendPlan *a) {  // false: more batches than an int counts
+  *a = AppendPlan{};
+  BatchPlan old;
+  if (!plan_batches(n_old, B, rate, &old)) return false;
+  a->keep_from = open_tail_from(n_old, old);
+  a->b_recut = (int)(a->keep_from / B);
+  a->tail_n = n_old - a->keep_from;
+  a->packed_at = (int64_t)a->b_recut * old.per_batch;
+  return plan_batches(a->tail_n + count, B, rate, &a->scratch) && plan_batches(n_old + count, B, rate, &a->plan);
+}
+
 // the contiguous range of whole batches a group hands member `rank` (cmax_slam_amd/dist.py: batch_range)
 inline void batch_range(int64_t n, int B, int rank, int world, int64_t *beg, int64_t *end) {
   const int64_t nb = (n + B - 1) / B, per = (nb + world - 1) / world;

@@ -9,7 +9,9 @@
 // bound once (recon_bind_from), evaluated through a batch-pose table, a tile sort of the reconstruction's own and LDS votes
 // (recon_eval_bound).  And for the online case -- a settled head, a free tail: the batches under fixed knots voted once
 // into a base plane (recon_freeze_head), and the evaluation side of the native bundle adjustment (recon_solve_*, driven by
-// cmx_solver.cpp's FR-CG machine).
+// cmx_solver.cpp's FR-CG machine).  And for a recording that grows: the spline lengthened (recon_extend), events appended
+// to the binding (recon_bind_append_from), the freeze line moved forward (recon_advance_head) and the settled events' memory given
+// back (recon_release_head) -- book-keeping around the same kernels over sub-ranges.
 // Kernels: cmx_recon.hip.
 #include <limits>
 
@@ -57,8 +59,26 @@ struct ReconBound {
   bool sorted = false;
   int64_t sorts = 0;
   double fallback_frac = 0;
+  // ---- a binding that grows (bind_append_from, release_head).  n_events, plan and every batch / packed index above
+  // count from the bind; d_xy, d_bt and d_poseR start at packed event base_sampled / batch base_batches: packed event i is
+  // d_xy[i - base_sampled], batch b is d_bt[b - base_batches].  rel_* are what release_head has given back (base_* <= rel_*: the
+  // entries between them are dead space until the live ones move, see release_head) -- neither to be confused with the frozen
+  // head's counts, which say where the active events start, not where the arrays do.
+  size_t xy_cap = 0, bt_cap = 0;        // elements of d_xy, and of d_bt and d_poseR
+  int64_t rel_batches = 0, rel_sampled = 0, rel_events = 0;
+  int64_t base_batches = 0, base_sampled = 0;  // batch / packed event at element 0 of the arrays: at most the released counts
+  // the raw events of the open tail [open_tail_from(n_events), n_events), as the store held them: what the next append cuts again
+  uint32_t *d_tail_xy = nullptr;
+  int64_t *d_tail_t = nullptr;
+  size_t tail_cap = 0;
+  int64_t tail_n = 0;
+  long long t_last = 0;                 // time of the last bound event (n_events > 0)
+  uint32_t *xy_at(int64_t i) const { return d_xy + (i - base_sampled); }
+  long long *bt_at(int b) const { return d_bt + (b - base_batches); }
+  PoseR *pose_at(int b) const { return d_poseR + (b - base_batches); }
+  int64_t resident_sampled() const { return plan.n_packed - rel_sampled; }
   void release() {
-    void *dev[] = {d_xy, d_bt, d_poseR};
+    void *dev[] = {d_xy, d_bt, d_poseR, d_tail_xy, d_tail_t};
     for (void *p : dev) (void)hipFree(p);
     ts.release();
     if (h_stat) (void)hipHostFree(h_stat);
@@ -146,7 +166,10 @@ struct ReconState {
   ReconFrozen frozen;                     // of the binding: dropped with it, and by restart
   int g_num_fixed = 0;                    // the open gradient pass is a frozen evaluation's: grad[0, 3 g_num_fixed) is zero by definition
   ReconSolve solve;
-  int64_t host_waits = 0;                 // times a host thread has waited for the device in this reconstruction's calls
+  uint32_t *d_app_xy = nullptr;           // bind_append_from's scratch stream, "open tail ++ new range": raw events ...
+  int64_t *d_app_t = nullptr;             // ... and their times, count + B of them at most
+  size_t app_cap = 0;
+  int64_t host_waits = 0;                // times a host thread has waited for the device in this reconstruction's calls
 };
 // every place one of these calls blocks on the stream goes through here (cmx_backend_recon_solve reports the count per evaluation)
 static hipError_t recon_wait(cmx_ctx *c, ReconState *r) {
@@ -177,7 +200,7 @@ void recon_release(cmx_ctx *c) {
     if (s.done) (void)hipEventDestroy(s.done);
   }
   void *dev[] = {r->d_knots, r->d_delta, r->d_plane, r->d_fixed, r->d_inside, r->d_err, r->d_cx, r->d_cy, r->d_tflags, r->d_tile_list,
-                 r->d_tile_count, r->d_partials, r->d_cm, r->d_jt, r->d_gsum, r->d_voted, r->d_rows, r->d_row_win};
+                 r->d_tile_count, r->d_partials, r->d_cm, r->d_jt, r->d_gsum, r->d_voted, r->d_rows, r->d_row_win, r->d_app_xy, r->d_app_t};
   for (void *p : dev) (void)hipFree(p);
   r->bnd.release();
   r->frozen.release();
@@ -524,12 +547,54 @@ int cmx_backend_recon_grad_add_from(cmx_ctx *c, const cmx_events *e, int64_t fir
   return recon_add_range(c, true, e, first, count);
 }
 
+// events of the binding have been released (cmx_backend_recon_release_head): their votes live in the frozen base alone, so whatever
+// would drop or rebuild that base -- and keep the binding -- is refused
+static int recon_refuse_released(cmx_ctx *c, const ReconState *r, const char *what) {
+  if (!r->bound || r->bnd.rel_batches == 0) return CMX_OK;
+  return fail(c, CMX_ERR_STATE, "%s would lose the %lld events released from the binding (cmx_backend_recon_release_head)", what,
+              (long long)r->bnd.rel_events);
+}
+
 int cmx_backend_recon_restart(cmx_ctx *c, const double *knots_xyzw) {
   int rc = recon_enter(c, true);
   if (rc) return rc;
   if (!knots_xyzw) return fail(c, CMX_ERR_INVALID_ARG, "null knot array");
+  rc = recon_refuse_released(c, c->recon, "restart");
+  if (rc) return rc;
   frozen_drop(c, c->recon);  // (new knots: what the frozen batches voted no longer holds)
   return recon_start_over(c, c->recon, knots_xyzw);
+}
+
+// restart that may lengthen the spline and keeps a frozen head: everything sized by K grows with it -- the knots and
+// their logarithms, the 2 x 3K sums, the solve's staging (allocated again by the next solve) -- before anything changes
+int cmx_backend_recon_extend(cmx_ctx *c, int K_new, const double *knots_xyzw) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  ReconState *r = c->recon;
+  const int K = r->sup.K;
+  if (!knots_xyzw) return fail(c, CMX_ERR_INVALID_ARG, "null knot array");
+  if (K_new < K || K_new > (1 << 28)) return fail(c, CMX_ERR_INVALID_ARG, "K_new=%d outside [%d, 2^28]", K_new, K);
+  const ReconFrozen &fz = r->frozen;
+  if (fz.num_fixed > 0 && memcmp(knots_xyzw, fz.knots.data(), (size_t)fz.num_fixed * sizeof(Quat)) != 0)
+    return fail(c, CMX_ERR_INVALID_ARG, "the first %d knots differ from those the head was frozen at", fz.num_fixed);
+  if (K_new > K) {
+    Quat *knots = nullptr;
+    double *delta = nullptr, *gsum = nullptr;
+    hipError_t e = hipMalloc((void **)&knots, (size_t)K_new * sizeof(Quat));
+    if (e == hipSuccess) e = hipMalloc((void **)&delta, (size_t)(K_new - 1) * 3 * sizeof(double));
+    if (e == hipSuccess && r->d_gsum) e = hipMalloc((void **)&gsum, 2 * 3 * (size_t)K_new * sizeof(double));
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (nothing queued reads the old ones any more)
+    if (e != hipSuccess) {
+      (void)hipFree(knots); (void)hipFree(delta); (void)hipFree(gsum);
+      return fail(c, CMX_ERR_HIP, "growing the spline to %d knots: %s", K_new, hipGetErrorString(e));
+    }
+    (void)hipFree(r->d_knots); (void)hipFree(r->d_delta); (void)hipFree(r->d_gsum);
+    r->d_knots = knots; r->d_delta = delta; r->d_gsum = gsum;
+    r->solve.release();
+    r->sup.K = K_new;
+  }
+  if (fz.num_fixed == 0) frozen_drop(c, r);  // (as restart: a base allocated without a head goes)
+  return recon_start_over(c, r, knots_xyzw);
 }
 
 static void recon_refresh_plane(cmx_ctx *c, ReconState *r);
@@ -678,6 +743,10 @@ int cmx_backend_recon_eval_from(cmx_ctx *c, const cmx_events *e, int64_t first, 
   if (rc) return rc;
   if (!contrast) return fail(c, CMX_ERR_INVALID_ARG, "null output");
   ReconState *r = c->recon;
+  if (knots_xyzw) {
+    rc = recon_refuse_released(c, r, "eval_from with knots");
+    if (rc) return rc;
+  }
   if (grad) {  // (before anything is changed: the one argument error the later steps would find)
     rc = recon_grad_precheck(c, r, blur_sigma);
     if (rc) return rc;
@@ -702,13 +771,39 @@ int cmx_backend_recon_eval_from(cmx_ctx *c, const cmx_events *e, int64_t first, 
 //             pass over the time-ordered copy in the slices of every add (slice_at)
 constexpr int64_t kMaxBoundSampled = 1LL << 30;  // (sorted positions, chunk bounds and keys are 32-bit)
 
+// the open tail of a binding for its next append: the last n raw events, as a store replica or the append's scratch holds them, into
+// buffers of the binding's own (queued; large enough, or new ones -- the caller has made sure nothing queued reads the old ones)
+static int tail_keep(cmx_ctx *c, ReconBound *b, const uint32_t *d_xy, const int64_t *d_t, int64_t n) {
+  if ((size_t)n > b->tail_cap) {
+    (void)hipFree(b->d_tail_xy); (void)hipFree(b->d_tail_t);
+    b->d_tail_xy = nullptr; b->d_tail_t = nullptr; b->tail_cap = 0;
+    HIP_TRY(c, hipMalloc((void **)&b->d_tail_xy, (size_t)n * sizeof(uint32_t)));
+    HIP_TRY(c, hipMalloc((void **)&b->d_tail_t, (size_t)n * sizeof(int64_t)));
+    b->tail_cap = (size_t)n;
+  }
+  if (n > 0) {
+    HIP_TRY(c, hipMemcpyAsync(b->d_tail_xy, d_xy, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(b->d_tail_t, d_t, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, c->stream));
+  }
+  b->tail_n = n;
+  return CMX_OK;
+}
+
 static int bound_build(cmx_ctx *c, ReconState *r, const EventSource &src, const BatchPlan &p, ReconBound *b) {
   b->n_events = src.n;
   b->plan = p;
   HIP_TRY(c, hipHostMalloc((void **)&b->h_stat, 2 * sizeof(unsigned long long), hipHostMallocDefault));
   b->h_stat[0] = b->h_stat[1] = 0ull;
-  if (p.nb == 0) return CMX_OK;  // (0 or 1 events: nothing to vote)
+  const int64_t tail_from = open_tail_from(src.n, p);
+  if (src.n > 0) b->t_last = (long long)src.soa.t[src.n - 1];
+  if (p.nb == 0) {  // (0 or 1 events: nothing to vote)
+    const int rc0 = tail_keep(c, b, src.d_xy, src.d_t, src.n);
+    if (rc0) return rc0;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return CMX_OK;
+  }
   HIP_TRY(c, hipMalloc((void **)&b->d_bt, (size_t)p.nb * sizeof(long long)));
+  b->bt_cap = (size_t)p.nb;
   int rc = queue_batch_times(c, src.d_t, src.n, r->B, p.nb, r->sup, b->d_bt, r->d_err, true);
   if (rc) return rc;
   HIP_TRY(c, hipGetLastError());
@@ -721,7 +816,10 @@ static int bound_build(cmx_ctx *c, ReconState *r, const EventSource &src, const 
   const int tiles = ((c->Wp + kBinTile - 1) / kBinTile) * ((c->Hp + kBinTile - 1) / kBinTile);
   const int ntiles = 2 * tiles;  // (the back end's sort keys carry the old / new bit: no bound event sets it, half of the bins stay empty)
   HIP_TRY(c, hipMalloc((void **)&b->d_xy, n * sizeof(uint32_t)));
+  b->xy_cap = n;
   HIP_TRY(c, hipMalloc((void **)&b->d_poseR, (size_t)p.nb * sizeof(PoseR)));
+  rc = tail_keep(c, b, src.d_xy + tail_from, src.d_t + tail_from, src.n - tail_from);
+  if (rc) return rc;
   const ChunkPlan cp = plan_chunks(p.n_packed, ntiles, kBackEndChunkDiv);
   b->chunk_events = cp.chunk_events;
   b->max_chunks = (int)cp.max_chunks;  // (n <= 2^30, at most 2^20 tiles: below 2^23)
@@ -817,8 +915,8 @@ static int bound_gather(cmx_ctx *c, ReconState *r, int b_first, bool wait) {
   ReconArgs &a = ga.ev;
   for (int b_lo = b_first; b_lo < p.nb; b_lo += slice_batches) {
     const Slice sl = slice_at(p, b.n_events, b_lo, slice_batches);
-    a.xy = b.d_xy + sl.first; a.stride = 0;
-    a.batch_t = b.d_bt + b_lo; a.nb = sl.b_hi - b_lo;
+    a.xy = b.xy_at(sl.first); a.stride = 0;  // (resident addresses: b_first is never in front of what release_head gave back)
+    a.batch_t = b.bt_at(b_lo); a.nb = sl.b_hi - b_lo;
     a.n = (int)sl.n;
     Span sp(c, CMX_T_GATHER);
     const int rc = queue_slice(c, r, ga, true);
@@ -845,18 +943,19 @@ static int bound_eval(cmx_ctx *c, ReconState *r, const double *knots_xyzw, doubl
   int rc = recon_start_over(c, r, knots_xyzw, /*from_base=*/true, /*staged=*/sv != nullptr);
   if (rc) return rc;
   const int b0 = frozen ? fz.b_act : 0;
+  // `first`: the first active event's packed index since the bind -- where it lies in the resident arrays is xy_at's business
   const int64_t first = frozen ? fz.sampled : 0, n_act = b.plan.n_packed - first;
   if (n_act > 0) {
     ReconArgs a = recon_args(c, r);
-    a.batch_t = b.d_bt + b0; a.nb = b.plan.nb - b0;
+    a.batch_t = b.bt_at(b0); a.nb = b.plan.nb - b0;
     {
       Span sp(c, CMX_T_POSE, /*exact=*/true);
-      launch_recon_pose_table(a, b.d_poseR + b0, c->stream, sp.t0(), sp.t1());
+      launch_recon_pose_table(a, b.pose_at(b0), c->stream, sp.t0(), sp.t1());
     }
     ReconLdsArgs g{};
     g.cam = a.cam;
-    g.cam.poseR = b.d_poseR + b0;
-    g.cam.xy = b.d_xy + first;
+    g.cam.poseR = b.pose_at(b0);
+    g.cam.xy = b.xy_at(first);
     g.cam.per_batch = b.plan.per_batch;
     g.cam.n = (int)n_act;
     g.cam.order = r->sup.order;
@@ -949,13 +1048,63 @@ int cmx_backend_recon_eval_bound(cmx_ctx *c, const double *knots_xyzw, double bl
   return bound_eval(c, r, knots_xyzw, blur_sigma, contrast_measure, contrast, grad, nullptr);
 }
 
-// ---- frozen head (DESIGN 4.14)
+// ---- frozen head (DESIGN 4.14, 4.15)
+// eval_bound's own vote pass over the batches [b_lo, b_hi) of the binding, at the knots the reconstruction holds, into a base plane
+// and its counter ON TOP of what they hold: pose table, the binding's TileSort filled with THOSE events (the next evaluation sorts
+// the active ones into it, as it would anyway), LDS votes.  freeze_head: [0, b_act) into a cleared base; advance_head: the batches
+// the moved line newly names.  Queued; the caller waits.
+static int frozen_vote(cmx_ctx *c, ReconState *r, void *d_base, unsigned long long *d_inside, int b_lo, int b_hi) {
+  ReconBound &b = r->bnd;
+  const BatchPlan &p = b.plan;
+  const int64_t first = p.packed(0, b_lo), n = p.packed(b_lo, b_hi);
+  if (n > 0) {
+    const int tiles = ((c->Wp + kBinTile - 1) / kBinTile) * ((c->Hp + kBinTile - 1) / kBinTile);
+    ReconArgs a = recon_args(c, r);
+    a.batch_t = b.bt_at(b_lo); a.nb = b_hi - b_lo;
+    launch_recon_pose_table(a, b.pose_at(b_lo), c->stream);
+    ReconLdsArgs g{};
+    g.cam = a.cam;
+    g.cam.poseR = b.pose_at(b_lo);
+    g.cam.xy = b.xy_at(first);
+    g.cam.per_batch = p.per_batch;
+    g.cam.n = (int)n;
+    g.cam.order = r->sup.order;
+    const ChunkPlan cp = plan_chunks(n, 2 * tiles, kBackEndChunkDiv);
+    int rc = b.ts.reserve(c, n, 2 * tiles, cp.max_chunks);
+    if (!rc) rc = bound_sort(c, b, g.cam, cp.chunk_events);
+    if (rc) return rc;
+    b.sorted = false;
+    g.ev.sxy = b.ts.d_sxy; g.ev.sbatch = b.ts.d_sbatch;
+    g.ev.chunks = b.ts.d_chunks; g.ev.nchunks = (int)cp.max_chunks; g.ev.nchunks_dev = b.ts.d_nchunks;
+    g.ev.fallback = b.ts.d_fallback;
+    g.ev.fixed = r->deterministic ? static_cast<unsigned long long *>(d_base) : nullptr;
+    g.plane = r->deterministic ? nullptr : static_cast<float *>(d_base);
+    g.n_inside = d_inside;
+    HIP_TRY(c, hipMemsetAsync(b.ts.d_fallback, 0, sizeof(unsigned), c->stream));
+    launch_recon_votes_lds(g, c->stream);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return CMX_OK;
+}
+// the active part's chunk table: the chunk rule at ITS count (the table may be longer than the one the bind reserved)
+static int frozen_plan_active(cmx_ctx *c, ReconState *r, ReconFrozen *fz) {
+  const int64_t n_act = r->bnd.plan.n_packed - fz->sampled;
+  if (n_act <= 0) return CMX_OK;
+  const int tiles = ((c->Wp + kBinTile - 1) / kBinTile) * ((c->Hp + kBinTile - 1) / kBinTile);
+  const ChunkPlan cp = plan_chunks(n_act, 2 * tiles, kBackEndChunkDiv);
+  fz->chunk_events = cp.chunk_events;
+  fz->max_chunks = (int)cp.max_chunks;
+  return r->bnd.ts.reserve(c, n_act, 2 * tiles, cp.max_chunks);
+}
+
 int cmx_backend_recon_freeze_head(cmx_ctx *c, int num_fixed) {
   int rc = recon_enter(c, true);
   if (rc) return rc;
   ReconState *r = c->recon;
   if (!r->bound) return fail(c, CMX_ERR_STATE, "no events are bound (cmx_backend_recon_bind_from)");
   if (num_fixed < 0 || num_fixed >= r->sup.K) return fail(c, CMX_ERR_INVALID_ARG, "num_fixed=%d outside [0, %d)", num_fixed, r->sup.K);
+  rc = recon_refuse_released(c, r, "freeze_head");
+  if (rc) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   (void)recon_pass_enter(c, r, false);  // as a bind: an open gradient pass is closed
   frozen_drop(c, r);
@@ -977,46 +1126,12 @@ int cmx_backend_recon_freeze_head(cmx_ctx *c, int num_fixed) {
     HIP_TRY(c, hipMalloc((void **)&fz.d_inside, sizeof(unsigned long long)));
     HIP_TRY(c, hipMemsetAsync(fz.d_base, 0, np * cell, c->stream));
     HIP_TRY(c, hipMemsetAsync(fz.d_inside, 0, sizeof(unsigned long long), c->stream));
-    const int tiles = ((c->Wp + kBinTile - 1) / kBinTile) * ((c->Hp + kBinTile - 1) / kBinTile);
-    if (fz.sampled > 0) {
-      // eval_bound's own vote pass over the range [0, b_act): pose table, the binding's TileSort filled with the FROZEN events (the
-      // next evaluation sorts the active ones into it, as it would anyway), LDS votes -- into the base instead of the plane
-      ReconArgs a = recon_args(c, r);
-      a.batch_t = b.d_bt; a.nb = fz.b_act;
-      launch_recon_pose_table(a, b.d_poseR, c->stream);
-      ReconLdsArgs g{};
-      g.cam = a.cam;
-      g.cam.poseR = b.d_poseR;
-      g.cam.xy = b.d_xy;
-      g.cam.per_batch = p.per_batch;
-      g.cam.n = (int)fz.sampled;
-      g.cam.order = r->sup.order;
-      const ChunkPlan cp = plan_chunks(fz.sampled, 2 * tiles, kBackEndChunkDiv);
-      int rc2 = b.ts.reserve(c, fz.sampled, 2 * tiles, cp.max_chunks);
-      if (!rc2) rc2 = bound_sort(c, b, g.cam, cp.chunk_events);
-      if (rc2) return rc2;
-      b.sorted = false;
-      g.ev.sxy = b.ts.d_sxy; g.ev.sbatch = b.ts.d_sbatch;
-      g.ev.chunks = b.ts.d_chunks; g.ev.nchunks = (int)cp.max_chunks; g.ev.nchunks_dev = b.ts.d_nchunks;
-      g.ev.fallback = b.ts.d_fallback;
-      g.ev.fixed = r->deterministic ? static_cast<unsigned long long *>(fz.d_base) : nullptr;
-      g.plane = r->deterministic ? nullptr : static_cast<float *>(fz.d_base);
-      g.n_inside = fz.d_inside;
-      HIP_TRY(c, hipMemsetAsync(b.ts.d_fallback, 0, sizeof(unsigned), c->stream));
-      launch_recon_votes_lds(g, c->stream);
-    }
-    HIP_TRY(c, hipGetLastError());
+    int rc2 = frozen_vote(c, r, fz.d_base, fz.d_inside, 0, fz.b_act);
+    if (rc2) return rc2;
     HIP_TRY(c, hipMemcpyAsync(&fz.inside, fz.d_inside, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    // the active part's chunk table: the chunk rule at ITS count (the table may be longer than the one the bind reserved)
-    const int64_t n_act = p.n_packed - fz.sampled;
-    if (n_act > 0) {
-      const ChunkPlan cp = plan_chunks(n_act, 2 * tiles, kBackEndChunkDiv);
-      fz.chunk_events = cp.chunk_events;
-      fz.max_chunks = (int)cp.max_chunks;
-      const int rc2 = b.ts.reserve(c, n_act, 2 * tiles, cp.max_chunks);
-      if (rc2) return rc2;
-    }
+    rc2 = frozen_plan_active(c, r, &fz);
+    if (rc2) return rc2;
     fz.num_fixed = num_fixed;
     return CMX_OK;
   };
@@ -1041,6 +1156,228 @@ int cmx_backend_recon_frozen_info(cmx_ctx *c, int *num_fixed, int64_t *frozen_ba
   return CMX_OK;
 }
 
+// ---- a binding that grows
+// The freeze line moves forward: the batches [b_act, b_act') the prefix rule newly names under num_fixed_new fixed knots vote once, at
+// the knots the reconstruction holds, into the base as it stands.  Frozen batches read fixed knots alone, and those are bytewise the
+// same at every evaluation and extend since the freeze, so the base is what one freeze of [0, b_act') would have voted.
+int cmx_backend_recon_advance_head(cmx_ctx *c, int num_fixed_new) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  ReconState *r = c->recon;
+  if (!r->bound) return fail(c, CMX_ERR_STATE, "no events are bound (cmx_backend_recon_bind_from)");
+  ReconFrozen &fz = r->frozen;
+  if (num_fixed_new < fz.num_fixed || num_fixed_new >= r->sup.K)
+    return fail(c, CMX_ERR_INVALID_ARG, "num_fixed_new=%d outside [%d, %d)", num_fixed_new, fz.num_fixed, r->sup.K);
+  if (fz.num_fixed == 0) return cmx_backend_recon_freeze_head(c, num_fixed_new);
+  ReconBound &b = r->bnd;
+  const BatchPlan &p = b.plan;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // the prefix rule from the line on, over the active batches' times
+  const int n_act_b = p.nb - fz.b_act;
+  std::vector<long long> bt((size_t)n_act_b);
+  if (n_act_b > 0) HIP_TRY(c, hipMemcpy(bt.data(), b.bt_at(fz.b_act), (size_t)n_act_b * sizeof(long long), hipMemcpyDeviceToHost));
+  const int b_new = fz.b_act + frozen_prefix(r->sup, num_fixed_new, bt.data(), n_act_b);
+  std::vector<double> knots(4 * (size_t)num_fixed_new);
+  HIP_TRY(c, hipMemcpy(knots.data(), r->d_knots, (size_t)num_fixed_new * sizeof(Quat), hipMemcpyDeviceToHost));
+  // from here on only a runtime error can end the call
+  (void)recon_pass_enter(c, r, false);  // as freeze_head: an open gradient pass is closed
+  rc = frozen_vote(c, r, fz.d_base, fz.d_inside, fz.b_act, b_new);
+  if (!rc) {
+    const hipError_t e = hipMemcpyAsync(&fz.inside, fz.d_inside, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) rc = fail(c, CMX_ERR_HIP, "reading the base's counter: %s", hipGetErrorString(e));
+  }
+  const hipError_t waited = hipStreamSynchronize(c->stream);
+  if (!rc && waited != hipSuccess) rc = fail(c, CMX_ERR_HIP, "the votes of the newly frozen batches failed: %s", hipGetErrorString(waited));
+  if (rc) return rc;
+  fz.b_act = b_new;
+  fz.sampled = p.packed(0, b_new);
+  fz.knots = knots;
+  fz.num_fixed = num_fixed_new;
+  b.sorted = false;  // (the sort holds the newly frozen events, or the old active ones)
+  return frozen_plan_active(c, r, &fz);
+}
+
+// The frozen batches' resident entries go: the active tail moves into buffers of its own size and the old ones are freed, so the
+// binding holds (and its capacity follows) the active tail, not the recording.  The open tail's raw events stay.
+int cmx_backend_recon_release_head(cmx_ctx *c) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  ReconState *r = c->recon;
+  if (!r->bound) return fail(c, CMX_ERR_STATE, "no events are bound (cmx_backend_recon_bind_from)");
+  ReconBound &b = r->bnd;
+  const ReconFrozen &fz = r->frozen;
+  const BatchPlan &p = b.plan;
+  if (fz.num_fixed == 0 || fz.b_act <= b.rel_batches) return CMX_OK;  // nothing (new) to give back
+  // The released entries are dead space in front of the live ones.  Once there is more dead than live the live tail moves into
+  // buffers of twice its size and the old ones are freed (a copy of `live` entries per more than `live` released: amortised, and
+  // the capacity stays within twice the active tail); until then -- and an append that runs out of room does the same -- the
+  // release is book-keeping alone.
+  const size_t n_xy = (size_t)(p.n_packed - fz.sampled), n_bt = (size_t)(p.nb - fz.b_act);
+  if ((size_t)(fz.sampled - b.base_sampled) > n_xy) {
+    const size_t cap_xy = n_xy ? 2 * n_xy : 1, cap_bt = n_bt ? 2 * n_bt : 1;
+    uint32_t *xy = nullptr;
+    long long *bt = nullptr;
+    PoseR *pose = nullptr;
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMalloc((void **)&xy, cap_xy * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&bt, cap_bt * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc((void **)&pose, cap_bt * sizeof(PoseR));
+    if (e == hipSuccess && n_xy) e = hipMemcpyAsync(xy, b.xy_at(fz.sampled), n_xy * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess && n_bt) e = hipMemcpyAsync(bt, b.bt_at(fz.b_act), n_bt * sizeof(long long), hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {  // (the binding is as it was)
+      (void)hipStreamSynchronize(c->stream);
+      (void)hipFree(xy); (void)hipFree(bt); (void)hipFree(pose);
+      return fail(c, CMX_ERR_HIP, "moving the active tail: %s", hipGetErrorString(e));
+    }
+    (void)hipFree(b.d_xy); (void)hipFree(b.d_bt); (void)hipFree(b.d_poseR);
+    b.d_xy = xy; b.d_bt = bt; b.d_poseR = pose;
+    b.xy_cap = cap_xy;
+    b.bt_cap = cap_bt;
+    b.base_sampled = fz.sampled;
+    b.base_batches = fz.b_act;
+  }
+  b.rel_batches = fz.b_act;
+  b.rel_sampled = fz.sampled;
+  // (whole batches in front of an active one; all of them: every event a batch holds -- a lone trailing event is in none)
+  b.rel_events = fz.b_act < p.nb ? (int64_t)fz.b_act * p.B : (int64_t)(p.nb - 1) * p.B + p.last_len;
+  return CMX_OK;
+}
+
+int cmx_backend_recon_online_info(cmx_ctx *c, int64_t *released_batches, int64_t *released_events, int64_t *released_sampled,
+                                  int64_t *resident_sampled) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  const ReconState *r = c->recon;  // (without a binding: all zero)
+  if (released_batches) *released_batches = r->bound ? r->bnd.rel_batches : 0;
+  if (released_events) *released_events = r->bound ? r->bnd.rel_events : 0;
+  if (released_sampled) *released_sampled = r->bound ? r->bnd.rel_sampled : 0;
+  if (resident_sampled) *resident_sampled = r->bound ? r->bnd.resident_sampled() : 0;
+  return CMX_OK;
+}
+
+// `count` events behind the bound ones: the binding afterwards is bind_from's over the concatenation.  plan_append (cmx_ingest.hpp)
+// names the batch that is cut again; "the kept open tail ++ the new range" is assembled in a scratch of count + B events at most, and
+// the batch-time and packing kernels of bind_from run over that scratch alone.
+int cmx_backend_recon_bind_append_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  ReconState *r = c->recon;
+  if (!r->bound) return fail(c, CMX_ERR_STATE, "no events are bound (cmx_backend_recon_bind_from)");
+  EventSource src;
+  rc = store_source(c, e, first, count, &src);
+  if (rc) return rc;
+  (void)recon_pass_enter(c, r, false);  // as every add: an open gradient pass is closed
+  if (src.n > kMaxEvents) return fail(c, CMX_ERR_INVALID_ARG, "bad event count %lld", (long long)src.n);
+  if (src.n == 0) return CMX_OK;
+  ReconBound &b = r->bnd;
+  ReconFrozen &fz = r->frozen;
+  if (b.n_events > 0 && (long long)src.soa.t[0] < b.t_last)
+    return fail(c, CMX_ERR_TIME_ORDER, "the first new event (%lld ns) is earlier than the last bound one (%lld ns)", (long long)src.soa.t[0],
+                b.t_last);
+  AppendPlan ap;
+  if (!plan_append(b.n_events, src.n, r->B, r->rate, &ap)) return fail(c, CMX_ERR_INVALID_ARG, "too many batches");
+  if (fz.num_fixed > 0 && ap.b_recut < fz.b_act)
+    return fail(c, CMX_ERR_STATE, "batch %d, which the new events cut again, is part of the frozen head (%d batches)", ap.b_recut, fz.b_act);
+  if (ap.plan.n_packed - b.rel_sampled > kMaxBoundSampled)
+    return fail(c, CMX_ERR_INVALID_ARG, "%lld resident sampled events above the limit of a binding (2^30)",
+                (long long)(ap.plan.n_packed - b.rel_sampled));
+  if (ap.tail_n != b.tail_n) return fail(c, CMX_ERR_STATE, "the binding's open tail holds %lld events, its plan says %lld", (long long)b.tail_n,
+                                         (long long)ap.tail_n);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // ---- the scratch stream and its batch times (staging: nothing of the binding is touched)
+  const int64_t m = ap.tail_n + src.n;
+  if ((size_t)m > r->app_cap) {
+    (void)hipFree(r->d_app_xy); (void)hipFree(r->d_app_t);
+    r->d_app_xy = nullptr; r->d_app_t = nullptr; r->app_cap = 0;
+    const size_t cap = (size_t)m + (size_t)m / 2;
+    HIP_TRY(c, hipMalloc((void **)&r->d_app_xy, cap * sizeof(uint32_t)));
+    HIP_TRY(c, hipMalloc((void **)&r->d_app_t, cap * sizeof(int64_t)));
+    r->app_cap = cap;
+  }
+  if (ap.tail_n > 0) {
+    HIP_TRY(c, hipMemcpyAsync(r->d_app_xy, b.d_tail_xy, (size_t)ap.tail_n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(r->d_app_t, b.d_tail_t, (size_t)ap.tail_n * sizeof(int64_t), hipMemcpyDeviceToDevice, c->stream));
+  }
+  HIP_TRY(c, hipMemcpyAsync(r->d_app_xy + ap.tail_n, src.d_xy, (size_t)src.n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(r->d_app_t + ap.tail_n, src.d_t, (size_t)src.n * sizeof(int64_t), hipMemcpyDeviceToDevice, c->stream));
+  const BatchPlan &sp = ap.scratch;
+  ReconSlot &s = r->slot[0];
+  if (sp.nb > 0) {
+    rc = slot_ensure(c, s, 0, (size_t)sp.nb, false);
+    if (rc) return rc;
+    rc = queue_batch_times(c, r->d_app_t, m, r->B, sp.nb, r->sup, s.d_bt, r->d_err, true);
+    if (rc) return rc;
+    HIP_TRY(c, hipGetLastError());
+    BatchTimeError bad;
+    rc = read_batch_errors(c, r->d_err, &bad);
+    if (rc) return rc;
+    if (bad.kind) return fail_batch_time(c, bad, r->sup, /*with_event=*/false);
+  }
+  // ---- valid.  Room for the longer binding, beside the buffers in use, when the arrays' end is reached: twice the LIVE entries (so
+  // dead space in front, left by release_head, is dropped on the way and the capacity follows the active tail), the live part
+  // copied across; a failure frees the new buffers alone
+  const int tiles = ((c->Wp + kBinTile - 1) / kBinTile) * ((c->Hp + kBinTile - 1) / kBinTile);
+  const int64_t n_act = ap.plan.n_packed - (fz.num_fixed > 0 ? fz.sampled : 0);
+  const ChunkPlan cp = plan_chunks(n_act > 0 ? n_act : 1, 2 * tiles, kBackEndChunkDiv);
+  const size_t need_xy = (size_t)(ap.plan.n_packed - b.rel_sampled), need_bt = (size_t)(ap.plan.nb - b.rel_batches);
+  const size_t keep_xy = (size_t)(ap.packed_at - b.rel_sampled), keep_bt = (size_t)(ap.b_recut - b.rel_batches);
+  const int64_t tail_from = open_tail_from(b.n_events + src.n, ap.plan), tail_new = b.n_events + src.n - tail_from;  // the next open tail
+  uint32_t *xy = nullptr, *tail_xy = nullptr;
+  long long *bt = nullptr;
+  PoseR *pose = nullptr;
+  int64_t *tail_t = nullptr;
+  size_t xy_cap = b.xy_cap, bt_cap = b.bt_cap, tail_cap = b.tail_cap;
+  hipError_t he = hipSuccess;
+  if ((size_t)(ap.plan.n_packed - b.base_sampled) > b.xy_cap) {
+    xy_cap = 2 * need_xy;
+    he = hipMalloc((void **)&xy, xy_cap * sizeof(uint32_t));
+    if (he == hipSuccess && keep_xy) he = hipMemcpyAsync(xy, b.xy_at(b.rel_sampled), keep_xy * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream);
+  }
+  if (he == hipSuccess && (size_t)(ap.plan.nb - b.base_batches) > b.bt_cap) {
+    bt_cap = 2 * need_bt;
+    he = hipMalloc((void **)&bt, bt_cap * sizeof(long long));
+    if (he == hipSuccess) he = hipMalloc((void **)&pose, bt_cap * sizeof(PoseR));
+    if (he == hipSuccess && keep_bt) he = hipMemcpyAsync(bt, b.bt_at(b.rel_batches), keep_bt * sizeof(long long), hipMemcpyDeviceToDevice, c->stream);
+  }
+  if (he == hipSuccess && (size_t)tail_new > b.tail_cap) {
+    tail_cap = (size_t)tail_new > 2 * b.tail_cap ? (size_t)tail_new : 2 * b.tail_cap;
+    he = hipMalloc((void **)&tail_xy, tail_cap * sizeof(uint32_t));
+    if (he == hipSuccess) he = hipMalloc((void **)&tail_t, tail_cap * sizeof(int64_t));
+  }
+  if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+  rc = he == hipSuccess ? (n_act > 0 ? b.ts.reserve(c, n_act, 2 * tiles, cp.max_chunks) : (int)CMX_OK)
+                        : fail(c, CMX_ERR_HIP, "growing the binding: %s", hipGetErrorString(he));
+  if (rc) {  // (the binding is as it was)
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(xy); (void)hipFree(bt); (void)hipFree(pose); (void)hipFree(tail_xy); (void)hipFree(tail_t);
+    return rc;
+  }
+  // ---- commit: from here on only a runtime error can end the call
+  if (xy) { (void)hipFree(b.d_xy); b.d_xy = xy; b.xy_cap = xy_cap; b.base_sampled = b.rel_sampled; }
+  if (bt) { (void)hipFree(b.d_bt); (void)hipFree(b.d_poseR); b.d_bt = bt; b.d_poseR = pose; b.bt_cap = bt_cap; b.base_batches = b.rel_batches; }
+  if (tail_xy) { (void)hipFree(b.d_tail_xy); (void)hipFree(b.d_tail_t); b.d_tail_xy = tail_xy; b.d_tail_t = tail_t; b.tail_cap = tail_cap; }
+  b.n_events += src.n;
+  b.plan = ap.plan;
+  b.t_last = (long long)src.soa.t[src.n - 1];
+  b.sorted = false;
+  if (n_act > 0) {  // the chunk rule at the new (active) count
+    if (fz.num_fixed > 0) { fz.chunk_events = cp.chunk_events; fz.max_chunks = (int)cp.max_chunks; }
+    else { b.chunk_events = cp.chunk_events; b.max_chunks = (int)cp.max_chunks; }
+  }
+  if (sp.nb > 0) {
+    HIP_TRY(c, hipMemcpyAsync(b.bt_at(ap.b_recut), s.d_bt, (size_t)sp.nb * sizeof(long long), hipMemcpyDeviceToDevice, c->stream));
+    // (t_next = the smallest time: no event carries the old flag)
+    launch_be_pack_from_store(r->d_app_xy, reinterpret_cast<const long long *>(r->d_app_t), (long long)m, r->B, r->rate, sp.per_batch,
+                              (int)sp.n_packed, std::numeric_limits<long long>::min(), b.xy_at(ap.packed_at), c->stream);
+    HIP_TRY(c, hipGetLastError());
+  }
+  rc = tail_keep(c, &b, r->d_app_xy + (tail_from - ap.keep_from), r->d_app_t + (tail_from - ap.keep_from), tail_new);
+  if (rc) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the store may be pushed to, compacted or closed from here on
+  return CMX_OK;
+}
+
 // ---- cmx_backend_recon_solve's three hooks (the FR-CG loop itself is cmx_solver.cpp's)
 // begin: every argument error, before anything changes; then the staging, the start knots on the device and -- asked for -- the
 // frozen head at them
@@ -1054,6 +1391,17 @@ int recon_solve_begin(cmx_ctx *c, const double *knots_xyzw, int num_fixed, int f
   const int K = r->sup.K;
   if (num_fixed < 0 || num_fixed >= K) return fail(c, CMX_ERR_INVALID_ARG, "num_fixed=%d outside [0, %d)", num_fixed, K);
   if (!std::isfinite(blur_sigma)) return fail(c, CMX_ERR_INVALID_ARG, "blur_sigma is not finite");
+  const bool keep = freeze_head == CMX_RECON_KEEP_HEAD;
+  if (keep) {  // under the frozen head as it stands
+    const ReconFrozen &fz = r->frozen;
+    if (fz.num_fixed == 0) return fail(c, CMX_ERR_STATE, "no frozen head to keep (cmx_backend_recon_freeze_head / _advance_head)");
+    if (num_fixed != fz.num_fixed) return fail(c, CMX_ERR_INVALID_ARG, "num_fixed=%d, the frozen head has %d", num_fixed, fz.num_fixed);
+    if (memcmp(knots_xyzw, fz.knots.data(), (size_t)fz.num_fixed * sizeof(Quat)) != 0)
+      return fail(c, CMX_ERR_INVALID_ARG, "the first %d knots differ from those the head was frozen at", fz.num_fixed);
+  } else {
+    rc = recon_refuse_released(c, r, "a solve that freezes again or drops the head");
+    if (rc) return rc;
+  }
   rc = recon_grad_precheck(c, r, blur_sigma);
   if (rc) return rc;
   ReconSolve &sv = r->solve;
@@ -1071,7 +1419,9 @@ int recon_solve_begin(cmx_ctx *c, const double *knots_xyzw, int num_fixed, int f
   sv.have_last = false;
   sv.evals = 0;
   sv.waits = 0;
-  if (freeze_head) {  // at the start knots: they go to the device first (restart, which also drops an earlier head)
+  if (keep) {  // the start knots by extend's path: the head survives
+    rc = cmx_backend_recon_extend(c, K, knots_xyzw);
+  } else if (freeze_head) {  // at the start knots: they go to the device first (restart, which also drops an earlier head)
     rc = cmx_backend_recon_restart(c, knots_xyzw);
     if (!rc) rc = cmx_backend_recon_freeze_head(c, num_fixed);
   } else {  // every event, every time

@@ -758,18 +758,53 @@ class BackendEvaluator(_Evaluator):
     def reconstruct_solve(self, knots, num_fixed, sigma=1.0, measure=VARIANCE, freeze_head=False, **solver_kw):
         """reconstruct_refine(bind=True)'s bundle adjustment over the events bound to the open reconstruction as ONE native call
         (FR-CG, the back end's constants unless given; freeze_head: the batches under the fixed knots are voted once).  The
-        reconstruction is left at the refined knots' evaluation.  Returns (knots, report)."""
+        reconstruction is left at the refined knots' evaluation.  freeze_head="keep": under the frozen head as it stands
+        (reconstruct_advance_head), with num_fixed the head's and its knots unchanged.  Returns (knots, report)."""
         from . import solver
         k = np.array(_c(knots, np.float64).reshape(-1, 4), copy=True)
         if self._recon_K and k.shape[0] != self._recon_K:
-            raise ValueError("solve takes the %d knots of begin, got %d" % (self._recon_K, k.shape[0]))
+            raise ValueError("solve takes the %d knots of the reconstruction, got %d" % (self._recon_K, k.shape[0]))
         kw = dict(solver.BACKEND)
         kw.update(solver_kw)
         rep = _lib.SolveReport()
-        self._ck(self._L.cmx_backend_recon_solve(self._ctx, _dp(k), int(num_fixed), 1 if freeze_head else 0, float(sigma), int(measure),
+        if isinstance(freeze_head, str):
+            if freeze_head != "keep":
+                raise ValueError("freeze_head is False, True or 'keep'")
+            mode = _lib.RECON_KEEP_HEAD
+        else:
+            mode = 1 if freeze_head else 0
+        self._ck(self._L.cmx_backend_recon_solve(self._ctx, _dp(k), int(num_fixed), mode, float(sigma), int(measure),
                                                  float(kw["step_size"]), float(kw["tol"]), float(kw["epsabs_grad"]),
                                                  float(kw["tolfun"]), int(kw["max_iterations"]), C.byref(rep)))
         return k, {f: getattr(rep, f) for f, _ in rep._fields_}
+
+    # --- a binding that grows (cmx_backend_recon_extend / _bind_append_from / _advance_head / _release_head / _online_info)
+    def reconstruct_extend(self, knots_xyzw):
+        """reconstruct_restart that may lengthen the spline (at least as many knots as now) and keeps a frozen head, whose
+        knots must be unchanged; the binding stays."""
+        k = _c(knots_xyzw, np.float64).reshape(-1, 4)
+        self._ck(self._L.cmx_backend_recon_extend(self._ctx, k.shape[0], _dp(k)))
+        self._recon_K = k.shape[0]
+
+    def reconstruct_bind_append(self, store, first, count):
+        """Append events_[first, first+count) of an EventStore to the binding: afterwards it is what reconstruct_bind over all
+        ranges bound so far, concatenated, would hold.  Only this range is read from the store; a frozen head is kept."""
+        self._ck(self._L.cmx_backend_recon_bind_append_from(self._ctx, store._h, int(first), int(count)))
+
+    def reconstruct_advance_head(self, num_fixed):
+        """Move the freeze line forward to num_fixed knots: the newly frozen batches vote once, at the current knots, on top
+        of the base.  Without a frozen head: reconstruct_freeze_head."""
+        self._ck(self._L.cmx_backend_recon_advance_head(self._ctx, int(num_fixed)))
+
+    def reconstruct_release_head(self):
+        """Free the resident memory of the frozen batches' events; evaluations are unchanged."""
+        self._ck(self._L.cmx_backend_recon_release_head(self._ctx))
+
+    def reconstruct_online_info(self):
+        """{'released_batches', 'released_events', 'released_sampled', 'resident_sampled'}; all zero without a binding."""
+        v = [C.c_int64() for _ in range(4)]
+        self._ck(self._L.cmx_backend_recon_online_info(self._ctx, *[C.byref(a) for a in v]))
+        return dict(zip(("released_batches", "released_events", "released_sampled", "resident_sampled"), (a.value for a in v)))
 
     def reconstruct_solve_counts(self):
         """(evaluations, host waits inside them) of the last reconstruct_solve (cmx_diag_recon_solve_counts)."""

@@ -116,6 +116,51 @@ def refine_trajectory(be, traj, x, y, t, prm, store=None, bind=False, native=Fal
     return knots, rep
 
 
+def refine_trajectory_online(be, traj, x, y, t, prm, store, stride_s, free=8, log=None):
+    """refine_trajectory(native=True) the way an online host runs it: the recording is replayed in strides of stride_s seconds, and
+    per stride the spline grows (reconstruct_extend), the stride's events are appended to the binding (reconstruct_bind_append), the
+    tail is solved under the frozen head as it stands (reconstruct_solve(freeze_head="keep")), the freeze line moves up to `free`
+    knots behind the end (reconstruct_advance_head) and the settled events' memory is given back (reconstruct_release_head).  The cost
+    of a stride follows its events, the memory the active tail.  Returns (refined knots, report); the report carries
+    contrast_after, strides, iterations and resident_max, the largest number of sampled events resident after a release."""
+    i0, i1 = _support_range(traj, t)
+    K_all, order = traj.size(), traj.order
+    stride = max(1, int(round(stride_s * 1e9 / traj.dt_ns)))
+    knots = np.array(traj.knots, np.float64, copy=True)
+    rep = dict(strides=0, iterations=0, resident_max=0, events=i1 - i0)
+    K, done = min(K_all, order + free), i0
+    try:
+        while True:
+            hi = int(np.searchsorted(t, traj.t_beg_ns + (K - order + 1) * traj.dt_ns, side="left")) if K < K_all else i1
+            q = np.ascontiguousarray(knots[:K])
+            if rep["strides"] == 0:
+                be.reconstruct_begin(order, q, traj.t_beg_ns, traj.dt_ns, prm.event_batch_size, prm.backend_event_sample_rate)
+                be.reconstruct_bind(store, done, hi - done)
+                be.reconstruct_advance_head(order - 1)  # (the gauge: a head that freezes nothing yet)
+            else:
+                be.reconstruct_extend(q)
+                be.reconstruct_bind_append(store, done, hi - done)
+            nf = be.reconstruct_frozen_info()["num_fixed"]
+            knots[:K], r = be.reconstruct_solve(q, nf, sigma=prm.backend_blur_sigma, freeze_head="keep")
+            be.reconstruct_advance_head(max(nf, K - free))
+            be.reconstruct_release_head()
+            on = be.reconstruct_online_info()
+            rep["strides"] += 1
+            rep["iterations"] += r["iterations"]
+            rep["resident_max"] = max(rep["resident_max"], on["resident_sampled"])
+            if log:
+                log("  stride %d: %d knots (%d fixed), %d new events, %d iterations, contrast %.6g; %d sampled events resident, %d released" %
+                    (rep["strides"], K, nf, hi - done, r["iterations"], -r["final_cost"], on["resident_sampled"], on["released_sampled"]))
+            done = hi
+            if K == K_all:
+                break
+            K = min(K + stride, K_all)
+        rep["contrast_after"] = be.reconstruct_eval_bound(None, prm.backend_blur_sigma, want_grad=False)[0]
+    finally:
+        be.reconstruct_end()
+    return knots, rep
+
+
 def reconstruct_panorama(be, traj, x, y, t, prm, store=None, knots=None):
     """All events inside the support of the refined trajectory, re-warped along the WHOLE of it (any number of control poses)
     into one panorama: BackendEvaluator.reconstruct_* (cmx_backend_recon_*).  Leaves the evaluator's window and map untouched.
@@ -134,7 +179,7 @@ def reconstruct_panorama(be, traj, x, y, t, prm, store=None, knots=None):
 
 
 def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefix=None, reconstruct=False, refine_global=False,
-                 refine_bound=False, refine_native=False, freeze_head=None):
+                 refine_bound=False, refine_native=False, freeze_head=None, refine_online=None, online_free=8):
     """stream: synth.EventStream (or anything with x, y, t_ns, W, H, fx, fy, cx, cy, lut).  Returns a dict.
     display_prefix: write the final panorama with the last pose's FOV and the last packet's local-IWE pair there.
     reconstruct: after the last window, re-warp all events along the whole refined trajectory (res["recon"]; with
@@ -143,7 +188,9 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
     res["refine_report"]); the trajectory in res["traj"] stays the sliding windows' -- reconstruct then warps along the refined knots.
     refine_bound: that bundle adjustment binds the events once (reconstruct_refine(bind=True)).
     refine_native: it runs as one native call over the bound events (reconstruct_solve); freeze_head = N: with the first N control
-    poses fixed and the batches under them voted once."""
+    poses fixed and the batches under them voted once.
+    refine_online = STRIDE_S: after that, the recording replayed in strides of STRIDE_S seconds through a binding that grows
+    (refine_trajectory_online; res["online_knots"], res["online_report"]), with the last online_free control poses free."""
     prm = prm or Params()
     x, y, t = stream.x, stream.y, stream.t_ns
     n_total = len(t)
@@ -305,6 +352,23 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
             log("global refinement: %d events, %d control poses, %d iterations (%d f, %d df) in %.2f ms; contrast %.6g -> %.6g" %
                 (r["events"], traj.size(), r["iterations"], r["n_f"], r["n_df"], (time.perf_counter() - t0) * 1e3,
                  r["contrast_before"], r["contrast_after"]))
+    if refine_online and traj.size() >= traj.order:
+        t0 = time.perf_counter()
+        own = store is None
+        st = store
+        if own:  # (the online path reads its events from a device-resident store; indices are the stream's)
+            st = evaluator.EventStore(be.W, be.H, max(len(x), 1))
+            st.push(x, y, t)
+        try:
+            res["online_knots"], res["online_report"] = refine_trajectory_online(be, traj, x, y, t, prm, st, refine_online, online_free, log)
+        finally:
+            if own:
+                st.close()
+        if log:
+            r = res["online_report"]
+            log("online refinement: %d events in %d strides of %.3g s, last %d control poses free: %d iterations in %.2f ms; contrast %.6g; "
+                "at most %d sampled events resident" % (r["events"], r["strides"], refine_online, online_free, r["iterations"],
+                                                         (time.perf_counter() - t0) * 1e3, r["contrast_after"], r["resident_max"]))
     if reconstruct and traj.size() >= traj.order:
         t0 = time.perf_counter()
         _, n_rec = reconstruct_panorama(be, traj, x, y, t, prm, store, res.get("refined_knots"))
@@ -382,9 +446,15 @@ def main():
                     help="with --refine-global: the bundle adjustment as one native call over the bound events (cmx_backend_recon_solve)")
     ap.add_argument("--freeze-head", type=int, metavar="N", default=None,
                     help="with --refine-native: fix the first N control poses and vote the event batches under them once")
+    ap.add_argument("--refine-online", type=float, metavar="STRIDE_S", default=None,
+                    help="after the usual pipeline, replay the recording in strides of STRIDE_S seconds through a binding that grows: "
+                         "extend, append, solve under the kept head, advance and release per stride")
+    ap.add_argument("--online-free", type=int, metavar="N", default=8, help="with --refine-online: the last N control poses stay free")
     a = ap.parse_args()
     if a.freeze_head is not None and not a.refine_native:
         ap.error("--freeze-head needs --refine-native")
+    if a.refine_online is not None and (a.refine_online <= 0 or a.online_free < 1):
+        ap.error("--refine-online takes a stride > 0 and --online-free at least 1")
     stream = synth.event_stream(a.rate, a.seconds, 240, 180, 200.0, 200.0, 119.5, 89.5, omega_mean=(0.2, 1.8, 0.3),
                                 omega_amp=(1.0, 0.8, 1.0))
     prm = Params()
@@ -393,7 +463,7 @@ def main():
     t0 = time.perf_counter()
     res = run_pipeline(stream, prm, use_event_store=not a.host_events, log=print, display_prefix=a.display, reconstruct=a.reconstruct,
                        refine_global=a.refine_global or a.refine_native, refine_bound=a.refine_bound, refine_native=a.refine_native,
-                       freeze_head=a.freeze_head)
+                       freeze_head=a.freeze_head, refine_online=a.refine_online, online_free=a.online_free)
     wall = time.perf_counter() - t0
     m = evaluate_against_truth(stream, res)
     print("%.2f s of events (%d) processed in %.2f s wall" % (a.seconds, len(stream.x), wall))
@@ -408,6 +478,12 @@ def main():
         m2 = evaluate_against_truth(stream, res)
         print("global refinement: contrast %.6g -> %.6g; orientation error rms %.3f deg -> %.3f deg" %
               (r["contrast_before"], r["contrast_after"], m["ba_err_deg_rms"], m2["ba_err_deg_rms"]))
+    if "online_knots" in res:
+        r = res["online_report"]
+        res["traj"].knots = res["online_knots"]
+        m3 = evaluate_against_truth(stream, res)
+        print("online refinement: contrast %.6g; orientation error rms %.3f deg -> %.3f deg; at most %d sampled events resident of %d" %
+              (r["contrast_after"], m["ba_err_deg_rms"], m3["ba_err_deg_rms"], r["resident_max"], r["events"]))
     if "recon" in res:
         print("reconstruction along the whole trajectory: %.0f votes, %.0f%% of pixels touched" %
               (float(res["recon"].sum(dtype=np.float64)), 100.0 * float((res["recon"] > 0).mean())))

@@ -455,6 +455,59 @@ int cmx_backend_recon_bound_info(cmx_ctx *ctx, int64_t *n_events, int64_t *n_sam
 int cmx_backend_recon_freeze_head(cmx_ctx *ctx, int num_fixed);
 int cmx_backend_recon_frozen_info(cmx_ctx *ctx, int *num_fixed, int64_t *frozen_batches, int64_t *frozen_sampled);
 /* (cmx_backend_recon_solve is declared with the other solves, below cmx_solve_report) */
+/* A binding that grows: the recording gets longer, the spline with it, the freeze line moves forward and the settled events'
+ * memory is given back.  Per step of an online host:
+ *     recon_extend(K_new, knots)   recon_bind_append_from(new events)   recon_solve(CMX_RECON_KEEP_HEAD) | recon_eval_bound ...
+ *     recon_advance_head(num_fixed_new)   recon_release_head()
+ * All of them: a plain back-end context with a reconstruction begun (CMX_ERR_STATE on NULL, on a group handle, before begin), and
+ * complete validation before any device state changes -- a call that fails validation leaves the reconstruction as it was.
+ *   extend         restart that may lengthen the spline and keeps a frozen head.  K_new >= K (CMX_ERR_INVALID_ARG below, and above
+ *                  begin's limit); order, start_ns, dt_ns, batch size, sample rate and the deterministic setting stay those of begin.
+ *                  Replaces the knots, zeroes the plane, both counters and the gradient state, closes an open gradient pass, keeps
+ *                  the binding.  With a frozen head the first num_fixed quaternions must be bytewise those of the freeze
+ *                  (CMX_ERR_INVALID_ARG otherwise).  With K_new == K and no frozen head it is restart.
+ *   bind_append_from  needs a binding (CMX_ERR_STATE).  Afterwards the binding is exactly what bind_from over the concatenation of
+ *                  all ranges bound so far would hold: batch cuts, batch pose times, the sampled events in packed order, bound_info's
+ *                  counts.  Validation and status codes of bind_from, plus: the first new event may not be earlier than the last
+ *                  bound one (CMX_ERR_TIME_ORDER); CMX_ERR_SPLINE_RANGE is judged against the K of this moment, so an online
+ *                  caller extends first.  Reads only [first, first + count) of the store: events bound earlier may have been dropped
+ *                  from it.  The last batch of a binding may be open -- fewer than event_batch_size events, or a lone trailing event
+ *                  no batch has opened -- and an append cuts it again: its pose time moves with its new last event, the sampling
+ *                  stride continues from its start.  The binding keeps the raw events of that open tail (at most
+ *                  event_batch_size of them) for this.  Work is proportional to count + event_batch_size; buffers grow
+ *                  geometrically; a failed allocation leaves the binding as it was.  A frozen head is kept; when the batch to be cut
+ *                  again is itself frozen: CMX_ERR_STATE, nothing changes.  (New batches behind a head that had frozen EVERY batch
+ *                  are evaluated as active ones until advance_head looks at them: exact, but the deterministic gradient then agrees
+ *                  with a fresh freeze's to summation order only.)  The limit of 2^30 sampled events applies to the RESIDENT ones
+ *                  (see release_head).  count == 0 is valid and changes nothing but closing an open gradient pass.
+ *   advance_head   needs a binding (CMX_ERR_STATE) and num_fixed <= num_fixed_new < K (CMX_ERR_INVALID_ARG; going back is
+ *                  freeze_head's job); without a frozen head it is freeze_head(num_fixed_new).  At the knots the reconstruction
+ *                  holds, the batches the prefix rule newly names are voted ONCE into the existing base, on top of what is there,
+ *                  and their voting count is added to the base's; the base is neither cleared nor voted again.  It may freeze nothing
+ *                  new.  Deterministic mode: base, counters and every later evaluation are bitwise those of a fresh bind_from over
+ *                  everything + freeze_head(num_fixed_new) at the same knots; default mode: equal to summation order.
+ *   release_head   needs a binding (CMX_ERR_STATE).  Frees the resident memory of the frozen batches' events (their packed events,
+ *                  batch times and pose-table rows).  The released entries are dead space until there is more of it than live entries, or
+ *                  an append runs out of room; then the active tail moves into buffers of twice its size and the old ones are freed,
+ *                  so the capacity stays within a small constant factor of the largest active tail, whatever the recording's length.
+ *                  Evaluations are unchanged -- plane, counters, contrast, and the gradient bitwise in deterministic mode;
+ *                  bound_info keeps reporting the totals since the bind.  Nothing to release (no frozen head, nothing newly
+ *                  frozen) is valid.  Once events are released their votes live in the base alone, so restart, eval_from with knots,
+ *                  freeze_head (any argument) and recon_solve with freeze_head 0 or 1 return CMX_ERR_STATE and change nothing;
+ *                  begin, end, bind_from and unbind work and drop everything.
+ *   online_info    any pointer may be NULL; all zero without a binding.  Batches, events and sampled events released so far, and the
+ *                  sampled events resident now.
+ *   solve          freeze_head == CMX_RECON_KEEP_HEAD: the solve runs under the frozen head as it stands.  CMX_ERR_STATE without
+ *                  one; CMX_ERR_INVALID_ARG unless num_fixed equals the head's and the start knots carry the head's bytes.  In
+ *                  deterministic mode it returns the knots of a solve with freeze_head = 1 over a fresh binding of the same events
+ *                  from the same start, byte for byte. */
+#define CMX_RECON_KEEP_HEAD 2
+int cmx_backend_recon_extend(cmx_ctx *ctx, int K_new, const double *knots_xyzw /* K_new x 4 */);
+int cmx_backend_recon_bind_append_from(cmx_ctx *ctx, const cmx_events *ev, int64_t first, int64_t count);
+int cmx_backend_recon_advance_head(cmx_ctx *ctx, int num_fixed_new);
+int cmx_backend_recon_release_head(cmx_ctx *ctx);
+int cmx_backend_recon_online_info(cmx_ctx *ctx, int64_t *released_batches, int64_t *released_events, int64_t *released_sampled,
+                                  int64_t *resident_sampled);
 
 /* ------------------------------------------------------------------ split-phase (multi-GPU) ------------
  * The IWE is a sum over events, the contrast a non-linear function of the SUMMED image, so ranks exchange
@@ -675,7 +728,8 @@ int cmx_get_stats(cmx_ctx *ctx, double *stats, int n_stats); /* writes min(n_sta
  *     cmx_set_cu_mask moved to cmax_hip_diag.h;
  *     added without a bump (no signature or buffer layout changed): the seven cmx_backend_recon_* entry points, then
  *     recon_restart / _contrast / _grad_add[_aos|_from] / _grad_get / _eval_from, then recon_bind_from / _unbind / _eval_bound /
- *     _bound_info, then recon_freeze_head / _frozen_info / _solve) */
+ *     _bound_info, then recon_freeze_head / _frozen_info / _solve, then recon_extend / _bind_append_from / _advance_head /
+ *     _release_head / _online_info and the value CMX_RECON_KEEP_HEAD of recon_solve's freeze_head) */
 #define CMX_ABI_VERSION 6
 int cmx_abi_version(void);
 int cmx_timing_enable(cmx_ctx *ctx, int on);
