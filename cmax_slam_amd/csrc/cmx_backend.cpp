@@ -513,6 +513,7 @@ int cmx_backend_get_plane(cmx_ctx *c, int which, float *host) {
   if (rc) return rc;
   const size_t np = (size_t)c->Wp * c->Hp;
   const float *src = nullptr;
+  bool finalize_ran = false;
   if (which == CMX_PLANE_IL_OLD) src = c->d_accum;
   else if (which == CMX_PLANE_IL_NEW) src = c->d_accum + np;
   else if (which == CMX_PLANE_IWE || (which >= CMX_PLANE_DERIV0 && which < CMX_PLANE_DERIV0 + c->last_P)) {
@@ -523,12 +524,13 @@ int cmx_backend_get_plane(cmx_ctx *c, int which, float *host) {
     if (rc) return rc;
     rc = run_image_and_finalize(c, P, c->d_scratch, P ? c->d_scratch + np : nullptr);
     if (rc) return rc;
+    finalize_ran = true;
     src = (which == CMX_PLANE_IWE) ? c->d_scratch : c->d_scratch + (size_t)(1 + which - CMX_PLANE_DERIV0) * np;
   } else {
     return fail(c, CMX_ERR_INVALID_ARG, "plane %d not available", which);
   }
   HIP_TRY(c, hipMemcpyAsync(host, src, np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  return sync_and_collect(c);
+  return sync_and_collect(c, false, finalize_ran);
 }
 
 // One context's rows, computed into SCRATCH tables from a COPY of the spline description: neither the live pose table (the tile

@@ -23,7 +23,12 @@ constexpr int kAhead = 2;        // slots kept queued ahead of the one whose res
 constexpr int kRingSlots = 8;    // ring of result blocks (2 per slot); > kAhead + 1
 constexpr int kBlock = 4096;     // doubles per result block (the layout of the one-evaluation result buffer)
 
-struct SlotTickets { unsigned long long a = 0, g = 0; int nout_a = 0, nout_g = 0; bool gated = false, self_gating = false, fused = false; };
+struct SlotTickets {
+  unsigned long long a = 0, g = 0;
+  int nout_a = 0, nout_g = 0;
+  bool gated = false, self_gating = false, fused = false;
+  unsigned bin_id = 0;  // binning under which the slot's splat was queued (votes_bin_id right after its fe_accumulate)
+};
 
 int ensure_chain_buffers(cmx_ctx *c) {
   if (c->d_chain) return CMX_OK;
@@ -220,6 +225,7 @@ int chain_run_frontend(cmx_ctx *c, FrcgSM &hs, bool *completed) {
       rc = self_gating_ok(c) ? queue_slot_self_gating(c, queued, &tick[queued % kRingSlots]) : queue_slot(c, queued, &tick[queued % kRingSlots]);
       c->chain_first = false;
       if (rc) break;
+      tick[queued % kRingSlots].bin_id = c->votes_bin_id;
       all_self_gating = all_self_gating && tick[queued % kRingSlots].self_gating;
       if (!tick[queued % kRingSlots].gated) { unsupported = true; }  // no gated gradient pass in this configuration
       queued++;
@@ -326,6 +332,13 @@ int chain_run_frontend(cmx_ctx *c, FrcgSM &hs, bool *completed) {
     }
     c->accum_clean = false;
     c->alt_clean = true;
+    // ... and the sort those votes were made under is the one slot consumed-1 was queued with.  The sort kernels of a skipped slot
+    // do not read the stop word: if one of them sorted again, the chunk table is no longer the one the votes belong to, and no
+    // table's tile passes are known to cover them (0: the next fused evaluation clears the partner with the memset)
+    unsigned votes_id = tick[(consumed - 1) % kRingSlots].bin_id;
+    for (int s = consumed; s < queued; s++)
+      if (tick[s % kRingSlots].bin_id != votes_id) votes_id = 0u;
+    c->votes_bin_id = votes_id;
     c->chain_seq += (unsigned)consumed;
     c->chain_warm = true;
   } else {

@@ -440,7 +440,7 @@ int run_adjoint(cmx_ctx *c, int P, int phase = 0);  // phase 3: image pass + cos
 int finish_cost_only_speculative(cmx_ctx *c, int P);  // phase 3 (+ the gated pass when a hint is set), then the wait
 int collect_gated(cmx_ctx *c, int P, double *contrast, double *grad, bool *served);  // a df served by the pass already queued
 bool speculative_jt_ok(const cmx_ctx *c);
-int sync_and_collect(cmx_ctx *c, bool ends_in_finalize = false);
+int sync_and_collect(cmx_ctx *c, bool ends_in_finalize = false, bool finalize_ran = false);
 bool can_reuse(const cmx_ctx *c, const double *x, int n, bool want_grad);
 bool spin_for_ticket(const double *h_block, unsigned long long want, int nout, int budget_us = -1);
 int fe_accumulate(cmx_ctx *c, const double omega[3], int nplanes, bool allow_fuse = false, bool allow_full = false);  // cmx_frontend.cpp

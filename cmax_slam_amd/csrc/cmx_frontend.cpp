@@ -391,7 +391,8 @@ int cmx_frontend_get_iwe(cmx_ctx *c, const double omega[3], int blur, float *iwe
   rc = ensure(c, c->d_scratch, c->scratch_cap, 7 * np);
   if (rc) return rc;
   const float *src = c->d_accum;
-  if (blur && c->radius > 0) {
+  const bool blurred = blur && c->radius > 0;
+  if (blurred) {
     rc = run_image_and_finalize(c, nplanes - 1, c->d_scratch, c->d_scratch + np);
     if (rc) return rc;
     src = c->d_scratch;
@@ -402,7 +403,7 @@ int cmx_frontend_get_iwe(cmx_ctx *c, const double omega[3], int blur, float *iwe
     launch_interleave3(src + np, inter, (int)np, c->stream);
     HIP_TRY(c, hipMemcpyAsync(deriv, inter, 3 * np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   }
-  return sync_and_collect(c);
+  return sync_and_collect(c, false, /*finalize_ran=*/blurred);
 }
 
 

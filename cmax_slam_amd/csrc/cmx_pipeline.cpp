@@ -771,11 +771,13 @@ static int wait_hostfin(cmx_ctx *c, bool *spun) {
   return CMX_OK;
 }
 
-int sync_and_collect(cmx_ctx *c, bool ends_in_finalize) {
+int sync_and_collect(cmx_ctx *c, bool ends_in_finalize, bool finalize_ran) {
   // ends_in_finalize: the last thing queued on the stream is an evaluation's finalize kernel.  Wait for it through
   // its completion ticket in mapped host memory (a few microseconds earlier than the runtime reports the stream idle);
   // anything slower than the spin budget, and every caller that queued copies or other kernels after the finalize,
   // takes the ordinary stream synchronisation.
+  // finalize_ran: a finalize of this call ran, with copies or other kernels queued behind it (a blurred image read-back): once the
+  // stream is idle the result block is this call's, fallback word included.
   bool done = false;
   const bool hostfin = ends_in_finalize && c->ticket_issued && c->hostfin_ticket == c->ticket_issued;
   if (hostfin) {
@@ -809,8 +811,15 @@ int sync_and_collect(cmx_ctx *c, bool ends_in_finalize) {
     c->nchunks_exact = true;
   }
   if (c->fallback_pending && c->n_packed > 0) {
-    c->last_fallback_frac = fallback_count(c->h_result[kFallbackSlot]) / (double)c->n_packed;
-    c->last_fallback_flags = fallback_flags(c->h_result[kFallbackSlot]);
+    if (ends_in_finalize || finalize_ran) {
+      c->last_fallback_frac = fallback_count(c->h_result[kFallbackSlot]) / (double)c->n_packed;
+      c->last_fallback_flags = fallback_flags(c->h_result[kFallbackSlot]);
+    } else {
+      // unblurred image read-backs and renders: no finalize of this call has reported the splat's fallback word to the result
+      // block, which still holds an earlier evaluation's.  Where these votes went is not known: the next fused evaluation must
+      // not take the partner as covered by its tiles' passes (it clears it with the memset)
+      c->last_fallback_flags = kFuseUnsafe;
+    }
   }
   c->fallback_pending = false;
   // timing spans are resolved lazily (cmx_timing_get) so that timed evaluations wait exactly like untimed ones
@@ -984,8 +993,12 @@ static int eval_many(cmx_ctx *c, int kind, int m, const double *xs, double *cont
     contrasts[i] = r[0];
     if (grads) for (int k = 0; k < n; k++) grads[(size_t)i * n + k] = r[2 + k];
   }
-  if (m > 0 && c->n_packed > 0 && c->last_used_lds)
-    c->last_fallback_frac = fallback_count(c->h_many[(size_t)(m - 1) * kBlock + kFallbackSlot]) / (double)c->n_packed;
+  if (m > 0 && c->n_packed > 0 && c->last_used_lds) {
+    // the planes hold the votes of the list's LAST point: count and reach flags of that point's block, as sync_and_collect takes them
+    const double slot = c->h_many[(size_t)(m - 1) * kBlock + kFallbackSlot];
+    c->last_fallback_frac = fallback_count(slot) / (double)c->n_packed;
+    c->last_fallback_flags = fallback_flags(slot);
+  }
   c->fallback_pending = false;
   return CMX_OK;
 }
