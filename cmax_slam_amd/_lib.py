@@ -22,6 +22,8 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
 OPT_GRAD_MODE, OPT_SPLAT_MODE, OPT_REUSE_IMAGE, OPT_SPIN_WAIT, OPT_DETERMINISTIC, OPT_TAIL_FINALIZE = 1, 2, 3, 4, 5, 6
 OPT_COMPOSITE_IMAGE, OPT_FOLD_BATCH, OPT_GATED_DF, OPT_CHAIN_SOLVE, OPT_FUSED_IMAGE = 8, 9, 10, 11, 12
 DIAG_FORCE_CROSS_DEVICE, DIAG_RECON_SLICE_EVENTS = 1, 2  # cmx_diag_set keys (include/cmax_hip_diag.h)
+WARP_F64, WARP_F32 = 0, 1  # cmx_backend_recon_warp*: output format
+WARP_SAMPLED, WARP_INSIDE = 1, 2  # ... and the flag bits
 PLANE_IL_OLD, PLANE_IL_NEW, PLANE_IWE, PLANE_DERIV0 = 0, 1, 2, 16
 T_SPLAT, T_IMAGE, T_POSE, T_GATHER, T_ZERO, T_COMM, T_FINAL, T_BATCH, T_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8
 T_NAMES = ("splat", "image", "pose", "gather", "zero", "comm", "final", "batch")
@@ -124,6 +126,10 @@ SYMBOLS = {
     "cmx_backend_recon_add": (C.c_int, [ctx_p, C.c_int64, c_u16p, c_u16p, c_i64p]),
     "cmx_backend_recon_add_aos": (C.c_int, [ctx_p, C.c_int64, C.c_void_p, C.POINTER(AosLayout)]),
     "cmx_backend_recon_add_from": (C.c_int, [ctx_p, C.c_void_p, C.c_int64, C.c_int64]),
+    "cmx_backend_recon_warp": (C.c_int, [ctx_p, C.c_int64, c_u16p, c_u16p, c_i64p, C.c_int, C.c_void_p, C.c_void_p]),
+    "cmx_backend_recon_warp_aos": (C.c_int, [ctx_p, C.c_int64, C.c_void_p, C.POINTER(AosLayout), C.c_int, C.c_void_p, C.c_void_p]),
+    "cmx_backend_recon_warp_from": (C.c_int, [ctx_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "cmx_backend_recon_warp_from_device": (C.c_int, [ctx_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "cmx_backend_recon_get": (C.c_int, [ctx_p, c_fp, c_i64p, c_i64p]),
     "cmx_backend_recon_render": (C.c_int, [ctx_p, C.c_double, c_dp, C.POINTER(C.c_uint8)]),
     "cmx_backend_recon_end": (C.c_int, [ctx_p]),

@@ -451,6 +451,20 @@ int recon_run(int per_batch);
 void launch_recon_delta(const Quat *knots, int K, double *delta, hipStream_t s);
 void launch_recon_votes(const ReconArgs &a, hipStream_t s);
 void launch_recon_fixed_to_float(const unsigned long long *fixed, float *plane, size_t n, hipStream_t s);  // non-destructive
+// per-event export (cmx_backend_recon_warp*): the panorama coordinate and the flags of EVERY raw event of a slice, sampled or not.
+// ev as for the votes with xy = the slice's raw events, n = their count (a lone trailing event included), per_batch = B,
+// run = recon_run(B) raw events per workgroup; plane / fixed / n_inside are not used.
+struct ReconWarpArgs {
+  ReconArgs ev;
+  int rate;                  // SAMPLED: (i - b * B) % rate == 0
+  int lone;                  // 1: the slice's last event is the call's lone trailing one -- no batch holds it
+  long long lone_t;          // ... and its own time, the time of its pose
+  void *xy_out;              // [n] pairs (px, py): double2, or float2 with f32
+  unsigned char *flags_out;  // [n] CMX_WARP_SAMPLED | CMX_WARP_INSIDE, or null
+  int f32;
+  int vec;                   // xy_out is aligned for one 16- / 8-byte pair store per lane
+};
+void launch_recon_warp(const ReconWarpArgs &g, hipStream_t s);
 // bound events (cmx_backend_recon_bind_from / _eval_bound): the batch poses of a spline of any knot count as a table in global
 // memory (recon_pose<N>, one thread per batch: a.batch_t, a.nb) -- what the tile sort (launch_count_sort with poseR = the table)
 // and the vote kernel below read -- and the vote pass over the tile-sorted events: one workgroup per chunk, votes into a

@@ -128,8 +128,88 @@ void launch_recon_votes(const ReconArgs &a, hipStream_t s) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------- per-event export
+// recon_warp     cmx_backend_recon_warp*: where every event of a slice lands.  The run structure of recon_votes over the slice's RAW
+//                events (run = recon_run(B)): the first lanes evaluate the run's batch poses into LDS -- and, in the workgroup that
+//                holds it, the pose of the call's lone trailing event at its own time into a slot of its own -- one barrier, then all
+//                lanes walk the run, one event per lane and step.  load_bearing + be_warp_math<0> is the vote kernel's own
+//                arithmetic, which hands out (px, py) beside the vote cell and the weights it takes from them: the same bits.
+//                No atomics: per event one 16-byte (fp64) or 8-byte (fp32) pair store and one flag byte.  Flag bytes packed four
+//                to a store were tried both ways -- a lane owning four consecutive events, and one event per lane with the
+//                neighbours' bytes fetched by shuffles -- and neither beat the byte store (profiles/recon_warp_timing.txt).
+typedef double warp_pair_f64 __attribute__((ext_vector_type(2)));  // (vector types: the struct double2 is stored member by member)
+typedef float warp_pair_f32 __attribute__((ext_vector_type(2)));
+template <bool F32>
+__device__ __forceinline__ void warp_store_pair(void *out, size_t i, double px, double py, bool vec) {
+  if (F32) {
+    float *o = static_cast<float *>(out) + 2 * i;
+    if (vec) *reinterpret_cast<warp_pair_f32 *>(o) = warp_pair_f32{(float)px, (float)py};
+    else { o[0] = (float)px; o[1] = (float)py; }
+  } else {
+    double *o = static_cast<double *>(out) + 2 * i;
+    if (vec) *reinterpret_cast<warp_pair_f64 *>(o) = warp_pair_f64{px, py};
+    else { o[0] = px; o[1] = py; }
+  }
+}
+
+template <int N, bool F32>
+__global__ __launch_bounds__(kReconThreads) void recon_warp_kernel(const ReconWarpArgs g) {
+  __shared__ double sh_R[(kReconMaxRun + 3) * 9];
+  const ReconArgs &a = g.ev;
+  const int tid = threadIdx.x;
+  const int e0 = blockIdx.x * a.run;  // (the grid covers [0, n): e0 < n)
+  const int e1 = (a.n - e0 > a.run) ? e0 + a.run : a.n;
+  const int nbe = a.n - g.lone;       // events of the slice that batches hold
+  const int eb1 = e1 < nbe ? e1 : nbe;
+  const int b0 = e0 / a.B;
+  int nbw = eb1 > e0 ? (eb1 - 1) / a.B - b0 + 1 : 0;
+  if (nbw > kReconMaxRun + 2) nbw = kReconMaxRun + 2;  // (cannot happen with run = recon_run(B))
+  const bool has_lone = g.lone && e1 == a.n;           // this workgroup holds the lone trailing event: pose slot nbw
+  for (int j = tid; j < nbw + (has_lone ? 1 : 0); j += kReconThreads) {
+    long long t = g.lone_t;
+    if (j < nbw) t = a.batch_t[b0 + j < a.nb ? b0 + j : a.nb - 1];
+    recon_pose<N>(a, t, sh_R + 9 * j);
+  }
+  __syncthreads();
+  const bool vec = g.vec != 0;
+  int cur = -1;
+  double R[9];
+  for (int i = e0 + tid; i < e1; i += kReconThreads) {
+    const bool is_lone = i >= nbe;
+    const int b = i / a.B;
+    int j = b - b0;
+    j = is_lone ? nbw : (j < nbw ? j : nbw - 1);
+    if (j != cur) {
+#pragma unroll
+      for (int c = 0; c < 9; c++) R[c] = sh_R[9 * j + c];
+      cur = j;
+    }
+    const uint32_t e = a.xy[i] & 0x7fffffffu;
+    const int ex = e & 0xffff, ey = e >> 16;
+    double v0, v1, v2, pxy[2];
+    load_bearing(a.cam, ex, ey, v0, v1, v2);
+    const BeWarp w = be_warp_math<0, true>(a.cam, e, b, v0, v1, v2, R, pxy);
+    warp_store_pair<F32>(g.xy_out, (size_t)i, pxy[0], pxy[1], vec);
+    if (g.flags_out)
+      g.flags_out[i] = (unsigned char)(((!is_lone && (i - b * a.B) % g.rate == 0) ? CMX_WARP_SAMPLED : 0) | (w.ok ? CMX_WARP_INSIDE : 0));
+  }
+}
+
+void launch_recon_warp(const ReconWarpArgs &g, hipStream_t s) {
+  const ReconArgs &a = g.ev;
+  if (a.n <= 0) return;
+  const dim3 gr((unsigned)(((long long)a.n + a.run - 1) / a.run)), b(kReconThreads);  // (a.n <= 2^30 + 1: cmx_reconstruct.cpp)
+  if (a.order == 2) {
+    if (g.f32) hipLaunchKernelGGL((recon_warp_kernel<2, true>), gr, b, 0, s, g);
+    else hipLaunchKernelGGL((recon_warp_kernel<2, false>), gr, b, 0, s, g);
+  } else {
+    if (g.f32) hipLaunchKernelGGL((recon_warp_kernel<4, true>), gr, b, 0, s, g);
+    else hipLaunchKernelGGL((recon_warp_kernel<4, false>), gr, b, 0, s, g);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------- bound events
-// recon_pose_table       the batch poses of an evaluation as a table in global memory: recon_pose<N> once per batch, the value the
+// recon_pose_table      the batch poses of an evaluation as a table in global memory: recon_pose<N> once per batch, the value the
 //                        votes kernel above forms in LDS, bit for bit (72 B per batch)
 // recon_votes_lds        the vote pass over events sorted by the destination tile of their vote (launch_count_sort /
 //                        launch_build_chunks with poseR = the table): be_splat_lds_kernel's structure with ONE plane and the

@@ -39,6 +39,15 @@ struct ReconSlot {
   bool busy = false;
 };
 
+// Output staging of the per-event export (cmx_backend_recon_warp*, host output): the kernel of slice k writes into d_*, a copy on the
+// download stream moves it into pinned h_*, and the host pool copies it into the caller's arrays while slice k+1 runs.
+struct ReconWarpSlot {
+  void *d_xy = nullptr, *h_xy = nullptr;
+  unsigned char *d_fl = nullptr, *h_fl = nullptr;
+  size_t cap = 0;                            // events (16 bytes of coordinates each, the wider format)
+  hipEvent_t kdone = nullptr, down = nullptr;  // kernel complete (context stream) / download complete (download stream)
+};
+
 // Events bound to the reconstruction (cmx_backend_recon_bind_from): the sampled events of the range in time order, their batch
 // times, and what the tile-sorted vote pass of cmx_backend_recon_eval_bound needs -- all of it the reconstruction's own, a TileSort
 // beside the context's (cmx_ctx::sort, bin_valid, ...), which is not used: the window's sort survives a whole-trajectory evaluation.
@@ -141,6 +150,8 @@ struct ReconState {
   int64_t n_sampled = 0;
   hipStream_t copy_stream = nullptr;      // uploads of slice i+1 beside the vote kernel of slice i
   ReconSlot slot[2];
+  hipStream_t down_stream = nullptr;      // per-event export: downloads of slice i beside the kernel of slice i+1 (created at first use)
+  ReconWarpSlot wslot[2];
   // ---- contrast and gradient (all of it the reconstruction's own: the context's blur state and image buffers are not touched)
   double sigma_built = -1.0;              // sigma the taps / G^T 1 factors below were built for (-1: none)
   int radius = 0;
@@ -198,6 +209,15 @@ void recon_release(cmx_ctx *c) {
     (void)hipFree(s.d_bt);
     if (s.up) (void)hipEventDestroy(s.up);
     if (s.done) (void)hipEventDestroy(s.done);
+  }
+  if (r->down_stream) { (void)hipStreamSynchronize(r->down_stream); (void)hipStreamDestroy(r->down_stream); }
+  for (ReconWarpSlot &s : r->wslot) {
+    if (s.h_xy) (void)hipHostFree(s.h_xy);
+    if (s.h_fl) (void)hipHostFree(s.h_fl);
+    (void)hipFree(s.d_xy);
+    (void)hipFree(s.d_fl);
+    if (s.kdone) (void)hipEventDestroy(s.kdone);
+    if (s.down) (void)hipEventDestroy(s.down);
   }
   void *dev[] = {r->d_knots, r->d_delta, r->d_plane, r->d_fixed, r->d_inside, r->d_err, r->d_cx, r->d_cy, r->d_tflags, r->d_tile_list,
                  r->d_tile_count, r->d_partials, r->d_cm, r->d_jt, r->d_gsum, r->d_voted, r->d_rows, r->d_row_win, r->d_app_xy, r->d_app_t};
@@ -545,6 +565,209 @@ int cmx_backend_recon_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, i
 }
 int cmx_backend_recon_grad_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
   return recon_add_range(c, true, e, first, count);
+}
+
+// ---- per-event export (cmx_backend_recon_warp*): where every event handed in lands under the knots the reconstruction
+// holds now.  The batch plan, the batch times, the slices and the validation of add*; ALL events of a slice reach the kernel (the
+// host paths pack at rate 1, the store is read in place), the true rate only decides the SAMPLED bit.  Nothing of the reconstruction
+// but the knots is read and nothing of it is written: no recon_pass_enter, no counter, no plane.
+static int warp_slot_ensure(cmx_ctx *c, ReconState *r, ReconWarpSlot &s, size_t n) {
+  if (!r->down_stream) HIP_TRY(c, hipStreamCreateWithFlags(&r->down_stream, hipStreamNonBlocking));
+  if (!s.kdone) HIP_TRY(c, hipEventCreateWithFlags(&s.kdone, hipEventDisableTiming));
+  if (!s.down) HIP_TRY(c, hipEventCreateWithFlags(&s.down, hipEventDisableTiming));
+  if (n <= s.cap) return CMX_OK;
+  if (s.h_xy) HIP_TRY(c, hipHostFree(s.h_xy));
+  if (s.h_fl) HIP_TRY(c, hipHostFree(s.h_fl));
+  (void)hipFree(s.d_xy);
+  (void)hipFree(s.d_fl);
+  s.h_xy = s.d_xy = nullptr; s.h_fl = s.d_fl = nullptr; s.cap = 0;
+  HIP_TRY(c, hipHostMalloc(&s.h_xy, n * 2 * sizeof(double), hipHostMallocDefault));
+  HIP_TRY(c, hipHostMalloc((void **)&s.h_fl, n, hipHostMallocDefault));
+  HIP_TRY(c, hipMalloc(&s.d_xy, n * 2 * sizeof(double)));
+  HIP_TRY(c, hipMalloc((void **)&s.d_fl, n));
+  s.cap = n;
+  return CMX_OK;
+}
+
+static int recon_warp_source(cmx_ctx *c, const EventSource &src, int format, void *xy_out, unsigned char *flags_out, bool dev_out) {
+  ReconState *r = c->recon;
+  const bool store = src.on_device();
+  const int64_t n = src.n;
+  int rc = CMX_OK;
+  if (store) {
+    if (n < 0 || n > kMaxEvents) return fail(c, CMX_ERR_INVALID_ARG, "bad event count %lld", (long long)n);
+  } else {
+    rc = check_events(c, src);
+    if (rc) return rc;
+  }
+  if (n > 0 && !xy_out) return fail(c, CMX_ERR_INVALID_ARG, "null coordinate output");
+  if (n == 0) return CMX_OK;
+  BatchPlan p;
+  int slice_batches = 1;
+  rc = recon_plan(c, r, n, &p, &slice_batches);
+  if (rc) return rc;
+  const int B = r->B;
+  const bool lone = (int64_t)p.nb * B < n;  // the trailing event no batch holds (n = nb B + 1)
+  const long long lone_t = lone ? (long long)src.view([&](const auto &v) { return v.T(n - 1); }) : 0;  // (store: its host mirror)
+  ReconSlot &s0 = r->slot[0];
+  auto slice_times = [&](int b_lo, const Slice &sl, bool clear_err) {
+    return queue_batch_times(c, src.d_t + sl.ev_first, sl.ev_n, B, sl.b_hi - b_lo, r->sup, s0.d_bt, r->d_err, clear_err);
+  };
+  if (store && p.nb > 0) {
+    rc = slot_ensure(c, s0, 0, (size_t)(p.nb < slice_batches ? p.nb : slice_batches), false);
+    if (rc) return rc;
+    for (int b_lo = 0; b_lo < p.nb && !rc; b_lo += slice_batches) rc = slice_times(b_lo, slice_at(p, n, b_lo, slice_batches), b_lo == 0);
+    if (rc) return rc;
+    HIP_TRY(c, hipGetLastError());
+    BatchTimeError bad;
+    rc = read_batch_errors(c, r->d_err, &bad);
+    if (rc) return rc;
+    if (bad.kind) return fail_batch_time(c, bad, r->sup, /*with_event=*/false);
+  } else if (p.nb > 0) {
+    const BatchTimeError bad = src.view([&](const auto &v) { return batch_times(v, n, B, 0, p.nb, &r->sup, [](int64_t, long long) {}); });
+    if (bad.kind) return fail_batch_time(c, bad, r->sup);
+  }
+  if (lone) {  // its own time is its pose time: inside the spline like a batch time
+    const long long st = lone_t - r->sup.start_ns;
+    if (st < 0 || st / r->sup.dt_ns + r->sup.order > r->sup.K) return fail_batch_time(c, BatchTimeError{CMX_ERR_SPLINE_RANGE, lone_t}, r->sup);
+  }
+  // From here on only a runtime error (CMX_ERR_HIP) can end the call.
+  const bool f32 = format == CMX_WARP_F32;
+  const size_t pair = f32 ? 2 * sizeof(float) : 2 * sizeof(double);
+  ReconWarpArgs g{};
+  g.ev = recon_args(c, r);
+  g.ev.per_batch = B; g.ev.stride = 0;
+  g.ev.run = recon_run(B);
+  g.rate = r->rate;
+  g.lone_t = lone_t;
+  g.f32 = f32 ? 1 : 0;
+  struct Pending { ReconWarpSlot *o = nullptr; int64_t first = 0, count = 0; } pend;
+  auto finish = [&](Pending &q) -> int {  // the download of a slice is complete: into the caller's arrays
+    if (!q.o) return CMX_OK;
+    HIP_TRY(c, hipEventSynchronize(q.o->down));
+    const char *hx = static_cast<const char *>(q.o->h_xy);
+    const unsigned char *hf = q.o->h_fl;
+    char *ox = static_cast<char *>(xy_out) + (size_t)q.first * pair;
+    unsigned char *of = flags_out ? flags_out + q.first : nullptr;
+    parallel_ranges(q.count, [=](int64_t a0, int64_t a1) {
+      memcpy(ox + (size_t)a0 * pair, hx + (size_t)a0 * pair, (size_t)(a1 - a0) * pair);
+      if (of) memcpy(of + a0, hf + a0, (size_t)(a1 - a0));
+    });
+    q.o = nullptr;
+    return CMX_OK;
+  };
+  auto slices = [&]() -> int {
+    const bool one_slice = p.nb <= slice_batches;  // (store: its batch times are those the validation pass has just written)
+    int k = 0;
+    for (int b_lo = 0; b_lo < p.nb || k == 0; b_lo += slice_batches, k++) {
+      Slice sl;
+      if (p.nb > 0) sl = slice_at(p, n, b_lo, slice_batches);
+      else sl.ev_n = n;  // (n == 1: the lone event alone)
+      const int b_hi = sl.b_hi, nbs = b_hi - b_lo;
+      const int64_t ev_off = sl.ev_first, ev_n = sl.ev_n;
+      const bool with_lone = lone && b_hi == p.nb;
+      if (store) {
+        if (!one_slice) {
+          rc = slice_times(b_lo, sl, false);
+          if (rc) return rc;
+        }
+        g.ev.xy = src.d_xy + ev_off;
+        g.ev.batch_t = s0.d_bt;
+      } else {
+        ReconSlot &s = r->slot[k & 1];
+        if (s.busy) { HIP_TRY(c, hipEventSynchronize(s.done)); s.busy = false; }  // its previous slice has been read
+        rc = slot_ensure(c, s, (size_t)ev_n, (size_t)nbs, true);
+        if (rc) return rc;
+        uint32_t *xy = s.h_xy;
+        long long *bt = s.h_bt;
+        src.view([&](const auto &v) {  // (validated above: neither pass finds anything)
+          if (nbs > 0) batch_times(v, n, B, b_lo, b_hi, nullptr, [&](int64_t b, long long tb) { bt[b - b_lo] = tb; });
+          const auto vs = v.from(ev_off);
+          unsigned outside = pack_events<false>(vs, n - ev_off, nbs, B, 1, (unsigned)c->W, (unsigned)c->H, 0, xy);  // every event: rate 1
+          if (with_lone) xy[ev_n - 1] = pack_word<false>(vs, ev_n - 1, (unsigned)c->W, (unsigned)c->H, 0, outside);
+          return outside;
+        });
+        HIP_TRY(c, hipMemcpyAsync(s.d_xy, xy, (size_t)ev_n * sizeof(uint32_t), hipMemcpyHostToDevice, r->copy_stream));
+        if (nbs > 0) HIP_TRY(c, hipMemcpyAsync(s.d_bt, bt, (size_t)nbs * sizeof(long long), hipMemcpyHostToDevice, r->copy_stream));
+        HIP_TRY(c, hipEventRecord(s.up, r->copy_stream));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, s.up, 0));
+        g.ev.xy = s.d_xy;
+        g.ev.batch_t = s.d_bt;
+      }
+      g.ev.nb = nbs;
+      g.ev.n = (int)ev_n;
+      g.lone = with_lone ? 1 : 0;
+      ReconWarpSlot *o = nullptr;
+      if (dev_out) {
+        g.xy_out = static_cast<char *>(xy_out) + (size_t)ev_off * pair;
+        g.flags_out = flags_out ? flags_out + ev_off : nullptr;
+      } else {
+        o = &r->wslot[k & 1];  // (free: the slice before the last was finished while the last one ran)
+        rc = warp_slot_ensure(c, r, *o, (size_t)ev_n);
+        if (rc) return rc;
+        g.xy_out = o->d_xy;
+        g.flags_out = flags_out ? o->d_fl : nullptr;
+      }
+      g.vec = (uintptr_t)g.xy_out % (f32 ? 8 : 16) == 0 ? 1 : 0;
+      launch_recon_warp(g, c->stream);
+      HIP_TRY(c, hipGetLastError());
+      if (!store) {
+        ReconSlot &s = r->slot[k & 1];
+        HIP_TRY(c, hipEventRecord(s.done, c->stream));
+        s.busy = true;
+      }
+      if (o) {
+        HIP_TRY(c, hipEventRecord(o->kdone, c->stream));
+        HIP_TRY(c, hipStreamWaitEvent(r->down_stream, o->kdone, 0));
+        HIP_TRY(c, hipMemcpyAsync(o->h_xy, o->d_xy, (size_t)ev_n * pair, hipMemcpyDeviceToHost, r->down_stream));
+        if (flags_out) HIP_TRY(c, hipMemcpyAsync(o->h_fl, o->d_fl, (size_t)ev_n, hipMemcpyDeviceToHost, r->down_stream));
+        HIP_TRY(c, hipEventRecord(o->down, r->down_stream));
+        rc = finish(pend);  // the slice before this one, while this one runs
+        if (rc) return rc;
+        pend.o = o; pend.first = ev_off; pend.count = ev_n;
+      }
+    }
+    rc = finish(pend);
+    if (rc) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return CMX_OK;
+  };
+  rc = slices();
+  if (rc) {
+    (void)hipStreamSynchronize(r->copy_stream);
+    (void)hipStreamSynchronize(c->stream);
+    if (r->down_stream) (void)hipStreamSynchronize(r->down_stream);
+  }
+  r->slot[0].busy = r->slot[1].busy = false;
+  return rc;
+}
+
+template <typename MakeSource>
+static int recon_warp_entry(cmx_ctx *c, int format, void *xy_out, unsigned char *flags_out, bool dev_out, MakeSource make) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (format != CMX_WARP_F64 && format != CMX_WARP_F32) return fail(c, CMX_ERR_INVALID_ARG, "unknown output format %d", format);
+  EventSource src;
+  rc = make(&src);
+  if (rc) return rc;
+  return recon_warp_source(c, src, format, xy_out, flags_out, dev_out);
+}
+int cmx_backend_recon_warp(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, int format, void *xy_out,
+                           unsigned char *flags_out) {
+  return recon_warp_entry(c, format, xy_out, flags_out, false,
+                          [&](EventSource *src) { *src = EventSource::arrays(n, x, y, t_ns); return (int)CMX_OK; });
+}
+int cmx_backend_recon_warp_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout, int format, void *xy_out,
+                               unsigned char *flags_out) {
+  return recon_warp_entry(c, format, xy_out, flags_out, false, [&](EventSource *src) { return make_aos(c, n, events, layout, src); });
+}
+int cmx_backend_recon_warp_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count, int format, void *xy_out,
+                                unsigned char *flags_out) {
+  return recon_warp_entry(c, format, xy_out, flags_out, false, [&](EventSource *src) { return store_source(c, e, first, count, src); });
+}
+int cmx_backend_recon_warp_from_device(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count, int format, void *d_xy_out,
+                                       unsigned char *d_flags_out) {
+  return recon_warp_entry(c, format, d_xy_out, d_flags_out, true, [&](EventSource *src) { return store_source(c, e, first, count, src); });
 }
 
 // events of the binding have been released (cmx_backend_recon_release_head): their votes live in the frozen base alone, so whatever

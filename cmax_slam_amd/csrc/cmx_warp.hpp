@@ -135,8 +135,11 @@ __device__ __forceinline__ void be_rotate(const double *R, double b0, double b1,
 // DERIV = 2: the same five entries evaluated in fp32 from the fp64 ray (the reference multiplies them in fp32 anyway,
 //            event_pano_warper.cpp:281-285); relative difference ~1e-7 per entry, saves five fp64 divisions and a
 //            square root per event in the ALU-bound gather pass of the adjoint mode.
-template <int DERIV>
-__device__ __forceinline__ BeWarp be_project(const BeSplatArgs &a, uint32_t e, int batch, double x, double y, double z) {
+// EXPORT: the fp64 panorama coordinate (pxm, pym) the vote cell and the weights are taken from goes to pxy[0], pxy[1] as well -- the
+//         per-event export (recon_warp_kernel, cmx_recon.hip) hands out the vote kernels' own values
+template <int DERIV, bool EXPORT = false>
+__device__ __forceinline__ BeWarp be_project(const BeSplatArgs &a, uint32_t e, int batch, double x, double y, double z,
+                                             double *pxy = nullptr) {
   BeWarp w;
   w.is_old = (e >> 31) != 0;
   w.batch = batch;
@@ -162,6 +165,7 @@ __device__ __forceinline__ BeWarp be_project(const BeSplatArgs &a, uint32_t e, i
   w.ok = (1 <= w.xx && w.xx < a.Wp - 2 && 1 <= w.yy && w.yy < a.Hp - 2);
   w.dx = (float)(pxm - w.xx);
   w.dy = (float)(pym - w.yy);
+  if (EXPORT) { pxy[0] = pxm; pxy[1] = pym; }
   if (DERIV == 2) {
     const float xf = (float)x, yf = (float)y, zf = (float)z, rhof = (float)rho;
     const float fxf = (float)a.fx, fyf = (float)a.fy;
@@ -203,12 +207,12 @@ __device__ __forceinline__ BeWarp be_project(const BeSplatArgs &a, uint32_t e, i
 }
 
 // rotation + projection on already-loaded operands: bearing (b0, b1, b2) and the batch rotation R[9]
-template <int DERIV>
+template <int DERIV, bool EXPORT = false>
 __device__ __forceinline__ BeWarp be_warp_math(const BeSplatArgs &a, uint32_t e, int batch, double b0, double b1,
-                                              double b2, const double *R) {
+                                              double b2, const double *R, double *pxy = nullptr) {
   double x, y, z;
   be_rotate<false>(R, b0, b1, b2, x, y, z);
-  return be_project<DERIV>(a, e, batch, x, y, z);
+  return be_project<DERIV, EXPORT>(a, e, batch, x, y, z, pxy);
 }
 
 template <int DERIV>

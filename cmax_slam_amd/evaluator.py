@@ -610,6 +610,50 @@ class BackendEvaluator(_Evaluator):
         """The same over events_[first, first+count) of a device-resident EventStore (nothing crosses the host)."""
         self._ck(self._L.cmx_backend_recon_add_from(self._ctx, store._h, int(first), int(count)))
 
+    # --- per-event export: where every event lands under the knots the reconstruction holds now (cmx_backend_recon_warp*)
+    @staticmethod
+    def _warp_out(n, dtype):
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError("dtype must be float64 or float32")
+        return (_lib.WARP_F64 if dt == np.dtype(np.float64) else _lib.WARP_F32), np.empty((n, 2), dt), np.empty(n, np.uint8)
+
+    def reconstruct_warp(self, x, y, t_ns, dtype=np.float64):
+        """(xy[n, 2], flags[n] uint8) of exactly these events, sampled or not, in input order: the panorama coordinate the vote
+        kernels take cell and weights from, and flags = WARP_SAMPLED | WARP_INSIDE (3: the event votes in reconstruct_add).
+        Reads the knots only; changes nothing."""
+        x, y, t = _c(x, np.uint16), _c(y, np.uint16), _c(t_ns, np.int64)
+        if not (len(x) == len(y) == len(t)):
+            raise ValueError("x, y, t_ns must have equal length")
+        fmt, xy, fl = self._warp_out(len(x), dtype)
+        self._ck(self._L.cmx_backend_recon_warp(self._ctx, len(x), x.ctypes.data_as(c_u16p), y.ctypes.data_as(c_u16p),
+                                                t.ctypes.data_as(c_i64p), fmt, xy.ctypes.data, fl.ctypes.data))
+        return xy, fl
+
+    def reconstruct_warp_aos(self, events, dtype=np.float64):
+        """The same from a structured array of records with fields x, y, sec, nsec."""
+        ev = np.ascontiguousarray(events)
+        lay = _lib.aos_layout_of(ev)
+        fmt, xy, fl = self._warp_out(len(ev), dtype)
+        self._ck(self._L.cmx_backend_recon_warp_aos(self._ctx, len(ev), ev.ctypes.data_as(C.c_void_p), C.byref(lay), fmt,
+                                                    xy.ctypes.data, fl.ctypes.data))
+        return xy, fl
+
+    def reconstruct_warp_from(self, store, first, count, dtype=np.float64, out=None):
+        """The same over events_[first, first+count) of an EventStore.  out = (xy, flags), objects with data_ptr() (torch tensors on
+        the context's device: xy of `count` x 2 elements of dtype, flags of `count` bytes or None): the kernel writes straight into
+        them, nothing crosses the host, and out is returned.  The call runs on the context's stream and returns when the outputs are
+        complete; work of the caller's that still writes the tensors on another stream must be finished before it."""
+        if out is not None:
+            xy, fl = out
+            fmt = self._warp_out(0, dtype)[0]
+            self._ck(self._L.cmx_backend_recon_warp_from_device(self._ctx, store._h, int(first), int(count), fmt, xy.data_ptr(),
+                                                                fl.data_ptr() if fl is not None else None))
+            return out
+        fmt, xy, fl = self._warp_out(int(count), dtype)
+        self._ck(self._L.cmx_backend_recon_warp_from(self._ctx, store._h, int(first), int(count), fmt, xy.ctypes.data, fl.ctypes.data))
+        return xy, fl
+
     def reconstruct_get(self, with_counts=False):
         """The (Hp, Wp) fp32 plane [, events the sampling selected so far, events that voted so far]."""
         out = np.empty((self.Hp, self.Wp), np.float32)

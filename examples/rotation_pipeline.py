@@ -179,7 +179,7 @@ def reconstruct_panorama(be, traj, x, y, t, prm, store=None, knots=None):
 
 
 def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefix=None, reconstruct=False, refine_global=False,
-                 refine_bound=False, refine_native=False, freeze_head=None, refine_online=None, online_free=8):
+                 refine_bound=False, refine_native=False, freeze_head=None, refine_online=None, online_free=8, export_warped=None):
     """stream: synth.EventStream (or anything with x, y, t_ns, W, H, fx, fy, cx, cy, lut).  Returns a dict.
     display_prefix: write the final panorama with the last pose's FOV and the last packet's local-IWE pair there.
     reconstruct: after the last window, re-warp all events along the whole refined trajectory (res["recon"]; with
@@ -190,7 +190,11 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
     refine_native: it runs as one native call over the bound events (reconstruct_solve); freeze_head = N: with the first N control
     poses fixed and the batches under them voted once.
     refine_online = STRIDE_S: after that, the recording replayed in strides of STRIDE_S seconds through a binding that grows
-    (refine_trajectory_online; res["online_knots"], res["online_report"]), with the last online_free control poses free."""
+    (refine_trajectory_online; res["online_knots"], res["online_report"]), with the last online_free control poses free.
+    export_warped = PATH (implies reconstruct): where EVERY event of the reconstruction lands along the final trajectory, written to
+    PATH.npz as xy (n x 2 panorama coordinates), flags (bit 0 sampled, bit 1 inside; 3 = the event voted) and index (the events'
+    indices in the stream) -- what a host joins with the polarity it kept; also res["warped"] = (index, xy, flags)."""
+    reconstruct = reconstruct or export_warped is not None
     prm = prm or Params()
     x, y, t = stream.x, stream.y, stream.t_ns
     n_total = len(t)
@@ -371,8 +375,18 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
                                                          (time.perf_counter() - t0) * 1e3, r["contrast_after"], r["resident_max"]))
     if reconstruct and traj.size() >= traj.order:
         t0 = time.perf_counter()
-        _, n_rec = reconstruct_panorama(be, traj, x, y, t, prm, store, res.get("refined_knots"))
+        i_rec, n_rec = reconstruct_panorama(be, traj, x, y, t, prm, store, res.get("refined_knots"))
         res["recon"], n_sampled, n_inside = be.reconstruct_get(with_counts=True)
+        if export_warped is not None:  # (the same range in one call: the batches are those of the vote loop above)
+            if store is not None:
+                xy, flags = be.reconstruct_warp_from(store, i_rec, n_rec)
+            else:
+                xy, flags = be.reconstruct_warp(x[i_rec:i_rec + n_rec], y[i_rec:i_rec + n_rec], t[i_rec:i_rec + n_rec])
+            index = np.arange(i_rec, i_rec + n_rec, dtype=np.int64)
+            res["warped"] = (index, xy, flags)
+            np.savez(export_warped + ".npz", xy=xy, flags=flags, index=index)
+            if log:
+                log("export: %d events to %s.npz, %d of them voted" % (n_rec, export_warped, int(np.count_nonzero(flags == 3))))
         if log:
             log("reconstruction: %d events along %d control poses in %.2f ms (%d sampled, %d voted)" %
                 (n_rec, traj.size(), (time.perf_counter() - t0) * 1e3, n_sampled, n_inside))
@@ -438,6 +452,9 @@ def main():
                     help="write PREFIX_pano.ppm (final panorama, last pose's FOV) and PREFIX_local_iwe.pgm (one local-IWE pair)")
     ap.add_argument("--reconstruct", action="store_true",
                     help="after the last window, re-warp ALL events along the whole refined trajectory (with --display: PREFIX_recon.pgm)")
+    ap.add_argument("--export-warped", metavar="PATH", default=None,
+                    help="after the final refinement, write PATH.npz: the panorama coordinate (xy) and flags of every event warped along "
+                         "the whole trajectory, and the events' indices (implies --reconstruct)")
     ap.add_argument("--refine-global", action="store_true",
                     help="after the last window, one bundle adjustment over the whole trajectory (--reconstruct then uses its result)")
     ap.add_argument("--refine-bound", action="store_true",
@@ -463,7 +480,7 @@ def main():
     t0 = time.perf_counter()
     res = run_pipeline(stream, prm, use_event_store=not a.host_events, log=print, display_prefix=a.display, reconstruct=a.reconstruct,
                        refine_global=a.refine_global or a.refine_native, refine_bound=a.refine_bound, refine_native=a.refine_native,
-                       freeze_head=a.freeze_head, refine_online=a.refine_online, online_free=a.online_free)
+                       freeze_head=a.freeze_head, refine_online=a.refine_online, online_free=a.online_free, export_warped=a.export_warped)
     wall = time.perf_counter() - t0
     m = evaluate_against_truth(stream, res)
     print("%.2f s of events (%d) processed in %.2f s wall" % (a.seconds, len(stream.x), wall))

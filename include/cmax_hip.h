@@ -344,6 +344,43 @@ int cmx_backend_recon_add_from(cmx_ctx *ctx, const cmx_events *ev, int64_t first
 int cmx_backend_recon_get(cmx_ctx *ctx, float *pano /* Hp*Wp or NULL */, int64_t *n_sampled, int64_t *n_inside /* either may be NULL */);
 int cmx_backend_recon_render(cmx_ctx *ctx, double gamma, const double fov_quat_xyzw[4] /* or NULL */, unsigned char *out);
 int cmx_backend_recon_end(cmx_ctx *ctx);
+/* Per-event export: WHERE every event lands under the trajectory the reconstruction holds -- what a host needs for any product other
+ * than the count panorama (a signed polarity map, a time surface, a cropped or super-resolved mosaic, outlier flags): the library
+ * never reads polarity, the host joins the entries with whatever it kept.
+ *   output   ONE entry per event handed in, sampled or not, in input order: xy_out[2i], xy_out[2i+1] = (px, py), flags_out[i]
+ *            (flags_out may be NULL).  CMX_WARP_F64: 2 doubles per event; CMX_WARP_F32: 2 floats, (float)px and (float)py.
+ *   poses    spline, batch size and sample rate are those of recon_begin / restart / extend; the knots are the ones the
+ *            reconstruction holds NOW (e.g. the result of recon_solve).  Batches start at the call's first event, exactly as in
+ *            add*: event i belongs to batch b = i / B and is warped with that batch's pose at the batch time add* uses.  (px, py)
+ *            is the fp64 panorama coordinate the vote kernels take their cell xx = (int)px and weight dx = (float)(px - xx) from --
+ *            the same device functions, so the same bits.  With event_batch_size = 1 every event gets the pose at its own time.
+ *   the lone trailing event   add* skips a trailing batch of exactly one event.  The export warps that event with the pose at its
+ *            OWN timestamp and clears its SAMPLED bit.  Its time is validated against the spline like a batch time
+ *            (CMX_ERR_SPLINE_RANGE): the one place where warp* is stricter than add*.
+ *   flags    CMX_WARP_SAMPLED: (i - b*B) % rate == 0 and the event is not the lone trailing one -- exactly the events add* reads.
+ *            CMX_WARP_INSIDE: 1 <= xx < Wp-2 && 1 <= yy < Hp-2.  flags == 3: this event voted in add*.
+ *   state    read-only on the reconstruction: the plane, the counters, the knots, an open gradient pass, a binding, a frozen head
+ *            and a released head are untouched, and so are the window, IG and the exchange sets.  Works after release_head (only
+ *            the knots are read).
+ *   status   validation and status codes of add* / add_from, complete before anything is written: a call that fails validation
+ *            writes nothing to the outputs.  CMX_ERR_STATE before begin and on a group handle; CMX_ERR_INVALID_ARG for an unknown
+ *            format or a NULL xy_out with n > 0; n == 0 is valid.
+ *   long inputs run in the internal slices of whole batches of add*; staging memory does not grow with n.  Host output: the kernel of
+ *            slice k writes device staging, a copy on a stream of its own moves it to pinned memory, and host threads copy it into
+ *            the caller's arrays while slice k+1 runs.  _from_device writes straight into device pointers on the context's device
+ *            (no staging; any alignment of the element type works, one store per pair needs d_xy_out 16- / 8-byte aligned). */
+#define CMX_WARP_F64 0          /* xy_out: 2 doubles per event (px, py) */
+#define CMX_WARP_F32 1          /* xy_out: 2 floats per event: (float)px, (float)py */
+#define CMX_WARP_SAMPLED 1      /* flag bit 0 */
+#define CMX_WARP_INSIDE  2      /* flag bit 1 */
+int cmx_backend_recon_warp(cmx_ctx *ctx, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, int format, void *xy_out,
+                           unsigned char *flags_out /* n bytes or NULL */);
+int cmx_backend_recon_warp_aos(cmx_ctx *ctx, int64_t n, const void *events, const cmx_aos_layout *layout, int format, void *xy_out,
+                               unsigned char *flags_out);
+int cmx_backend_recon_warp_from(cmx_ctx *ctx, const cmx_events *ev, int64_t first, int64_t count, int format, void *xy_out,
+                                unsigned char *flags_out);
+int cmx_backend_recon_warp_from_device(cmx_ctx *ctx, const cmx_events *ev, int64_t first, int64_t count, int format, void *d_xy_out,
+                                       unsigned char *d_flags_out /* device pointers on the context's device */);
 /* Whole-trajectory contrast and its gradient with respect to a LEFT increment of every control pose, on top of an open
  * reconstruction -- the evaluation one bundle adjustment over the whole recording needs, for a spline of any knot count:
  *     recon_begin   recon_add*(events) ...   recon_contrast(want_grad)   recon_grad_add*(the same events) ...   recon_grad_get
