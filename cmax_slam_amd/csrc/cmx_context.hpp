@@ -44,7 +44,7 @@ inline unsigned fallback_flags(double slot) { return fallback_word(slot) & ~cmx:
 struct TimedSpan { int cls; hipEvent_t a, b; };
 typedef struct ncclComm *ncclComm_t;  // as <rccl/rccl.h> declares it; only cmx_comm.cpp includes that header
 
-struct ReconState;  // cmx_reconstruct.cpp: whole-trajectory reconstruction (cmx_backend_recon_*)
+struct ReconState;  // cmx_recon_state.hpp: whole-trajectory reconstruction (cmx_backend_recon_*)
 struct cmx_group;  // cmx_group.cpp: one-process multi-GPU group (members, worker threads, transport)
 
 struct cmx_ctx {
@@ -371,6 +371,23 @@ int ensure(cmx_ctx *c, T *&ptr, size_t &cap, size_t need) {
   cap = n;
   return CMX_OK;
 }
+template <typename T>
+int ensure_pinned(cmx_ctx *c, T *&ptr, size_t &cap, size_t need) {  // the same for pinned host memory
+  if (need <= cap && ptr) return CMX_OK;
+  if (ptr) HIP_TRY(c, hipHostFree(ptr));
+  ptr = nullptr;
+  cap = 0;
+  size_t n = need ? need : 1;
+  HIP_TRY(c, hipHostMalloc((void **)&ptr, n * sizeof(T), hipHostMallocDefault));
+  cap = n;
+  return CMX_OK;
+}
+template <typename A, typename B>
+int ensure_pair(cmx_ctx *c, A *&a, B *&b, size_t &cap, size_t need) {  // two device arrays that grow together under one capacity
+  size_t cap_b = cap;
+  const int rc = ensure(c, a, cap, need);
+  return rc ? rc : ensure(c, b, cap_b, need);
+}
 
 // ---- cmx_context.cpp
 int bind_device(cmx_ctx *c);
@@ -476,10 +493,12 @@ int be_eval_one(cmx_ctx *c, const double *drotv, double *contrast, double *grad)
 #define CMX_NOT_FOR_GROUPS(c, what) \
   do { if ((c) && (c)->group) return fail((c), CMX_ERR_STATE, what " is not available on a group (the group runs its own exchange)"); } while (0)
 
-// ---- cmx_reconstruct.cpp
+// ---- whole-trajectory reconstruction: what the rest of the library sees of it (its own shared state and helpers:
+// cmx_recon_state.hpp).  cmx_reconstruct.cpp: life cycle, contrast, get / render; cmx_recon_feed.cpp: add*, grad_add*, warp*;
+// cmx_recon_bound.cpp: the binding, its frozen head, the solve's hooks
 int recon_diag_slice_events(int n);  // CMX_DIAG_RECON_SLICE_EVENTS (cmax_hip_diag.h)
 void recon_release(cmx_ctx *c);  // frees whatever a reconstruction holds (cmx_backend_recon_end, cmx_destroy)
-// cmx_backend_recon_solve (cmx_solver.cpp) around the bound evaluation: begin validates everything before anything changes, sets
+// cmx_recon_bound.cpp -- cmx_backend_recon_solve (cmx_solver.cpp) around the bound evaluation: begin validates everything before anything changes, sets
 // up staging and (freeze_head) the frozen head at the start knots, *n_params = 3 (K - num_fixed); eval is one trial point at
 // increment x (grad_free: the 3 (K - num_fixed) free entries, or NULL); end evaluates x once more only if the last trial point was
 // another one, and writes the knots of x to knots_out (cmx_diag_recon_solve_counts reads the solve's evaluations and host waits)

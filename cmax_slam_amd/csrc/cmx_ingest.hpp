@@ -178,6 +178,28 @@ inline Slice slice_at(const BatchPlan &p, int64_t n_events, int b_lo, int slice_
   s.n = p.packed(b_lo, s.b_hi);
   return s;
 }
+// ... and the walk over a whole hand-over of n_events events (recon_add*, recon_grad_add*, recon_warp*): slice k of it, false
+// behind the last.  every_event (the per-event export): the trailing event no batch holds (n_events = nb B + 1) rides on the last
+// slice, and n_events == 1 -- no batch at all -- is one slice of that event alone; a sampling pass has nothing to do there.
+struct FeedSlice : Slice {
+  int b_lo = 0;
+  bool lone = false;  // every_event: the lone trailing event is element ev_n - 1 of this slice
+};
+inline bool feed_slice_at(const BatchPlan &p, int64_t n_events, int slice_batches, bool every_event, int64_t k, FeedSlice *f) {
+  *f = FeedSlice{};
+  if (p.nb == 0) {
+    if (!(every_event && n_events == 1 && k == 0)) return false;
+    f->ev_n = 1;
+    f->lone = true;
+    return true;
+  }
+  const int64_t b_lo = k * slice_batches;
+  if (b_lo >= p.nb) return false;
+  static_cast<Slice &>(*f) = slice_at(p, n_events, (int)b_lo, slice_batches);
+  f->b_lo = (int)b_lo;
+  f->lone = every_event && f->b_hi == p.nb && (int64_t)p.nb * p.B < n_events;
+  return true;
+}
 
 // ---- the frozen head of a bound whole-trajectory evaluation (cmx_backend_recon_freeze_head): the batches whose pose no free knot
 // can move.  A batch at pose time t lies in segment s = (t - start) / dt, clamped to [0, K - order] as the kernels clamp it

@@ -1,0 +1,305 @@
+// cmx_recon_feed.cpp -- every cmx_backend_recon_* call that is handed events: ONE walk over them (feed) in slices of whole batches
+// (feed_slice_at, cmx_ingest.hpp), and what each call does with a slice on the device.
+//   add*       the vote loop of EventWarper::computeImageOfWarpedEvents (event_pano_warper.cpp:188-196, :233-311) over the sampled
+//              events, into the reconstruction's plane
+//   grad_add*  the second pass over the same events, their share of the gradient sums
+//   warp*      the per-event export: where EVERY event handed in lands under the knots the reconstruction holds now
+// Host arrays (SoA, or the host's own records) are packed slice by slice into two slots of pinned memory and uploaded on the copy
+// stream while the slice before runs; a range of an event store is read in place, its batch times formed on the device.
+#include "cmx_recon_state.hpp"
+
+int queue_gather(cmx_ctx *c, ReconState *r, ReconGatherArgs &g) {
+  const int blocks = recon_gather_blocks(g.ev);
+  if (blocks <= 0) return CMX_OK;
+  if (r->deterministic) {
+    if ((size_t)blocks > r->rows_cap) HIP_TRY(c, hipStreamSynchronize(c->stream));  // (an earlier slice may still be reading the rows)
+    const int rc = ensure_pair(c, r->d_rows, r->d_row_win, r->rows_cap, (size_t)blocks);
+    if (rc) return rc;
+    g.rows = r->d_rows[0];
+    g.row_win = r->d_row_win;
+  }
+  launch_recon_gather(g, c->stream);
+  launch_recon_gather_rows(g, blocks, c->stream);
+  return CMX_OK;
+}
+
+int validate_store_times(cmx_ctx *c, ReconState *r, const int64_t *d_t, int64_t n, const BatchPlan &p, int slice_batches, long long *d_bt) {
+  int rc = CMX_OK;
+  FeedSlice f;
+  for (int64_t k = 0; !rc && feed_slice_at(p, n, slice_batches, false, k, &f); k++)
+    rc = queue_batch_times(c, d_t + f.ev_first, f.ev_n, p.B, f.b_hi - f.b_lo, r->sup, d_bt, r->d_err, k == 0);
+  if (rc) return rc;
+  HIP_TRY(c, hipGetLastError());
+  BatchTimeError bad;
+  rc = read_batch_errors(c, r->d_err, &bad);
+  if (rc) return rc;
+  if (bad.kind) return fail_batch_time(c, bad, r->sup, /*with_event=*/false);  // (its index would be relative to a slice)
+  return CMX_OK;
+}
+
+static int slot_ensure(cmx_ctx *c, ReconSlot &s, size_t n_xy, size_t n_bt) {
+  int rc = ensure_pinned(c, s.h_xy, s.h_xy_cap, n_xy);
+  if (!rc) rc = ensure(c, s.d_xy, s.xy_cap, n_xy);
+  if (!rc) rc = ensure_pinned(c, s.h_bt, s.h_bt_cap, n_bt);
+  if (!rc) rc = ensure(c, s.d_bt, s.bt_cap, n_bt);
+  return rc;
+}
+
+// ---- the feeder
+// argument checks of a hand-over, and for host sources EVERY coordinate inside the sensor, those the sampling or the one-event rule
+// skip included: what cmx_backend_set_window checks when it sub-samples, here at every rate (cmax_hip.h).  First thing of every
+// call, in front of feed (the export has a check of its own between the two).
+static int feed_checks(cmx_ctx *c, const EventSource &src) {
+  if (!src.on_device()) return check_events(c, src);
+  if (src.n < 0 || src.n > kMaxEvents) return fail(c, CMX_ERR_INVALID_ARG, "bad event count %lld", (long long)src.n);
+  return CMX_OK;
+}
+
+// a slice as its consumer finds it on the device
+struct FedSlice : FeedSlice {
+  int64_t k = 0;
+  const uint32_t *d_xy = nullptr;     // its events: packed (host sources; every_event: all ev_n of them, else the n sampled ones), or the
+                                      // store's own from ev_first on, to be read in place
+  const long long *d_bt = nullptr;    // its batch times
+  long long lone_t = 0;               // every_event: the time of the call's lone trailing event
+};
+
+// The batch plan of the n events of src, then validation of EVERYTHING -- a call that fails adds nothing: every batch time (host:
+// batch_times; store: validate_store_times) and, every_event, the lone trailing event's own time -- and only then slice by slice:
+// stage it, on_slice(slice), mark the staging in use.  Host sources: slice k+1 is packed (at the call's rate, or every event) and
+// uploaded while the kernels of slice k run.  Store sources: the batch times of the slice into slot[0]'s table; a single slice finds
+// there what the validation pass has just written.  From the first slice on only a runtime error (CMX_ERR_HIP) can end the call,
+// and slices queued before it have run.  Returns after the context's stream has run dry, the slots idle either way.
+template <typename OnSlice>
+static int feed(cmx_ctx *c, ReconState *r, const EventSource &src, bool every_event, BatchPlan *plan, OnSlice on_slice) {
+  const bool store = src.on_device();
+  const int64_t n = src.n;
+  const int B = r->B;
+  BatchPlan &p = *plan;
+  int slice_batches = 1;
+  int rc = recon_plan(c, r, n, &p, &slice_batches);
+  if (rc) return rc;
+  FedSlice f;
+  if (!feed_slice_at(p, n, slice_batches, every_event, 0, &f)) return CMX_OK;
+  const bool lone = every_event && (int64_t)p.nb * B < n;  // the trailing event no batch holds (n = nb B + 1)
+  f.lone_t = lone ? (long long)src.view([&](const auto &v) { return v.T(n - 1); }) : 0;  // (store: its host mirror)
+  ReconSlot &s0 = r->slot[0];
+  if (store && p.nb > 0) {
+    rc = ensure(c, s0.d_bt, s0.bt_cap, (size_t)(p.nb < slice_batches ? p.nb : slice_batches));
+    if (!rc) rc = validate_store_times(c, r, src.d_t, n, p, slice_batches, s0.d_bt);
+    if (rc) return rc;
+  } else if (p.nb > 0) {
+    const BatchTimeError bad = src.view([&](const auto &v) { return batch_times(v, n, B, 0, p.nb, &r->sup, [](int64_t, long long) {}); });
+    if (bad.kind) return fail_batch_time(c, bad, r->sup);
+  }
+  if (lone) {  // its own time is its pose time: inside the spline like a batch time
+    const long long st = f.lone_t - r->sup.start_ns;
+    if (st < 0 || st / r->sup.dt_ns + r->sup.order > r->sup.K) return fail_batch_time(c, BatchTimeError{CMX_ERR_SPLINE_RANGE, f.lone_t}, r->sup);
+  }
+  const bool one_slice = p.nb <= slice_batches;
+  auto slices = [&]() -> int {
+    for (f.k = 0; feed_slice_at(p, n, slice_batches, every_event, f.k, &f); f.k++) {
+      const int nbs = f.b_hi - f.b_lo;
+      ReconSlot &s = r->slot[f.k & 1];
+      if (store) {
+        if (!one_slice) {
+          rc = queue_batch_times(c, src.d_t + f.ev_first, f.ev_n, B, nbs, r->sup, s0.d_bt, r->d_err, false);
+          if (rc) return rc;
+        }
+        f.d_xy = src.d_xy + f.ev_first;
+        f.d_bt = s0.d_bt;
+      } else {
+        const int64_t n_xy = every_event ? f.ev_n : f.n;
+        if (s.busy) { HIP_TRY(c, hipEventSynchronize(s.done)); s.busy = false; }  // its previous slice has been consumed
+        rc = slot_ensure(c, s, (size_t)n_xy, (size_t)nbs);
+        if (rc) return rc;
+        uint32_t *xy = s.h_xy;
+        long long *bt = s.h_bt;
+        src.view([&](const auto &v) {  // (validated above: neither pass finds anything)
+          if (nbs > 0) batch_times(v, n, B, f.b_lo, f.b_hi, nullptr, [&](int64_t b, long long tb) { bt[b - f.b_lo] = tb; });
+          const auto vs = v.from(f.ev_first);
+          unsigned outside = pack_events<false>(vs, n - f.ev_first, nbs, B, every_event ? 1 : r->rate, (unsigned)c->W, (unsigned)c->H, 0, xy);
+          if (f.lone) xy[f.ev_n - 1] = pack_word<false>(vs, f.ev_n - 1, (unsigned)c->W, (unsigned)c->H, 0, outside);
+          return outside;
+        });
+        HIP_TRY(c, hipMemcpyAsync(s.d_xy, xy, (size_t)n_xy * sizeof(uint32_t), hipMemcpyHostToDevice, r->copy_stream));
+        if (nbs > 0) HIP_TRY(c, hipMemcpyAsync(s.d_bt, bt, (size_t)nbs * sizeof(long long), hipMemcpyHostToDevice, r->copy_stream));
+        HIP_TRY(c, hipEventRecord(s.up, r->copy_stream));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, s.up, 0));
+        f.d_xy = s.d_xy;
+        f.d_bt = s.d_bt;
+      }
+      rc = on_slice(f);
+      if (rc) return rc;
+      HIP_TRY(c, hipGetLastError());
+      if (!store) {
+        HIP_TRY(c, hipEventRecord(s.done, c->stream));
+        s.busy = true;
+      }
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return CMX_OK;
+  };
+  rc = slices();
+  if (rc) { (void)hipStreamSynchronize(r->copy_stream); (void)hipStreamSynchronize(c->stream); }
+  r->slot[0].busy = r->slot[1].busy = false;
+  return rc;
+}
+
+// ---- add*, grad_add*: the vote pass or the gradient pass over the events handed in
+int recon_add_source(cmx_ctx *c, const EventSource &src, bool grad) {
+  ReconState *r = c->recon;
+  if (int rc0 = recon_pass_enter(c, r, grad)) return rc0;
+  int rc = feed_checks(c, src);
+  if (rc) return rc;
+  ReconGatherArgs ga = recon_gather_args(c, r);
+  ReconArgs &a = ga.ev;
+  BatchPlan p;
+  rc = feed(c, r, src, false, &p, [&](const FedSlice &s) {
+    a.xy = s.d_xy; a.stride = src.on_device() ? r->rate : 0;  // (the store's events in place: the sampling is an index map)
+    a.batch_t = s.d_bt; a.nb = s.b_hi - s.b_lo;
+    a.n = (int)s.n;
+    if (grad) return queue_gather(c, r, ga);
+    launch_recon_votes(a, c->stream);
+    return (int)CMX_OK;
+  });
+  if (rc) return rc;
+  (grad ? r->g_sampled : r->n_sampled) += p.n_packed;
+  return CMX_OK;
+}
+
+// the six entry points: the front door, the call's own way to its source (host arrays, the host's records, a range of an event
+// store -- with that form's argument checks), then the pass over it
+template <typename MakeSource>
+static int recon_add_entry(cmx_ctx *c, bool grad, MakeSource make) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  EventSource src;
+  rc = make(&src);
+  if (rc) return rc;
+  return recon_add_source(c, src, grad);
+}
+int cmx_backend_recon_add(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns) {
+  return recon_add_entry(c, false, [&](EventSource *src) { *src = EventSource::arrays(n, x, y, t_ns); return (int)CMX_OK; });
+}
+int cmx_backend_recon_grad_add(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns) {
+  return recon_add_entry(c, true, [&](EventSource *src) { *src = EventSource::arrays(n, x, y, t_ns); return (int)CMX_OK; });
+}
+int cmx_backend_recon_add_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout) {
+  return recon_add_entry(c, false, [&](EventSource *src) { return make_aos(c, n, events, layout, src); });
+}
+int cmx_backend_recon_grad_add_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout) {
+  return recon_add_entry(c, true, [&](EventSource *src) { return make_aos(c, n, events, layout, src); });
+}
+int cmx_backend_recon_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
+  return recon_add_entry(c, false, [&](EventSource *src) { return store_source(c, e, first, count, src); });
+}
+int cmx_backend_recon_grad_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
+  return recon_add_entry(c, true, [&](EventSource *src) { return store_source(c, e, first, count, src); });
+}
+
+// ---- warp*: ALL events of a slice reach the kernel (the host paths pack at rate 1, the store is read in place), the true rate only
+// decides the SAMPLED bit.  Nothing of the reconstruction but the knots is read and nothing of it is written: no recon_pass_enter,
+// no counter, no plane.  The output staging (host output) is the export's own.
+static int warp_slot_ensure(cmx_ctx *c, ReconState *r, ReconWarpSlot &s, size_t n) {
+  if (!r->down_stream) HIP_TRY(c, hipStreamCreateWithFlags(&r->down_stream, hipStreamNonBlocking));
+  if (!s.kdone) HIP_TRY(c, hipEventCreateWithFlags(&s.kdone, hipEventDisableTiming));
+  if (!s.down) HIP_TRY(c, hipEventCreateWithFlags(&s.down, hipEventDisableTiming));
+  int rc = ensure_pinned(c, s.h_xy, s.h_xy_cap, 2 * n);
+  if (!rc) rc = ensure_pinned(c, s.h_fl, s.h_fl_cap, n);
+  if (!rc) rc = ensure(c, s.d_xy, s.d_xy_cap, 2 * n);
+  if (!rc) rc = ensure(c, s.d_fl, s.d_fl_cap, n);
+  return rc;
+}
+
+static int recon_warp_source(cmx_ctx *c, const EventSource &src, int format, void *xy_out, unsigned char *flags_out, bool dev_out) {
+  ReconState *r = c->recon;
+  int rc = feed_checks(c, src);
+  if (rc) return rc;
+  if (src.n > 0 && !xy_out) return fail(c, CMX_ERR_INVALID_ARG, "null coordinate output");
+  const bool f32 = format == CMX_WARP_F32;
+  const size_t pair = f32 ? 2 * sizeof(float) : 2 * sizeof(double);
+  ReconWarpArgs g{};
+  g.ev = recon_args(c, r);
+  g.ev.per_batch = r->B; g.ev.stride = 0;
+  g.ev.run = recon_run(r->B);
+  g.rate = r->rate;
+  g.f32 = f32 ? 1 : 0;
+  struct Pending { ReconWarpSlot *o = nullptr; int64_t first = 0, count = 0; } pend;
+  auto finish = [&](Pending &q) -> int {  // the download of a slice is complete: into the caller's arrays
+    if (!q.o) return CMX_OK;
+    HIP_TRY(c, hipEventSynchronize(q.o->down));
+    const char *hx = reinterpret_cast<const char *>(q.o->h_xy);
+    const unsigned char *hf = q.o->h_fl;
+    char *ox = static_cast<char *>(xy_out) + (size_t)q.first * pair;
+    unsigned char *of = flags_out ? flags_out + q.first : nullptr;
+    parallel_ranges(q.count, [=](int64_t a0, int64_t a1) {
+      memcpy(ox + (size_t)a0 * pair, hx + (size_t)a0 * pair, (size_t)(a1 - a0) * pair);
+      if (of) memcpy(of + a0, hf + a0, (size_t)(a1 - a0));
+    });
+    q.o = nullptr;
+    return CMX_OK;
+  };
+  BatchPlan p;
+  rc = feed(c, r, src, true, &p, [&](const FedSlice &s) -> int {
+    g.ev.xy = s.d_xy;
+    g.ev.batch_t = s.d_bt; g.ev.nb = s.b_hi - s.b_lo;
+    g.ev.n = (int)s.ev_n;
+    g.lone = s.lone ? 1 : 0;
+    g.lone_t = s.lone_t;
+    ReconWarpSlot *o = nullptr;
+    if (dev_out) {
+      g.xy_out = static_cast<char *>(xy_out) + (size_t)s.ev_first * pair;
+      g.flags_out = flags_out ? flags_out + s.ev_first : nullptr;
+    } else {
+      o = &r->wslot[s.k & 1];  // (free: the slice before the last was finished while the last one ran)
+      const int rc2 = warp_slot_ensure(c, r, *o, (size_t)s.ev_n);
+      if (rc2) return rc2;
+      g.xy_out = o->d_xy;
+      g.flags_out = flags_out ? o->d_fl : nullptr;
+    }
+    g.vec = (uintptr_t)g.xy_out % (f32 ? 8 : 16) == 0 ? 1 : 0;
+    launch_recon_warp(g, c->stream);
+    if (!o) return CMX_OK;
+    HIP_TRY(c, hipEventRecord(o->kdone, c->stream));
+    HIP_TRY(c, hipStreamWaitEvent(r->down_stream, o->kdone, 0));
+    HIP_TRY(c, hipMemcpyAsync(o->h_xy, o->d_xy, (size_t)s.ev_n * pair, hipMemcpyDeviceToHost, r->down_stream));
+    if (flags_out) HIP_TRY(c, hipMemcpyAsync(o->h_fl, o->d_fl, (size_t)s.ev_n, hipMemcpyDeviceToHost, r->down_stream));
+    HIP_TRY(c, hipEventRecord(o->down, r->down_stream));
+    const int rc2 = finish(pend);  // the slice before this one, while this one runs
+    if (rc2) return rc2;
+    pend.o = o; pend.first = s.ev_first; pend.count = s.ev_n;
+    return CMX_OK;
+  });
+  if (!rc) rc = finish(pend);
+  if (rc && r->down_stream) (void)hipStreamSynchronize(r->down_stream);
+  return rc;
+}
+
+template <typename MakeSource>
+static int recon_warp_entry(cmx_ctx *c, int format, void *xy_out, unsigned char *flags_out, bool dev_out, MakeSource make) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (format != CMX_WARP_F64 && format != CMX_WARP_F32) return fail(c, CMX_ERR_INVALID_ARG, "unknown output format %d", format);
+  EventSource src;
+  rc = make(&src);
+  if (rc) return rc;
+  return recon_warp_source(c, src, format, xy_out, flags_out, dev_out);
+}
+int cmx_backend_recon_warp(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, int format, void *xy_out,
+                           unsigned char *flags_out) {
+  return recon_warp_entry(c, format, xy_out, flags_out, false,
+                          [&](EventSource *src) { *src = EventSource::arrays(n, x, y, t_ns); return (int)CMX_OK; });
+}
+int cmx_backend_recon_warp_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout, int format, void *xy_out,
+                               unsigned char *flags_out) {
+  return recon_warp_entry(c, format, xy_out, flags_out, false, [&](EventSource *src) { return make_aos(c, n, events, layout, src); });
+}
+int cmx_backend_recon_warp_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count, int format, void *xy_out,
+                                unsigned char *flags_out) {
+  return recon_warp_entry(c, format, xy_out, flags_out, false, [&](EventSource *src) { return store_source(c, e, first, count, src); });
+}
+int cmx_backend_recon_warp_from_device(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count, int format, void *d_xy_out,
+                                       unsigned char *d_flags_out) {
+  return recon_warp_entry(c, format, d_xy_out, d_flags_out, true, [&](EventSource *src) { return store_source(c, e, first, count, src); });
+}

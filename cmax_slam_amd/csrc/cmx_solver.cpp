@@ -114,7 +114,7 @@ int solve(cmx_ctx *ctx, bool backend, int n, double *x_inout, double tol, double
   return st.err;
 }
 
-// ---- cmx_backend_recon_solve: the same machine over the bound whole-trajectory evaluation (cmx_reconstruct.cpp: recon_solve_*).
+// ---- cmx_backend_recon_solve: the same machine over the bound whole-trajectory evaluation (cmx_recon_bound.cpp: recon_solve_*).
 // f = -contrast, df = -(the free gradient entries): BackendEvaluator.reconstruct_refine(bind=True)'s functor, call for call.
 struct ReconSolveState {
   cmx_ctx *ctx;

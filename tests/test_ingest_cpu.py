@@ -203,3 +203,17 @@ def test_pool_path_equals_the_single_range(program, tmp_path, rate):
     t_old = int(t[n // 2 + 17])
     r = run(program, tmp_path, x, y, t, rate, t_old, slice_batches=2048)   # slices of 131 072 events: each a single range
     assert check(r, x, y, t, rate, t_old) == OK
+
+
+def test_the_slice_planner_against_brute_force(tmp_path):
+    """feed_slice_at alone (the slices of every cmx_backend_recon_add* / _grad_add* / _warp* call), under the address and
+    undefined-behaviour sanitizers, run directly: every n in 0 .. 3 B + 2 with B in {1, 3, 64}, rates 1 to 3, 1, 2 and 7 batches per
+    slice, the sampling mode and the export's "every event, lone tail included" (tests/feed_plan_host.cpp)."""
+    exe = str(tmp_path / "feed_plan_host")
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++")
+    assert cxx, "no host C++ compiler"
+    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(ROOT, "tests", "feed_plan_host.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0 and r.stdout.startswith("ok ")
