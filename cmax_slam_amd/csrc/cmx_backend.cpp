@@ -354,7 +354,7 @@ static int be_finish_one(cmx_ctx *c, double *contrast, double *grad) {
   if (!c || c->kind != KIND_BE) return fail(c, CMX_ERR_STATE, "not a back-end context");
   if (!c->accumulated) return fail(c, CMX_ERR_STATE, "finish without accumulate");
   if (!contrast) return fail(c, CMX_ERR_INVALID_ARG, "null contrast");
-  const int P = 3 * (c->K - c->num_fixed);
+  const int P = n_params(c);
   if (grad && c->last_P != P && !c->last_adjoint)
     return fail(c, CMX_ERR_STATE, "gradient requested but accumulate ran without it");
   int rc = bind_device(c);
@@ -366,11 +366,11 @@ static int be_finish_one(cmx_ctx *c, double *contrast, double *grad) {
     c->gate_mode = 0;  // a hint not consumed by a cost-only evaluation does not outlive the next evaluation of any kind
     rc = collect_gated(c, P, contrast, grad, &served);  // the gradient pass may already be in flight (cmx_hint_next_df)
     if (rc || served) return rc;
-    rc = run_adjoint(c, P);
+    rc = adjoint_eval(c, P);
   } else if (!grad && speculative_jt_ok(c) && P > 0) {
     rc = finish_cost_only_speculative(c, P);
     if (rc) return rc;
-    *contrast = c->h_result[0];
+    read_result(c, P, contrast, grad);
     return CMX_OK;
   } else {
     c->gated_pending = false;
@@ -380,8 +380,7 @@ static int be_finish_one(cmx_ctx *c, double *contrast, double *grad) {
   if (rc) return rc;
   rc = sync_and_collect(c, true);
   if (rc) return rc;
-  *contrast = c->h_result[0];
-  if (grad) for (int k = 0; k < P; k++) grad[k] = c->h_result[2 + k];
+  read_result(c, P, contrast, grad);
   return CMX_OK;
 }
 
@@ -392,7 +391,7 @@ int cmx_backend_eval(cmx_ctx *c, const double *drotv, double *contrast, double *
 }
 int be_eval_one(cmx_ctx *c, const double *drotv, double *contrast, double *grad) {
   const bool sharded = c && c->sharded();
-  if (c && c->kind == KIND_BE && drotv && can_reuse(c, drotv, 3 * (c->K - c->num_fixed), grad != nullptr)) {
+  if (c && c->kind == KIND_BE && drotv && can_reuse(c, drotv, n_params(c), grad != nullptr)) {
     c->last_adjoint = true;
     c->reuse_hits++;
     if (sharded) return finish_sharded(c, KIND_BE, false, contrast, grad);

@@ -57,14 +57,12 @@ int queue_slot(cmx_ctx *c, int slot, SlotTickets *t) {
   c->last_adjoint = true;
   int rc = fe_accumulate(c, zero, 1);
   if (rc) return rc;
-  c->gate_arm = true;
-  rc = run_adjoint(c, 3, /*phase=*/3);  // image pass + cost finalize + machine step (decides the gate)
-  c->gate_arm = false;
+  rc = adjoint_cost_only(c, 3, /*arm_gate=*/true);  // image pass + cost finalize + machine step (decides the gate)
   if (rc) return rc;
   t->a = c->ticket_issued;
   t->nout_a = c->ticket_nout;
   c->gated_pending = false;
-  rc = run_adjoint(c, 3, /*phase=*/4);  // gradient pass behind the gate (+ finalize + machine step)
+  rc = adjoint_gated_grad(c, 3);  // gradient pass behind the gate (+ finalize + machine step)
   if (rc) return rc;
   t->gated = c->gated_pending;
   c->gated_pending = false;
@@ -82,8 +80,6 @@ bool self_gating_ok(const cmx_ctx *c) {
          c->d_cx && c->d_cy;
 }
 int queue_slot_self_gating(cmx_ctx *c, int slot, SlotTickets *t) {
-  const int W = c->imgW, H = c->imgH;
-  const size_t np = (size_t)W * H;
   const int r = slot % kRingSlots;
   const double zero[3] = {0, 0, 0};
   const bool first = c->chain_first;              // warm start: omega as kernel arguments, no end-of-solve flag, machine from the host
@@ -97,28 +93,14 @@ int queue_slot_self_gating(cmx_ctx *c, int slot, SlotTickets *t) {
   c->fuse_macc = nullptr;
   if (rc) return rc;
   if (!c->streams_valid || !c->bin_valid) return fail(c, CMX_ERR_STATE, "self-gating slot without the tile-ordered streams");
-  float *jt_before = c->d_itilde;
-  rc = ensure(c, c->d_itilde, c->itilde_cap, np);
+  rc = ensure_jt(c);
   if (rc) return rc;
-  if (c->d_itilde != jt_before) HIP_TRY(c, hipMemsetAsync(c->d_itilde, 0, c->itilde_cap * sizeof(float), c->stream));
   // ---- image pass: B = G*I moments -> accumulator rows of buffer (slot & 1), Jt = G^T G I, clears the ping-pong partner
   ImgAdjArgs ia{};
   ImgArgs &a = ia.img;
-  ia.Mx = c->d_Mx; ia.My = c->d_My;
-  ia.jt = c->d_itilde;
-  a.W = W; a.H = H; a.r = c->radius;
-  memcpy(a.taps, c->taps, sizeof(a.taps));
-  a.src_a = c->d_accum;
-  a.P = 0;
-  a.tiles_x = image_adjoint_tiles_x(W);
-  a.nblk = image_adjoint_tiles(W, H);
-  a.tiles_y = (H + kTileY - 1) / kTileY;
-  if (!c->fused_done && c->pingpong_planes > 0 && c->d_accum_alt && !c->alt_clean) {
-    a.zero_ptr = c->d_accum_alt;
-    a.zero_planes = c->pingpong_planes;
-    c->alt_clean = true;
-  }
-  a.skip = first ? nullptr : &c->d_chain->done;
+  image_adjoint_args(c, ia);  // (self_gating_ok: the composite operator; a.skip unless this is a warm start's first slot)
+  a.tiles_y = (a.H + kTileY - 1) / kTileY;
+  if (!c->fused_done) claim_partner_clear(c, a);
   a.macc = &c->d_chain->macc[par][0][0];
   if (!c->fused_done) launch_image_adjoint(ia, c->stream);
   // ---- the self-gating launch: cost finalize + machine step, and the gradient pass when the machine's test says so
@@ -132,7 +114,7 @@ int queue_slot_self_gating(cmx_ctx *c, int slot, SlotTickets *t) {
   f.P = 0;
   f.nblk = a.nblk;
   f.measure = c->measure;
-  f.npix = (double)np;
+  f.npix = (double)((size_t)a.W * a.H);
   f.result = c->d_chain_ring + (size_t)(2 * r) * kBlock;
   f.gP = 3;
   f.mu_free = 1;

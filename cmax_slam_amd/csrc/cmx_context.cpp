@@ -651,7 +651,7 @@ int cmx_timing_get(cmx_ctx *c, double ms[CMX_T_COUNT], int64_t launches[CMX_T_CO
 size_t cmx_accum_capacity(const cmx_ctx *c) {
   if (!c) return 0;
   if (c->kind == KIND_FE) return (size_t)4 * c->W * c->H;
-  const int P = 3 * (c->K - c->num_fixed);
+  const int P = n_params(c);
   return (size_t)(2 + (P > 0 ? P : 0)) * c->Wp * c->Hp;
 }
 int cmx_set_accum_buffer(cmx_ctx *c, void *device_ptr, size_t n_floats) {

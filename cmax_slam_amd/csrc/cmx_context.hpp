@@ -126,7 +126,7 @@ struct cmx_ctx {
   int Mx_radius = -1;                      // blur radius the tables were built for (-1: none)
   bool composite_image = true;             // CMX_OPT_COMPOSITE_IMAGE
   bool fold_batch = true;                  // CMX_OPT_FOLD_BATCH
-  bool shard_acc = false;                  // set by cmx_comm.cpp around a split evaluation it all-reduces itself (see run_adjoint)
+  bool shard_acc = false;                  // set by cmx_comm.cpp around a split evaluation it all-reduces itself (see acc_rows)
   double *d_gpartials = nullptr;
   size_t gpartials_cap = 0;
   double *d_vparts = nullptr;  // back end: per-batch partial V sums of the gather pass
@@ -148,7 +148,7 @@ struct cmx_ctx {
   size_t tile_list_cap = 0;
   int tile_count_sel = 0;
   bool adj_direct = false;                   // shape of the moment partials the last adjoint image pass produced
-  const unsigned *adj_tile_count = nullptr;  // (run_adjoint phase 1 -> phase 2)
+  const unsigned *adj_tile_count = nullptr;  // (image_step -> the finalize of a later call: adjoint_finalize_sums, a df at the same point)
   bool x_valid = false;       // plane 0 (and the pose table) hold the accumulation for last_x
   bool jt_valid = false;      // ... and Jt + the moment rows hold the adjoint image pass of those planes (speculative, see
                               // speculative_jt_ok); cleared by every accumulate
@@ -226,13 +226,12 @@ struct cmx_ctx {
   double *h_many = nullptr, *d_many = nullptr;  // cmx_*_eval_many: one 4096-double result block per evaluation of the list
   size_t many_cap = 0;
   double *result_override = nullptr;            // where the next finalize writes instead of d_result (eval_many)
-  // gated gradient pass behind a cost-only evaluation (cmx_hint_next_df; cmx_pipeline.cpp run_adjoint / finish_cost_only)
+  // gated gradient pass behind a cost-only evaluation (cmx_hint_next_df; cmx_pipeline.cpp adjoint_gated_grad / finish_cost_only)
   double *h_result2 = nullptr, *d_result2 = nullptr;  // second mapped result block: the gated pass reports here
   int *d_gate = nullptr;                        // written by the cost-only evaluation's finalize, read by the gated launch
   int gate_mode = 0;                            // hint for the NEXT cost-only evaluation (consumed by it): 0 none, 1..4 see gate_condition
   double gate_thr = 0;
   bool gated_df = true;                         // CMX_OPT_GATED_DF
-  bool gate_arm = false;                        // set around run_adjoint(phase 3) when a gated pass will be queued behind it
   bool gated_pending = false, gated_fired = false;  // a gated pass is queued behind the last evaluation / its gate opened
   unsigned long long ticket2_issued = 0;
   int ticket2_nout = 0;
@@ -440,6 +439,13 @@ struct Span {
 
 // ---- cmx_pipeline.cpp
 inline double *result_ptr(const cmx_ctx *c) { return c->result_override ? c->result_override : c->d_result; }
+inline int n_params(const cmx_ctx *c) { return c->kind == KIND_FE ? 3 : 3 * (c->K - c->num_fixed); }
+// contrast and gradient (may be null) of the evaluation just waited for, from its result block (default: h_result)
+inline void read_result(const cmx_ctx *c, int P, double *contrast, double *grad, const double *block = nullptr) {
+  if (!block) block = c->h_result;
+  *contrast = block[0];
+  if (grad) for (int k = 0; k < P; k++) grad[k] = block[2 + k];
+}
 int begin_accum(cmx_ctx *c, int nplanes, size_t np, bool fast);
 int ensure_accum(cmx_ctx *c, size_t need);
 int do_binning(cmx_ctx *c, const FeSplatArgs *fe, const BeSplatArgs *be);
@@ -453,8 +459,17 @@ bool arm_tail(cmx_ctx *c, FinalizeArgs &f, TailArgs &tail, bool gated = false); 
 int attach_tiles(cmx_ctx *c, ImgArgs &a, bool may_skip);
 int maybe_tile_list(cmx_ctx *c, ImgArgs &a, int reach);
 int run_image_and_finalize(cmx_ctx *c, int P, float *out_blur0, float *out_blurd);
-int run_adjoint(cmx_ctx *c, int P, int phase = 0);  // phase 3: image pass + cost-only finalize, Jt kept; 4: gated gradient pass
-int finish_cost_only_speculative(cmx_ctx *c, int P);  // phase 3 (+ the gated pass when a hint is set), then the wait
+void image_args(const cmx_ctx *c, ImgArgs &a);               // size, blur and sources of any image pass
+void image_adjoint_args(const cmx_ctx *c, ImgAdjArgs &ia);   // ... the adjoint pass on top: its tiling, Jt, Mx / My
+int ensure_jt(cmx_ctx *c);                                   // Jt plane, zeroed when it is a fresh allocation
+void claim_partner_clear(cmx_ctx *c, ImgArgs &a);            // this pass clears the ping-pong partner (before attach_tiles)
+// the five forms of an adjoint evaluation: what each one queues reads top to bottom in cmx_pipeline.cpp
+int adjoint_eval(cmx_ctx *c, int P);           // whole gradient evaluation: image pass unless Jt is resident, gather, finalize
+int adjoint_partial_sums(cmx_ctx *c, int P);   // split evaluation, first half: image pass, gather, this rank's sums; no finalize
+int adjoint_finalize_sums(cmx_ctx *c, int P);  // ... second half: finalize only
+int adjoint_cost_only(cmx_ctx *c, int P, bool arm_gate);  // image pass + cost-only finalize, Jt kept; arm_gate: it decides the gate
+int adjoint_gated_grad(cmx_ctx *c, int P);     // the gradient pass queued behind that one, into the second result block
+int finish_cost_only_speculative(cmx_ctx *c, int P);  // adjoint_cost_only (+ the gated pass when a hint is set), then the wait
 int collect_gated(cmx_ctx *c, int P, double *contrast, double *grad, bool *served);  // a df served by the pass already queued
 bool speculative_jt_ok(const cmx_ctx *c);
 int sync_and_collect(cmx_ctx *c, bool ends_in_finalize = false, bool finalize_ran = false);

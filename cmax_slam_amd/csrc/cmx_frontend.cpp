@@ -299,7 +299,7 @@ int cmx_frontend_finish(cmx_ctx *c, double *contrast, double *grad) {
     rc = collect_gated(c, 3, contrast, grad, &served);  // the gradient pass may already be in flight (cmx_hint_next_df)
     if (rc || served) return rc;
     const bool fused = c->fused_done;
-    if (!c->fused_full_done) rc = run_adjoint(c, 3);  // (one-launch evaluation: gather and finalize are already in flight)
+    if (!c->fused_full_done) rc = adjoint_eval(c, 3);  // (one-launch evaluation: gather and finalize are already in flight)
     if (!rc && fused) {
       // the fused image pass is exact only while every vote lands within reach of its chunk's tile (the tiles' arrival counts cover
       // kFuseReach = 56 px around it; votes beyond that, or a tile that gave up waiting, raise a flag in the fallback word): such
@@ -335,18 +335,17 @@ int cmx_frontend_finish(cmx_ctx *c, double *contrast, double *grad) {
         rc = fe_accumulate(c, om, 1, /*allow_fuse=*/again_fused, /*allow_full=*/again_fused);
         if (rc) return rc;
         if (!c->fused_full_done) {
-          rc = run_adjoint(c, 3);
+          rc = adjoint_eval(c, 3);
           if (rc) return rc;
         }
       }
-      *contrast = c->h_result[0];
-      for (int k = 0; k < 3; k++) grad[k] = c->h_result[2 + k];
+      read_result(c, 3, contrast, grad);
       return CMX_OK;
     }
   } else if (!grad && speculative_jt_ok(c)) {
     rc = finish_cost_only_speculative(c, 3);
     if (rc) return rc;
-    *contrast = c->h_result[0];
+    read_result(c, 3, contrast, grad);
     return CMX_OK;
   } else {
     c->gated_pending = false;
@@ -356,8 +355,7 @@ int cmx_frontend_finish(cmx_ctx *c, double *contrast, double *grad) {
   if (rc) return rc;
   rc = sync_and_collect(c, true);
   if (rc) return rc;
-  *contrast = c->h_result[0];
-  if (grad) for (int k = 0; k < 3; k++) grad[k] = c->h_result[2 + k];
+  read_result(c, 3, contrast, grad);
   return CMX_OK;
 }
 

@@ -21,7 +21,7 @@ static_assert(kHostShardsDefault >= 1 && kHostShardsDefault <= cmx::kHostShardsM
 int begin_accum(cmx_ctx *c, int nplanes, size_t np, bool fast) {
   c->pingpong_planes = 0;
   if (c->acc_dirty) {  // a split evaluation added to the accumulator rows and never reached its finalize (an error between the
-                       // two phases): every later gradient would carry those sums -- the buffers are all-zero between launches
+                       // two halves): every later gradient would carry those sums -- the buffers are all-zero between launches
     if (c->d_gacc) HIP_TRY(c, hipMemsetAsync(c->d_gacc, 0, kGaccDoubles * sizeof(double), c->stream));
     if (c->d_tail_counters) HIP_TRY(c, hipMemsetAsync(c->d_tail_counters, 0, kTailCounterWords * sizeof(unsigned), c->stream));
     c->acc_dirty = false;
@@ -238,11 +238,14 @@ static bool sobel_adjoint(const cmx_ctx *c) { return c->kind == KIND_FE && c->me
 // FinalizeArgs means the Sobel partial table of the derivative-plane form, run_image_and_finalize.)
 static int adjoint_finalize_measure(const cmx_ctx *c) { return sobel_adjoint(c) ? CMX_MEAN_SQUARE : c->measure; }
 
+// result words a finalize writes: contrast, mean, gradient (+ what a chained one appends)
+static int result_words(const FinalizeArgs &f) { return 2 + (f.P > f.gP ? f.P : f.gP) + (f.chain.sm ? kChainExtra : 0); }
+
 // every evaluation ends in exactly one finalize -- its own launch (here) or the tail of the evaluation's last kernel
 // (arm_tail) -- which carries the ticket sync_and_collect() waits for
 void issue_finalize(cmx_ctx *c, FinalizeArgs &f, bool with_reduce) {
   f.ticket = ++c->ticket_issued;
-  c->ticket_nout = 2 + (f.P > f.gP ? f.P : f.gP) + (f.chain.sm ? kChainExtra : 0);
+  c->ticket_nout = result_words(f);
   Span sp(c, CMX_T_FINAL, /*exact=*/true);
   if (with_reduce) launch_finalize(f, c->stream, sp.t0(), sp.t1());
   else launch_finalize_only(f, c->stream, sp.t0(), sp.t1());
@@ -270,10 +273,10 @@ bool arm_tail(cmx_ctx *c, FinalizeArgs &f, TailArgs &tail, bool gated) {
   }
   if (gated) {  // the gated pass reports to the second result block with its own ticket sequence
     f.ticket = ++c->ticket2_issued;
-    c->ticket2_nout = 2 + (f.P > f.gP ? f.P : f.gP) + (f.chain.sm ? kChainExtra : 0);
+    c->ticket2_nout = result_words(f);
   } else {
     f.ticket = ++c->ticket_issued;
-    c->ticket_nout = 2 + (f.P > f.gP ? f.P : f.gP) + (f.chain.sm ? kChainExtra : 0);
+    c->ticket_nout = result_words(f);
   }
   tail.counters = c->d_tail_counters;
   tail.fin = f;
@@ -300,6 +303,27 @@ bool arm_tail(cmx_ctx *c, FinalizeArgs &f, TailArgs &tail, bool gated) {
     c->hostfin_npix = f.npix;
   }
   return true;
+}
+
+// what every image pass takes from the context: size, blur, and the kind's sources (front end: the one vote plane)
+void image_args(const cmx_ctx *c, ImgArgs &a) {
+  a.W = c->imgW; a.H = c->imgH; a.r = c->radius;
+  memcpy(a.taps, c->taps, sizeof(a.taps));
+  a.src_a = c->d_accum;
+  if (c->kind == KIND_BE) {
+    a.src_b = c->d_accum + (size_t)c->imgW * c->imgH;
+    a.igp = c->ig_nonzero ? c->d_IGp : nullptr;
+    a.alpha = c->d_alpha;
+  }
+}
+
+// the pass clears the ping-pong partner while it is at it, once per evaluation (call before attach_tiles)
+void claim_partner_clear(cmx_ctx *c, ImgArgs &a) {
+  if (c->pingpong_planes > 0 && c->d_accum_alt && !c->alt_clean) {
+    a.zero_ptr = c->d_accum_alt;
+    a.zero_planes = c->pingpong_planes;
+    c->alt_clean = true;  // stream-ordered: clean by the time the next accumulate's splat runs
+  }
 }
 
 // ping-pong partner clearing + tile-occupancy flags of an image pass (see ImgArgs)
@@ -353,31 +377,12 @@ int run_image_and_finalize(cmx_ctx *c, int P, float *out_blur0, float *out_blurd
   const int W = c->imgW, H = c->imgH;
   const size_t np = (size_t)W * H;
   ImgArgs a{};
-  a.W = W;
-  a.H = H;
-  a.r = c->radius;
-  memcpy(a.taps, c->taps, sizeof(a.taps));
-  if (c->kind == KIND_FE) {
-    a.src_a = c->d_accum;
-    a.src_b = nullptr;
-    a.igp = nullptr;
-    a.alpha = nullptr;
-    a.dplanes = c->d_accum + np;
-  } else {
-    a.src_a = c->d_accum;
-    a.src_b = c->d_accum + np;
-    a.igp = c->ig_nonzero ? c->d_IGp : nullptr;
-    a.alpha = c->d_alpha;
-    a.dplanes = c->d_accum + 2 * np;
-  }
+  image_args(c, a);
+  a.dplanes = c->d_accum + (c->kind == KIND_FE ? 1 : 2) * np;
   a.P = P;
   a.out_blur0 = out_blur0;
   a.out_blurd = out_blurd;
-  if (c->pingpong_planes > 0 && c->d_accum_alt && !c->alt_clean) {
-    a.zero_ptr = c->d_accum_alt;
-    a.zero_planes = c->pingpong_planes;
-    c->alt_clean = true;  // stream-ordered: clean by the time the next accumulate's splat runs
-  }
+  claim_partner_clear(c, a);
   a.tiles_x = (W + kTileX - 1) / kTileX;
   a.nblk = a.tiles_x * ((H + kTileY - 1) / kTileY);
   const size_t nq = 2 + 2 * (size_t)P;
@@ -389,9 +394,17 @@ int run_image_and_finalize(cmx_ctx *c, int P, float *out_blur0, float *out_blurd
   if (rc) return rc;
   if (2 + (size_t)P > c->result_cap - 1) return fail(c, CMX_ERR_INVALID_ARG, "too many derivative planes (%d)", P);
   a.partials = c->d_partials;
+  FinalizeArgs f{};
+  f.P = P;
+  f.nblk = a.nblk;
+  f.measure = c->measure;
+  f.npix = (double)np;
+  f.partials = c->d_partials;
+  f.sums = c->d_sums;
+  f.result = result_ptr(c);
+  f.fallback = c->sort.d_fallback;
   if (c->measure == CMX_GRADIENT_MAGNITUDE && c->kind == KIND_FE) {
     // blurred planes -> scratch, then Sobel moments (reference local_focus_funcs.cpp:47-73), then finalize
-    const size_t np = (size_t)W * H;
     float *blur = out_blur0;
     if (!blur) {
       rc = ensure(c, c->d_scratch, c->scratch_cap, 7 * np);
@@ -410,25 +423,12 @@ int run_image_and_finalize(cmx_ctx *c, int P, float *out_blur0, float *out_blurd
     Span sp(c, CMX_T_IMAGE, /*exact=*/true);
     launch_image_moments(a, c->stream, sp.t0(), sp.t1());
     launch_sobel_moments(sa, c->stream);
-    FinalizeArgs f{};
-    f.P = 0; f.nblk = a.nblk; f.measure = 2; f.npix = (double)np;
-    f.partials = c->d_partials; f.sums = c->d_sums; f.result = result_ptr(c);
-    f.direct = 1;
+    f.P = 0; f.direct = 1;  // (measure 2: the derivative planes' moments are the Sobel partial table's)
     f.gpartials = c->d_gpartials; f.gblocks = sa.nblk; f.gP = P;
-    f.fallback = c->sort.d_fallback;
     issue_finalize(c, f, false);
     HIP_TRY(c, hipGetLastError());
     return CMX_OK;
   }
-  FinalizeArgs f{};
-  f.P = P;
-  f.nblk = a.nblk;
-  f.measure = c->measure;
-  f.npix = (double)np;
-  f.partials = c->d_partials;
-  f.sums = c->d_sums;
-  f.result = result_ptr(c);
-  f.fallback = c->sort.d_fallback;
   bool tailed = false;
   {
     Span sp(c, CMX_T_IMAGE, /*exact=*/true);
@@ -448,245 +448,287 @@ int run_image_and_finalize(cmx_ctx *c, int P, float *out_blur0, float *out_blurd
 
 // A cost-only evaluation that a gradient evaluation at the same parameters is likely to follow (the optimiser's f-then-df
 // pattern, CMX_OPT_REUSE_IMAGE): run the fused adjoint image pass instead of the moments-only pass, so that the df finds
-// Jt and the moment rows ready and launches its gather straight away (phase 3 of run_adjoint; +3..4 us per f, -12 us per df).
+// Jt and the moment rows ready and launches its gather straight away (adjoint_cost_only; +3..4 us per f, -12 us per df).
 bool speculative_jt_ok(const cmx_ctx *c) {
   return c->reuse_image && adjoint_ok(c) && !c->accum_external && !c->sharded() && c->last_P == 0 && c->n_packed > 0;
 }
 
-// adjoint gradient: fused image pass (B = G*A with its moments, Jt = G^T B^) -> gather over the events (S1, and S2 for
-// the votes next to the border) -> finalize: contrast from the moments, grad = (2/N)(S1 - mu*S2).
-// phase 0 = everything; 1 = up to the per-rank partial sums (d_gsum, 2P doubles); 2 = finalize from d_gsum.
-// (3: image pass + cost-only finalize, Jt kept; 4: the gated gradient pass behind it.)
-int run_adjoint(cmx_ctx *c, int P, int phase) {
-  const int W = c->imgW, H = c->imgH;
-  const size_t np = (size_t)W * H;
-  // image pass already done for these very planes (phase 2: by finish_begin; phase 0 after a speculative cost-only pass)
-  // phase 4: the gated gradient pass queued behind a cost-only evaluation (phase 3) of the same point -- gather + tail finalize
-  // into the second result block, running only if that evaluation's finalize opens the gate (cmx_hint_next_df)
-  const bool have_image = phase == 2 || ((phase == 0 || phase == 4) && c->jt_valid);
-  if (phase == 4 && !have_image) return CMX_OK;
+// ---- adjoint gradient: fused image pass (B = G*A with its moments, Jt = G^T B^) -> gather over the events (S1, and S2 for
+// the votes next to the border) -> finalize: contrast from the moments, grad = (2/N)(S1 - mu*S2).  First the steps, each
+// present once; the five forms of the evaluation (adjoint_eval ... adjoint_gated_grad, below them) queue them top to bottom.
+int ensure_jt(cmx_ctx *c) {
   float *jt_before = c->d_itilde;
-  int rc = ensure(c, c->d_itilde, c->itilde_cap, np);
-  if (rc) return rc;
+  if (int rc = ensure(c, c->d_itilde, c->itilde_cap, (size_t)c->imgW * c->imgH)) return rc;
   if (c->d_itilde != jt_before)  // tiles the image pass skips keep whatever they held: make that finite from the start
     HIP_TRY(c, hipMemsetAsync(c->d_itilde, 0, c->itilde_cap * sizeof(float), c->stream));
-  ImgAdjArgs ia{};
-  ImgArgs &a = ia.img;
-  const bool sobel = sobel_adjoint(c);  // (no composite-operator form: Sobel sits between G and G^T)
-  if (!sobel && c->composite_image && c->radius >= 1 && c->d_Mx && c->d_My && c->Mx_radius == c->radius) { ia.Mx = c->d_Mx; ia.My = c->d_My; }
-  a.W = W; a.H = H; a.r = c->radius;
-  memcpy(a.taps, c->taps, sizeof(a.taps));
-  a.src_a = c->d_accum;
-  if (c->kind == KIND_BE) {
-    a.src_b = c->d_accum + np;
-    a.igp = c->ig_nonzero ? c->d_IGp : nullptr;
-    a.alpha = c->d_alpha;
-  }
-  a.P = 0;
-  a.tiles_x = image_adjoint_tiles_x(W);
-  a.nblk = image_adjoint_tiles(W, H);
-  if (!have_image && c->pingpong_planes > 0 && c->d_accum_alt && !c->alt_clean) {
-    a.zero_ptr = c->d_accum_alt;
-    a.zero_planes = c->pingpong_planes;
-    c->alt_clean = true;
-  }
-  if (!have_image) {
-    rc = attach_tiles(c, a, /*may_skip=*/true);
-    if (rc) return rc;
-  }
+  return CMX_OK;
+}
+
+// the adjoint pass on top of image_args: its own tiling, Jt (ensure_jt first), the composite operator where it applies
+void image_adjoint_args(const cmx_ctx *c, ImgAdjArgs &ia) {
+  image_args(c, ia.img);
+  ia.img.P = 0;
+  ia.img.tiles_x = image_adjoint_tiles_x(c->imgW);
+  ia.img.nblk = image_adjoint_tiles(c->imgW, c->imgH);
   ia.jt = c->d_itilde;
-  rc = ensure(c, c->d_partials, c->partials_cap, (size_t)2 * a.nblk);
-  if (rc) return rc;
-  rc = ensure(c, c->d_sums, c->sums_cap, 2);
-  if (rc) return rc;
+  if (c->chain_active && !c->chain_first) ia.img.skip = &c->d_chain->done;  // device-driven solve: as the splat's (fe_args)
+  // (no composite-operator form of the Sobel pass: Sobel sits between G and G^T)
+  if (!sobel_adjoint(c) && c->composite_image && c->radius >= 1 && c->d_Mx && c->d_My && c->Mx_radius == c->radius) { ia.Mx = c->d_Mx; ia.My = c->d_My; }
+}
+
+struct AdjEval {    // what the steps of one evaluation share
+  int P;
+  bool fused_rows;  // the moment rows are those of a pass that ran inside the splat launch: d_fpartials, in the fused tiles' shape
+  ImgAdjArgs ia;
+  int gb, P2;                        // rows and doubles per row of the gather partial table
+  int slice_shift, parts_per_batch;  // back-end gather: events per slice (as a shift), slices per batch
+};
+
+// image arguments, and every buffer the evaluation may touch
+static int adjoint_begin(cmx_ctx *c, int P, AdjEval &e) {
+  e = AdjEval{};
+  e.P = P;
+  e.fused_rows = c->adj_fused;  // (until an image step of this evaluation writes d_partials)
+  if (int rc = ensure_jt(c)) return rc;
+  image_adjoint_args(c, e.ia);
+  if (int rc = ensure(c, c->d_partials, c->partials_cap, (size_t)2 * e.ia.img.nblk)) return rc;
+  if (int rc = ensure(c, c->d_sums, c->sums_cap, 2)) return rc;
   // rows of the gather partial table: front end = gather workgroups; back end = workgroups of the per-batch pass
-  const int gb = (c->kind == KIND_FE) ? fe_gather_blocks(c->n_packed) : be_batch_blocks(c->nb);
-  const int P2 = 2 * (P > 0 ? P : 1);
-  rc = ensure(c, c->d_gpartials, c->gpartials_cap, (size_t)gb * P2);
-  if (rc) return rc;
+  e.gb = (c->kind == KIND_FE) ? fe_gather_blocks(c->n_packed) : be_batch_blocks(c->nb);
+  e.P2 = 2 * (P > 0 ? P : 1);
+  if (int rc = ensure(c, c->d_gpartials, c->gpartials_cap, (size_t)e.gb * e.P2)) return rc;
   // four events per lane in the back-end gather when a lane's four events cannot straddle a batch boundary
-  const int slice_shift = (c->kind == KIND_BE && c->per_batch % 4 == 0) ? 8 : 6;
-  const int parts_per_batch = ((c->per_batch + (1 << slice_shift) - 2) >> slice_shift) + 1;
-  if (c->kind == KIND_BE) {
-    rc = ensure(c, c->d_vparts, c->vparts_cap, (size_t)(c->nb > 0 ? c->nb : 1) * parts_per_batch * 6);
-    if (rc) return rc;
-  }
+  e.slice_shift = (c->kind == KIND_BE && c->per_batch % 4 == 0) ? 8 : 6;
+  e.parts_per_batch = ((c->per_batch + (1 << e.slice_shift) - 2) >> e.slice_shift) + 1;
+  if (c->kind == KIND_BE)
+    if (int rc = ensure(c, c->d_vparts, c->vparts_cap, (size_t)(c->nb > 0 ? c->nb : 1) * e.parts_per_batch * 6)) return rc;
   if (2 + (size_t)P > c->result_cap - 2) return fail(c, CMX_ERR_INVALID_ARG, "too many parameters (%d)", P);
   if (!c->gsum_external) {
-    rc = ensure(c, c->d_gsum, c->gsum_cap, (size_t)P2);
-    if (rc) return rc;
-  } else if ((size_t)P2 > c->gsum_cap) {
-    return fail(c, CMX_ERR_INVALID_ARG, "external gradient buffer too small: %zu < %d doubles", c->gsum_cap, P2);
+    if (int rc = ensure(c, c->d_gsum, c->gsum_cap, (size_t)e.P2)) return rc;
+  } else if ((size_t)e.P2 > c->gsum_cap) {
+    return fail(c, CMX_ERR_INVALID_ARG, "external gradient buffer too small: %zu < %d doubles", c->gsum_cap, e.P2);
   }
-  a.partials = c->d_partials;
-  if (!have_image) c->adj_fused = false;  // the separate image pass below writes d_partials
-  const bool fused_rows = have_image && c->adj_fused && phase != 2;  // moment rows of a pass that ran inside the splat launch
+  e.ia.img.partials = c->d_partials;
+  return CMX_OK;
+}
+
+// where the finalize finds the gradient sums: nowhere (cost only), in the gather's block partials (one call), in the
+// accumulator rows or in d_gsum (the two ways of a split call: acc_rows)
+enum GradSums { GRAD_NONE, GRAD_BLOCKS, GRAD_ROWS, GRAD_GSUM };
+
+// split call with the evaluator's own communicator: the workgroups' sums go to the accumulator rows (FinalizeArgs::gacc),
+// the rows are all-reduced as they are (cmx_comm.cpp) and the finalize sums them -- no per-batch kernel, no
+// reduce_gpartials launch.  Callers that all-reduce cmx_grad_ptr() themselves keep the 2P-double buffer.
+// (rank-invariant condition: every rank must issue the same collective, also one whose shard is empty)
+static bool acc_rows(const cmx_ctx *c, int P) { return c->shard_acc && !c->deterministic && c->d_gacc && 2 * P <= kGaccStride && P > 0; }
+
+// second: the gated pass's result block (of a chain slot: its gradient block, stage 1); arm_gate: this finalize decides whether
+// the pass queued behind it runs.  The moment rows have the shape image_step left in adj_direct / adj_tile_count
+static FinalizeArgs finalize_args(const cmx_ctx *c, const AdjEval &e, GradSums grad, bool second = false, bool arm_gate = false) {
   FinalizeArgs f{};
   f.P = 0;
-  f.nblk = fused_rows ? c->fused_tiles_x * c->fused_tiles_y * kFuseStrips : a.nblk;
+  f.nblk = e.fused_rows ? c->fused_tiles_x * c->fused_tiles_y * kFuseStrips : e.ia.img.nblk;
   f.measure = adjoint_finalize_measure(c);
-  f.npix = (double)np;
-  f.partials = fused_rows ? c->d_fpartials : c->d_partials;
+  f.npix = (double)((size_t)c->imgW * c->imgH);
+  f.partials = e.fused_rows ? c->d_fpartials : c->d_partials;
   f.sums = c->d_sums;
-  f.result = phase == 4 ? c->d_result2 : result_ptr(c);
+  f.result = second ? c->d_result2 : result_ptr(c);
   if (c->chain_active) {  // device-driven solve: this finalize advances the machine; results go to the slot's blocks of the ring
-    f.result = phase == 4 ? c->chain_block_g : c->chain_block_a;
+    f.result = second ? c->chain_block_g : c->chain_block_a;
     f.chain.sm = &c->d_chain->sm;
     f.chain.x_req = c->d_chain->x_req;
     f.chain.done = &c->d_chain->done;
-    f.chain.stage = phase == 4 ? 1 : 0;
-    a.skip = &c->d_chain->done;
+    f.chain.stage = second ? 1 : 0;
   }
-  // (not the Sobel pass: it has no list form -- front-end images stay below kTileListMin tiles -- and takes its reach, 2r+2, itself)
-  if (!have_image && !sobel) {  // large panoramas: compact work list (a pre-pass kernel; partial rows become compact too)
-    rc = maybe_tile_list(c, a, 2 * c->radius);
-    if (rc) return rc;
-  }
-  bool direct = a.nblk <= 2048 || a.tile_list;  // few entries: finalize sums the per-tile moments itself
-  if (have_image) {  // the image pass ran earlier -- its partial rows have the shape decided there
-    direct = c->adj_direct;
-    a.tile_count = c->adj_tile_count;
-  } else {
-    c->adj_direct = direct;
-    c->adj_tile_count = a.tile_count;
-  }
-  f.direct = direct ? 1 : 0;
-  f.nvalid = a.tile_count;
+  f.direct = c->adj_direct ? 1 : 0;
+  f.nvalid = c->adj_tile_count;
   f.mu_free = 1;
-  // split call with the evaluator's own communicator: the workgroups' sums go to the accumulator rows (FinalizeArgs::gacc),
-  // the rows are all-reduced as they are (cmx_comm.cpp) and the finalize sums them -- no per-batch kernel, no
-  // reduce_gpartials launch.  Callers that all-reduce cmx_grad_ptr() themselves keep the 2P-double buffer.
-  // (rank-invariant condition: every rank must issue the same collective, also one whose shard is empty)
-  const bool acc_split = phase != 0 && c->shard_acc && !c->deterministic && c->d_gacc && 2 * P <= kGaccStride && P > 0;
-  if (phase == 0 || phase == 4) {  // single call: finalize sums the gather kernel's block partials itself
-    f.gpartials = c->d_gpartials;
-    f.gblocks = gb;
-  } else if (acc_split) {
-    f.gacc = c->d_gacc;
-    f.gacc_stride = kGaccStride;
-  } else {           // split call: finalize reads the (all-reduced) per-parameter sums
-    f.gpartials = c->d_gsum;
-    f.gblocks = 1;
-  }
-  f.gP = P;
+  if (grad == GRAD_BLOCKS) { f.gpartials = c->d_gpartials; f.gblocks = e.gb; }
+  else if (grad == GRAD_ROWS) { f.gacc = c->d_gacc; f.gacc_stride = kGaccStride; }
+  else if (grad == GRAD_GSUM) { f.gpartials = c->d_gsum; f.gblocks = 1; }  // the (all-reduced) per-parameter sums
+  f.gP = grad == GRAD_NONE ? 0 : e.P;
   f.fallback = c->sort.d_fallback;
-  if (phase == 2) {
-    issue_finalize(c, f, false);
-    HIP_TRY(c, hipGetLastError());
-    c->acc_dirty = false;  // that finalize stores the zeros back
-    return CMX_OK;
+  if (arm_gate) { f.gate_out = c->d_gate; f.gate_thr = c->gate_thr; f.gate_mode = c->gate_mode; }
+  return f;
+}
+
+// the image pass for planes that have none yet; builds `f` once the shape of its moment rows is decided.  cost_tailed (the
+// cost-only form): the pass may carry the finalize as its tail, and whether it does
+static int image_step(cmx_ctx *c, AdjEval &e, GradSums grad, FinalizeArgs &f, bool arm_gate = false, bool *cost_tailed = nullptr) {
+  ImgArgs &a = e.ia.img;
+  const bool sobel = sobel_adjoint(c);
+  claim_partner_clear(c, a);  // (before attach_tiles: it decides its flag memset from a.zero_ptr)
+  if (int rc = attach_tiles(c, a, /*may_skip=*/true)) return rc;
+  Span sp(c, CMX_T_IMAGE, /*exact=*/true);
+  // large panoramas: compact work list (a pre-pass kernel; partial rows become compact too)
+  // (not the Sobel pass: it has no list form -- front-end images stay below kTileListMin tiles -- and takes its reach, 2r+2, itself)
+  if (!sobel)
+    if (int rc = maybe_tile_list(c, a, 2 * c->radius)) return rc;
+  c->adj_direct = a.nblk <= 2048 || a.tile_list;  // few entries: finalize sums the per-tile moments itself
+  c->adj_tile_count = a.tile_count;
+  c->adj_fused = e.fused_rows = false;  // this pass writes d_partials
+  f = finalize_args(c, e, grad, /*second=*/false, arm_gate);
+  // the three-phase image pass has the registers to carry the finalize as its tail
+  // (the five-phase kernel did not: inlined, its taps spilled and the pass went 11 -> 20 us)
+  if (cost_tailed && !sobel && e.ia.Mx && c->radius == 4) *cost_tailed = arm_tail(c, f, a.tail);
+  if (sobel) launch_image_adjoint_sobel(e.ia, c->stream, sp.t0(), sp.t1());
+  else launch_image_adjoint(e.ia, c->stream, sp.t0(), sp.t1());
+  if (!c->adj_direct) launch_reduce_partials(f, c->stream);
+  return CMX_OK;
+}
+
+// ---- gather step.  What the launch carries behind its sums: the finalize as its tail (whole and gated forms), the
+// accumulator rows of a split (f.gacc; no counters: accumulators without the tail), or nothing
+enum GatherForm { GATHER_WHOLE, GATHER_GATED, GATHER_SPLIT };
+static bool gate_fits(const FeGatherArgs &) { return true; }
+static bool gate_fits(const BeGatherArgs &g) { return be_gather_folds(g); }  // only the one-kernel form can be gated
+// false: no tail available in this configuration, or no gather that fits: no gated pass (the df will run as usual)
+template <class GatherArgs> static bool arm_gather(cmx_ctx *c, GatherForm form, FinalizeArgs &f, GatherArgs &g, bool *tailed) {
+  if (form != GATHER_SPLIT) *tailed = arm_tail(c, f, g.tail, form == GATHER_GATED);
+  else if (f.gacc) g.tail.fin = f;
+  if (form != GATHER_GATED) return true;
+  if (!*tailed || !gate_fits(g)) return false;
+  g.gate = c->d_gate;
+  c->gated_pending = true;
+  c->gated_launches++;
+  return true;
+}
+
+static int fe_gather_step(cmx_ctx *c, const AdjEval &e, FinalizeArgs &f, GatherForm form, Span &sp, bool *tailed) {
+  FeGatherArgs g{};
+  g.ev = fe_args(c, c->last_x);
+  g.itilde = c->d_itilde;
+  g.gpartials = c->d_gpartials;
+  g.cx = c->d_cx; g.cy = c->d_cy; g.r = c->radius;
+  if (c->splat_mode == 1 && c->bin_valid && !c->deterministic) {  // tile order: the sorted arrays the LDS splat consumes
+    // (deterministic mode: time order -- the order inside a tile depends on the scatter's atomics)
+    g.sxy = c->sort.d_sxy;
+    g.sbatch = c->sort.d_sbatch;
+    if (c->streams_valid) { g.sb = c->d_sb; g.sdt = c->d_sdt; }
   }
-  if (phase == 1 && acc_split) c->acc_dirty = true;  // until phase 2's finalize has been queued (see begin_accum)
-  if (phase == 3) {
-    f.gP = 0;
-    f.gpartials = nullptr;
-    f.gblocks = 0;
-    if (c->gate_arm) {  // this finalize decides whether the pass queued behind it runs
-      f.gate_out = c->d_gate;
-      f.gate_thr = c->gate_thr;
-      f.gate_mode = c->gate_mode;
+  if (!g.sxy && c->d_lut2 && c->n_packed > 0) {  // time-ordered gather: the events' bearings as a stream, once per packet
+    if (!c->tb_valid) {
+      if (int rc = ensure(c, c->d_tb, c->tb_cap, (size_t)2 * c->n_packed)) return rc;
+      launch_bearing_stream(c->d_xy, c->d_lut2, c->W, c->n_packed, c->d_tb, c->stream);
+      c->tb_valid = true;
     }
+    g.tb = c->d_tb;
   }
-  bool image_tailed = false;
-  if (!have_image) {
-    Span sp(c, CMX_T_IMAGE, /*exact=*/true);
-    // cost-only with Jt kept (phase 3): the three-phase image pass has the registers to carry the finalize as its tail
-    // (the five-phase kernel did not: inlined, its taps spilled and the pass went 11 -> 20 us)
-    if (phase == 3 && !sobel && ia.Mx && c->radius == 4) image_tailed = arm_tail(c, f, a.tail);
-    if (sobel) launch_image_adjoint_sobel(ia, c->stream, sp.t0(), sp.t1());
-    else launch_image_adjoint(ia, c->stream, sp.t0(), sp.t1());
-    if (!direct) launch_reduce_partials(f, c->stream);
+  if (c->n_packed > 0) {
+    if (arm_gather(c, form, f, g, tailed)) launch_fe_gather(g, c->stream, sp.t0(), sp.t1());
+  } else {
+    HIP_TRY(c, hipMemsetAsync(c->d_gpartials, 0, (size_t)e.gb * e.P2 * sizeof(double), c->stream));
   }
-  if (phase == 3) {  // cost-only: contrast from the moment rows; Jt and the rows stay for a gradient call at the same point
-    if (!image_tailed) issue_finalize(c, f, false);
-    HIP_TRY(c, hipGetLastError());
-    c->jt_valid = true;
-    c->spec_images++;
-    return CMX_OK;
+  return CMX_OK;
+}
+
+static int be_gather_step(cmx_ctx *c, const AdjEval &e, FinalizeArgs &f, GatherForm form, Span &sp, bool *tailed) {
+  BeGatherArgs g{};
+  g.ev = be_args(c);
+  g.itilde = c->d_itilde;
+  g.P = e.P;
+  g.gpartials = c->d_gpartials;
+  g.cx = c->d_cx; g.cy = c->d_cy; g.r = c->radius;
+  g.vparts = c->d_vparts;
+  g.parts_per_batch = e.parts_per_batch;
+  g.slice_shift = e.slice_shift;
+  g.deterministic = c->deterministic ? 1 : 0;
+  g.fold = c->fold_batch ? 1 : 0;
+  if (c->d_lut2 && e.slice_shift == 8 && c->n_packed > 0) {  // once per window: the events' bearings in time order
+    if (int rc = be_ensure_time_bearings(c)) return rc;
+    g.tb = c->d_tb;
   }
-  if (have_image && phase == 0 && !c->fused_done) c->spec_hits++;
-  const bool gated = phase == 4;
-  bool tailed = false;  // the gather launch carries the finalize
-  {
-    // (a gated launch may return on its first instruction: it is not a sample of the gather's duration)
-    Span sp(c, CMX_T_GATHER, /*exact=*/true, /*enable=*/!gated);
-    if (c->kind == KIND_FE) {
-      FeGatherArgs g{};
-      g.ev = fe_args(c, c->last_x);
-      g.itilde = c->d_itilde;
-      g.gpartials = c->d_gpartials;
-      g.cx = c->d_cx; g.cy = c->d_cy; g.r = c->radius;
-      if (c->splat_mode == 1 && c->bin_valid && !c->deterministic) {  // tile order: the sorted arrays the LDS splat consumes
-        // (deterministic mode: time order -- the order inside a tile depends on the scatter's atomics)
-        g.sxy = c->sort.d_sxy;
-        g.sbatch = c->sort.d_sbatch;
-        if (c->streams_valid) { g.sb = c->d_sb; g.sdt = c->d_sdt; }
-      }
-      if (!g.sxy && c->d_lut2 && c->n_packed > 0) {  // time-ordered gather: the events' bearings as a stream, once per packet
-        if (!c->tb_valid) {
-          int rc2 = ensure(c, c->d_tb, c->tb_cap, (size_t)2 * c->n_packed);
-          if (rc2) return rc2;
-          launch_bearing_stream(c->d_xy, c->d_lut2, c->W, c->n_packed, c->d_tb, c->stream);
-          c->tb_valid = true;
-        }
-        g.tb = c->d_tb;
-      }
-      if (c->n_packed > 0) {
-        if (phase == 0 || gated) tailed = arm_tail(c, f, g.tail, gated);
-        else if (acc_split) g.tail.fin = f;  // (no counters: accumulators without the tail)
-        if (gated) {
-          if (!tailed) return CMX_OK;  // no tail available in this configuration: no gated pass (the df will run as usual)
-          g.gate = c->d_gate;
-          c->gated_pending = true;
-          c->gated_launches++;
-        }
-        launch_fe_gather(g, c->stream, sp.t0(), sp.t1());
-      } else {
-        HIP_TRY(c, hipMemsetAsync(c->d_gpartials, 0, (size_t)gb * P2 * sizeof(double), c->stream));
-      }
+  if (c->n_packed > 0 && e.P > 0) {
+    if (!arm_gather(c, form, f, g, tailed)) return CMX_OK;
+    if (be_gather_folds(g)) {  // one kernel: gather, per-batch pass and finalize
+      launch_be_gather(g, c->nb, c->stream, sp.t0(), sp.t1(), nullptr, nullptr);
     } else {
-      BeGatherArgs g{};
-      g.ev = be_args(c);
-      g.itilde = c->d_itilde;
-      g.P = P;
-      g.gpartials = c->d_gpartials;
-      g.cx = c->d_cx; g.cy = c->d_cy; g.r = c->radius;
-      g.vparts = c->d_vparts;
-      g.parts_per_batch = parts_per_batch;
-      g.slice_shift = slice_shift;
-      g.deterministic = c->deterministic ? 1 : 0;
-      if (c->d_lut2 && slice_shift == 8 && c->n_packed > 0) {  // once per window: the events' bearings in time order
-        const int rc2 = be_ensure_time_bearings(c);
-        if (rc2) return rc2;
-        g.tb = c->d_tb;
-      }
-      if (c->n_packed > 0 && P > 0) {
-        if (phase == 0 || gated) tailed = arm_tail(c, f, g.tail, gated);
-        else if (acc_split) g.tail.fin = f;  // (no counters: accumulators without the tail)
-        g.fold = c->fold_batch ? 1 : 0;
-        if (gated) {  // only the one-kernel form can be gated
-          if (!tailed || !be_gather_folds(g)) return CMX_OK;
-          g.gate = c->d_gate;
-          c->gated_pending = true;
-          c->gated_launches++;
-        }
-        if (be_gather_folds(g)) {  // one kernel: gather, per-batch pass and finalize
-          launch_be_gather(g, c->nb, c->stream, sp.t0(), sp.t1(), nullptr, nullptr);
-        } else {
-          Span sb(c, CMX_T_BATCH, /*exact=*/true);
-          launch_be_gather(g, c->nb, c->stream, sp.t0(), sp.t1(), sb.t0(), sb.t1());
-        }
-      } else {
-        HIP_TRY(c, hipMemsetAsync(c->d_gpartials, 0, (size_t)gb * P2 * sizeof(double), c->stream));
-      }
+      Span sb(c, CMX_T_BATCH, /*exact=*/true);
+      launch_be_gather(g, c->nb, c->stream, sp.t0(), sp.t1(), sb.t0(), sb.t1());
     }
-    if (phase == 1 && !acc_split) launch_reduce_gpartials(c->d_gpartials, gb, 2 * P, c->d_gsum, c->stream);
+  } else {
+    HIP_TRY(c, hipMemsetAsync(c->d_gpartials, 0, (size_t)e.gb * e.P2 * sizeof(double), c->stream));
   }
-  if (phase == 1 || gated) {
-    HIP_TRY(c, hipGetLastError());
-    return CMX_OK;
+  return CMX_OK;
+}
+
+static int gather_step(cmx_ctx *c, const AdjEval &e, FinalizeArgs &f, GatherForm form, bool *tailed) {
+  // (a gated launch may return on its first instruction: it is not a sample of the gather's duration)
+  Span sp(c, CMX_T_GATHER, /*exact=*/true, /*enable=*/form != GATHER_GATED);
+  return c->kind == KIND_FE ? fe_gather_step(c, e, f, form, sp, tailed) : be_gather_step(c, e, f, form, sp, tailed);
+}
+
+// ---- the five forms.  Whole gradient evaluation: image pass unless Jt is resident (a cost-only evaluation of this point, or
+// a splat that carried the pass), gather with the finalize as its tail where one is available, else the finalize launch
+int adjoint_eval(cmx_ctx *c, int P) {
+  AdjEval e;
+  FinalizeArgs f{};
+  bool tailed = false;  // the gather launch carries the finalize
+  if (int rc = adjoint_begin(c, P, e)) return rc;
+  if (c->jt_valid) {
+    f = finalize_args(c, e, GRAD_BLOCKS);
+    if (!c->fused_done) c->spec_hits++;
+  } else if (int rc = image_step(c, e, GRAD_BLOCKS, f)) {
+    return rc;
   }
+  if (int rc = gather_step(c, e, f, GATHER_WHOLE, &tailed)) return rc;
   if (!tailed) issue_finalize(c, f, false);
+  HIP_TRY(c, hipGetLastError());
+  return CMX_OK;
+}
+
+// split evaluation, first half: image pass and gather, up to this rank's partial sums (accumulator rows, or d_gsum: 2P doubles)
+int adjoint_partial_sums(cmx_ctx *c, int P) {
+  AdjEval e;
+  FinalizeArgs f{};
+  bool tailed = false;
+  if (int rc = adjoint_begin(c, P, e)) return rc;
+  const bool rows = acc_rows(c, P);
+  if (rows) c->acc_dirty = true;  // until adjoint_finalize_sums has queued its finalize (see begin_accum)
+  if (int rc = image_step(c, e, rows ? GRAD_ROWS : GRAD_GSUM, f)) return rc;
+  if (int rc = gather_step(c, e, f, GATHER_SPLIT, &tailed)) return rc;
+  if (!rows) launch_reduce_gpartials(c->d_gpartials, e.gb, 2 * P, c->d_gsum, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return CMX_OK;
+}
+
+// ... second half: the finalize, from the (all-reduced) sums
+int adjoint_finalize_sums(cmx_ctx *c, int P) {
+  AdjEval e;
+  if (int rc = adjoint_begin(c, P, e)) return rc;
+  e.fused_rows = false;  // the first half ran its own image pass, whatever a splat in between may have left
+  FinalizeArgs f = finalize_args(c, e, acc_rows(c, P) ? GRAD_ROWS : GRAD_GSUM);
+  issue_finalize(c, f, false);
+  HIP_TRY(c, hipGetLastError());
+  c->acc_dirty = false;  // that finalize stores the zeros back
+  return CMX_OK;
+}
+
+// cost only: contrast from the moment rows; Jt and the rows stay for a gradient call at the same point (speculative_jt_ok).
+// arm_gate: the finalize also decides whether the pass queued behind it (adjoint_gated_grad) runs
+int adjoint_cost_only(cmx_ctx *c, int P, bool arm_gate) {
+  AdjEval e;
+  FinalizeArgs f{};
+  bool tailed = false;  // the image launch carries the finalize
+  if (int rc = adjoint_begin(c, P, e)) return rc;
+  if (int rc = image_step(c, e, GRAD_NONE, f, arm_gate, &tailed)) return rc;
+  if (!tailed) issue_finalize(c, f, false);
+  HIP_TRY(c, hipGetLastError());
+  c->jt_valid = true;
+  c->spec_images++;
+  return CMX_OK;
+}
+
+// the gradient pass queued behind a cost-only evaluation of the same point: gather + tail finalize into the second result
+// block, running only if that evaluation's finalize opens the gate (cmx_hint_next_df).  Sets gated_pending when it could be queued
+int adjoint_gated_grad(cmx_ctx *c, int P) {
+  if (!c->jt_valid) return CMX_OK;
+  AdjEval e;
+  bool tailed = false;
+  if (int rc = adjoint_begin(c, P, e)) return rc;
+  FinalizeArgs f = finalize_args(c, e, GRAD_BLOCKS, /*second=*/true);
+  if (int rc = gather_step(c, e, f, GATHER_GATED, &tailed)) return rc;
+  if (!c->gated_pending) return CMX_OK;  // given up: nothing was launched
   HIP_TRY(c, hipGetLastError());
   return CMX_OK;
 }
@@ -845,15 +887,13 @@ bool can_reuse(const cmx_ctx *c, const double *x, int n, bool want_grad) {
 int finish_cost_only_speculative(cmx_ctx *c, int P) {
   const bool want_gate = c->gated_df && c->gate_mode != 0 && !c->sharded() && !c->accum_external && c->ticket_wait;
   c->gated_pending = false;
-  c->gate_arm = want_gate;
-  int rc = run_adjoint(c, P, /*phase=*/3);
-  c->gate_arm = false;
+  int rc = adjoint_cost_only(c, P, /*arm_gate=*/want_gate);
   const int mode = c->gate_mode;
   const double thr = c->gate_thr;
   c->gate_mode = 0;  // the hint is for ONE evaluation
   if (rc) return rc;
   if (want_gate) {
-    rc = run_adjoint(c, P, /*phase=*/4);  // sets gated_pending when the pass could be queued
+    rc = adjoint_gated_grad(c, P);  // sets gated_pending when the pass could be queued
     if (rc) return rc;
   }
   rc = sync_and_collect(c, true);  // waits for the cost-only finalize's ticket, not for the pass queued behind it
@@ -874,28 +914,27 @@ int collect_gated(cmx_ctx *c, int P, double *contrast, double *grad, bool *serve
     if (reinterpret_cast<const unsigned long long *>(c->h_result2)[kTicketSlot] != c->ticket2_issued)
       return CMX_OK;  // the stream is idle and the pass did not report (its gate stayed shut): ordinary gradient pass
   }
-  *contrast = c->h_result2[0];
-  for (int k = 0; k < P; k++) grad[k] = c->h_result2[2 + k];
+  read_result(c, P, contrast, grad, c->h_result2);
   c->gated_hits++;
   c->spec_hits++;
   *served = true;
   return CMX_OK;
 }
 
-// ---- three-phase finish for sharded adjoint evaluations: begin (image, adjoint blur, gather -> partial gradient
+// ---- three-step finish for sharded adjoint evaluations: begin (image, adjoint blur, gather -> partial gradient
 // sums on the device), caller all-reduces cmx_grad_ptr(), end (finalize + read-back)
 int finish_begin(cmx_ctx *c, int kind, int want_grad) {
   if (!c || c->kind != kind) return fail(c, CMX_ERR_STATE, "wrong context kind");
   if (!c->accumulated) return fail(c, CMX_ERR_STATE, "finish_begin without accumulate");
   int rc = bind_device(c);
   if (rc) return rc;
-  const int P = (kind == KIND_FE) ? 3 : 3 * (c->K - c->num_fixed);
+  const int P = n_params(c);
   if (kind == KIND_BE) {
     rc = be_first_iter(c);
     if (rc) return rc;
   }
   if (want_grad && c->last_adjoint) {
-    rc = run_adjoint(c, P, 1);
+    rc = adjoint_partial_sums(c, P);
     c->pending_P = P;
   } else {
     if (want_grad && c->last_P != P) return fail(c, CMX_ERR_STATE, "gradient requested but accumulate ran without it");
@@ -912,16 +951,14 @@ int finish_end(cmx_ctx *c, int kind, double *contrast, double *grad) {
   if (!contrast) return fail(c, CMX_ERR_INVALID_ARG, "null contrast");
   int rc = bind_device(c);
   if (rc) return rc;
-  const int P = (kind == KIND_FE) ? 3 : 3 * (c->K - c->num_fixed);
   if (c->pending_P >= 0) {
-    rc = run_adjoint(c, c->pending_P, 2);
+    rc = adjoint_finalize_sums(c, c->pending_P);
     if (rc) return rc;
   }
   c->finish_pending = false;
   rc = sync_and_collect(c, true);
   if (rc) return rc;
-  *contrast = c->h_result[0];
-  if (grad) for (int k = 0; k < P; k++) grad[k] = c->h_result[2 + k];
+  read_result(c, n_params(c), contrast, grad);
   return CMX_OK;
 }
 int cmx_frontend_finish_begin(cmx_ctx *c, int want_grad) { return finish_begin(c, KIND_FE, want_grad); }
@@ -956,7 +993,7 @@ static int eval_many(cmx_ctx *c, int kind, int m, const double *xs, double *cont
   if (c->sharded()) return fail(c, CMX_ERR_STATE, "eval_many is not available with a communicator attached");
   int rc = bind_device(c);
   if (rc) return rc;
-  const int n = kind == KIND_FE ? 3 : 3 * (c->K - c->num_fixed);
+  const int n = n_params(c);
   constexpr int kBlock = 4096;  // doubles per evaluation: the layout of the one-evaluation result buffer (slots at its tail)
   if ((size_t)m > c->many_cap) {
     if (c->h_many) HIP_TRY(c, hipHostFree(c->h_many));
@@ -979,7 +1016,7 @@ static int eval_many(cmx_ctx *c, int kind, int m, const double *xs, double *cont
       if (rc) break;
     }
     c->result_override = c->d_many + (size_t)i * kBlock;
-    if (grads && c->last_adjoint) rc = run_adjoint(c, n);
+    if (grads && c->last_adjoint) rc = adjoint_eval(c, n);
     else rc = run_image_and_finalize(c, grads ? n : 0, nullptr, nullptr);
     c->result_override = nullptr;
   }
@@ -988,11 +1025,7 @@ static int eval_many(cmx_ctx *c, int kind, int m, const double *xs, double *cont
   const hipError_t e = hipStreamSynchronize(c->stream);
   if (rc) return rc;
   HIP_TRY(c, e);
-  for (int i = 0; i < m; i++) {
-    const double *r = c->h_many + (size_t)i * kBlock;
-    contrasts[i] = r[0];
-    if (grads) for (int k = 0; k < n; k++) grads[(size_t)i * n + k] = r[2 + k];
-  }
+  for (int i = 0; i < m; i++) read_result(c, n, contrasts + i, grads ? grads + (size_t)i * n : nullptr, c->h_many + (size_t)i * kBlock);
   if (m > 0 && c->n_packed > 0 && c->last_used_lds) {
     // the planes hold the votes of the list's LAST point: count and reach flags of that point's block, as sync_and_collect takes them
     const double slot = c->h_many[(size_t)(m - 1) * kBlock + kFallbackSlot];
