@@ -24,6 +24,8 @@ OPT_COMPOSITE_IMAGE, OPT_FOLD_BATCH, OPT_GATED_DF, OPT_CHAIN_SOLVE, OPT_FUSED_IM
 DIAG_FORCE_CROSS_DEVICE, DIAG_RECON_SLICE_EVENTS = 1, 2  # cmx_diag_set keys (include/cmax_hip_diag.h)
 WARP_F64, WARP_F32 = 0, 1  # cmx_backend_recon_warp*: output format
 WARP_SAMPLED, WARP_INSIDE = 1, 2  # ... and the flag bits
+POL_MONO8, POL_BGR8 = 0, 1  # cmx_backend_recon_pol_render: mode
+AOS_DVS_POLARITY = 12  # byte offset of dvs_msgs::Event's polarity
 PLANE_IL_OLD, PLANE_IL_NEW, PLANE_IWE, PLANE_DERIV0 = 0, 1, 2, 16
 T_SPLAT, T_IMAGE, T_POSE, T_GATHER, T_ZERO, T_COMM, T_FINAL, T_BATCH, T_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8
 T_NAMES = ("splat", "image", "pose", "gather", "zero", "comm", "final", "batch")
@@ -32,6 +34,7 @@ c_dp = C.POINTER(C.c_double)
 c_fp = C.POINTER(C.c_float)
 c_u16p = C.POINTER(C.c_uint16)
 c_i64p = C.POINTER(C.c_int64)
+c_u8p = C.POINTER(C.c_uint8)
 ctx_p = C.c_void_p
 
 # every symbol include/cmax_hip.h declares: (restype, argtypes)
@@ -111,6 +114,9 @@ SYMBOLS = {
     "cmx_events_last_error": (C.c_char_p, [C.c_void_p]),
     "cmx_events_push": (C.c_int, [C.c_void_p, C.c_int64, c_u16p, c_u16p, c_i64p]),
     "cmx_events_push_aos": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(AosLayout)]),
+    "cmx_events_push_pol": (C.c_int, [C.c_void_p, C.c_int64, c_u16p, c_u16p, c_i64p, c_u8p]),
+    "cmx_events_push_aos_pol": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(AosLayout), C.c_size_t]),
+    "cmx_events_has_polarity": (C.c_int, [C.c_void_p]),
     "cmx_frontend_set_packet_aos": (C.c_int, [ctx_p, C.c_int64, C.c_void_p, C.POINTER(AosLayout), C.c_int64, C.c_double, C.c_double,
                                             C.c_double, C.c_double, C.c_int, C.c_double, C.c_int]),
     "cmx_backend_set_window_aos": (C.c_int, [ctx_p, C.c_int64, C.c_void_p, C.POINTER(AosLayout), C.c_int, C.c_int, c_dp, C.c_int64,
@@ -130,6 +136,12 @@ SYMBOLS = {
     "cmx_backend_recon_warp_aos": (C.c_int, [ctx_p, C.c_int64, C.c_void_p, C.POINTER(AosLayout), C.c_int, C.c_void_p, C.c_void_p]),
     "cmx_backend_recon_warp_from": (C.c_int, [ctx_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "cmx_backend_recon_warp_from_device": (C.c_int, [ctx_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "cmx_backend_recon_pol_add": (C.c_int, [ctx_p, C.c_int64, c_u16p, c_u16p, c_i64p, c_u8p]),
+    "cmx_backend_recon_pol_add_aos": (C.c_int, [ctx_p, C.c_int64, C.c_void_p, C.POINTER(AosLayout), C.c_size_t]),
+    "cmx_backend_recon_pol_add_from": (C.c_int, [ctx_p, C.c_void_p, C.c_int64, C.c_int64]),
+    "cmx_backend_recon_pol_get": (C.c_int, [ctx_p, c_fp, c_fp, c_i64p, c_i64p]),
+    "cmx_backend_recon_pol_render": (C.c_int, [ctx_p, C.c_double, C.c_int, c_u8p]),
+    "cmx_backend_recon_pol_reset": (C.c_int, [ctx_p]),
     "cmx_backend_recon_get": (C.c_int, [ctx_p, c_fp, c_i64p, c_i64p]),
     "cmx_backend_recon_render": (C.c_int, [ctx_p, C.c_double, c_dp, C.POINTER(C.c_uint8)]),
     "cmx_backend_recon_end": (C.c_int, [ctx_p]),

@@ -332,6 +332,7 @@ struct cmx_events {
     int device = 0;
     uint32_t *d_xy[2] = {nullptr, nullptr};  // x | y << 16 ; two buffers: drop_before compacts into the other one
     int64_t *d_t[2] = {nullptr, nullptr};
+    uint8_t *d_pol[2] = {nullptr, nullptr};  // polarity, 0 / 1 per event, parallel to d_xy / d_t: allocated by the first _pol push
     hipStream_t stream = nullptr;            // uploads / compactions of the replicas run side by side
   };
   std::vector<Replica> rep;
@@ -339,6 +340,9 @@ struct cmx_events {
   uint32_t *h_xy = nullptr;  // pinned staging of a push (packed coordinates, then the timestamps): one host pass, N async uploads
   int64_t *h_tp = nullptr;
   size_t stage_cap = 0;
+  uint8_t *h_pol = nullptr;  // ... and of a _pol push's polarity bytes
+  size_t pol_stage_cap = 0;
+  bool has_pol = false;      // the events held carry polarity: all of them or none (decided by the first push into an empty store)
   std::vector<int64_t> h_t;  // host mirror of the timestamps (per-batch pose times are formed on the host)
   std::string err;
   const Replica *on(int dev) const {

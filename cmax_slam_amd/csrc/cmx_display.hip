@@ -11,6 +11,8 @@
 //   tone_*_kernel     reads the two keys, forms the fp64 scale / fp32 (a, b) pair of cv::normalize itself, 4 pixels per lane
 //                     in, one packed 32-bit store (mono) or three (BGR) out
 //   fov_kernel        2 (W + H) threads, fp64 projection of the sensor border, byte stores into the BGR image
+// and, for the signed polarity map of a reconstruction (no counterpart in the reference), range_signed_kernel / tone_signed_kernel:
+// the same two steps over the difference of an ON and an OFF plane.
 // cv::normalize(NORM_MINMAX) is  scale = (hi - lo > DBL_EPSILON) ? (dmax - dmin) / (hi - lo) : 0,  shift = dmin - lo * scale
 // in fp64, then convertTo: fp32 multiply, fp32 add (the build has -ffp-contract=off), and for an 8-bit destination
 // saturate_cast<uchar>(cvRound(.)) = round half to even.
@@ -163,6 +165,88 @@ __global__ __launch_bounds__(kDispThreads) void tone_map_kernel(const float *__r
   }
 }
 
+// ---- signed polarity map (cmx_backend_recon_pol_render): s = ON - OFF, m = max |s|, v = sign(s) (|s| / m)^gamma in fp32;
+//   mono8: rint(127.5f + 127.5f v), so OFF is dark, ON is bright and no votes is 128;
+//   bgr8 on white: a = rint(255 |v|), ON (B, G, R) = (255 - a, 255 - a, 255) red, OFF (255, 255 - a, 255 - a) blue.
+// range_kernel's reduction over the difference of the two planes: its extremes give m = max(|lo|, |hi|) -- min / max are exact,
+// so m does not depend on the order.  The planes are n floats each; 16-byte loads when both start on a 16-byte boundary.
+__global__ __launch_bounds__(kDispThreads) void range_signed_kernel(const float *__restrict__ on, const float *__restrict__ off, size_t n,
+                                                                    unsigned *range) {
+  float lo = INFINITY, hi = -INFINITY;
+  const bool vec = (((uintptr_t)on | (uintptr_t)off) & 15) == 0;
+  const size_t n4 = vec ? n / 4 : 0, stride = (size_t)gridDim.x * kDispThreads, t0 = (size_t)blockIdx.x * kDispThreads + threadIdx.x;
+  for (size_t i = t0; i < n4; i += stride) {
+    const float4 a = reinterpret_cast<const float4 *>(on)[i], b = reinterpret_cast<const float4 *>(off)[i];
+    minmax4(make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w), lo, hi);
+  }
+  for (size_t i = 4 * n4 + t0; i < n; i += stride) {
+    const float s = on[i] - off[i];
+    lo = fminf(lo, s); hi = fmaxf(hi, s);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {  // wave = 64 lanes
+    lo = fminf(lo, __shfl_xor(lo, o));
+    hi = fmaxf(hi, __shfl_xor(hi, o));
+  }
+  __shared__ float s_lo[kDispThreads / 64], s_hi[kDispThreads / 64];
+  if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 1; w < kDispThreads / 64; w++) { lo = fminf(lo, s_lo[w]); hi = fmaxf(hi, s_hi[w]); }
+    if (lo <= hi) {
+      atomicMin(&range[0], disp_key(lo));
+      atomicMin(&range[1], ~disp_key(hi));
+    }
+  }
+}
+
+struct PolTone { float m, gamma; int linear; };
+__device__ __forceinline__ float pol_v(float s, const PolTone &t) {  // sign(s) (|s| / m)^gamma; m == 0: the neutral image
+  const float q = t.m > 0.f ? fabsf(s) / t.m : 0.f;
+  return copysignf(t.linear ? q : powf(q, t.gamma), s);
+}
+// the pixel as B | G << 8 | R << 16 (BGR), or its grey level
+template <bool BGR>
+__device__ __forceinline__ unsigned pol_level(float s, const PolTone &t) {
+  const float v = pol_v(s, t);
+  if (!BGR) return sat_u8(127.5f + 127.5f * v);
+  const unsigned c = 255u - sat_u8(255.f * fabsf(v));
+  return s > 0.f ? (c | (c << 8) | (255u << 16)) : (255u | (c << 8) | (c << 16));
+}
+
+template <bool BGR>
+__global__ __launch_bounds__(kDispThreads) void tone_signed_kernel(const float *__restrict__ on, const float *__restrict__ off, size_t n,
+                                                                   float gamma, const unsigned *__restrict__ range,
+                                                                   unsigned char *__restrict__ out) {
+  float lo, hi;
+  disp_range(range, lo, hi);
+  PolTone t;
+  t.m = fmaxf(fabsf(lo), fabsf(hi));
+  t.gamma = gamma;
+  t.linear = gamma == 1.f;
+  const bool vec = (((uintptr_t)on | (uintptr_t)off) & 15) == 0;
+  const size_t n4 = vec ? n / 4 : 0, stride = (size_t)gridDim.x * kDispThreads, t0 = (size_t)blockIdx.x * kDispThreads + threadIdx.x;
+  unsigned *out32 = reinterpret_cast<unsigned *>(out);
+  for (size_t g = t0; g < n4; g += stride) {
+    const float4 a = reinterpret_cast<const float4 *>(on)[g], b = reinterpret_cast<const float4 *>(off)[g];
+    const unsigned l0 = pol_level<BGR>(a.x - b.x, t), l1 = pol_level<BGR>(a.y - b.y, t), l2 = pol_level<BGR>(a.z - b.z, t),
+                   l3 = pol_level<BGR>(a.w - b.w, t);
+    if (BGR) {  // 12 bytes: B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3
+      out32[3 * g] = l0 | (l1 << 24);
+      out32[3 * g + 1] = (l1 >> 8) | (l2 << 16);
+      out32[3 * g + 2] = (l2 >> 16) | (l3 << 8);
+    } else {
+      out32[g] = l0 | (l1 << 8) | (l2 << 16) | (l3 << 24);
+    }
+  }
+  for (size_t i = 4 * n4 + t0; i < n; i += stride) {  // the last n % 4 pixels (all of them when a plane is off the 16-byte grid)
+    const unsigned l = pol_level<BGR>(on[i] - off[i], t);
+    if (BGR) { out[3 * i] = (unsigned char)l; out[3 * i + 1] = (unsigned char)(l >> 8); out[3 * i + 2] = (unsigned char)(l >> 16); }
+    else out[i] = (unsigned char)l;
+  }
+}
+
 // ---- EventWarper::drawSensorFOV: every sensor border pixel -> bearing (LUT) -> rotate -> equirectangular projection (as
 // mark_mask_kernel, cmx_kernels.hip) -> cv::Point2d -> cv::Point rounds half to even -> (B, G, R) = (255, 0, 0).
 // Points that fall outside the panorama are skipped (the reference writes them out of bounds).
@@ -207,6 +291,14 @@ void launch_display_pair(const float *A, const float *B, int W, int H, const uns
 void launch_display_map(const float *IG, size_t n, float gamma, bool bgr, const unsigned *range, unsigned char *out, hipStream_t s) {
   if (bgr) hipLaunchKernelGGL(tone_map_kernel<true>, dim3(disp_blocks(n / 4 + 3)), dim3(kDispThreads), 0, s, IG, n, gamma, range, out);
   else hipLaunchKernelGGL(tone_map_kernel<false>, dim3(disp_blocks(n / 4 + 3)), dim3(kDispThreads), 0, s, IG, n, gamma, range, out);
+}
+void launch_display_range_signed(const float *on, const float *off, size_t n, unsigned *range, hipStream_t s) {
+  hipLaunchKernelGGL(range_signed_kernel, dim3(disp_blocks(n / 4 + 3)), dim3(kDispThreads), 0, s, on, off, n, range);
+}
+void launch_display_signed(const float *on, const float *off, size_t n, float gamma, bool bgr, const unsigned *range, unsigned char *out,
+                           hipStream_t s) {
+  if (bgr) hipLaunchKernelGGL(tone_signed_kernel<true>, dim3(disp_blocks(n / 4 + 3)), dim3(kDispThreads), 0, s, on, off, n, gamma, range, out);
+  else hipLaunchKernelGGL(tone_signed_kernel<false>, dim3(disp_blocks(n / 4 + 3)), dim3(kDispThreads), 0, s, on, off, n, gamma, range, out);
 }
 void launch_display_fov(const BeSplatArgs &cam, const double R[9], int sensor_h, unsigned char *bgr, hipStream_t s) {
   FovArgs a;

@@ -47,10 +47,11 @@ void cmx_events_destroy(cmx_events *e) {
   for (cmx_events::Replica &r : e->rep) {
     (void)hipSetDevice(r.device);
     if (r.stream) { (void)hipStreamSynchronize(r.stream); (void)hipStreamDestroy(r.stream); }
-    for (int k = 0; k < 2; k++) { (void)hipFree(r.d_xy[k]); (void)hipFree(r.d_t[k]); }
+    for (int k = 0; k < 2; k++) { (void)hipFree(r.d_xy[k]); (void)hipFree(r.d_t[k]); (void)hipFree(r.d_pol[k]); }
   }
   if (e->h_xy) (void)hipHostFree(e->h_xy);
   if (e->h_tp) (void)hipHostFree(e->h_tp);
+  if (e->h_pol) (void)hipHostFree(e->h_pol);
   delete e;
 }
 const char *cmx_events_last_error(const cmx_events *e) { return e ? e->err.c_str() : "null event store"; }
@@ -64,7 +65,24 @@ int cmx_events_devices(const cmx_events *e, int *devices, int max_devices) {
 
 // append a chunk of the (time-ordered) stream: AngVelEstimator::pushEvent's events_.push_back (ang_vel_estimator.cpp:68-78).
 // One packing pass on the host into pinned staging, then one asynchronous upload per replica (the devices copy side by side).
-static int events_push_impl(cmx_events *e, const EventSource &src);
+// with_pol (the _pol forms): the events' polarity goes into a byte array of its own beside d_xy / d_t -- never into bit 31 of the
+// packed word, which cmx_backend_set_window_from uses for the old / new flag -- so every consumer that does not ask for polarity
+// reads the bytes it always read.  A store holds polarity for all of its events or for none: the first push into an EMPTY store
+// decides, and the other form is CMX_ERR_STATE until the store is empty again.
+static int events_push_impl(cmx_events *e, const EventSource &src, bool with_pol = false);
+int cmx_events_has_polarity(const cmx_events *e) { return e && e->has_pol && e->size > 0 ? 1 : 0; }
+int cmx_events_push_pol(cmx_events *e, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, const uint8_t *pol) {
+  if (!e || n < 0 || (n > 0 && (!x || !y || !t_ns || !pol))) return efail(e, CMX_ERR_INVALID_ARG, "bad arguments");
+  EventSource src = EventSource::arrays(n, x, y, t_ns);
+  src.soa.p = pol;
+  return events_push_impl(e, src, true);
+}
+int cmx_events_push_aos_pol(cmx_events *e, int64_t n, const void *events, const cmx_aos_layout *layout, size_t off_polarity) {
+  if (!e || n < 0 || !layout || (n > 0 && !events)) return efail(e, CMX_ERR_INVALID_ARG, "bad arguments");
+  EventSource src{EventSource::AOS, n};
+  if (!aos_view_pol(events, layout, off_polarity, &src.aos)) return efail(e, CMX_ERR_INVALID_ARG, "record layout: fields outside the record");
+  return events_push_impl(e, src, true);
+}
 int cmx_events_push(cmx_events *e, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns) {
   if (!e || n < 0 || (n > 0 && (!x || !y || !t_ns))) return efail(e, CMX_ERR_INVALID_ARG, "bad arguments");
   return events_push_impl(e, EventSource::arrays(n, x, y, t_ns));
@@ -77,10 +95,25 @@ int cmx_events_push_aos(cmx_events *e, int64_t n, const void *events, const cmx_
   if (!aos_view(events, layout, &src.aos)) return efail(e, CMX_ERR_INVALID_ARG, "record layout: fields outside the record");
   return events_push_impl(e, src);
 }
-static int events_push_impl(cmx_events *e, const EventSource &src) {
+static int events_push_impl(cmx_events *e, const EventSource &src, bool with_pol) {
   const int64_t n = src.n;
+  if (e->size > 0 && with_pol != e->has_pol)
+    return efail(e, CMX_ERR_STATE, e->has_pol ? "the store's events carry polarity: push with polarity" : "the store's events carry no polarity");
   if (e->size + (size_t)n > e->capacity) return efail(e, CMX_ERR_INVALID_ARG, "event store full: drop old events first");
   if (n == 0) return CMX_OK;
+  if (with_pol) {  // the byte arrays, at the first _pol push; the staging, as the other two
+    for (cmx_events::Replica &r : e->rep)
+      for (int b = 0; b < 2; b++)
+        if (!r.d_pol[b] && (hipSetDevice(r.device) != hipSuccess || hipMalloc((void **)&r.d_pol[b], e->capacity) != hipSuccess))
+          return efail(e, CMX_ERR_HIP, "hipMalloc failed");
+    if ((size_t)n > e->pol_stage_cap) {
+      if (e->h_pol) (void)hipHostFree(e->h_pol);
+      e->h_pol = nullptr; e->pol_stage_cap = 0;
+      const size_t cap = std::max<size_t>((size_t)n, 1u << 16);
+      if (hipHostMalloc((void **)&e->h_pol, cap, hipHostMallocPortable) != hipSuccess) return efail(e, CMX_ERR_HIP, "pinned staging allocation failed");
+      e->pol_stage_cap = cap;
+    }
+  }
   if ((size_t)n > e->stage_cap) {
     if (e->h_xy) (void)hipHostFree(e->h_xy);
     if (e->h_tp) (void)hipHostFree(e->h_tp);
@@ -97,10 +130,13 @@ static int events_push_impl(cmx_events *e, const EventSource &src) {
     return pack_events<false>(v, n, 1, n, 1, (unsigned)e->W, (unsigned)e->H, 0, xy, tp);
   });
   if (outside) return efail(e, CMX_ERR_EVENT_RANGE, "event coordinates outside the sensor");
+  if (with_pol) src.view([&](const auto &v) { pack_polarity(v, n, e->h_pol); return 0; });
   for (cmx_events::Replica &r : e->rep) {
     if (hipSetDevice(r.device) != hipSuccess) return efail(e, CMX_ERR_HIP, "hipSetDevice failed");
     if (hipMemcpyAsync(r.d_xy[e->cur] + e->size, xy, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, r.stream) != hipSuccess ||
         hipMemcpyAsync(r.d_t[e->cur] + e->size, tp, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, r.stream) != hipSuccess)
+      return efail(e, CMX_ERR_HIP, "upload failed");
+    if (with_pol && hipMemcpyAsync(r.d_pol[e->cur] + e->size, e->h_pol, (size_t)n, hipMemcpyHostToDevice, r.stream) != hipSuccess)
       return efail(e, CMX_ERR_HIP, "upload failed");
   }
   for (cmx_events::Replica &r : e->rep) {
@@ -109,6 +145,7 @@ static int events_push_impl(cmx_events *e, const EventSource &src) {
   (void)hipSetDevice(e->device);
   e->h_t.insert(e->h_t.end(), tp, tp + n);  // (the packed timestamps: the AoS form has no t_ns[] of its own)
   e->size += (size_t)n;
+  e->has_pol = with_pol;
   return CMX_OK;
 }
 
@@ -124,6 +161,8 @@ int cmx_events_drop_before(cmx_events *e, int64_t global_index) {
       if (hipSetDevice(r.device) != hipSuccess) return efail(e, CMX_ERR_HIP, "hipSetDevice failed");
       if (hipMemcpyAsync(r.d_xy[other], r.d_xy[e->cur] + k, keep * sizeof(uint32_t), hipMemcpyDeviceToDevice, r.stream) != hipSuccess ||
           hipMemcpyAsync(r.d_t[other], r.d_t[e->cur] + k, keep * sizeof(int64_t), hipMemcpyDeviceToDevice, r.stream) != hipSuccess)
+        return efail(e, CMX_ERR_HIP, "compaction failed");
+      if (e->has_pol && hipMemcpyAsync(r.d_pol[other], r.d_pol[e->cur] + k, keep, hipMemcpyDeviceToDevice, r.stream) != hipSuccess)
         return efail(e, CMX_ERR_HIP, "compaction failed");
     }
     // the contexts that cut packets / windows from the store use their own non-blocking streams: the compaction is complete
@@ -153,7 +192,7 @@ int store_source(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count, 
                 (long long)(first + count), (long long)e->first_index, (long long)(e->first_index + (int64_t)e->size));
   const size_t off = (size_t)(first - e->first_index);
   *out = EventSource{EventSource::DEVICE, count, EvSoa{nullptr, nullptr, e->h_t.data() + off}, EvAos{}, e, first,
-                     rep->d_xy[e->cur] + off, rep->d_t[e->cur] + off};
+                     rep->d_xy[e->cur] + off, rep->d_t[e->cur] + off, e->has_pol && e->size > 0 ? rep->d_pol[e->cur] + off : nullptr};
   return CMX_OK;
 }
 

@@ -13,18 +13,21 @@
 namespace cmx {
 
 // ---- event views: element i of a range of events, whatever the host keeps them in
+// (p / op: the polarity of event i, read by the _pol hand-overs alone -- everything else never looks at it)
 struct EvSoa {
   const uint16_t *x = nullptr, *y = nullptr;
   const int64_t *t = nullptr;
+  const uint8_t *p = nullptr;
   unsigned X(int64_t i) const { return x[i]; }
   unsigned Y(int64_t i) const { return y[i]; }
   int64_t T(int64_t i) const { return t[i]; }
-  EvSoa from(int64_t first) const { return EvSoa{x + first, y + first, t + first}; }
+  unsigned P(int64_t i) const { return p[i] != 0; }
+  EvSoa from(int64_t first) const { return EvSoa{x + first, y + first, t + first, p ? p + first : nullptr}; }
 };
 // an array of records (cmx_aos_layout, e.g. dvs_msgs::Event)
 struct EvAos {
   const unsigned char *base = nullptr;
-  size_t stride = 0, ox = 0, oy = 0, os = 0, on = 0;
+  size_t stride = 0, ox = 0, oy = 0, os = 0, on = 0, op = 0;
   unsigned X(int64_t i) const { uint16_t v; memcpy(&v, base + (size_t)i * stride + ox, 2); return v; }
   unsigned Y(int64_t i) const { uint16_t v; memcpy(&v, base + (size_t)i * stride + oy, 2); return v; }
   int64_t T(int64_t i) const {
@@ -33,6 +36,7 @@ struct EvAos {
     memcpy(&nsec, base + (size_t)i * stride + on, 4);
     return (int64_t)sec * 1000000000LL + (int64_t)nsec;
   }
+  unsigned P(int64_t i) const { return base[(size_t)i * stride + op] != 0; }
   EvAos from(int64_t first) const { EvAos r = *this; r.base = base + (size_t)first * stride; return r; }
 };
 // the one layout check (`layout` is not null); the callers report a failure in their own words
@@ -41,6 +45,12 @@ inline bool aos_view(const void *events, const cmx_aos_layout *layout, EvAos *ou
   if (st < 12 || layout->off_x + 2 > st || layout->off_y + 2 > st || layout->off_sec + 4 > st || layout->off_nsec + 4 > st) return false;
   out->base = static_cast<const unsigned char *>(events);
   out->stride = st; out->ox = layout->off_x; out->oy = layout->off_y; out->os = layout->off_sec; out->on = layout->off_nsec;
+  return true;
+}
+// ... with the byte offset of a polarity field (one byte, nonzero = ON) inside the record: the _pol hand-overs
+inline bool aos_view_pol(const void *events, const cmx_aos_layout *layout, size_t off_polarity, EvAos *out) {
+  if (!aos_view(events, layout, out) || off_polarity >= layout->stride) return false;
+  out->op = off_polarity;
   return true;
 }
 
@@ -56,6 +66,7 @@ struct EventSource {
   int64_t first = 0;
   const uint32_t *d_xy = nullptr;
   const int64_t *d_t = nullptr;
+  const uint8_t *d_pol = nullptr;  // DEVICE: the replica's polarity bytes (0 / 1), null when the store holds none
 
   static EventSource arrays(int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t) { return EventSource{SOA, n, EvSoa{x, y, t}}; }
   bool on_device() const { return kind == DEVICE; }
@@ -66,6 +77,7 @@ struct EventSource {
     if (kind == AOS) r.aos = aos.from(beg);
     r.first = first + beg;
     if (d_xy) { r.soa.t = soa.t + beg; r.d_xy = d_xy + beg; r.d_t = d_t + beg; }
+    if (d_pol) r.d_pol = d_pol + beg;
     return r;
   }
   template <typename F>
@@ -266,15 +278,19 @@ inline void member_range(int64_t n, int B, int rank, int world, int64_t *beg, in
 // ---- the packing pass.  Batch j of the n events of `v` is [j B, min(j B + B, n)); of the batches [0, nb) every rate-th event
 // from its batch's start becomes the word x | y << 16 [| (t < t_old) << 31] at out[j per_batch ...] (and its timestamp at
 // t_out, when given).  Returns non-zero when a packed event lies outside the W x H sensor.
-template <bool kOldFlag, typename View>
+// kPol (the polarity votes of a reconstruction, host paths): bit 31 carries the event's polarity instead, 1 = ON -- the
+// reconstruction kernels mask the bit off before they read the coordinates, so the word serves them as it is.
+template <bool kOldFlag, bool kPol = false, typename View>
 inline uint32_t pack_word(const View &v, int64_t i, unsigned W, unsigned H, int64_t t_old, unsigned &outside) {
+  static_assert(!(kOldFlag && kPol), "bit 31 holds one flag");
   const unsigned ex = v.X(i), ey = v.Y(i);
   outside |= (unsigned)(ex >= W) | (unsigned)(ey >= H);
   uint32_t w = ex | (ey << 16);
   if (kOldFlag) w |= (uint32_t)(v.T(i) < t_old) << 31;
+  if (kPol) w |= (uint32_t)v.P(i) << 31;
   return w;
 }
-template <bool kOldFlag, typename View>
+template <bool kOldFlag, bool kPol = false, typename View>
 unsigned pack_events(const View &v, int64_t n, int64_t nb, int64_t B, int rate, unsigned W, unsigned H, int64_t t_old, uint32_t *out,
                      int64_t *t_out = nullptr) {
   std::atomic<unsigned> outside(0);
@@ -284,7 +300,7 @@ unsigned pack_events(const View &v, int64_t n, int64_t nb, int64_t B, int rate, 
     parallel_ranges(count, [&, W, H, t_old, out, t_out](int64_t a0, int64_t a1) {
       unsigned acc = 0;
       for (int64_t i = a0; i < a1; i++) {
-        out[i] = pack_word<kOldFlag>(v, i, W, H, t_old, acc);
+        out[i] = pack_word<kOldFlag, kPol>(v, i, W, H, t_old, acc);
         if (t_out) t_out[i] = v.T(i);
       }
       if (acc) outside = 1;
@@ -297,7 +313,7 @@ unsigned pack_events(const View &v, int64_t n, int64_t nb, int64_t B, int rate, 
         const int64_t beg = j * B, end = (n - beg > B) ? beg + B : n;
         int64_t k = j * per_batch;
         for (int64_t i = beg; i < end; i += rate, k++) {
-          out[k] = pack_word<kOldFlag>(v, i, W, H, t_old, acc);
+          out[k] = pack_word<kOldFlag, kPol>(v, i, W, H, t_old, acc);
           if (t_out) t_out[k] = v.T(i);
         }
       }
@@ -305,6 +321,14 @@ unsigned pack_events(const View &v, int64_t n, int64_t nb, int64_t B, int rate, 
     });
   }
   return outside.load();
+}
+
+// the polarity bytes of an event store: out[i] = 1 for an ON event (any nonzero input), else 0
+template <typename View>
+void pack_polarity(const View &v, int64_t n, uint8_t *out) {
+  parallel_ranges(n, [&, out](int64_t a0, int64_t a1) {
+    for (int64_t i = a0; i < a1; i++) out[i] = (uint8_t)v.P(i);
+  });
 }
 
 // index of the first event outside the W x H sensor, -1 when there is none

@@ -446,10 +446,15 @@ struct ReconArgs {
   float *plane;              // votes: fp32 atomics ...
   unsigned long long *fixed; // ... or, when set, 64-bit integer adds into the 2^-30 fixed-point plane
   unsigned long long *n_inside;
+  // the polarity votes alone (launch_recon_votes_pol): plane / fixed hold TWO planes, ON then OFF, n_inside two counters in that
+  // order; an event is ON when pol[src] != 0 -- src the index its packed word is read at -- or, with pol == null, when bit 31 of
+  // that word is set (the host paths pack it there)
+  const unsigned char *pol;
 };
 int recon_run(int per_batch);
 void launch_recon_delta(const Quat *knots, int K, double *delta, hipStream_t s);
 void launch_recon_votes(const ReconArgs &a, hipStream_t s);
+void launch_recon_votes_pol(const ReconArgs &a, hipStream_t s);
 void launch_recon_fixed_to_float(const unsigned long long *fixed, float *plane, size_t n, hipStream_t s);  // non-destructive
 // per-event export (cmx_backend_recon_warp*): the panorama coordinate and the flags of EVERY raw event of a slice, sampled or not.
 // ev as for the votes with xy = the slice's raw events, n = their count (a lone trailing event included), per_batch = B,
@@ -522,5 +527,9 @@ void launch_display_range(const float *p0, const float *p1 /* or null */, size_t
 void launch_display_pair(const float *A, const float *B, int W, int H, const unsigned *range, unsigned char *out, hipStream_t s);
 void launch_display_map(const float *IG, size_t n, float gamma, bool bgr, const unsigned *range, unsigned char *out, hipStream_t s);
 void launch_display_fov(const BeSplatArgs &cam, const double R[9], int sensor_h, unsigned char *bgr, hipStream_t s);
+// the signed map s = on - off: its extremes into range (as launch_display_range), then mono8 or bgr8 (cmx_backend_recon_pol_render)
+void launch_display_range_signed(const float *on, const float *off, size_t n, unsigned *range, hipStream_t s);
+void launch_display_signed(const float *on, const float *off, size_t n, float gamma, bool bgr, const unsigned *range, unsigned char *out,
+                           hipStream_t s);
 
 }  // namespace cmx

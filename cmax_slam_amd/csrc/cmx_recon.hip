@@ -8,6 +8,8 @@
 //                   of spline_eval<N, false> with knots / delta read from global memory at segment s .. s+N-1), and after one
 //                   barrier all lanes walk the run's events with be_warp_math<0> and vote (event_pano_warper.cpp:262-311
 //                   without the old / new split).  No pose table in global memory, no tile sort, no second launch.
+//                   POL (cmx_backend_recon_pol_add*): the same walk, the same cell and weights, but the four adds go to the ON or
+//                   the OFF plane by the event's polarity, and the voting events are counted per plane.
 //   recon_fixed_to_float   deterministic mode: the 2^-30 fixed-point plane as fp32, leaving it as it is (accumulation goes on)
 #include "../../include/cmax_hip.h"
 #include "cmx_internal.hpp"
@@ -68,22 +70,25 @@ __device__ __forceinline__ void recon_pose(const ReconArgs &a, long long t_ns, d
   for (int c = 0; c < 9; c++) R[c] = M.m[c];
 }
 
-template <int N, bool FIXED>
+template <int N, bool FIXED, bool POL = false>
 __global__ __launch_bounds__(kReconThreads) void recon_votes_kernel(const ReconArgs a) {
   __shared__ double sh_R[(kReconMaxRun + 2) * 9];
   __shared__ unsigned sh_inside;
+  __shared__ unsigned sh_inside_off;  // (POL: sh_inside counts the ON votes, this one the OFF votes)
   const int e0 = blockIdx.x * a.run;  // (the grid covers [0, n): e0 < n)
   const int e1 = (a.n - e0 > a.run) ? e0 + a.run : a.n;
   const int b0 = e0 / a.per_batch;
   int nbw = (e1 - 1) / a.per_batch - b0 + 1;
   if (nbw > kReconMaxRun + 2) nbw = kReconMaxRun + 2;  // (cannot happen with run = recon_run(per_batch))
   if (threadIdx.x == 0) sh_inside = 0;
+  if (POL && threadIdx.x == 0) sh_inside_off = 0;
   for (int j = threadIdx.x; j < nbw; j += kReconThreads) {
     const int b = b0 + j < a.nb ? b0 + j : a.nb - 1;
     recon_pose<N>(a, a.batch_t[b], sh_R + 9 * j);
   }
   __syncthreads();
-  unsigned inside = 0;
+  unsigned inside = 0, inside_off = 0;
+  const size_t off_plane = (size_t)a.cam.Hp * a.cam.Wp;
   int cur = -1;
   double R[9];
   for (int i = e0 + threadIdx.x; i < e1; i += kReconThreads) {
@@ -97,23 +102,34 @@ __global__ __launch_bounds__(kReconThreads) void recon_votes_kernel(const ReconA
     }
     // sampling restarts at every batch start (event_pano_warper.cpp:262): packed slot k of batch b is raw event b * B + k * stride
     const size_t src = a.stride ? (size_t)b * a.B + (size_t)(i - b * a.per_batch) * a.stride : (size_t)i;
-    const uint32_t e = a.xy[src] & 0x7fffffffu;
+    const uint32_t word = a.xy[src];
+    const uint32_t e = word & 0x7fffffffu;
+    // POL: the store's byte (a.pol is a kernel argument: uniform), read beside the word, or the word's own bit 31
+    const bool on = POL && (a.pol ? a.pol[src] != 0 : (word >> 31) != 0);
     const int ex = e & 0xffff, ey = e >> 16;
     double v0, v1, v2;
     load_bearing(a.cam, ex, ey, v0, v1, v2);
     const BeWarp w = be_warp_math<0>(a.cam, e, b, v0, v1, v2, R);
     if (w.ok) {  // 1 <= xx < Wp - 2 && 1 <= yy < Hp - 2: the four cells are inside the plane
-      if (FIXED) vote4_global_fix(a.fixed, a.cam.Wp, w.xx, w.yy, w.dx, w.dy);
-      else vote4_global(a.plane, a.cam.Wp, w.xx, w.yy, w.dx, w.dy);
-      inside++;
+      const size_t at = POL && !on ? off_plane : 0;  // (POL: the same four adds, into the plane the polarity selects)
+      if (FIXED) vote4_global_fix(a.fixed + at, a.cam.Wp, w.xx, w.yy, w.dx, w.dy);
+      else vote4_global(a.plane + at, a.cam.Wp, w.xx, w.yy, w.dx, w.dy);
+      if (POL && !on) inside_off++;
+      else inside++;
     }
   }
-  // events that voted: one wave reduction, one atomic per workgroup
+  // events that voted: one wave reduction, one atomic per workgroup (POL: per plane)
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) inside += __shfl_down(inside, off, 64);
   if ((threadIdx.x & 63) == 0 && inside) atomicAdd(&sh_inside, inside);
+  if (POL) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) inside_off += __shfl_down(inside_off, off, 64);
+    if ((threadIdx.x & 63) == 0 && inside_off) atomicAdd(&sh_inside_off, inside_off);
+  }
   __syncthreads();
   if (threadIdx.x == 0 && sh_inside) atomicAdd(a.n_inside, (unsigned long long)sh_inside);
+  if (POL && threadIdx.x == 0 && sh_inside_off) atomicAdd(a.n_inside + 1, (unsigned long long)sh_inside_off);
 }
 
 void launch_recon_votes(const ReconArgs &a, hipStream_t s) {
@@ -125,6 +141,18 @@ void launch_recon_votes(const ReconArgs &a, hipStream_t s) {
   } else {
     if (a.fixed) hipLaunchKernelGGL((recon_votes_kernel<4, true>), g, b, 0, s, a);
     else hipLaunchKernelGGL((recon_votes_kernel<4, false>), g, b, 0, s, a);
+  }
+}
+
+void launch_recon_votes_pol(const ReconArgs &a, hipStream_t s) {
+  if (a.n <= 0 || a.nb <= 0) return;
+  const dim3 g((unsigned)(((long long)a.n + a.run - 1) / a.run)), b(kReconThreads);
+  if (a.order == 2) {
+    if (a.fixed) hipLaunchKernelGGL((recon_votes_kernel<2, true, true>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((recon_votes_kernel<2, false, true>), g, b, 0, s, a);
+  } else {
+    if (a.fixed) hipLaunchKernelGGL((recon_votes_kernel<4, true, true>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((recon_votes_kernel<4, false, true>), g, b, 0, s, a);
   }
 }
 

@@ -4,6 +4,7 @@
 //              events, into the reconstruction's plane
 //   grad_add*  the second pass over the same events, their share of the gradient sums
 //   warp*      the per-event export: where EVERY event handed in lands under the knots the reconstruction holds now
+//   pol_add*   add*'s vote loop into the ON / OFF planes of the signed polarity map
 // Host arrays (SoA, or the host's own records) are packed slice by slice into two slots of pinned memory and uploaded on the copy
 // stream while the slice before runs; a range of an event store is read in place, its batch times formed on the device.
 #include "cmx_recon_state.hpp"
@@ -70,8 +71,9 @@ struct FedSlice : FeedSlice {
 // uploaded while the kernels of slice k run.  Store sources: the batch times of the slice into slot[0]'s table; a single slice finds
 // there what the validation pass has just written.  From the first slice on only a runtime error (CMX_ERR_HIP) can end the call,
 // and slices queued before it have run.  Returns after the context's stream has run dry, the slots idle either way.
+// with_pol (pol_add*, host sources): the packed words carry the events' polarity in bit 31.
 template <typename OnSlice>
-static int feed(cmx_ctx *c, ReconState *r, const EventSource &src, bool every_event, BatchPlan *plan, OnSlice on_slice) {
+static int feed(cmx_ctx *c, ReconState *r, const EventSource &src, bool every_event, bool with_pol, BatchPlan *plan, OnSlice on_slice) {
   const bool store = src.on_device();
   const int64_t n = src.n;
   const int B = r->B;
@@ -118,7 +120,9 @@ static int feed(cmx_ctx *c, ReconState *r, const EventSource &src, bool every_ev
         src.view([&](const auto &v) {  // (validated above: neither pass finds anything)
           if (nbs > 0) batch_times(v, n, B, f.b_lo, f.b_hi, nullptr, [&](int64_t b, long long tb) { bt[b - f.b_lo] = tb; });
           const auto vs = v.from(f.ev_first);
-          unsigned outside = pack_events<false>(vs, n - f.ev_first, nbs, B, every_event ? 1 : r->rate, (unsigned)c->W, (unsigned)c->H, 0, xy);
+          const int rate = every_event ? 1 : r->rate;
+          unsigned outside = with_pol ? pack_events<false, true>(vs, n - f.ev_first, nbs, B, rate, (unsigned)c->W, (unsigned)c->H, 0, xy)
+                                      : pack_events<false>(vs, n - f.ev_first, nbs, B, rate, (unsigned)c->W, (unsigned)c->H, 0, xy);
           if (f.lone) xy[f.ev_n - 1] = pack_word<false>(vs, f.ev_n - 1, (unsigned)c->W, (unsigned)c->H, 0, outside);
           return outside;
         });
@@ -155,7 +159,7 @@ int recon_add_source(cmx_ctx *c, const EventSource &src, bool grad) {
   ReconGatherArgs ga = recon_gather_args(c, r);
   ReconArgs &a = ga.ev;
   BatchPlan p;
-  rc = feed(c, r, src, false, &p, [&](const FedSlice &s) {
+  rc = feed(c, r, src, false, false, &p, [&](const FedSlice &s) {
     a.xy = s.d_xy; a.stride = src.on_device() ? r->rate : 0;  // (the store's events in place: the sampling is an index map)
     a.batch_t = s.d_bt; a.nb = s.b_hi - s.b_lo;
     a.n = (int)s.n;
@@ -196,6 +200,64 @@ int cmx_backend_recon_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, i
 }
 int cmx_backend_recon_grad_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
   return recon_add_entry(c, true, [&](EventSource *src) { return store_source(c, e, first, count, src); });
+}
+
+// ---- pol_add*: add*'s vote pass with the ON / OFF planes as its target.  Nothing of the reconstruction but the knots is read, and
+// nothing but those two planes and their counters is written: no recon_pass_enter (an open gradient pass stays open), no n_sampled.
+// Host sources carry the polarity in bit 31 of the packed word, a store in its byte array at the index of the word.
+static int recon_pol_add_source(cmx_ctx *c, const EventSource &src) {
+  ReconState *r = c->recon;
+  int rc = feed_checks(c, src);
+  if (rc) return rc;
+  rc = recon_pol_ensure(c, r);
+  if (rc) return rc;
+  ReconArgs a = recon_args(c, r);
+  a.plane = r->d_pol;
+  a.fixed = r->d_pol_fixed;
+  a.n_inside = r->d_pol_inside;
+  BatchPlan p;
+  return feed(c, r, src, false, !src.on_device(), &p, [&](const FedSlice &s) {
+    a.xy = s.d_xy; a.stride = src.on_device() ? r->rate : 0;
+    a.pol = src.on_device() ? src.d_pol + s.ev_first : nullptr;
+    a.batch_t = s.d_bt; a.nb = s.b_hi - s.b_lo;
+    a.n = (int)s.n;
+    launch_recon_votes_pol(a, c->stream);
+    return (int)CMX_OK;
+  });
+}
+template <typename MakeSource>
+static int recon_pol_add_entry(cmx_ctx *c, MakeSource make) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  EventSource src;
+  rc = make(&src);
+  if (rc) return rc;
+  return recon_pol_add_source(c, src);
+}
+int cmx_backend_recon_pol_add(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, const uint8_t *pol) {
+  return recon_pol_add_entry(c, [&](EventSource *src) {
+    if (n > 0 && !pol) return fail(c, CMX_ERR_INVALID_ARG, "null polarity array");
+    *src = EventSource::arrays(n, x, y, t_ns);
+    src->soa.p = pol;
+    return (int)CMX_OK;
+  });
+}
+int cmx_backend_recon_pol_add_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout, size_t off_polarity) {
+  return recon_pol_add_entry(c, [&](EventSource *src) {
+    const int rc = make_aos(c, n, events, layout, src);
+    if (rc) return rc;
+    if (off_polarity >= layout->stride) return fail(c, CMX_ERR_INVALID_ARG, "record layout: polarity outside the %zu-byte record", layout->stride);
+    src->aos.op = off_polarity;
+    return (int)CMX_OK;
+  });
+}
+int cmx_backend_recon_pol_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
+  return recon_pol_add_entry(c, [&](EventSource *src) {
+    const int rc = store_source(c, e, first, count, src);
+    if (rc) return rc;
+    if (e->size > 0 && !e->has_pol) return fail(c, CMX_ERR_STATE, "the event store holds no polarity (cmx_events_push_pol)");
+    return (int)CMX_OK;
+  });
 }
 
 // ---- warp*: ALL events of a slice reach the kernel (the host paths pack at rate 1, the store is read in place), the true rate only
@@ -241,7 +303,7 @@ static int recon_warp_source(cmx_ctx *c, const EventSource &src, int format, voi
     return CMX_OK;
   };
   BatchPlan p;
-  rc = feed(c, r, src, true, &p, [&](const FedSlice &s) -> int {
+  rc = feed(c, r, src, true, false, &p, [&](const FedSlice &s) -> int {
     g.ev.xy = s.d_xy;
     g.ev.batch_t = s.d_bt; g.ev.nb = s.b_hi - s.b_lo;
     g.ev.n = (int)s.ev_n;

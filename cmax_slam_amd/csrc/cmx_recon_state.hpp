@@ -1,7 +1,7 @@
 // cmx_recon_state.hpp -- what the three sources of cmx_backend_recon_* share: the state a reconstruction keeps (cmx_ctx::recon) and
 // the helpers every one of them goes through.
 //   cmx_reconstruct.cpp  life cycle (begin, restart, extend, end), contrast / grad_get / eval_from, get / render
-//   cmx_recon_feed.cpp   one walk over the events handed in, in slices of whole batches: add*, grad_add*, warp*
+//   cmx_recon_feed.cpp   one walk over the events handed in, in slices of whole batches: add*, grad_add*, warp*, pol_add*
 //   cmx_recon_bound.cpp  events bound once and evaluated many times: bind / eval_bound, the frozen head, append / advance /
 //                        release, the hooks of cmx_backend_recon_solve
 // Kernels: cmx_recon.hip.
@@ -183,6 +183,11 @@ struct ReconState {
   uint32_t *d_app_xy = nullptr;           // bind_append_from's scratch stream, "open tail ++ new range": raw events ...
   int64_t *d_app_t = nullptr;             // ... and their times, count + B of them at most
   size_t app_cap = 0;
+  // ---- signed polarity map (cmx_backend_recon_pol_*): two planes of the reconstruction's own beside the count plane,
+  // allocated by the first pol_add*, cleared by restart and pol_reset, freed by end; nothing else reads or writes them
+  float *d_pol = nullptr;                      // [2][Hp * Wp] ON then OFF (default mode), or the fp32 view of d_pol_fixed made by pol_get / pol_render
+  unsigned long long *d_pol_fixed = nullptr;   // deterministic mode: their 2^-30 fixed-point twins
+  unsigned long long *d_pol_inside = nullptr;  // [2] events that voted into the ON / the OFF plane
   int64_t host_waits = 0;                // times a host thread has waited for the device in this reconstruction's calls
   // everything above that owns memory, a stream or an event (the streams idle: recon_release has waited for them)
   void release() {
@@ -191,7 +196,7 @@ struct ReconState {
     for (ReconSlot &s : slot) s.release();
     for (ReconWarpSlot &s : wslot) s.release();
     void *dev[] = {d_knots, d_delta, d_plane, d_fixed, d_inside, d_err, d_cx, d_cy, d_tflags, d_tile_list, d_tile_count, d_partials,
-                   d_cm, d_jt, d_gsum, d_voted, d_rows, d_row_win, d_app_xy, d_app_t};
+                   d_cm, d_jt, d_gsum, d_voted, d_rows, d_row_win, d_app_xy, d_app_t, d_pol, d_pol_fixed, d_pol_inside};
     for (void *p : dev) (void)hipFree(p);
     bnd.release();
     frozen.release();
@@ -226,6 +231,9 @@ int recon_refuse_released(cmx_ctx *c, const ReconState *r, const char *what);
 int recon_contrast_queue(cmx_ctx *c, ReconState *r, double blur_sigma, int contrast_measure, int want_grad, double *cm);
 // taps and border factors for this sigma, and the one argument error a gradient at it can find
 int recon_grad_precheck(cmx_ctx *c, ReconState *r, double sigma);
+// the polarity planes and their two counters: allocated (and zeroed) at the first pol_add*; zeroed, where they exist (queued)
+int recon_pol_ensure(cmx_ctx *c, ReconState *r);
+int recon_pol_clear(cmx_ctx *c, ReconState *r);
 
 // ---- cmx_recon_feed.cpp
 // one slice of the gradient pass, as g.ev describes it; deterministic mode: the workgroups' rows, then their sum in workgroup order

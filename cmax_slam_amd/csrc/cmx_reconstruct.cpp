@@ -5,7 +5,8 @@
 // the whole-trajectory contrast and its gradient with respect to a left increment of EVERY control pose (recon_contrast,
 // recon_grad_get, recon_eval_from): the image pass over the plane and a second pass over the same events, in the adjoint form of the
 // window path -- per batch one 3-vector through the 3 x 3N spline Jacobian, so nothing grows with the knot count
-// but the 2 x 3K sums -- and the plane's way out (get, render).  Events bound once and evaluated many times, the frozen head, the
+// but the 2 x 3K sums -- and the plane's way out (get, render); the same for the ON / OFF planes of the signed polarity map
+// (pol_get, pol_render, pol_reset).  Events bound once and evaluated many times, the frozen head, the
 // growing binding and the native solve's hooks: cmx_recon_bound.cpp.
 // Kernels: cmx_recon.hip.
 #include "cmx_recon_state.hpp"
@@ -185,6 +186,8 @@ int cmx_backend_recon_restart(cmx_ctx *c, const double *knots_xyzw) {
   rc = recon_refuse_released(c, c->recon, "restart");
   if (rc) return rc;
   frozen_drop(c, c->recon);  // (new knots: what the frozen batches voted no longer holds)
+  rc = recon_pol_clear(c, c->recon);  // (... nor what the polarity planes hold)
+  if (rc) return rc;
   return recon_start_over(c, c->recon, knots_xyzw);
 }
 
@@ -432,5 +435,89 @@ int cmx_backend_recon_render(cmx_ctx *c, double gamma, const double fov_quat_xyz
     const Mat3 R = q_to_R(q);
     launch_display_fov(be_args(c), R.m, c->H, c->d_disp, c->stream);
   }
+  return display_deliver(c, bytes, out);
+}
+
+// ---- signed polarity map: the ON / OFF planes of cmx_backend_recon_pol_add* (cmx_recon_feed.cpp)
+int recon_pol_clear(cmx_ctx *c, ReconState *r) {
+  if (!r->d_pol) return CMX_OK;
+  const size_t np2 = 2 * (size_t)c->Wp * c->Hp;
+  HIP_TRY(c, hipMemsetAsync(r->d_pol, 0, np2 * sizeof(float), c->stream));
+  if (r->d_pol_fixed) HIP_TRY(c, hipMemsetAsync(r->d_pol_fixed, 0, np2 * sizeof(unsigned long long), c->stream));
+  HIP_TRY(c, hipMemsetAsync(r->d_pol_inside, 0, 2 * sizeof(unsigned long long), c->stream));
+  return CMX_OK;
+}
+int recon_pol_ensure(cmx_ctx *c, ReconState *r) {
+  if (r->d_pol) return CMX_OK;
+  const size_t np2 = 2 * (size_t)c->Wp * c->Hp;
+  float *plane = nullptr;
+  unsigned long long *fixed = nullptr, *inside = nullptr;
+  hipError_t e = hipMalloc((void **)&plane, np2 * sizeof(float));
+  if (e == hipSuccess && r->deterministic) e = hipMalloc((void **)&fixed, np2 * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMalloc((void **)&inside, 2 * sizeof(unsigned long long));
+  if (e != hipSuccess) {  // (all three or none: d_pol says whether the planes exist)
+    (void)hipFree(plane); (void)hipFree(fixed); (void)hipFree(inside);
+    return fail(c, CMX_ERR_HIP, "allocating the polarity planes: %s", hipGetErrorString(e));
+  }
+  r->d_pol = plane; r->d_pol_fixed = fixed; r->d_pol_inside = inside;
+  return recon_pol_clear(c, r);
+}
+
+int cmx_backend_recon_pol_reset(cmx_ctx *c) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  rc = recon_pol_clear(c, c->recon);
+  if (rc) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return CMX_OK;
+}
+
+// the two planes as fp32 on the device: in deterministic mode the current fixed-point sums, converted (they stay: votes may follow)
+static void recon_pol_refresh(cmx_ctx *c, ReconState *r) {
+  if (r->d_pol_fixed) launch_recon_fixed_to_float(r->d_pol_fixed, r->d_pol, 2 * (size_t)c->Wp * c->Hp, c->stream);
+}
+
+int cmx_backend_recon_pol_get(cmx_ctx *c, float *on, float *off, int64_t *n_on, int64_t *n_off) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  ReconState *r = c->recon;
+  const size_t np = (size_t)c->Wp * c->Hp;
+  unsigned long long inside[2] = {0, 0};
+  if (!r->d_pol) {  // (no pol_add* yet: nothing has been allocated, and nothing is)
+    if (on) memset(on, 0, np * sizeof(float));
+    if (off) memset(off, 0, np * sizeof(float));
+  } else {
+    if (on || off) {
+      recon_pol_refresh(c, r);
+      HIP_TRY(c, hipGetLastError());
+    }
+    if (on) HIP_TRY(c, hipMemcpyAsync(on, r->d_pol, np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (off) HIP_TRY(c, hipMemcpyAsync(off, r->d_pol + np, np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (n_on || n_off) HIP_TRY(c, hipMemcpyAsync(inside, r->d_pol_inside, sizeof(inside), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  if (n_on) *n_on = (int64_t)inside[0];
+  if (n_off) *n_off = (int64_t)inside[1];
+  return CMX_OK;
+}
+
+// the signed map ON - OFF as an 8-bit image (cmx_display.hip): one range reduction and one tone pass over the difference of the planes
+int cmx_backend_recon_pol_render(cmx_ctx *c, double gamma, int mode, unsigned char *out) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (!out) return fail(c, CMX_ERR_INVALID_ARG, "null output buffer");
+  if (!std::isfinite(gamma) || !(gamma > 0.0)) return fail(c, CMX_ERR_INVALID_ARG, "gamma must be finite and > 0");
+  if (mode != CMX_POL_MONO8 && mode != CMX_POL_BGR8) return fail(c, CMX_ERR_INVALID_ARG, "unknown render mode %d", mode);
+  ReconState *r = c->recon;
+  const size_t np = (size_t)c->Wp * c->Hp, bytes = mode == CMX_POL_BGR8 ? 3 * np : np;
+  if (!r->d_pol) {  // (no pol_add* yet: the neutral image)
+    memset(out, mode == CMX_POL_BGR8 ? 255 : 128, bytes);
+    return CMX_OK;
+  }
+  rc = display_begin(c, bytes);
+  if (rc) return rc;
+  recon_pol_refresh(c, r);
+  launch_display_range_signed(r->d_pol, r->d_pol + np, np, c->d_disp_range, c->stream);
+  launch_display_signed(r->d_pol, r->d_pol + np, np, (float)gamma, mode == CMX_POL_BGR8, c->d_disp_range, c->d_disp, c->stream);
   return display_deliver(c, bytes, out);
 }

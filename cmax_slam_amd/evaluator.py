@@ -35,6 +35,21 @@ def _dp(a):
     return a.ctypes.data_as(c_dp)
 
 
+def _pol_bytes(polarity):
+    """one byte per event, nonzero = ON (bool, integer or +-1 float arrays alike: > 0 is ON for signed input)"""
+    p = np.asarray(polarity)
+    if p.dtype == np.uint8 or p.dtype == np.bool_:
+        return np.ascontiguousarray(p).view(np.uint8)
+    return np.ascontiguousarray(p > 0).view(np.uint8)
+
+
+def _pol_offset(ev, field):
+    dt, off = ev.dtype.fields[field][:2]
+    if dt.itemsize != 1:
+        raise ValueError("the polarity field must be one byte wide")
+    return int(off)
+
+
 class _Evaluator:
     def __init__(self):
         self._L = _lib.lib()
@@ -278,16 +293,34 @@ class EventStore:
             raise CmaxHipError(status, self._L.cmx_status_string(status).decode() + ": " +
                                self._L.cmx_events_last_error(self._h).decode())
 
-    def push(self, x, y, t_ns):
+    def push(self, x, y, t_ns, polarity=None):
+        """polarity (one value per event, nonzero = ON): cmx_events_push_pol -- the store keeps it for reconstruct_pol_add_from.
+        A store holds polarity for all of its events or for none."""
         x, y, t = _c(x, np.uint16), _c(y, np.uint16), _c(t_ns, np.int64)
-        self._ck(self._L.cmx_events_push(self._h, len(x), x.ctypes.data_as(c_u16p), y.ctypes.data_as(c_u16p),
-                                         t.ctypes.data_as(c_i64p)))
+        if polarity is None:
+            self._ck(self._L.cmx_events_push(self._h, len(x), x.ctypes.data_as(c_u16p), y.ctypes.data_as(c_u16p),
+                                             t.ctypes.data_as(c_i64p)))
+            return
+        p = _pol_bytes(polarity)
+        if not (len(x) == len(y) == len(t) == len(p)):
+            raise ValueError("x, y, t_ns, polarity must have equal length")
+        self._ck(self._L.cmx_events_push_pol(self._h, len(x), x.ctypes.data_as(c_u16p), y.ctypes.data_as(c_u16p),
+                                             t.ctypes.data_as(c_i64p), p.ctypes.data_as(_lib.c_u8p)))
 
-    def push_aos(self, events):
-        """cmx_events_push_aos: records with fields x, y, sec, nsec (msg->events as it lies in the host's memory)."""
+    def push_aos(self, events, polarity_field=None):
+        """cmx_events_push_aos: records with fields x, y, sec, nsec (msg->events as it lies in the host's memory).
+        polarity_field = the name of a one-byte field of the records (e.g. "polarity"): cmx_events_push_aos_pol."""
         ev = np.ascontiguousarray(events)
         lay = _lib.aos_layout_of(ev)
-        self._ck(self._L.cmx_events_push_aos(self._h, len(ev), ev.ctypes.data_as(C.c_void_p), C.byref(lay)))
+        if polarity_field is None:
+            self._ck(self._L.cmx_events_push_aos(self._h, len(ev), ev.ctypes.data_as(C.c_void_p), C.byref(lay)))
+        else:
+            self._ck(self._L.cmx_events_push_aos_pol(self._h, len(ev), ev.ctypes.data_as(C.c_void_p), C.byref(lay),
+                                                     _pol_offset(ev, polarity_field)))
+
+    @property
+    def has_polarity(self):
+        return bool(self._L.cmx_events_has_polarity(self._h))
 
     def drop_before(self, global_index):
         self._ck(self._L.cmx_events_drop_before(self._h, int(global_index)))
@@ -653,6 +686,46 @@ class BackendEvaluator(_Evaluator):
         fmt, xy, fl = self._warp_out(int(count), dtype)
         self._ck(self._L.cmx_backend_recon_warp_from(self._ctx, store._h, int(first), int(count), fmt, xy.ctypes.data, fl.ctypes.data))
         return xy, fl
+
+    # --- signed polarity map: ON / OFF planes of the same vote loop (cmx_backend_recon_pol_*)
+    def reconstruct_pol_add(self, x, y, t_ns, polarity):
+        """reconstruct_add's vote loop over exactly these events, into the ON plane (polarity nonzero) or the OFF plane.  The count
+        plane, its counters and every other state of the reconstruction are left alone."""
+        x, y, t, p = _c(x, np.uint16), _c(y, np.uint16), _c(t_ns, np.int64), _pol_bytes(polarity)
+        if not (len(x) == len(y) == len(t) == len(p)):
+            raise ValueError("x, y, t_ns, polarity must have equal length")
+        self._ck(self._L.cmx_backend_recon_pol_add(self._ctx, len(x), x.ctypes.data_as(c_u16p), y.ctypes.data_as(c_u16p),
+                                                   t.ctypes.data_as(c_i64p), p.ctypes.data_as(_lib.c_u8p)))
+
+    def reconstruct_pol_add_aos(self, events, polarity_field="polarity"):
+        """The same from a structured array of records with fields x, y, sec, nsec and a one-byte polarity field."""
+        ev = np.ascontiguousarray(events)
+        lay = _lib.aos_layout_of(ev)
+        self._ck(self._L.cmx_backend_recon_pol_add_aos(self._ctx, len(ev), ev.ctypes.data_as(C.c_void_p), C.byref(lay),
+                                                       _pol_offset(ev, polarity_field)))
+
+    def reconstruct_pol_add_from(self, store, first, count):
+        """The same over events_[first, first+count) of an EventStore that holds polarity (EventStore.push(..., polarity=))."""
+        self._ck(self._L.cmx_backend_recon_pol_add_from(self._ctx, store._h, int(first), int(count)))
+
+    def reconstruct_pol_get(self, with_counts=False):
+        """(on, off) -- two (Hp, Wp) fp32 planes [, events that voted ON, events that voted OFF]."""
+        on, off = np.empty((self.Hp, self.Wp), np.float32), np.empty((self.Hp, self.Wp), np.float32)
+        n_on, n_off = C.c_int64(), C.c_int64()
+        self._ck(self._L.cmx_backend_recon_pol_get(self._ctx, on.ctypes.data_as(c_fp), off.ctypes.data_as(c_fp),
+                                                   C.byref(n_on) if with_counts else None, C.byref(n_off) if with_counts else None))
+        return (on, off, n_on.value, n_off.value) if with_counts else (on, off)
+
+    def reconstruct_pol_render(self, gamma=0.75, mode=0):
+        """The signed map ON - OFF tone-mapped on the device: mode 0 (POL_MONO8) -> (Hp, Wp) uint8, OFF dark / ON bright / 128
+        where nothing voted; mode 1 (POL_BGR8) -> (Hp, Wp, 3) BGR on white, ON red, OFF blue."""
+        out = np.empty((self.Hp, self.Wp, 3) if int(mode) == _lib.POL_BGR8 else (self.Hp, self.Wp), np.uint8)
+        self._ck(self._L.cmx_backend_recon_pol_render(self._ctx, float(gamma), int(mode), out.ctypes.data_as(_lib.c_u8p)))
+        return out
+
+    def reconstruct_pol_reset(self):
+        """Clear the ON / OFF planes and their counters (after the knots have moved); nothing else changes."""
+        self._ck(self._L.cmx_backend_recon_pol_reset(self._ctx))
 
     def reconstruct_get(self, with_counts=False):
         """The (Hp, Wp) fp32 plane [, events the sampling selected so far, events that voted so far]."""

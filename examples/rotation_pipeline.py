@@ -161,6 +161,9 @@ def refine_trajectory_online(be, traj, x, y, t, prm, store, stride_s, free=8, lo
     return knots, rep
 
 
+POLARITY_SEED = 2024  # --polarity-map: the synthetic stream's polarities are drawn, not modelled
+
+
 def reconstruct_panorama(be, traj, x, y, t, prm, store=None, knots=None):
     """All events inside the support of the refined trajectory, re-warped along the WHOLE of it (any number of control poses)
     into one panorama: BackendEvaluator.reconstruct_* (cmx_backend_recon_*).  Leaves the evaluator's window and map untouched.
@@ -179,7 +182,8 @@ def reconstruct_panorama(be, traj, x, y, t, prm, store=None, knots=None):
 
 
 def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefix=None, reconstruct=False, refine_global=False,
-                 refine_bound=False, refine_native=False, freeze_head=None, refine_online=None, online_free=8, export_warped=None):
+                 refine_bound=False, refine_native=False, freeze_head=None, refine_online=None, online_free=8, export_warped=None,
+                 polarity_map=None):
     """stream: synth.EventStream (or anything with x, y, t_ns, W, H, fx, fy, cx, cy, lut).  Returns a dict.
     display_prefix: write the final panorama with the last pose's FOV and the last packet's local-IWE pair there.
     reconstruct: after the last window, re-warp all events along the whole refined trajectory (res["recon"]; with
@@ -193,8 +197,12 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
     (refine_trajectory_online; res["online_knots"], res["online_report"]), with the last online_free control poses free.
     export_warped = PATH (implies reconstruct): where EVERY event of the reconstruction lands along the final trajectory, written to
     PATH.npz as xy (n x 2 panorama coordinates), flags (bit 0 sampled, bit 1 inside; 3 = the event voted) and index (the events'
-    indices in the stream) -- what a host joins with the polarity it kept; also res["warped"] = (index, xy, flags)."""
-    reconstruct = reconstruct or export_warped is not None
+    indices in the stream) -- what a host joins with whatever it kept per event; also res["warped"] = (index, xy, flags).
+    polarity_map = PREFIX (implies reconstruct): the signed panorama ON - OFF of the same events along the final trajectory
+    (BackendEvaluator.reconstruct_pol_*), written as PREFIX.pgm (OFF dark, ON bright) and PREFIX.ppm (ON red, OFF blue on white);
+    also res["pol"] = (on, off).  The synthetic stream has no brightness model, so the polarities are DRAWN from a seeded generator
+    (stream.polarity, when the stream has one, is used instead): the images show the arithmetic, not a scene's edges' signs."""
+    reconstruct = reconstruct or export_warped is not None or polarity_map is not None
     prm = prm or Params()
     x, y, t = stream.x, stream.y, stream.t_ns
     n_total = len(t)
@@ -205,10 +213,14 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
     if prm.deterministic:
         fe.set_deterministic(True)
         be.set_deterministic(True)
+    pol = None
+    if polarity_map is not None:
+        pol = getattr(stream, "polarity", None)
+        pol = np.random.default_rng(POLARITY_SEED).integers(0, 2, n_total).astype(np.uint8) if pol is None else np.asarray(pol)
     store = None
     if use_event_store:
         store = evaluator.EventStore(stream.W, stream.H, n_total)
-        store.push(x, y, t)
+        store.push(x, y, t, polarity=pol)  # (with polarity: a byte array beside the events, which nothing but reconstruct_pol_add_from reads)
 
     # ------------------------------------------------------------------ front end: packets (pushEvent)
     dt_av = _dur_ns(prm.dt_ang_vel)
@@ -394,6 +406,22 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
             img = be.reconstruct_render(0.75)
             with open(display_prefix + "_recon.pgm", "wb") as f:
                 f.write(b"P5\n%d %d\n255\n" % (img.shape[1], img.shape[0]) + img.tobytes())
+        if polarity_map is not None:  # (the same range in one call again, under the knots the count panorama was voted at)
+            t0 = time.perf_counter()
+            if store is not None:
+                be.reconstruct_pol_add_from(store, i_rec, n_rec)
+            else:
+                be.reconstruct_pol_add(x[i_rec:i_rec + n_rec], y[i_rec:i_rec + n_rec], t[i_rec:i_rec + n_rec], pol[i_rec:i_rec + n_rec])
+            on, off, n_on, n_off = be.reconstruct_pol_get(with_counts=True)
+            res["pol"] = (on, off)
+            mono, bgr = be.reconstruct_pol_render(0.75, 0), be.reconstruct_pol_render(0.75, 1)
+            with open(polarity_map + ".pgm", "wb") as f:
+                f.write(b"P5\n%d %d\n255\n" % (mono.shape[1], mono.shape[0]) + mono.tobytes())
+            with open(polarity_map + ".ppm", "wb") as f:  # (PPM is RGB)
+                f.write(b"P6\n%d %d\n255\n" % (bgr.shape[1], bgr.shape[0]) + np.ascontiguousarray(bgr[:, :, ::-1]).tobytes())
+            if log:
+                log("polarity map: %d ON and %d OFF events voted in %.2f ms -> %s.pgm, %s.ppm" %
+                    (n_on, n_off, (time.perf_counter() - t0) * 1e3, polarity_map, polarity_map))
         be.reconstruct_end()
     return res
 
@@ -455,6 +483,10 @@ def main():
     ap.add_argument("--export-warped", metavar="PATH", default=None,
                     help="after the final refinement, write PATH.npz: the panorama coordinate (xy) and flags of every event warped along "
                          "the whole trajectory, and the events' indices (implies --reconstruct)")
+    ap.add_argument("--polarity-map", metavar="PREFIX", default=None,
+                    help="after the reconstruction, write the signed panorama ON - OFF as PREFIX.pgm and PREFIX.ppm (implies "
+                         "--reconstruct).  The synthetic stream has no brightness model: the polarities are drawn from a seeded "
+                         "random generator, so the images demonstrate the calls, not a scene")
     ap.add_argument("--refine-global", action="store_true",
                     help="after the last window, one bundle adjustment over the whole trajectory (--reconstruct then uses its result)")
     ap.add_argument("--refine-bound", action="store_true",
@@ -480,7 +512,8 @@ def main():
     t0 = time.perf_counter()
     res = run_pipeline(stream, prm, use_event_store=not a.host_events, log=print, display_prefix=a.display, reconstruct=a.reconstruct,
                        refine_global=a.refine_global or a.refine_native, refine_bound=a.refine_bound, refine_native=a.refine_native,
-                       freeze_head=a.freeze_head, refine_online=a.refine_online, online_free=a.online_free, export_warped=a.export_warped)
+                       freeze_head=a.freeze_head, refine_online=a.refine_online, online_free=a.online_free, export_warped=a.export_warped,
+                       polarity_map=a.polarity_map)
     wall = time.perf_counter() - t0
     m = evaluate_against_truth(stream, res)
     print("%.2f s of events (%d) processed in %.2f s wall" % (a.seconds, len(stream.x), wall))

@@ -132,6 +132,10 @@ int cmx_frontend_create(cmx_ctx **out, int device, int W, int H, const double *l
  * checks, same errors, bit-identical device contents as the SoA entry points given the same events. */
 typedef struct { size_t stride, off_x, off_y, off_sec, off_nsec; } cmx_aos_layout;
 #define CMX_AOS_DVS_EVENT {16, 0, 2, 4, 8}
+/* The calls that read polarity (cmx_events_push_aos_pol, cmx_backend_recon_pol_add_aos) take the byte offset of a one-byte
+ * polarity field inside the record beside the layout (nonzero = ON); CMX_AOS_DVS_POLARITY is dvs_msgs::Event's.  The layout
+ * struct itself stays as it is: it is passed by pointer and its size is part of the ABI. */
+#define CMX_AOS_DVS_POLARITY 12
 
 /* State AngVelEstimator hands over before a solve (src/frontend/ang_vel_estimator.cpp:137-147):
  * event_subset_ (SoA here; polarity is never read), time_packet_, camera_matrix_ (fx,fy,cx,cy),
@@ -282,7 +286,14 @@ int64_t cmx_traj_temp_start_ns(double t_beg, int idx_traj_beg, double dt_knots);
  * given to cmx_backend_create_group): cmx_events_push packs once on the host and uploads to all replicas side by side,
  * cmx_events_drop_before compacts all of them, cmx_backend_set_window_from on the group's handle lets every member cut ITS
  * batch range on its own device (no event crosses the host at hand-over), and any front-end / back-end context on one of
- * those devices can cut from it too.  cmx_events_devices lists the replicas' devices (returns their number). */
+ * those devices can cut from it too.  cmx_events_devices lists the replicas' devices (returns their number).
+ * Polarity.  cmx_events_push_pol / _push_aos_pol store one polarity byte per event (0 = OFF, 1 = ON; any nonzero input is ON) in
+ * an array of its own beside the coordinates and timestamps, on every replica, allocated by the first such push and compacted by
+ * cmx_events_drop_before like the other two.  A store holds polarity for ALL of its events or for none: the first push into an
+ * empty store decides, and the other form of push into a non-empty store returns CMX_ERR_STATE and pushes nothing.  A store that
+ * never saw a _pol push allocates and copies exactly what it did before these calls existed.  The only reader of the bytes is
+ * cmx_backend_recon_pol_add_from: packets, windows, recon_add_from, bind_from and warp_from cut from a store with polarity get
+ * the same bits as from one without.  cmx_events_has_polarity: 1 when the events held carry polarity, else 0 (an empty store: 0). */
 typedef struct cmx_events cmx_events;
 int cmx_events_create(cmx_events **out, int device, int W, int H, size_t capacity);
 int cmx_events_create_group(cmx_events **out, const int *devices, int n_devices, int W, int H, size_t capacity);
@@ -291,6 +302,9 @@ void cmx_events_destroy(cmx_events *ev);
 const char *cmx_events_last_error(const cmx_events *ev);
 int cmx_events_push(cmx_events *ev, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns);
 int cmx_events_push_aos(cmx_events *ev, int64_t n, const void *events, const cmx_aos_layout *layout); /* e.g. msg->events.data() */
+int cmx_events_push_pol(cmx_events *ev, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, const uint8_t *pol);
+int cmx_events_push_aos_pol(cmx_events *ev, int64_t n, const void *events, const cmx_aos_layout *layout, size_t off_polarity);
+int cmx_events_has_polarity(const cmx_events *ev);
 int cmx_events_drop_before(cmx_events *ev, int64_t global_index);
 int64_t cmx_events_begin(const cmx_events *ev); /* global index of the oldest event held */
 int64_t cmx_events_end(const cmx_events *ev);   /* one past the newest */
@@ -345,8 +359,8 @@ int cmx_backend_recon_get(cmx_ctx *ctx, float *pano /* Hp*Wp or NULL */, int64_t
 int cmx_backend_recon_render(cmx_ctx *ctx, double gamma, const double fov_quat_xyzw[4] /* or NULL */, unsigned char *out);
 int cmx_backend_recon_end(cmx_ctx *ctx);
 /* Per-event export: WHERE every event lands under the trajectory the reconstruction holds -- what a host needs for any product other
- * than the count panorama (a signed polarity map, a time surface, a cropped or super-resolved mosaic, outlier flags): the library
- * never reads polarity, the host joins the entries with whatever it kept.
+ * than the count panorama (a time surface, a cropped or super-resolved mosaic, outlier flags; the signed polarity map has calls of
+ * its own, cmx_backend_recon_pol_*): the export itself never reads polarity, the host joins the entries with whatever it kept.
  *   output   ONE entry per event handed in, sampled or not, in input order: xy_out[2i], xy_out[2i+1] = (px, py), flags_out[i]
  *            (flags_out may be NULL).  CMX_WARP_F64: 2 doubles per event; CMX_WARP_F32: 2 floats, (float)px and (float)py.
  *   poses    spline, batch size and sample rate are those of recon_begin / restart / extend; the knots are the ones the
@@ -381,6 +395,38 @@ int cmx_backend_recon_warp_from(cmx_ctx *ctx, const cmx_events *ev, int64_t firs
                                 unsigned char *flags_out);
 int cmx_backend_recon_warp_from_device(cmx_ctx *ctx, const cmx_events *ev, int64_t first, int64_t count, int format, void *d_xy_out,
                                        unsigned char *d_flags_out /* device pointers on the context's device */);
+/* Signed polarity panorama: the ON and the OFF events of the recording as two planes, ON - OFF being the map that feeds intensity
+ * reconstruction and the usual red / blue picture.  On an open reconstruction:
+ *     recon_pol_add*(events, polarity) ...   recon_pol_get / recon_pol_render (any number of times)   [recon_pol_reset]
+ *   pol_add*   ONE call = the vote loop of add* over exactly the events handed in -- the same batches and batch times, sampling
+ *              restarting at every batch start, the lone trailing event skipped, the same vote test, cell and weights (the same
+ *              device functions) -- with ONE difference: an event with polarity != 0 votes into the ON plane, any other into the OFF
+ *              plane.  Polarity: pol[i] (one byte per event), the byte at off_polarity of record i (CMX_AOS_DVS_POLARITY for
+ *              dvs_msgs::Event), or the store's own (pol_add_from: CMX_ERR_STATE when the store holds none).  Validation and status
+ *              codes are add*'s, complete before the first vote: a call that fails validation adds nothing to either plane.
+ *   planes     two Hp*Wp planes (and their 2^-30 fixed-point twins when CMX_OPT_DETERMINISTIC was 1 at begin: bitwise reproducible,
+ *              for any slicing at batch multiples and through every ingest path), allocated by the first pol_add*.  begin, restart
+ *              and pol_reset clear them -- votes under other knots are stale -- and end frees them.  EVERY other call leaves them
+ *              alone, extend, eval_bound and recon_solve included, although they move the knots: call pol_reset before voting anew.
+ *   state      the count plane of add*, its counters, an open gradient pass, a binding, a frozen or released head, the window, IG
+ *              and the exchange sets are neither read nor written: the calls work with a gradient pass open, with events bound,
+ *              after freeze_head and after release_head (only the knots are read).
+ *   pol_get    on / off = Hp*Wp fp32 each or NULL; *n_on / *n_off = events that voted into each plane so far; either may be NULL.
+ *              Before the first pol_add*: zeros.
+ *   pol_render one device pass over s = ON - OFF: m = max |s| (m == 0: the neutral image), v = sign(s) (|s| / m)^gamma in fp32;
+ *              CMX_POL_MONO8: out = Hp*Wp bytes, rint(127.5f + 127.5f v) -- OFF dark, ON bright, no votes 128;
+ *              CMX_POL_BGR8: out = Hp*Wp*3 bytes on white, a = rint(255 |v|): an ON pixel is (B, G, R) = (255 - a, 255 - a, 255),
+ *              an OFF pixel (255, 255 - a, 255 - a).  Any other mode, gamma <= 0 or not finite: CMX_ERR_INVALID_ARG.
+ *   pol_reset  clears the two planes and their counters, nothing else.
+ * All of them return CMX_ERR_STATE before begin and on a group handle. */
+#define CMX_POL_MONO8 0
+#define CMX_POL_BGR8  1
+int cmx_backend_recon_pol_add(cmx_ctx *ctx, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, const uint8_t *pol);
+int cmx_backend_recon_pol_add_aos(cmx_ctx *ctx, int64_t n, const void *events, const cmx_aos_layout *layout, size_t off_polarity);
+int cmx_backend_recon_pol_add_from(cmx_ctx *ctx, const cmx_events *ev, int64_t first, int64_t count);
+int cmx_backend_recon_pol_get(cmx_ctx *ctx, float *on, float *off /* Hp*Wp each, either may be NULL */, int64_t *n_on, int64_t *n_off);
+int cmx_backend_recon_pol_render(cmx_ctx *ctx, double gamma, int mode, unsigned char *out);
+int cmx_backend_recon_pol_reset(cmx_ctx *ctx);
 /* Whole-trajectory contrast and its gradient with respect to a LEFT increment of every control pose, on top of an open
  * reconstruction -- the evaluation one bundle adjustment over the whole recording needs, for a spline of any knot count:
  *     recon_begin   recon_add*(events) ...   recon_contrast(want_grad)   recon_grad_add*(the same events) ...   recon_grad_get
