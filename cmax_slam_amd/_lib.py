@@ -22,6 +22,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
 OPT_GRAD_MODE, OPT_SPLAT_MODE, OPT_REUSE_IMAGE, OPT_SPIN_WAIT, OPT_DETERMINISTIC, OPT_TAIL_FINALIZE = 1, 2, 3, 4, 5, 6
 OPT_COMPOSITE_IMAGE, OPT_FOLD_BATCH, OPT_GATED_DF, OPT_CHAIN_SOLVE, OPT_FUSED_IMAGE = 8, 9, 10, 11, 12
 DIAG_FORCE_CROSS_DEVICE, DIAG_RECON_SLICE_EVENTS = 1, 2  # cmx_diag_set keys (include/cmax_hip_diag.h)
+DIAG_JT_EVAL, DIAG_JT_RECON = 0, 1  # cmx_diag_get_adjoint_plane: which
 WARP_F64, WARP_F32 = 0, 1  # cmx_backend_recon_warp*: output format
 WARP_SAMPLED, WARP_INSIDE = 1, 2  # ... and the flag bits
 POL_MONO8, POL_BGR8 = 0, 1  # cmx_backend_recon_pol_render: mode
@@ -166,6 +167,7 @@ SYMBOLS = {
     "cmx_backend_recon_solve": (C.c_int, [ctx_p, c_dp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double,
                                           C.c_double, C.c_int, C.c_void_p]),
     "cmx_diag_recon_solve_counts": (C.c_int, [ctx_p, c_i64p, c_i64p]),
+    "cmx_diag_get_adjoint_plane": (C.c_int, [ctx_p, C.c_int, c_fp]),
     "cmx_traj_temp_start_ns": (C.c_int64, [C.c_double, C.c_int, C.c_double]),
     "cmx_accum_capacity": (C.c_size_t, [ctx_p]),
     "cmx_set_accum_buffer": (C.c_int, [ctx_p, C.c_void_p, C.c_size_t]),

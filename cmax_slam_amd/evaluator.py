@@ -100,6 +100,11 @@ class _Evaluator:
                 "chain_takeovers": int(s[15]), "chain_warm_starts": int(s[16]), "fused_evals": int(s[17]), "fused_redos": int(s[18]), "one_launch_evals": int(s[19]), "fused_timeouts": int(s[20]), "self_serve_evals": int(s[21]),
                 "host_finalize_evals": int(s[22])}
 
+    def _adjoint_plane(self, which, H, W):
+        out = np.empty((H, W), np.float32)
+        self._ck(self._L.cmx_diag_get_adjoint_plane(self._ctx, int(which), out.ctypes.data_as(c_fp)))
+        return out
+
     def hint_next_df(self, threshold, mode):
         """cmx_hint_next_df: the next cost-only evaluation's value f = -contrast decides (mode 1: f < threshold, 2: f <= threshold,
         3: not f >= threshold, 4: always) whether the gradient pass is queued behind it."""
@@ -408,6 +413,11 @@ class FrontendEvaluator(_Evaluator):
         self._ck(self._L.cmx_frontend_finish(self._ctx, C.byref(c), _dp(g) if want_grad else None))
         return c.value, (g if want_grad else None)
 
+    def adjoint_plane(self):
+        """Diagnostic (cmx_diag_get_adjoint_plane): Jt, (H, W) fp32, as the last adjoint image pass left it -- tiles that pass
+        skipped keep older values."""
+        return self._adjoint_plane(_lib.DIAG_JT_EVAL, self.H, self.W)
+
     # --- reference-named entry points
     def computeImageOfWarpedEvents(self, ang_vel, want_deriv=False, blur=True):
         """image_warped (H x W fp32) [, image_warped_deriv (H x W x 3 fp32)]."""
@@ -574,6 +584,15 @@ class BackendEvaluator(_Evaluator):
         out = np.empty((self.Hp, self.Wp), np.float32)
         self._ck(self._L.cmx_backend_get_plane(self._ctx, int(which), out.ctypes.data_as(c_fp)))
         return out
+
+    def adjoint_plane(self):
+        """Diagnostic (cmx_diag_get_adjoint_plane): the window's Jt, (Hp, Wp) fp32, as the last adjoint image pass left it --
+        tiles that pass skipped keep older values."""
+        return self._adjoint_plane(_lib.DIAG_JT_EVAL, self.Hp, self.Wp)
+
+    def reconstruct_adjoint_plane(self):
+        """... and the whole-trajectory reconstruction's Jt (its own plane, not the window's)."""
+        return self._adjoint_plane(_lib.DIAG_JT_RECON, self.Hp, self.Wp)
 
     @property
     def alpha(self):

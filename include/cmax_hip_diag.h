@@ -120,6 +120,21 @@ int cmx_diag_set(int key, int value);
  * (tools/time_recon_grad.py reports the quotient).  Either pointer may be NULL; zero before the first solve. */
 int cmx_diag_recon_solve_counts(cmx_ctx *ctx, int64_t *evaluations, int64_t *host_waits);
 
+/* Read-only read-back of Jt, the plane every gradient gather reads: G^T G A for variance / mean square, G^T (Sx^T Sx + Sy^T Sy) G A
+ * for the gradient-magnitude contrast (A the forward plane before the blur, G the REFLECT_101 Gaussian, Sx / Sy cv::Sobel 3 x 3).
+ *   CMX_DIAG_JT_EVAL   the context's own plane: a front-end packet's (H x W) or a back-end window's (pano_height x pano_width)
+ *   CMX_DIAG_JT_RECON  the whole-trajectory reconstruction's (pano_height x pano_width; cmx_backend_recon_contrast with want_grad,
+ *                      _eval_from, _eval_bound, _solve)
+ * host takes imgH * imgW floats, row-major.  The call waits for the context's stream, copies device to host and changes no state.
+ * The contents are whatever the LAST adjoint image pass left: a tile (64 x 16) that pass skipped -- nothing non-zero of the forward
+ * plane within the operator's reach of it, where Jt is exactly zero -- keeps what an earlier pass wrote there (zero at first), and
+ * the library keeps no record of which tiles were written; tests/dense_image_ops.py (compare_set) derives the set from the forward
+ * plane.  A cost-only evaluation may or may not run the pass (CMX_OPT_REUSE_IMAGE).
+ * CMX_ERR_STATE: the plane was never allocated (no adjoint gradient evaluation so far).  CMX_ERR_INVALID_ARG: a null pointer, an
+ * unknown `which`, a group handle (each member holds its own plane). */
+enum { CMX_DIAG_JT_EVAL = 0, CMX_DIAG_JT_RECON = 1 };
+int cmx_diag_get_adjoint_plane(cmx_ctx *ctx, int which, float *host /* imgH*imgW fp32 */);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

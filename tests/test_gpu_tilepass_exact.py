@@ -21,7 +21,8 @@ arithmetic alone:
 import numpy as np
 import pytest
 
-from cmax_slam_amd import _lib, synth
+from cmax_slam_amd import _lib
+from dense_image_ops import exact_packet as _packet  # (its construction; also the plane of tests/test_gpu_adjoint_plane.py)
 from util import rel_scalar, rel_vec
 
 pytestmark = pytest.mark.gpu
@@ -33,27 +34,6 @@ PARENT_GRAD_DIFF = {
     (100, 70, 0): 1.233e-15,
     (100, 70, 1): 1.205e-15,
 }
-
-
-def _packet(W, H):
-    """Integer-pixel events, uneven counts per pixel (blobs of different weight over a sparse uniform floor), fx = fy = 256."""
-    rng = np.random.default_rng(1000 * W + H)
-    n = max(20_000, (W * H * 2) // 3)
-    nb = 40
-    cxs, cys = rng.uniform(0, W, nb), rng.uniform(0, H, nb)
-    spread = rng.uniform(1.5, 0.08 * W, nb)
-    which = rng.choice(nb, size=n, p=rng.dirichlet(np.ones(nb)))
-    x = np.rint(cxs[which] + spread[which] * rng.standard_normal(n))
-    y = np.rint(cys[which] + spread[which] * rng.standard_normal(n))
-    floor = rng.random(n) < 0.15
-    x[floor] = rng.integers(0, W, int(floor.sum()))
-    y[floor] = rng.integers(0, H, int(floor.sum()))
-    x = np.clip(x, 0, W - 2).astype(np.uint16)  # (the vote's 2 x 2 cell stays inside the image)
-    y = np.clip(y, 0, H - 2).astype(np.uint16)
-    T = 0.05
-    t_ns = synth.T0_NS + np.sort(np.floor(rng.random(n) * T * 1e9).astype(np.int64))
-    return synth.FrontendPacket(W, H, 256.0, 256.0, float(W // 2), float(H // 2), x, y, t_ns, synth.T0_NS + int(round(T / 2 * 1e9)),
-                                np.zeros(3))
 
 
 def _fe(hip, p, fused, measure):
