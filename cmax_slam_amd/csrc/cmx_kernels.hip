@@ -560,7 +560,8 @@ __device__ __forceinline__ void direct_moment_sums(const FinalizeArgs &a, FinSme
   }
 }
 
-template <int NT, bool CHAIN = false>  // CHAIN: the device-driven solve's variant (the machine's step is compiled in)
+// WIDE: the back-end gathers' tails, whose S1 | S2 columns (2 gP, up to 2 * 3 * kMaxKnots) can outnumber the workgroup's threads
+template <int NT, bool CHAIN = false, bool WIDE = false>  // CHAIN: the device-driven solve's variant (the machine's step is compiled in)
 __device__ __forceinline__ void finalize_body(const FinalizeArgs &a, FinSmem &sm) {
   constexpr int NW = NT / 64;   // waves (direct_moment_sums: half of them per image-moment row)
   static_assert(NW >= 2 && NW <= 16 && 2 + 3 * kMaxKnots < NT, "finalize geometry");
@@ -663,6 +664,16 @@ __device__ __forceinline__ void finalize_body(const FinalizeArgs &a, FinSmem &sm
     sm.cols[t] = w;
 #pragma unroll
     for (int q = 0; q < kTailShards; q++) st_sc1(a.gacc + (size_t)q * a.gacc_stride + t, 0.0);
+  }
+  // columns beyond the workgroup's width -- S1 | S2 of more than NT / 6 free knots in a 256-thread tail (2 gP > NT: the S2 sums of
+  // the last knots) -- in further rounds, same order of the adds.  Without them those cols[] entries were whatever LDS held, times mu.
+  for (int col = t + NT; WIDE && col < ncol_acc; col += NT) {
+    double w = 0;
+#pragma unroll
+    for (int q = 0; q < kTailShards; q++) w += ld_sc1(a.gacc + (size_t)q * a.gacc_stride + col);
+    sm.cols[col] = w;
+#pragma unroll
+    for (int q = 0; q < kTailShards; q++) st_sc1(a.gacc + (size_t)q * a.gacc_stride + col, 0.0);
   }
   __syncthreads();
   const double s0 = sm.sh[0], s1 = sm.sh[1];
@@ -2194,7 +2205,7 @@ __global__ __launch_bounds__(256) void be_gather4_kernel(BeGatherArgs g) {
       if (v1 != 0.0) __hip_atomic_fetch_add(row + j, v1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (v2 != 0.0) __hip_atomic_fetch_add(row + g.P + j, v2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (g.tail.counters && tail_arrive(g.tail, (int)gridDim.x, (int)blockIdx.x, fin_sm)) finalize_body<256>(g.tail.fin, fin_sm);
+    if (g.tail.counters && tail_arrive(g.tail, (int)gridDim.x, (int)blockIdx.x, fin_sm)) finalize_body<256, false, true>(g.tail.fin, fin_sm);
   }
 }
 
@@ -2278,7 +2289,7 @@ __global__ __launch_bounds__(256) void be_gather_batch_kernel(BeGatherArgs g, in
       g.gpartials[(size_t)(g.P + j) * gridDim.x + blockIdx.x] = shG2[j];
     }
   }
-  if (tail && tail_arrive(g.tail, (int)gridDim.x, (int)blockIdx.x, fin_sm)) finalize_body<256>(g.tail.fin, fin_sm);
+  if (tail && tail_arrive(g.tail, (int)gridDim.x, (int)blockIdx.x, fin_sm)) finalize_body<256, false, true>(g.tail.fin, fin_sm);
 }
 
 __global__ __launch_bounds__(256) void bearing_stream_kernel(const uint32_t *xy, const double *lut2, int W, int n, double *tb) {
