@@ -168,6 +168,7 @@ SYMBOLS = {
                                           C.c_double, C.c_int, C.c_void_p]),
     "cmx_diag_recon_solve_counts": (C.c_int, [ctx_p, c_i64p, c_i64p]),
     "cmx_diag_get_adjoint_plane": (C.c_int, [ctx_p, C.c_int, c_fp]),
+    "cmx_diag_get_forward_plane": (C.c_int, [ctx_p, c_fp]),
     "cmx_traj_temp_start_ns": (C.c_int64, [C.c_double, C.c_int, C.c_double]),
     "cmx_accum_capacity": (C.c_size_t, [ctx_p]),
     "cmx_set_accum_buffer": (C.c_int, [ctx_p, C.c_void_p, C.c_size_t]),

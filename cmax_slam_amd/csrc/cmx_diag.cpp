@@ -24,3 +24,18 @@ int cmx_diag_get_adjoint_plane(cmx_ctx *c, int which, float *host) {
   HIP_TRY(c, hipMemcpy(host, src, np * sizeof(float), hipMemcpyDeviceToHost));
   return CMX_OK;
 }
+
+// The front end's forward plane: plane 0 of the buffer the last fe_accumulate voted into, whichever call ran it.
+int cmx_diag_get_forward_plane(cmx_ctx *c, float *host) {
+  if (!c || !host) return fail(c, CMX_ERR_INVALID_ARG, "null context / host buffer");
+  if (c->group) return fail(c, CMX_ERR_INVALID_ARG, "the forward plane of a group lives in its members: not available on a group handle");
+  if (c->kind != KIND_FE) return fail(c, CMX_ERR_STATE, "not a front-end context");
+  const size_t np = (size_t)c->W * c->H;
+  if (!c->have_data || !c->accumulated || !c->d_accum || np == 0 || c->accum_count < np)
+    return fail(c, CMX_ERR_STATE, "no accumulate since the packet was set: the plane holds no evaluation's votes");
+  int rc = bind_device(c);
+  if (rc) return rc;
+  if (c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(host, c->d_accum, np * sizeof(float), hipMemcpyDeviceToHost));
+  return CMX_OK;
+}

@@ -418,6 +418,13 @@ class FrontendEvaluator(_Evaluator):
         skipped keep older values."""
         return self._adjoint_plane(_lib.DIAG_JT_EVAL, self.H, self.W)
 
+    def forward_plane(self):
+        """Diagnostic (cmx_diag_get_forward_plane): the forward plane before the blur, (H, W) fp32 -- the votes of the context's last
+        splat, whichever call made it (an evaluation's fused splat included); nothing is launched."""
+        out = np.empty((self.H, self.W), np.float32)
+        self._ck(self._L.cmx_diag_get_forward_plane(self._ctx, out.ctypes.data_as(c_fp)))
+        return out
+
     # --- reference-named entry points
     def computeImageOfWarpedEvents(self, ang_vel, want_deriv=False, blur=True):
         """image_warped (H x W fp32) [, image_warped_deriv (H x W x 3 fp32)]."""

@@ -135,6 +135,16 @@ int cmx_diag_recon_solve_counts(cmx_ctx *ctx, int64_t *evaluations, int64_t *hos
 enum { CMX_DIAG_JT_EVAL = 0, CMX_DIAG_JT_RECON = 1 };
 int cmx_diag_get_adjoint_plane(cmx_ctx *ctx, int which, float *host /* imgH*imgW fp32 */);
 
+/* Read-only read-back of a front-end context's forward plane A (H x W fp32, row-major): the votes of the LAST splat the context
+ * ran, whichever call made it -- cmx_frontend_eval (also the fused forms, whose plane no other call hands out: cmx_frontend_get_iwe
+ * votes again, never fused), _accumulate, _get_iwe, the second pass of _render_display, a slot of a device-driven solve.  Plane 0 of
+ * the context's current accumulation buffer before the blur; in deterministic mode the fp32 plane the fixed-point votes were
+ * converted into.  The ping-pong partner is not readable.  The call waits for the context's stream, copies device to host, queues
+ * no kernel and changes no state.
+ * CMX_ERR_STATE: not a front-end context, or no accumulate since the packet was set.  CMX_ERR_INVALID_ARG: a null pointer, a
+ * group handle. */
+int cmx_diag_get_forward_plane(cmx_ctx *ctx, float *host /* H*W fp32 */);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

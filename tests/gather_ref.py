@@ -80,6 +80,15 @@ class EventList:
 
 
 # ---------------------------------------------------------------------------------------------------------------- front end
+def device_int(u):
+    """(int)u as the kernels' conversion instruction gives it: truncation, saturated to the int32 range, NaN -> 0 -- decided
+    before any integer cast on the host (a ray with rz near zero gives |u| beyond every integer type)"""
+    u = np.asarray(u, np.float64)
+    lo, hi = -2.0 ** 31, 2.0 ** 31 - 1
+    safe = np.clip(np.where(np.isnan(u), 0.0, u), lo, hi)
+    return np.trunc(safe).astype(np.int64)
+
+
 def fe_events(p, omega, batch=None):
     """EventList of a synth.FrontendPacket at angular velocity omega (fe_warp_math<true>, cmx_warp.hpp, operation for operation)"""
     batch = p.batch if batch is None else batch
@@ -97,17 +106,18 @@ def fe_events(p, omega, batch=None):
     rx = px + (dry * pz - drz * py)
     ry = py + (drz * px - drx * pz)
     rz = pz + (drx * py - dry * px)
-    iz = 1.0 / rz
-    cxn, cyn = rx * iz, ry * iz
-    u = p.fx * cxn + p.cx
-    v = p.fy * cyn + p.cy
-    xx, yy = np.trunc(u).astype(np.int64), np.trunc(v).astype(np.int64)
-    ok = (1 <= xx) & (xx < p.W - 2) & (1 <= yy) & (yy < p.H - 2)
-    dx, dy = (u - xx).astype(F32), (v - yy).astype(F32)
-    vx, vy, vz = (-dt) * px, (-dt) * py, (-dt) * pz
-    a02, a12 = -cxn * iz, -cyn * iz
-    r0 = np.stack([p.fx * (a02 * (-vy)), p.fx * (iz * (-vz) + a02 * vx), p.fx * (iz * vy)], axis=1).astype(F32)
-    r1 = np.stack([p.fy * (iz * vz + a12 * (-vy)), p.fy * (a12 * vx), p.fy * (iz * (-vx))], axis=1).astype(F32)
+    with np.errstate(all="ignore"):  # (rz == 0, overflow past fp32 of an event that does not vote: the kernels' values as well)
+        iz = 1.0 / rz
+        cxn, cyn = rx * iz, ry * iz
+        u = p.fx * cxn + p.cx
+        v = p.fy * cyn + p.cy
+        xx, yy = device_int(u), device_int(v)
+        ok = (1 <= xx) & (xx < p.W - 2) & (1 <= yy) & (yy < p.H - 2)
+        dx, dy = (u - xx).astype(F32), (v - yy).astype(F32)
+        vx, vy, vz = (-dt) * px, (-dt) * py, (-dt) * pz
+        a02, a12 = -cxn * iz, -cyn * iz
+        r0 = np.stack([p.fx * (a02 * (-vy)), p.fx * (iz * (-vz) + a02 * vx), p.fx * (iz * vy)], axis=1).astype(F32)
+        r1 = np.stack([p.fy * (iz * vz + a12 * (-vy)), p.fy * (a12 * vx), p.fy * (iz * (-vx))], axis=1).astype(F32)
     J = np.stack([r0, r1], axis=1)[ok]  # (n, 2, 3) fp32: the kernel holds r0, r1 in fp32 and widens the products
     return EventList(p.W, p.H, 3, xx[ok], yy[ok], dx[ok], dy[ok], J.astype(np.float64), J, np.zeros(int(ok.sum()), np.int64),
                      np.eye(3)[None], np.zeros(1, np.int64), src=np.nonzero(ok)[0], dx64=(u - xx)[ok], dy64=(v - yy)[ok],
