@@ -43,6 +43,16 @@ class AosLayout(C.Structure):  # cmx_aos_layout: record size + byte offsets of (
     _fields_ = [("stride", C.c_size_t), ("off_x", C.c_size_t), ("off_y", C.c_size_t), ("off_sec", C.c_size_t), ("off_nsec", C.c_size_t)]
 
 
+class ReconView(C.Structure):  # cmx_recon_view: one virtual pinhole camera of cmx_backend_recon_view_begin
+    _fields_ = [("quat_xyzw", C.c_double * 4), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("t_lo_ns", C.c_int64), ("t_hi_ns", C.c_int64)]
+
+
+def recon_view(quat_xyzw, fx, fy, cx, cy, t_lo_ns, t_hi_ns):
+    return ReconView((C.c_double * 4)(*[float(v) for v in quat_xyzw]), float(fx), float(fy), float(cx), float(cy),
+                     int(t_lo_ns), int(t_hi_ns))
+
+
 import numpy as _np  # noqa: E402
 # dvs_msgs::Event as the reference's std::vector holds it: {uint16 x, y; ros::Time ts {uint32 sec, nsec}; bool polarity} = 16 bytes
 DVS_EVENT_DTYPE = _np.dtype({"names": ["x", "y", "sec", "nsec", "polarity"], "formats": ["<u2", "<u2", "<u4", "<u4", "u1"],
@@ -143,6 +153,14 @@ SYMBOLS = {
     "cmx_backend_recon_pol_get": (C.c_int, [ctx_p, c_fp, c_fp, c_i64p, c_i64p]),
     "cmx_backend_recon_pol_render": (C.c_int, [ctx_p, C.c_double, C.c_int, c_u8p]),
     "cmx_backend_recon_pol_reset": (C.c_int, [ctx_p]),
+    "cmx_backend_recon_view_begin": (C.c_int, [ctx_p, C.c_int, C.c_int, C.c_int, C.POINTER(ReconView)]),
+    "cmx_backend_recon_view_add": (C.c_int, [ctx_p, C.c_int64, c_u16p, c_u16p, c_i64p]),
+    "cmx_backend_recon_view_add_aos": (C.c_int, [ctx_p, C.c_int64, C.c_void_p, C.POINTER(AosLayout)]),
+    "cmx_backend_recon_view_add_from": (C.c_int, [ctx_p, C.c_void_p, C.c_int64, C.c_int64]),
+    "cmx_backend_recon_view_get": (C.c_int, [ctx_p, C.c_int, C.c_int, c_fp, c_i64p]),
+    "cmx_backend_recon_view_render": (C.c_int, [ctx_p, C.c_int, C.c_double, c_u8p]),
+    "cmx_backend_recon_view_reset": (C.c_int, [ctx_p]),
+    "cmx_backend_recon_view_end": (C.c_int, [ctx_p]),
     "cmx_backend_recon_get": (C.c_int, [ctx_p, c_fp, c_i64p, c_i64p]),
     "cmx_backend_recon_render": (C.c_int, [ctx_p, C.c_double, c_dp, C.POINTER(C.c_uint8)]),
     "cmx_backend_recon_end": (C.c_int, [ctx_p]),

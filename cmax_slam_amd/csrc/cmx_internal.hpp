@@ -470,6 +470,30 @@ struct ReconWarpArgs {
   int vec;                   // xy_out is aligned for one 16- / 8-byte pair store per lane
 };
 void launch_recon_warp(const ReconWarpArgs &g, hipStream_t s);
+// pinhole views (cmx_backend_recon_view_*): the vote loop of launch_recon_votes with M virtual pinhole cameras as its targets.  An
+// event's world ray is formed once and voted into every view whose time range holds its batch time; planes / fixed hold n_views
+// planes of Wv x Hv, n_voted one counter per view.  ev.plane / ev.fixed / ev.n_inside / ev.pol are not used.
+struct ReconViewDev {        // one view as the kernel reads it: 16 eight-byte words
+  double Rt[9];              // R(quat)^T, row-major: ray_cam = Rt ray_world
+  double fx, fy, cx, cy;
+  long long t_lo, t_hi;      // votes of the batches with t_lo <= batch time < t_hi
+  long long index;           // of the view in the set: its plane and its counter
+};
+struct ReconViewRange { long long t_lo, t_hi; };  // the same range in a table of its own: what a workgroup scans
+// views a workgroup holds in LDS at a time; more that meet its run are taken chunk by chunk.  A run of 2048 events meets one or two
+// frames of a video, three when the exposure is twice the period; every view beyond that costs its projection anyway, next to which
+// the chunk's two barriers and the re-read bearing are small
+constexpr int kReconViewChunk = 3;
+struct ReconViewArgs {
+  ReconArgs ev;
+  const ReconViewDev *views;       // [n_views]
+  const ReconViewRange *ranges;    // [n_views]
+  int n_views, Wv, Hv;
+  float *planes;                   // [n_views][Hv * Wv]: fp32 atomics ...
+  unsigned long long *fixed;       // ... or, when set, 64-bit integer adds into the 2^-30 fixed-point twins
+  unsigned long long *n_voted;     // [n_views] events that voted into each view
+};
+void launch_recon_view_votes(const ReconViewArgs &g, hipStream_t s);
 // bound events (cmx_backend_recon_bind_from / _eval_bound): the batch poses of a spline of any knot count as a table in global
 // memory (recon_pose<N>, one thread per batch: a.batch_t, a.nb) -- what the tile sort (launch_count_sort with poseR = the table)
 // and the vote kernel below read -- and the vote pass over the tile-sorted events: one workgroup per chunk, votes into a

@@ -156,6 +156,133 @@ void launch_recon_votes_pol(const ReconArgs &a, hipStream_t s) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------- pinhole views
+// recon_view_votes   cmx_backend_recon_view_add*: the run structure of recon_votes -- the first lanes evaluate the run's batch poses into
+//                LDS, and keep the batch times beside them -- with M virtual pinhole cameras as the targets of the votes.  After the
+//                barrier the workgroup scans the table of view ranges ONCE, 16 bytes per view and lane, and lists the views whose
+//                [t_lo, t_hi) meets the span of its batch times; the per-event cost therefore depends on the views a run meets
+//                (one or two for disjoint frames), not on n_views.  The listed views are taken kReconViewChunk at a time: their
+//                128-byte entries (R^T, intrinsics, range, index) are copied into LDS, one barrier, then all lanes walk the run's
+//                events: the world ray R_batch * bearing is formed once per event and chunk (be_rotate, the vote kernel's own
+//                function on the vote kernel's own pose), and for every view of the chunk that holds the batch time it is turned
+//                into the camera, projected, tested in floating point and voted with the four bilinear adds of vote4_global /
+//                vote4_global_fix into that view's plane.  A run that meets more views than a chunk holds walks its events again
+//                for the next chunk (the bearing and the pose are re-read; the votes of a view do not depend on the chunking).
+//                Votes per view are counted in LDS and leave by one global atomic per listed view and workgroup.
+constexpr int kReconMaxViews = 4096;  // (cmx_backend_recon_view_begin refuses more: the list of a workgroup holds any subset)
+static_assert(sizeof(ReconViewDev) == 128 && sizeof(ReconViewRange) == 16, "view entries are copied word by word");
+
+template <int N, bool FIXED>
+__global__ __launch_bounds__(kReconThreads) void recon_view_votes_kernel(const ReconViewArgs g) {
+  constexpr int kWords = sizeof(ReconViewDev) / 8;
+  __shared__ double sh_R[(kReconMaxRun + 2) * 9];
+  __shared__ long long sh_bt[kReconMaxRun + 2];
+  __shared__ ReconViewDev sh_view[kReconViewChunk];
+  __shared__ unsigned sh_cnt[kReconViewChunk];
+  __shared__ unsigned short sh_match[kReconMaxViews];
+  __shared__ unsigned sh_nmatch;
+  __shared__ long long sh_tmin, sh_tmax;
+  const ReconArgs &a = g.ev;
+  const int tid = threadIdx.x;
+  const int e0 = blockIdx.x * a.run;  // (the grid covers [0, n): e0 < n)
+  const int e1 = (a.n - e0 > a.run) ? e0 + a.run : a.n;
+  const int b0 = e0 / a.per_batch;
+  int nbw = (e1 - 1) / a.per_batch - b0 + 1;
+  if (nbw > kReconMaxRun + 2) nbw = kReconMaxRun + 2;  // (cannot happen with run = recon_run(per_batch))
+  if (tid == 0) { sh_nmatch = 0; sh_tmin = 0x7fffffffffffffffLL; sh_tmax = -0x7fffffffffffffffLL - 1; }
+  __syncthreads();
+  for (int j = tid; j < nbw; j += kReconThreads) {
+    const int b = b0 + j < a.nb ? b0 + j : a.nb - 1;
+    const long long t = a.batch_t[b];
+    recon_pose<N>(a, t, sh_R + 9 * j);
+    sh_bt[j] = t;
+    atomicMin(&sh_tmin, t);
+    atomicMax(&sh_tmax, t);
+  }
+  __syncthreads();
+  // the views that meet the run's batch times [tmin, tmax], in no particular order (integer sums and counts do not depend on it)
+  const long long tmin = sh_tmin, tmax = sh_tmax;
+  for (int v = tid; v < g.n_views; v += kReconThreads) {
+    const ReconViewRange r = g.ranges[v];
+    if (r.t_lo <= tmax && r.t_hi > tmin) {
+      const unsigned pos = atomicAdd(&sh_nmatch, 1u);
+      if (pos < (unsigned)kReconMaxViews) sh_match[pos] = (unsigned short)v;
+    }
+  }
+  __syncthreads();
+  int nmatch = (int)sh_nmatch;
+  nmatch = nmatch < kReconMaxViews ? nmatch : kReconMaxViews;
+  const double u_hi = (double)(g.Wv - 2), w_hi = (double)(g.Hv - 2);
+  const size_t np = (size_t)g.Hv * g.Wv;
+  for (int c0 = 0; c0 < nmatch; c0 += kReconViewChunk) {  // (uniform: nmatch is the workgroup's)
+    const int nl = nmatch - c0 < kReconViewChunk ? nmatch - c0 : kReconViewChunk;
+    if (tid < nl * kWords) {
+      const int k = tid / kWords, wd = tid - k * kWords;
+      reinterpret_cast<long long *>(sh_view)[tid] = reinterpret_cast<const long long *>(g.views + sh_match[c0 + k])[wd];
+    }
+    if (tid < kReconViewChunk) sh_cnt[tid] = 0;
+    __syncthreads();
+    int cur = -1;
+    double R[9];
+    long long tb = 0;
+    for (int i = e0 + tid; i < e1; i += kReconThreads) {
+      const int b = i / a.per_batch;
+      int j = b - b0;
+      j = j < nbw ? j : nbw - 1;
+      if (j != cur) {
+#pragma unroll
+        for (int c = 0; c < 9; c++) R[c] = sh_R[9 * j + c];
+        tb = sh_bt[j];
+        cur = j;
+      }
+      // sampling restarts at every batch start: packed slot k of batch b is raw event b * B + k * stride (recon_votes_kernel)
+      const size_t src = a.stride ? (size_t)b * a.B + (size_t)(i - b * a.per_batch) * a.stride : (size_t)i;
+      const uint32_t e = a.xy[src] & 0x7fffffffu;
+      const int ex = e & 0xffff, ey = e >> 16;
+      double v0, v1, v2, rx, ry, rz;
+      load_bearing(a.cam, ex, ey, v0, v1, v2);
+      be_rotate<false>(R, v0, v1, v2, rx, ry, rz);
+      for (int k = 0; k < nl; k++) {
+        const ReconViewDev &V = sh_view[k];  // (one address for all lanes: LDS broadcasts)
+        if (tb < V.t_lo || tb >= V.t_hi) continue;
+        double x, y, z;
+        be_rotate<false>(V.Rt, rx, ry, rz, x, y, z);
+        const double iz = 1.0 / z;
+        const double u = V.fx * (x * iz) + V.cx;
+        const double w = V.fy * (y * iz) + V.cy;
+        // the vote test in floating point, before any conversion: a NaN fails it, and only values inside the plane are cast
+        if (z > 0.0 && u >= 1.0 && u < u_hi && w >= 1.0 && w < w_hi) {
+          const int xx = (int)u, yy = (int)w;
+          const float dx = (float)(u - xx), dy = (float)(w - yy);
+          const size_t at = (size_t)V.index * np;
+          if (FIXED) vote4_global_fix(g.fixed + at, g.Wv, xx, yy, dx, dy);
+          else vote4_global(g.planes + at, g.Wv, xx, yy, dx, dy);
+          atomicAdd(&sh_cnt[k], 1u);
+        }
+      }
+    }
+    __syncthreads();
+    if (tid < nl) {  // (the lane that zeroes the counter of the next chunk)
+      const unsigned cnt = sh_cnt[tid];
+      if (cnt) atomicAdd(g.n_voted + sh_view[tid].index, (unsigned long long)cnt);
+    }
+    __syncthreads();  // (the next chunk's entries overwrite sh_view)
+  }
+}
+
+void launch_recon_view_votes(const ReconViewArgs &g, hipStream_t s) {
+  const ReconArgs &a = g.ev;
+  if (a.n <= 0 || a.nb <= 0 || g.n_views <= 0) return;
+  const dim3 gr((unsigned)(((long long)a.n + a.run - 1) / a.run)), b(kReconThreads);  // (a.n <= 2^30: cmx_reconstruct.cpp)
+  if (a.order == 2) {
+    if (g.fixed) hipLaunchKernelGGL((recon_view_votes_kernel<2, true>), gr, b, 0, s, g);
+    else hipLaunchKernelGGL((recon_view_votes_kernel<2, false>), gr, b, 0, s, g);
+  } else {
+    if (g.fixed) hipLaunchKernelGGL((recon_view_votes_kernel<4, true>), gr, b, 0, s, g);
+    else hipLaunchKernelGGL((recon_view_votes_kernel<4, false>), gr, b, 0, s, g);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------- per-event export
 // recon_warp     cmx_backend_recon_warp*: where every event of a slice lands.  The run structure of recon_votes over the slice's RAW
 //                events (run = recon_run(B)): the first lanes evaluate the run's batch poses into LDS -- and, in the workgroup that

@@ -5,6 +5,7 @@
 //   grad_add*  the second pass over the same events, their share of the gradient sums
 //   warp*      the per-event export: where EVERY event handed in lands under the knots the reconstruction holds now
 //   pol_add*   add*'s vote loop into the ON / OFF planes of the signed polarity map
+//   view_add*  add*'s vote loop into the planes of the pinhole views
 // Host arrays (SoA, or the host's own records) are packed slice by slice into two slots of pinned memory and uploaded on the copy
 // stream while the slice before runs; a range of an event store is read in place, its batch times formed on the device.
 #include "cmx_recon_state.hpp"
@@ -258,6 +259,51 @@ int cmx_backend_recon_pol_add_from(cmx_ctx *c, const cmx_events *e, int64_t firs
     if (e->size > 0 && !e->has_pol) return fail(c, CMX_ERR_STATE, "the event store holds no polarity (cmx_events_push_pol)");
     return (int)CMX_OK;
   });
+}
+
+// ---- view_add*: add*'s vote pass with the planes of the pinhole views as its targets.  As pol_add*: nothing of the
+// reconstruction but the knots is read, nothing but the view planes and their counters is written, an open gradient pass stays open.
+// The packed words are those of add*.
+static int recon_view_add_source(cmx_ctx *c, const EventSource &src) {
+  ReconState *r = c->recon;
+  int rc = feed_checks(c, src);
+  if (rc) return rc;
+  ReconViewArgs g{};
+  g.ev = recon_args(c, r);
+  g.ev.plane = nullptr; g.ev.fixed = nullptr; g.ev.n_inside = nullptr;
+  g.views = r->d_views; g.ranges = r->d_vranges;
+  g.n_views = r->n_views; g.Wv = r->Wv; g.Hv = r->Hv;
+  g.planes = r->d_vplanes;
+  g.fixed = r->d_vfixed;
+  g.n_voted = r->d_vvoted;
+  ReconArgs &a = g.ev;
+  BatchPlan p;
+  return feed(c, r, src, false, false, &p, [&](const FedSlice &s) {
+    a.xy = s.d_xy; a.stride = src.on_device() ? r->rate : 0;
+    a.batch_t = s.d_bt; a.nb = s.b_hi - s.b_lo;
+    a.n = (int)s.n;
+    launch_recon_view_votes(g, c->stream);
+    return (int)CMX_OK;
+  });
+}
+template <typename MakeSource>
+static int recon_view_add_entry(cmx_ctx *c, MakeSource make) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (!c->recon->d_views) return fail(c, CMX_ERR_STATE, "cmx_backend_recon_view_begin has not succeeded");
+  EventSource src;
+  rc = make(&src);
+  if (rc) return rc;
+  return recon_view_add_source(c, src);
+}
+int cmx_backend_recon_view_add(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns) {
+  return recon_view_add_entry(c, [&](EventSource *src) { *src = EventSource::arrays(n, x, y, t_ns); return (int)CMX_OK; });
+}
+int cmx_backend_recon_view_add_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout) {
+  return recon_view_add_entry(c, [&](EventSource *src) { return make_aos(c, n, events, layout, src); });
+}
+int cmx_backend_recon_view_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
+  return recon_view_add_entry(c, [&](EventSource *src) { return store_source(c, e, first, count, src); });
 }
 
 // ---- warp*: ALL events of a slice reach the kernel (the host paths pack at rate 1, the store is read in place), the true rate only

@@ -1,7 +1,7 @@
 // cmx_recon_state.hpp -- what the three sources of cmx_backend_recon_* share: the state a reconstruction keeps (cmx_ctx::recon) and
 // the helpers every one of them goes through.
-//   cmx_reconstruct.cpp  life cycle (begin, restart, extend, end), contrast / grad_get / eval_from, get / render
-//   cmx_recon_feed.cpp   one walk over the events handed in, in slices of whole batches: add*, grad_add*, warp*, pol_add*
+//   cmx_reconstruct.cpp  life cycle (begin, restart, extend, end), contrast / grad_get / eval_from, get / render, the view set
+//   cmx_recon_feed.cpp   one walk over the events handed in, in slices of whole batches: add*, grad_add*, warp*, pol_add*, view_add*
 //   cmx_recon_bound.cpp  events bound once and evaluated many times: bind / eval_bound, the frozen head, append / advance /
 //                        release, the hooks of cmx_backend_recon_solve
 // Kernels: cmx_recon.hip.
@@ -188,6 +188,14 @@ struct ReconState {
   float *d_pol = nullptr;                      // [2][Hp * Wp] ON then OFF (default mode), or the fp32 view of d_pol_fixed made by pol_get / pol_render
   unsigned long long *d_pol_fixed = nullptr;   // deterministic mode: their 2^-30 fixed-point twins
   unsigned long long *d_pol_inside = nullptr;  // [2] events that voted into the ON / the OFF plane
+  // ---- pinhole views (cmx_backend_recon_view_*): M virtual cameras and their planes, the reconstruction's own:
+  // made by view_begin, cleared by restart and view_reset, freed by view_end, begin and end; nothing else reads or writes them
+  int n_views = 0, Wv = 0, Hv = 0;             // n_views == 0: no view set
+  ReconViewDev *d_views = nullptr;             // [n_views]
+  ReconViewRange *d_vranges = nullptr;         // [n_views] the time ranges alone: what a vote workgroup scans
+  float *d_vplanes = nullptr;                  // [n_views][Hv * Wv] (default mode), or the fp32 view of d_vfixed made by view_get / view_render
+  unsigned long long *d_vfixed = nullptr;      // deterministic mode: their 2^-30 fixed-point twins
+  unsigned long long *d_vvoted = nullptr;      // [n_views] events that voted into each view
   int64_t host_waits = 0;                // times a host thread has waited for the device in this reconstruction's calls
   // everything above that owns memory, a stream or an event (the streams idle: recon_release has waited for them)
   void release() {
@@ -196,7 +204,8 @@ struct ReconState {
     for (ReconSlot &s : slot) s.release();
     for (ReconWarpSlot &s : wslot) s.release();
     void *dev[] = {d_knots, d_delta, d_plane, d_fixed, d_inside, d_err, d_cx, d_cy, d_tflags, d_tile_list, d_tile_count, d_partials,
-                   d_cm, d_jt, d_gsum, d_voted, d_rows, d_row_win, d_app_xy, d_app_t, d_pol, d_pol_fixed, d_pol_inside};
+                   d_cm, d_jt, d_gsum, d_voted, d_rows, d_row_win, d_app_xy, d_app_t, d_pol, d_pol_fixed, d_pol_inside,
+                   d_views, d_vranges, d_vplanes, d_vfixed, d_vvoted};
     for (void *p : dev) (void)hipFree(p);
     bnd.release();
     frozen.release();
@@ -234,6 +243,8 @@ int recon_grad_precheck(cmx_ctx *c, ReconState *r, double sigma);
 // the polarity planes and their two counters: allocated (and zeroed) at the first pol_add*; zeroed, where they exist (queued)
 int recon_pol_ensure(cmx_ctx *c, ReconState *r);
 int recon_pol_clear(cmx_ctx *c, ReconState *r);
+// the view planes and their counters zeroed, where a view set exists (queued)
+int recon_view_clear(cmx_ctx *c, ReconState *r);
 
 // ---- cmx_recon_feed.cpp
 // one slice of the gradient pass, as g.ev describes it; deterministic mode: the workgroups' rows, then their sum in workgroup order

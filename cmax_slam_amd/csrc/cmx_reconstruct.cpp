@@ -6,7 +6,8 @@
 // recon_grad_get, recon_eval_from): the image pass over the plane and a second pass over the same events, in the adjoint form of the
 // window path -- per batch one 3-vector through the 3 x 3N spline Jacobian, so nothing grows with the knot count
 // but the 2 x 3K sums -- and the plane's way out (get, render); the same for the ON / OFF planes of the signed polarity map
-// (pol_get, pol_render, pol_reset).  Events bound once and evaluated many times, the frozen head, the
+// (pol_get, pol_render, pol_reset) and for the planes of a set of pinhole views (view_begin, view_get, view_render,
+// view_reset, view_end).  Events bound once and evaluated many times, the frozen head, the
 // growing binding and the native solve's hooks: cmx_recon_bound.cpp.
 // Kernels: cmx_recon.hip.
 #include "cmx_recon_state.hpp"
@@ -187,6 +188,8 @@ int cmx_backend_recon_restart(cmx_ctx *c, const double *knots_xyzw) {
   if (rc) return rc;
   frozen_drop(c, c->recon);  // (new knots: what the frozen batches voted no longer holds)
   rc = recon_pol_clear(c, c->recon);  // (... nor what the polarity planes hold)
+  if (rc) return rc;
+  rc = recon_view_clear(c, c->recon);  // (... nor the view planes; the views themselves stay)
   if (rc) return rc;
   return recon_start_over(c, c->recon, knots_xyzw);
 }
@@ -520,4 +523,142 @@ int cmx_backend_recon_pol_render(cmx_ctx *c, double gamma, int mode, unsigned ch
   launch_display_range_signed(r->d_pol, r->d_pol + np, np, c->d_disp_range, c->stream);
   launch_display_signed(r->d_pol, r->d_pol + np, np, (float)gamma, mode == CMX_POL_BGR8, c->d_disp_range, c->d_disp, c->stream);
   return display_deliver(c, bytes, out);
+}
+
+// ---- pinhole views: the set of virtual cameras cmx_backend_recon_view_add* (cmx_recon_feed.cpp) votes into, and its planes' way out
+static void recon_view_free(cmx_ctx *c, ReconState *r) {
+  if (!r->d_views) return;
+  (void)hipStreamSynchronize(c->stream);  // (a vote pass queued earlier may still write the planes)
+  void *dev[] = {r->d_views, r->d_vranges, r->d_vplanes, r->d_vfixed, r->d_vvoted};
+  for (void *p : dev) (void)hipFree(p);
+  r->d_views = nullptr; r->d_vranges = nullptr; r->d_vplanes = nullptr; r->d_vfixed = nullptr; r->d_vvoted = nullptr;
+  r->n_views = r->Wv = r->Hv = 0;
+}
+
+int recon_view_clear(cmx_ctx *c, ReconState *r) {
+  if (!r->d_views) return CMX_OK;
+  const size_t np = (size_t)r->n_views * r->Wv * r->Hv;
+  HIP_TRY(c, hipMemsetAsync(r->d_vplanes, 0, np * sizeof(float), c->stream));
+  if (r->d_vfixed) HIP_TRY(c, hipMemsetAsync(r->d_vfixed, 0, np * sizeof(unsigned long long), c->stream));
+  HIP_TRY(c, hipMemsetAsync(r->d_vvoted, 0, (size_t)r->n_views * sizeof(unsigned long long), c->stream));
+  return CMX_OK;
+}
+
+static int recon_view_enter(cmx_ctx *c) {
+  const int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (!c->recon->d_views) return fail(c, CMX_ERR_STATE, "cmx_backend_recon_view_begin has not succeeded");
+  return CMX_OK;
+}
+
+int cmx_backend_recon_view_begin(cmx_ctx *c, int Wv, int Hv, int n_views, const cmx_recon_view *views) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (Wv < 4 || Wv > 8192 || Hv < 4 || Hv > 8192) return fail(c, CMX_ERR_INVALID_ARG, "view size %d x %d outside [4, 8192]", Wv, Hv);
+  if (n_views < 1 || n_views > 4096) return fail(c, CMX_ERR_INVALID_ARG, "n_views=%d outside [1, 4096]", n_views);
+  if ((long long)n_views * Wv * Hv > (1LL << 28)) return fail(c, CMX_ERR_INVALID_ARG, "%d views of %d x %d: more than 2^28 cells", n_views, Wv, Hv);
+  if (!views) return fail(c, CMX_ERR_INVALID_ARG, "null view array");
+  std::vector<ReconViewDev> dev((size_t)n_views);
+  std::vector<ReconViewRange> ranges((size_t)n_views);
+  for (int i = 0; i < n_views; i++) {
+    const cmx_recon_view &v = views[i];
+    const double *q = v.quat_xyzw;
+    const double nrm = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    if (!std::isfinite(nrm) || !(nrm > 0.0)) return fail(c, CMX_ERR_INVALID_ARG, "view %d: the quaternion has no direction", i);
+    if (!std::isfinite(v.fx) || !std::isfinite(v.fy) || !(v.fx > 0.0) || !(v.fy > 0.0))
+      return fail(c, CMX_ERR_INVALID_ARG, "view %d: fx, fy must be finite and > 0", i);
+    if (!std::isfinite(v.cx) || !std::isfinite(v.cy)) return fail(c, CMX_ERR_INVALID_ARG, "view %d: cx, cy must be finite", i);
+    if (v.t_lo_ns >= v.t_hi_ns) return fail(c, CMX_ERR_INVALID_ARG, "view %d: empty time range", i);
+    const Mat3 R = q_to_R(Quat{q[0] / nrm, q[1] / nrm, q[2] / nrm, q[3] / nrm});
+    ReconViewDev &d = dev[(size_t)i];
+    for (int a = 0; a < 3; a++)
+      for (int b = 0; b < 3; b++) d.Rt[3 * a + b] = R.m[3 * b + a];
+    d.fx = v.fx; d.fy = v.fy; d.cx = v.cx; d.cy = v.cy;
+    d.t_lo = (long long)v.t_lo_ns; d.t_hi = (long long)v.t_hi_ns;
+    d.index = i;
+    ranges[(size_t)i] = ReconViewRange{d.t_lo, d.t_hi};
+  }
+  ReconState *r = c->recon;
+  recon_view_free(c, r);  // a second begin starts over
+  const size_t np = (size_t)n_views * Wv * Hv;
+  ReconViewDev *d_views = nullptr;
+  ReconViewRange *d_ranges = nullptr;
+  float *planes = nullptr;
+  unsigned long long *fixed = nullptr, *voted = nullptr;
+  hipError_t e = hipMalloc((void **)&d_views, dev.size() * sizeof(ReconViewDev));
+  if (e == hipSuccess) e = hipMalloc((void **)&d_ranges, ranges.size() * sizeof(ReconViewRange));
+  if (e == hipSuccess) e = hipMalloc((void **)&planes, np * sizeof(float));
+  if (e == hipSuccess && r->deterministic) e = hipMalloc((void **)&fixed, np * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMalloc((void **)&voted, (size_t)n_views * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMemcpy(d_views, dev.data(), dev.size() * sizeof(ReconViewDev), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_ranges, ranges.data(), ranges.size() * sizeof(ReconViewRange), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {  // (all of it or none: d_views says whether a view set exists)
+    (void)hipFree(d_views); (void)hipFree(d_ranges); (void)hipFree(planes); (void)hipFree(fixed); (void)hipFree(voted);
+    return fail(c, CMX_ERR_HIP, "allocating %d views of %d x %d: %s", n_views, Wv, Hv, hipGetErrorString(e));
+  }
+  r->d_views = d_views; r->d_vranges = d_ranges; r->d_vplanes = planes; r->d_vfixed = fixed; r->d_vvoted = voted;
+  r->n_views = n_views; r->Wv = Wv; r->Hv = Hv;
+  rc = recon_view_clear(c, r);
+  if (rc) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return CMX_OK;
+}
+
+int cmx_backend_recon_view_reset(cmx_ctx *c) {
+  int rc = recon_view_enter(c);
+  if (rc) return rc;
+  rc = recon_view_clear(c, c->recon);
+  if (rc) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return CMX_OK;
+}
+
+int cmx_backend_recon_view_end(cmx_ctx *c) {
+  const int rc = recon_enter(c, true);
+  if (rc) return rc;
+  recon_view_free(c, c->recon);  // (no view set: nothing to free, not an error)
+  return CMX_OK;
+}
+
+// views [first, first + count) as fp32 on the device: in deterministic mode the current fixed-point sums, converted (they stay)
+static void recon_view_refresh(cmx_ctx *c, ReconState *r, int first, int count) {
+  const size_t np = (size_t)r->Wv * r->Hv;
+  if (r->d_vfixed) launch_recon_fixed_to_float(r->d_vfixed + (size_t)first * np, r->d_vplanes + (size_t)first * np, (size_t)count * np, c->stream);
+}
+
+int cmx_backend_recon_view_get(cmx_ctx *c, int first_view, int count, float *planes, int64_t *n_voted) {
+  int rc = recon_view_enter(c);
+  if (rc) return rc;
+  ReconState *r = c->recon;
+  if (first_view < 0 || count < 0 || first_view > r->n_views || count > r->n_views - first_view)
+    return fail(c, CMX_ERR_INVALID_ARG, "views [%d, %d + %d) outside the %d of the set", first_view, first_view, count, r->n_views);
+  if (count == 0) return CMX_OK;
+  const size_t np = (size_t)r->Wv * r->Hv;
+  static_assert(sizeof(int64_t) == sizeof(unsigned long long), "the counters travel as they are");
+  if (planes) {
+    recon_view_refresh(c, r, first_view, count);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(planes, r->d_vplanes + (size_t)first_view * np, (size_t)count * np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (n_voted) HIP_TRY(c, hipMemcpyAsync(n_voted, r->d_vvoted + first_view, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return CMX_OK;
+}
+
+// cmx_backend_recon_render's tone map, without the outline, on one view's plane
+int cmx_backend_recon_view_render(cmx_ctx *c, int view, double gamma, unsigned char *out) {
+  int rc = recon_view_enter(c);
+  if (rc) return rc;
+  ReconState *r = c->recon;
+  if (view < 0 || view >= r->n_views) return fail(c, CMX_ERR_INVALID_ARG, "view %d outside the %d of the set", view, r->n_views);
+  if (!out) return fail(c, CMX_ERR_INVALID_ARG, "null output buffer");
+  if (!std::isfinite(gamma) || !(gamma > 0.0)) return fail(c, CMX_ERR_INVALID_ARG, "gamma must be finite and > 0");
+  const size_t np = (size_t)r->Wv * r->Hv;
+  rc = display_begin(c, np);
+  if (rc) return rc;
+  recon_view_refresh(c, r, view, 1);
+  const float *plane = r->d_vplanes + (size_t)view * np;
+  launch_display_range(plane, nullptr, np, c->d_disp_range, c->stream);
+  launch_display_map(plane, np, (float)gamma, false, c->d_disp_range, c->d_disp, c->stream);
+  return display_deliver(c, np, out);
 }

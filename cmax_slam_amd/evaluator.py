@@ -648,6 +648,7 @@ class BackendEvaluator(_Evaluator):
         belongs to the reconstruction alone and records the current deterministic setting.  A second call starts over."""
         k = _c(knots_xyzw, np.float64).reshape(-1, 4)
         self._recon_K = k.shape[0]
+        self._view_shape = None  # (begin frees a view set)
         self._ck(self._L.cmx_backend_recon_begin(self._ctx, int(order), k.shape[0], _dp(k), int(start_ns), int(dt_ns),
                                                  int(event_batch_size), int(event_sample_rate)))
 
@@ -752,6 +753,62 @@ class BackendEvaluator(_Evaluator):
     def reconstruct_pol_reset(self):
         """Clear the ON / OFF planes and their counters (after the knots have moved); nothing else changes."""
         self._ck(self._L.cmx_backend_recon_pol_reset(self._ctx))
+
+    # --- pinhole views: motion-compensated frames and crops of the same vote loop (cmx_backend_recon_view_*)
+    _view_shape = None  # (n_views, Hv, Wv) of the last reconstruct_view_begin
+
+    def reconstruct_view_begin(self, views, Wv, Hv):
+        """Attach virtual pinhole cameras to the open reconstruction and zero their (Hv, Wv) planes.  views: _lib.ReconView
+        structures, or tuples (quat_xyzw, fx, fy, cx, cy, t_lo_ns, t_hi_ns) -- see trajectory.frame_views / crop_view."""
+        vs = [v if isinstance(v, _lib.ReconView) else _lib.recon_view(*v) for v in views]
+        arr = (_lib.ReconView * max(len(vs), 1))(*vs)
+        self._view_shape = None
+        self._ck(self._L.cmx_backend_recon_view_begin(self._ctx, int(Wv), int(Hv), len(vs), arr))
+        self._view_shape = (len(vs), int(Hv), int(Wv))
+
+    def reconstruct_view_add(self, x, y, t_ns):
+        """reconstruct_add's vote loop over exactly these events: every sampled event is warped once into the world frame and
+        voted into every view whose time range holds its batch time.  Nothing else of the reconstruction is read or written."""
+        x, y, t = _c(x, np.uint16), _c(y, np.uint16), _c(t_ns, np.int64)
+        if not (len(x) == len(y) == len(t)):
+            raise ValueError("x, y, t_ns must have equal length")
+        self._ck(self._L.cmx_backend_recon_view_add(self._ctx, len(x), x.ctypes.data_as(c_u16p), y.ctypes.data_as(c_u16p),
+                                                    t.ctypes.data_as(c_i64p)))
+
+    def reconstruct_view_add_aos(self, events):
+        """The same from a structured array of records with fields x, y, sec, nsec."""
+        ev = np.ascontiguousarray(events)
+        lay = _lib.aos_layout_of(ev)
+        self._ck(self._L.cmx_backend_recon_view_add_aos(self._ctx, len(ev), ev.ctypes.data_as(C.c_void_p), C.byref(lay)))
+
+    def reconstruct_view_add_from(self, store, first, count):
+        """The same over events_[first, first+count) of a device-resident EventStore."""
+        self._ck(self._L.cmx_backend_recon_view_add_from(self._ctx, store._h, int(first), int(count)))
+
+    def reconstruct_view_get(self, first=0, count=None, with_counts=False):
+        """(count, Hv, Wv) fp32 planes of views [first, first+count) [, int64 events that voted into each]."""
+        n, Hv, Wv = self._view_shape or (0, 0, 0)
+        count = n - int(first) if count is None else int(count)
+        shape = (max(count, 0), Hv, Wv)
+        out, cnt = np.empty(shape, np.float32), np.zeros(shape[0], np.int64)
+        self._ck(self._L.cmx_backend_recon_view_get(self._ctx, int(first), count, out.ctypes.data_as(c_fp),
+                                                    cnt.ctypes.data_as(c_i64p) if with_counts else None))
+        return (out, cnt) if with_counts else out
+
+    def reconstruct_view_render(self, view, gamma=0.75):
+        """reconstruct_render's tone map (no outline) on one view's plane: (Hv, Wv) uint8."""
+        _, Hv, Wv = self._view_shape or (0, 0, 0)
+        out = np.empty((Hv, Wv), np.uint8)
+        self._ck(self._L.cmx_backend_recon_view_render(self._ctx, int(view), float(gamma), out.ctypes.data_as(_lib.c_u8p)))
+        return out
+
+    def reconstruct_view_reset(self):
+        """Clear the view planes and their counters (after the knots have moved); the views stay."""
+        self._ck(self._L.cmx_backend_recon_view_reset(self._ctx))
+
+    def reconstruct_view_end(self):
+        self._ck(self._L.cmx_backend_recon_view_end(self._ctx))
+        self._view_shape = None
 
     def reconstruct_get(self, with_counts=False):
         """The (Hp, Wp) fp32 plane [, events the sampling selected so far, events that voted so far]."""

@@ -108,6 +108,44 @@ class Trajectory:
         return np.ascontiguousarray(self.knots[idx_traj_beg:]), int(start_ns), self.dt_ns
 
 
+def frame_views(order, knots, start_ns, dt_ns, period_ns, intrinsics, exposure_ns=None, t_beg_ns=None, t_end_ns=None):
+    """The view list of a motion-compensated video (BackendEvaluator.reconstruct_view_begin): one _lib.ReconView per frame of
+    period_ns over [t_beg_ns, t_end_ns) -- by default the whole knot support of the spline -- the last one cut at t_end_ns.
+    A view's orientation is the spline's pose at the centre of its slice (cmx_traj_evaluate), its intrinsics are
+    (fx, fy, cx, cy), and its time range is the slice, or exposure_ns around the slice centre (longer than the period: neighbouring
+    frames share events; shorter: gaps)."""
+    k = np.ascontiguousarray(knots, np.float64).reshape(-1, 4)
+    start_ns, dt_ns, period_ns = int(start_ns), int(dt_ns), int(period_ns)
+    if period_ns <= 0 or (exposure_ns is not None and int(exposure_ns) <= 0):
+        raise ValueError("frame period and exposure must be > 0")
+    t_beg = start_ns if t_beg_ns is None else int(t_beg_ns)
+    t_end = start_ns + (len(k) - int(order) + 1) * dt_ns if t_end_ns is None else int(t_end_ns)
+    fx, fy, cx, cy = intrinsics
+    views = []
+    q = np.zeros(4)
+    for lo in range(t_beg, t_end, period_ns):
+        hi = min(lo + period_ns, t_end)
+        mid = lo + (hi - lo) // 2
+        _chk(_lib.lib().cmx_traj_evaluate(int(order), len(k), _d(k), start_ns, dt_ns, mid, _d(q)), "cmx_traj_evaluate")
+        if exposure_ns is not None:
+            lo, hi = mid - int(exposure_ns) // 2, mid - int(exposure_ns) // 2 + int(exposure_ns)
+        views.append(_lib.recon_view(q, fx, fy, cx, cy, lo, hi))
+    return views
+
+
+ALL_TIME_NS = (-2 ** 62, 2 ** 62)
+
+
+def crop_view(quat_xyzw, fov_deg, Wv, Hv, t_range_ns=ALL_TIME_NS):
+    """One view over all time (or t_range_ns) looking along quat_xyzw: a pinhole camera of Wv x Hv pixels whose horizontal field of
+    view is fov_deg, principal point at the centre.  A field of view below the sensor's is a zoom: a crop of the scene on a finer
+    grid than the sensor's or the panorama's."""
+    if not 0.0 < float(fov_deg) < 180.0:
+        raise ValueError("field of view must lie in (0, 180) degrees")
+    f = 0.5 * Wv / np.tan(np.radians(float(fov_deg)) / 2)
+    return _lib.recon_view(quat_xyzw, f, f, 0.5 * (Wv - 1), 0.5 * (Hv - 1), t_range_ns[0], t_range_ns[1])
+
+
 def _sec(t_ns):
     """ros::Time::toSec()"""
     return float(t_ns // 1000000000) + 1e-9 * float(t_ns % 1000000000)

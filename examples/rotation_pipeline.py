@@ -162,6 +162,7 @@ def refine_trajectory_online(be, traj, x, y, t, prm, store, stride_s, free=8, lo
 
 
 POLARITY_SEED = 2024  # --polarity-map: the synthetic stream's polarities are drawn, not modelled
+CROP_SIZE = (512, 384)  # --crop: the view's grid (a quarter of the sensor's field of view on about twice its pixels)
 
 
 def reconstruct_panorama(be, traj, x, y, t, prm, store=None, knots=None):
@@ -183,7 +184,7 @@ def reconstruct_panorama(be, traj, x, y, t, prm, store=None, knots=None):
 
 def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefix=None, reconstruct=False, refine_global=False,
                  refine_bound=False, refine_native=False, freeze_head=None, refine_online=None, online_free=8, export_warped=None,
-                 polarity_map=None):
+                 polarity_map=None, frames=None, frame_ms=20.0, crop=None):
     """stream: synth.EventStream (or anything with x, y, t_ns, W, H, fx, fy, cx, cy, lut).  Returns a dict.
     display_prefix: write the final panorama with the last pose's FOV and the last packet's local-IWE pair there.
     reconstruct: after the last window, re-warp all events along the whole refined trajectory (res["recon"]; with
@@ -201,8 +202,13 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
     polarity_map = PREFIX (implies reconstruct): the signed panorama ON - OFF of the same events along the final trajectory
     (BackendEvaluator.reconstruct_pol_*), written as PREFIX.pgm (OFF dark, ON bright) and PREFIX.ppm (ON red, OFF blue on white);
     also res["pol"] = (on, off).  The synthetic stream has no brightness model, so the polarities are DRAWN from a seeded generator
-    (stream.polarity, when the stream has one, is used instead): the images show the arithmetic, not a scene's edges' signs."""
-    reconstruct = reconstruct or export_warped is not None or polarity_map is not None
+    (stream.polarity, when the stream has one, is used instead): the images show the arithmetic, not a scene's edges' signs.
+    frames = PREFIX (implies reconstruct): the motion-compensated event frames of the final trajectory -- one pinhole view per
+    frame_ms milliseconds with the sensor's size and intrinsics and the spline's pose at the slice centre
+    (trajectory.frame_views, BackendEvaluator.reconstruct_view_*) -- written as PREFIX_0000.pgm ...; res["frames"] = (planes, counts).
+    crop = PREFIX (implies reconstruct): one zoomed view of all events around the last pose, a quarter of the sensor's field of
+    view on CROP_SIZE pixels (trajectory.crop_view), written as PREFIX.pgm; res["crop"] = (plane, count)."""
+    reconstruct = reconstruct or export_warped is not None or polarity_map is not None or frames is not None or crop is not None
     prm = prm or Params()
     x, y, t = stream.x, stream.y, stream.t_ns
     n_total = len(t)
@@ -422,6 +428,47 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
             if log:
                 log("polarity map: %d ON and %d OFF events voted in %.2f ms -> %s.pgm, %s.ppm" %
                     (n_on, n_off, (time.perf_counter() - t0) * 1e3, polarity_map, polarity_map))
+        knots_rec = traj.knots if res.get("refined_knots") is None else res["refined_knots"]
+
+        def view_votes(views, Wv, Hv):  # (the same range in one call again, under the knots the count panorama was voted at)
+            be.reconstruct_view_begin(views, Wv, Hv)
+            if store is not None:
+                be.reconstruct_view_add_from(store, i_rec, n_rec)
+            else:
+                be.reconstruct_view_add(x[i_rec:i_rec + n_rec], y[i_rec:i_rec + n_rec], t[i_rec:i_rec + n_rec])
+            planes, counts = be.reconstruct_view_get(with_counts=True)
+            images = [be.reconstruct_view_render(k, 0.75) for k in range(len(views))]
+            be.reconstruct_view_end()
+            return planes, counts, images
+
+        def write_pgm(path, img):
+            with open(path, "wb") as f:
+                f.write(b"P5\n%d %d\n255\n" % (img.shape[1], img.shape[0]) + img.tobytes())
+
+        if frames is not None:  # one de-rotated frame per frame_ms of the events the reconstruction holds, seen by the sensor itself
+            t0 = time.perf_counter()
+            views = trajectory.frame_views(traj.order, knots_rec, traj.t_beg_ns, traj.dt_ns, int(round(frame_ms * 1e6)),
+                                           (stream.fx, stream.fy, stream.cx, stream.cy), t_beg_ns=int(t[i_rec]),
+                                           t_end_ns=int(t[i_rec + n_rec - 1]) + 1)
+            planes, counts, images = view_votes(views, stream.W, stream.H)
+            res["frames"] = (planes, counts)
+            for k, img in enumerate(images):
+                write_pgm("%s_%04d.pgm" % (frames, k), img)
+            if log:
+                log("frames: %d motion-compensated frames of %.3g ms, %d to %d events each, in %.2f ms -> %s_0000.pgm ..." %
+                    (len(views), frame_ms, int(counts.min()), int(counts.max()), (time.perf_counter() - t0) * 1e3, frames))
+        if crop is not None:  # all events around the last pose, at a quarter of the sensor's field of view on a grid of its own
+            t_last = traj.t_beg_ns + (traj.size() - traj.order + 1) * traj.dt_ns - 1
+            final = trajectory.Trajectory(prm.spline_degree, traj.t_beg_ns, prm.dt_knots)
+            final.pushbackCtrlPoses(knots_rec)
+            q_last = final.evaluate(t_last)
+            fov = np.degrees(2 * np.arctan(0.5 * stream.W / stream.fx)) / 4
+            planes, counts, images = view_votes([trajectory.crop_view(q_last, fov, CROP_SIZE[0], CROP_SIZE[1])], *CROP_SIZE)
+            res["crop"] = (planes[0], int(counts[0]))
+            write_pgm(crop + ".pgm", images[0])
+            if log:
+                log("crop: %d events within %.1f degrees around the last pose on %d x %d -> %s.pgm" %
+                    (int(counts[0]), fov, CROP_SIZE[0], CROP_SIZE[1], crop))
         be.reconstruct_end()
     return res
 
@@ -487,6 +534,13 @@ def main():
                     help="after the reconstruction, write the signed panorama ON - OFF as PREFIX.pgm and PREFIX.ppm (implies "
                          "--reconstruct).  The synthetic stream has no brightness model: the polarities are drawn from a seeded "
                          "random generator, so the images demonstrate the calls, not a scene")
+    ap.add_argument("--frames", metavar="PREFIX", default=None,
+                    help="after the reconstruction, write the motion-compensated event frames of the final trajectory as "
+                         "PREFIX_0000.pgm ... (implies --reconstruct)")
+    ap.add_argument("--frame-ms", type=float, metavar="MS", default=20.0, help="with --frames: the frame period in milliseconds")
+    ap.add_argument("--crop", metavar="PREFIX", default=None,
+                    help="after the reconstruction, write one zoomed view of all events around the last pose as PREFIX.pgm "
+                         "(implies --reconstruct)")
     ap.add_argument("--refine-global", action="store_true",
                     help="after the last window, one bundle adjustment over the whole trajectory (--reconstruct then uses its result)")
     ap.add_argument("--refine-bound", action="store_true",
@@ -504,6 +558,8 @@ def main():
         ap.error("--freeze-head needs --refine-native")
     if a.refine_online is not None and (a.refine_online <= 0 or a.online_free < 1):
         ap.error("--refine-online takes a stride > 0 and --online-free at least 1")
+    if not a.frame_ms > 0:
+        ap.error("--frame-ms must be > 0")
     stream = synth.event_stream(a.rate, a.seconds, 240, 180, 200.0, 200.0, 119.5, 89.5, omega_mean=(0.2, 1.8, 0.3),
                                 omega_amp=(1.0, 0.8, 1.0))
     prm = Params()
@@ -513,7 +569,7 @@ def main():
     res = run_pipeline(stream, prm, use_event_store=not a.host_events, log=print, display_prefix=a.display, reconstruct=a.reconstruct,
                        refine_global=a.refine_global or a.refine_native, refine_bound=a.refine_bound, refine_native=a.refine_native,
                        freeze_head=a.freeze_head, refine_online=a.refine_online, online_free=a.online_free, export_warped=a.export_warped,
-                       polarity_map=a.polarity_map)
+                       polarity_map=a.polarity_map, frames=a.frames, frame_ms=a.frame_ms, crop=a.crop)
     wall = time.perf_counter() - t0
     m = evaluate_against_truth(stream, res)
     print("%.2f s of events (%d) processed in %.2f s wall" % (a.seconds, len(stream.x), wall))

@@ -359,8 +359,8 @@ int cmx_backend_recon_get(cmx_ctx *ctx, float *pano /* Hp*Wp or NULL */, int64_t
 int cmx_backend_recon_render(cmx_ctx *ctx, double gamma, const double fov_quat_xyzw[4] /* or NULL */, unsigned char *out);
 int cmx_backend_recon_end(cmx_ctx *ctx);
 /* Per-event export: WHERE every event lands under the trajectory the reconstruction holds -- what a host needs for any product other
- * than the count panorama (a time surface, a cropped or super-resolved mosaic, outlier flags; the signed polarity map has calls of
- * its own, cmx_backend_recon_pol_*): the export itself never reads polarity, the host joins the entries with whatever it kept.
+ * than the count panorama (a time surface, outlier flags; the signed polarity map and pinhole frames or crops have calls of their
+ * own, cmx_backend_recon_pol_* and cmx_backend_recon_view_*): the export itself never reads polarity, the host joins the entries with whatever it kept.
  *   output   ONE entry per event handed in, sampled or not, in input order: xy_out[2i], xy_out[2i+1] = (px, py), flags_out[i]
  *            (flags_out may be NULL).  CMX_WARP_F64: 2 doubles per event; CMX_WARP_F32: 2 floats, (float)px and (float)py.
  *   poses    spline, batch size and sample rate are those of recon_begin / restart / extend; the knots are the ones the
@@ -427,6 +427,56 @@ int cmx_backend_recon_pol_add_from(cmx_ctx *ctx, const cmx_events *ev, int64_t f
 int cmx_backend_recon_pol_get(cmx_ctx *ctx, float *on, float *off /* Hp*Wp each, either may be NULL */, int64_t *n_on, int64_t *n_off);
 int cmx_backend_recon_pol_render(cmx_ctx *ctx, double gamma, int mode, unsigned char *out);
 int cmx_backend_recon_pol_reset(cmx_ctx *ctx);
+/* Pinhole views: motion-compensated event frames and zoomed crops.  A set of M virtual pinhole cameras is attached to an open
+ * reconstruction; one vote pass warps every sampled event ONCE into the world frame with the trajectory the reconstruction holds and
+ * votes it into every view whose time range holds the event's batch time.  A video of de-rotated frames is M views with disjoint
+ * ranges and the spline's pose at each slice centre; a crop is one view over all time with a longer focal length.
+ *     recon_view_begin(views)   recon_view_add*(events) ...   recon_view_get / recon_view_render (any number of times)
+ *     [recon_view_reset]   recon_view_end
+ *   view_begin needs an open reconstruction.  Copies the views to the device -- R(quat)^T formed on the host in fp64 from the
+ *              normalised quaternion -- allocates n_views fp32 planes of Wv x Hv (and their 2^-30 fixed-point twins when
+ *              CMX_OPT_DETERMINISTIC was 1 at recon_begin) and zeroes them and one vote counter per view.  A second view_begin starts
+ *              over.  CMX_ERR_INVALID_ARG: Wv or Hv outside [4, 8192]; n_views outside [1, 4096]; n_views * Wv * Hv > 2^28; a
+ *              quaternion that is zero or not finite; fx or fy not finite or <= 0; cx or cy not finite; t_lo_ns >= t_hi_ns.  Time
+ *              ranges may overlap, nest or leave gaps, and the views need not be ordered.
+ *   view_add*  ONE call = the vote loop of add* over exactly the events handed in -- the same batches and batch times, sampling
+ *              restarting at every batch start, the lone trailing event skipped, the same validation and status codes, complete
+ *              before the first vote: a call that fails validation adds nothing to any plane.  Per sampled event, in fp64:
+ *                  ray_w = R_batch * bearing                      (the vote kernels' own function and pose: the same bits)
+ *                  for every view with t_lo_ns <= batch time < t_hi_ns:
+ *                      v = R(quat)^T ray_w,   iz = 1 / v.z,   u = fx (v.x iz) + cx,   w = fy (v.y iz) + cy
+ *                      the vote test, in floating point BEFORE any conversion:  v.z > 0 && 1 <= u < Wv-2 && 1 <= w < Hv-2
+ *                      (a NaN fails it, and no value outside the plane is ever cast to an integer)
+ *                      xx = (int)u, dx = (float)(u - xx), yy = (int)w, dy = (float)(w - yy): the four bilinear adds of add* into
+ *                      that view's plane (64-bit integer adds into its fixed-point twin in deterministic mode), and one count
+ *              Cost per event grows with the views that hold its batch time, not with n_views.
+ *   view_get   planes = count * Hv*Wv fp32 or NULL, n_voted = count counters or NULL, for views [first_view, first_view + count);
+ *              CMX_ERR_INVALID_ARG when the range leaves the set.  Accumulation may continue afterwards.
+ *   view_render  cmx_backend_recon_render's tone map and gamma rules, without the outline, on ONE view's plane: out = Hv*Wv mono8.
+ *   view_reset clears the planes and the counters and keeps the views.   view_end frees the set (without a set: CMX_OK).
+ *   state      the calls read the knots the reconstruction holds NOW and nothing else of it, and write only the view planes and
+ *              their counters: the count plane of add*, its counters, the polarity planes, an open gradient pass, a binding, a frozen
+ *              or released head, the window, IG and the exchange sets are untouched, and the calls work with a gradient pass open,
+ *              with events bound, after freeze_head and after release_head.  recon_begin and recon_end free the view set; restart and
+ *              view_reset clear planes and counters and keep the views.  EVERY other call leaves them alone, extend, eval_bound and
+ *              recon_solve included, although they move the knots: call view_reset before voting anew.
+ *   status     CMX_ERR_STATE before recon_begin, before view_begin (add*, get, render, reset) and on a group handle.
+ * Deterministic mode: every plane is a sum of integers -- bitwise identical from run to run, for any slicing at batch multiples,
+ * through the three ingest paths, and whatever other views are in the set.  Otherwise votes are fp32 atomics. */
+typedef struct cmx_recon_view {
+  double  quat_xyzw[4];      /* camera orientation in the spline's world frame: ray_cam = R(quat)^T ray_world */
+  double  fx, fy, cx, cy;    /* pinhole intrinsics of the view, in view pixels */
+  int64_t t_lo_ns, t_hi_ns;  /* a batch votes into this view when t_lo_ns <= batch time < t_hi_ns */
+} cmx_recon_view;
+int cmx_backend_recon_view_begin(cmx_ctx *ctx, int Wv, int Hv, int n_views, const cmx_recon_view *views);
+int cmx_backend_recon_view_add(cmx_ctx *ctx, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns);
+int cmx_backend_recon_view_add_aos(cmx_ctx *ctx, int64_t n, const void *events, const cmx_aos_layout *layout);
+int cmx_backend_recon_view_add_from(cmx_ctx *ctx, const cmx_events *ev, int64_t first, int64_t count);
+int cmx_backend_recon_view_get(cmx_ctx *ctx, int first_view, int count, float *planes /* count*Hv*Wv or NULL */,
+                               int64_t *n_voted /* count or NULL */);
+int cmx_backend_recon_view_render(cmx_ctx *ctx, int view, double gamma, unsigned char *out /* Hv*Wv mono8 */);
+int cmx_backend_recon_view_reset(cmx_ctx *ctx);
+int cmx_backend_recon_view_end(cmx_ctx *ctx);
 /* Whole-trajectory contrast and its gradient with respect to a LEFT increment of every control pose, on top of an open
  * reconstruction -- the evaluation one bundle adjustment over the whole recording needs, for a spline of any knot count:
  *     recon_begin   recon_add*(events) ...   recon_contrast(want_grad)   recon_grad_add*(the same events) ...   recon_grad_get
