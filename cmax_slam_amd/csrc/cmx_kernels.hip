@@ -19,6 +19,7 @@
 #include "../../include/cmax_hip.h"
 #include "cmx_internal.hpp"
 #include "cmx_warp.hpp"
+#include "cmx_imagephases.hpp"
 
 // launch with optional kernel-exact timing events (null, null = plain launch)
 #define CMX_LAUNCH(kernel, grid, block, lds, stream, t0, t1, ...)                                            \
@@ -210,12 +211,6 @@ void launch_be_splat(const BeSplatArgs &a, bool deriv, hipStream_t s, hipEvent_t
 }
 
 // ---------------------------------------------------------------------------------------------- K3+K5+K6
-__device__ __forceinline__ int reflect101(int p, int len) {
-  if (len == 1) return 0;
-  while (p < 0 || p >= len) p = (p < 0) ? -p : 2 * (len - 1) - p;
-  return p;
-}
-
 // wave64 sum of a double with DPP moves (no LDS crossbar): inclusive row_shr scan inside each row of 16 lanes, then
 // row_bcast15 / row_bcast31 carry the row totals upwards; lane 63 holds the total, read back as a wave-uniform value
 // (valid in every lane).
@@ -258,21 +253,6 @@ __device__ __forceinline__ void block_sum2(double v0, double v1, double *red, in
   t0 = 0;
   t1 = 0;
   for (int w = 0; w < nwaves; w++) { t0 += red[2 * w]; t1 += red[2 * w + 1]; }
-}
-
-// Tile occupancy (ImgArgs::flags_*): is there anything non-zero within `reach` pixels of tile (tx, ty)?
-__device__ __forceinline__ bool tile_active(const ImgArgs &a, int tx, int ty, int reach, int TX, int TY) {
-  if (!a.flags_cur) return true;
-  const int nx = (reach + TX - 1) / TX, ny = (reach + TY - 1) / TY;
-  bool any = false;
-  for (int dy = -ny; dy <= ny; dy++)
-    for (int dx = -nx; dx <= nx; dx++) {
-      const int x = tx + dx, y = ty + dy;
-      if (x < 0 || y < 0 || x >= a.tiles_x || y >= a.tiles_y) continue;  // REFLECT_101 mirrors pixels of the same tiles
-      const int t = y * a.tiles_x + x;
-      any = any || a.flags_cur[t] != 0 || (a.igp && a.flags_igp && a.flags_igp[t] != 0);
-    }
-  return any;
 }
 
 __global__ __launch_bounds__(256) void tile_flags_kernel(const float *plane, int W, int H, int tiles_x, unsigned char *flags) {
@@ -335,7 +315,7 @@ __global__ __launch_bounds__(1024) void tile_list_kernel(ImgArgs a, int reach, u
       }
     if (dirty && a.flags_other) a.flags_other[t] = 0;
     listed = active || dirty;
-    entry = (unsigned)t | (active ? 0x80000000u : 0u) | (dirty ? 0x40000000u : 0u);
+    entry = tile_entry(t, active, dirty);
   }
   const unsigned long long m = __ballot(listed);
   const unsigned before = (unsigned)__popcll(m & ((1ull << lane) - 1ull));
@@ -376,8 +356,7 @@ __global__ __launch_bounds__(1024) void tile_mark_kernel(ImgArgs a, int reach, u
       }
     }
   if (dirty && a.flags_other) a.flags_other[t] = 0;
-  // bit 29 marks "listed" (tile 0 has an all-zero index); the compaction clears it again
-  dense[t] = (active || dirty) ? ((unsigned)t | (active ? 0x80000000u : 0u) | (dirty ? 0x40000000u : 0u) | 0x20000000u) : 0u;
+  dense[t] = (active || dirty) ? (tile_entry(t, active, dirty) | kTileMarked) : 0u;  // (the compaction clears the mark again)
 }
 __global__ __launch_bounds__(1024) void tile_list_ordered_kernel(const unsigned *dense, int ntiles, unsigned *list, unsigned *count,
                                                                  unsigned *next_count) {
@@ -418,7 +397,7 @@ __global__ __launch_bounds__(1024) void tile_list_ordered_kernel(const unsigned 
     }
 #pragma unroll
     for (int k = 0; k < kPer; k++)
-      if (entry[k]) list[off++] = entry[k] & ~0x20000000u;
+      if (entry[k]) list[off++] = entry[k] & ~kTileMarked;
     __syncthreads();
     if (tid == 0) base_sh += tot;
     __syncthreads();
@@ -1044,8 +1023,7 @@ size_t image_lds_bytes(int r) {
 
 // One workgroup = one 64x16 output tile x one group of <= kPlaneGroup derivative planes (blockIdx.z).
 // LDS: raw tile with halo -> row-blurred tile -> column pass in registers -> fp64 moments.
-// Row pass:  s = k[0]*S[x-r]; s += k[j]*S[x-r+j]           (generic row filter order)
-// Col pass:  s = k[r]*T[y];   s += k[r+j]*(T[y+j]+T[y-j])  (symmetric column filter order)
+// (blur_row / blur_col: the reference's operation orders; the shared tile phases are in cmx_imagephases.hpp)
 // LIST: walk the compacted tile work list with a bounded grid (large panoramas); otherwise one tile per workgroup and
 // the loop below runs exactly once (kept as a loop so that both forms share one body; a runtime trip count costs the
 // one-tile form its register allocation -- the taps spill -- hence the compile-time switch)
@@ -1056,7 +1034,7 @@ __device__ __forceinline__ void image_moments_body(const ImgArgs &a) {
   const bool tail = a.tail.counters != nullptr;  // P == 0 by construction (host side)
   const int r = (R >= 0) ? R : a.r;
   const int W = a.W, H = a.H;
-  float taps[2 * kMaxRadius + 1];
+  float taps[2 * kMaxRadius + 1];  // (register copy, local: cmx_imagephases.hpp)
 #pragma unroll
   for (int j = 0; j < 2 * kMaxRadius + 1; j++) taps[j] = (R < 0 || j <= 2 * R) ? a.taps[j] : 0.f;
   const int rawW = kTileX + 2 * r, rawH = kTileY + 2 * r;
@@ -1072,17 +1050,15 @@ __device__ __forceinline__ void image_moments_body(const ImgArgs &a) {
   const int k_end = min(a.P, k_beg + kPlaneGroup);
   const int n_work = LIST ? (int)(*a.tile_count) : 0;
   for (int wi = blockIdx.x, once = 1; LIST ? (wi < n_work) : (once != 0); wi += gridDim.x, once = 0) {
-  const unsigned entry = LIST ? a.tile_list[wi] : (unsigned)wi;
-  const int tile = (int)(entry & 0x3fffffffu);
-  const int x0 = (tile % a.tiles_x) * kTileX, y0 = (tile / a.tiles_x) * kTileY;
-  if (LIST) __syncthreads();  // LDS of the previous tile is free
+  const TileWork w = tile_begin<kTileX, kTileY, LIST>(a, wi);
+  const int tile = w.tile, x0 = w.x0, y0 = w.y0, slot = w.slot;
 
   float I[4] = {0.f, 0.f, 0.f, 0.f};
   bool valid[4];
 #pragma unroll
   for (int j = 0; j < 4; j++) valid[j] = (x0 + tx < W) && (y0 + tq * 4 + j < H);
-  if (a.zero_ptr && g == 0) {  // clear this tile of the other accumulation buffer (nobody reads it during this launch)
-    const bool dirty = LIST ? (entry & 0x40000000u) != 0 : (!a.flags_other || a.flags_other[tile] != 0);
+  if (a.zero_ptr && g == 0) {  // tile_clear_partner, local: one plane group only, and four rows per thread (256 threads)
+    const bool dirty = tile_partner_dirty<LIST>(a, w);
     if (dirty) {
       for (int pl = 0; pl < a.zero_planes; pl++)
 #pragma unroll
@@ -1094,16 +1070,10 @@ __device__ __forceinline__ void image_moments_body(const ImgArgs &a) {
       if (tid == 0 && a.flags_other && dirty) a.flags_other[tile] = 0;
     }
   }
-  const int slot = LIST ? wi : tile;  // row position of this tile's partial moments
-  if (LIST ? !(entry & 0x80000000u) : !tile_active(a, tile % a.tiles_x, tile / a.tiles_x, r, kTileX, kTileY)) {
-    if (tid == 0 && g == 0) {  // nothing within reach: all sums are zero
-      if (tail) {
-        st_sc1(a.partials + (size_t)0 * a.nblk + slot, 0.0);
-        st_sc1(a.partials + (size_t)1 * a.nblk + slot, 0.0);
-      } else {
-        a.partials[(size_t)0 * a.nblk + slot] = 0.0;
-        a.partials[(size_t)1 * a.nblk + slot] = 0.0;
-      }
+  if (!tile_in_reach<kTileX, kTileY, LIST>(a, w, r)) {  // nothing within reach: all sums are zero
+    if (g == 0) {
+      if (tail) tile_store_moments<kMomentsWriteThrough>(a, slot, 0.0, 0.0);
+      else tile_store_moments<kMomentsPlain>(a, slot, 0.0, 0.0);
     }
     continue;
   }
@@ -1111,38 +1081,19 @@ __device__ __forceinline__ void image_moments_body(const ImgArgs &a) {
   // pass over plane 0 (k == -1) then the group's derivative planes
   for (int k = -1; k < k_end; k = (k < 0 ? k_beg : k + 1)) {
     __syncthreads();
-    for (int idx = tid; idx < rawW * rawH; idx += kImgThreads) {
-      const int ly = idx / rawW, lx = idx - ly * rawW;
-      const int gx = reflect101(x0 + lx - r, W), gy = reflect101(y0 + ly - r, H);
-      const size_t off = (size_t)gy * W + gx;
-      float v;
-      if (k < 0) {
-        v = a.src_a[off];
-        if (a.src_b) v = v + a.src_b[off];        // IL = IL_old + IL_new
-        if (a.igp) v = a.igp[off] * alpha + v;     // I = IGp*alpha + IL
-      } else {
-        v = a.dplanes[(size_t)k * np + off];
+    if (k < 0) tile_load_composed<kImgThreads>(a, alpha, x0, y0, r, rawW, rawH, raw);
+    else  // the same halo of a derivative plane (local: one plane, no composition)
+      for (int idx = tid; idx < rawW * rawH; idx += kImgThreads) {
+        const int ly = idx / rawW, lx = idx - ly * rawW;
+        raw[idx] = a.dplanes[(size_t)k * np + (size_t)reflect101(y0 + ly - r, H) * W + reflect101(x0 + lx - r, W)];
       }
-      raw[idx] = v;
-    }
     __syncthreads();
-    for (int idx = tid; idx < kTileX * rawH; idx += kImgThreads) {
-      const int ly = idx >> 6, lx = idx & 63;
-      const float *S = raw + ly * rawW + lx;
-      float s = taps[0] * S[0];
-#pragma unroll
-      for (int j = 1; j <= 2 * r; j++) s += taps[j] * S[j];
-      rowb[idx] = s;
-    }
+    tile_blur_rows<R, kImgThreads>(taps, r, raw, rawW, rowb, kTileX, rawH);
     __syncthreads();
     double sD = 0, sID = 0, sI = 0, sII = 0;
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-      const int ly = tq * 4 + j + r;
-      const float *T = rowb + ly * kTileX + tx;
-      float s = taps[r] * T[0];
-#pragma unroll
-      for (int t = 1; t <= r; t++) s += taps[r + t] * (T[t * kTileX] + T[-t * kTileX]);
+      const float s = blur_col<R>(taps, r, rowb + (tq * 4 + j + r) * kTileX + tx, kTileX);
       if (valid[j]) {
         const size_t o = (size_t)(y0 + tq * 4 + j) * W + (x0 + tx);
         if (k < 0) {
@@ -1161,15 +1112,8 @@ __device__ __forceinline__ void image_moments_body(const ImgArgs &a) {
       if (g == 0) {
         double t0, t1;
         block_sum2(sI, sII, red, kImgThreads / 64, t0, t1);
-        if (tid == 0) {
-          if (tail) {  // write-through: the last-arriving workgroup of this launch reads them
-            st_sc1(a.partials + (size_t)0 * a.nblk + slot, t0);
-            st_sc1(a.partials + (size_t)1 * a.nblk + slot, t1);
-          } else {
-            a.partials[(size_t)0 * a.nblk + slot] = t0;
-            a.partials[(size_t)1 * a.nblk + slot] = t1;
-          }
-        }
+        if (tail) tile_store_moments<kMomentsWriteThrough>(a, slot, t0, t1);
+        else tile_store_moments<kMomentsPlain>(a, slot, t0, t1);
       }
     } else {
       double t0, t1;
@@ -1284,12 +1228,13 @@ __global__ __launch_bounds__(NT) void image_adjoint_kernel(ImgAdjArgs g) {
   const float alpha = a.alpha ? (float)(*a.alpha) : 0.f;
   const int n_work = LIST ? (int)(*a.tile_count) : 0;
   for (int wi = blockIdx.x, once = 1; LIST ? (wi < n_work) : (once != 0); wi += gridDim.x, once = 0) {
+  // (every phase local in this kernel: cmx_imagephases.hpp says why)
   const unsigned entry = LIST ? a.tile_list[wi] : (unsigned)wi;
-  const int tile = (int)(entry & 0x3fffffffu);
+  const int tile = (int)(entry & kTileIndexMask);
   const int x0 = (tile % a.tiles_x) * TX, y0 = (tile / a.tiles_x) * TY;
   if (LIST) __syncthreads();  // LDS of the previous tile is free
   if (a.zero_ptr) {  // clear this tile of the other accumulation buffer (ping-pong: no memset launch next time)
-    const bool dirty = LIST ? (entry & 0x40000000u) != 0 : (!a.flags_other || a.flags_other[tile] != 0);
+    const bool dirty = LIST ? (entry & kTilePartnerDirty) != 0 : (!a.flags_other || a.flags_other[tile] != 0);
     if (dirty) {
       for (int idx = tid; idx < TX * TY * a.zero_planes; idx += NT) {
         const int pl = idx / (TX * TY), q = idx - pl * (TX * TY);
@@ -1305,7 +1250,7 @@ __global__ __launch_bounds__(NT) void image_adjoint_kernel(ImgAdjArgs g) {
   // nothing non-zero within 2r of this tile: B and Jt vanish on it, and no vote cell (the only place the gather
   // reads Jt) lies in it -- leave Jt untouched, contribute zero moments
   const int slot = LIST ? wi : tile;  // row position of this tile's partial moments
-  if (LIST ? !(entry & 0x80000000u) : !tile_active(a, tile % a.tiles_x, tile / a.tiles_x, 2 * r, TX, TY)) {
+  if (LIST ? !(entry & kTileActive) : !tile_active(a, tile % a.tiles_x, tile / a.tiles_x, 2 * r, TX, TY)) {
     if (tid == 0) {
       a.partials[(size_t)0 * a.nblk + slot] = 0.0;
       a.partials[(size_t)1 * a.nblk + slot] = 0.0;
@@ -1423,6 +1368,8 @@ __global__ __launch_bounds__(kAdjThreads) __attribute__((amdgpu_waves_per_eu(8, 
   static_assert(AH <= 2 * TY, "two row-pass rows per thread");
   const ImgArgs &a = g.img;
   const int W = a.W, H = a.H;
+  constexpr MomentStore kZeros = tail ? kMomentsWriteThrough : kMomentsPlain;  // (TAIL 3: an inactive tile zeroes its rows as TAIL 0 does)
+  constexpr MomentStore kStore = TAIL == 3 ? kMomentsAccumulate : kZeros;
   float taps[2 * R + 1];
 #pragma unroll
   for (int j = 0; j < 2 * R + 1; j++) taps[j] = a.taps[j];
@@ -1434,35 +1381,11 @@ __global__ __launch_bounds__(kAdjThreads) __attribute__((amdgpu_waves_per_eu(8, 
   const float alpha = a.alpha ? (float)(*a.alpha) : 0.f;
   const int n_work = LIST ? (int)(*a.tile_count) : 0;
   for (int wi = blockIdx.x, once = 1; LIST ? (wi < n_work) : (once != 0); wi += gridDim.x, once = 0) {
-  const unsigned entry = LIST ? a.tile_list[wi] : (unsigned)wi;
-  const int tile = (int)(entry & 0x3fffffffu);
-  const int x0 = (tile % a.tiles_x) * TX, y0 = (tile / a.tiles_x) * TY;
-  if (LIST) __syncthreads();  // LDS of the previous tile is free
-  if (a.zero_ptr) {  // clear this tile of the other accumulation buffer (ping-pong: no memset launch next time)
-    const bool dirty = LIST ? (entry & 0x40000000u) != 0 : (!a.flags_other || a.flags_other[tile] != 0);
-    if (dirty) {
-      for (int idx = tid; idx < TX * TY * a.zero_planes; idx += NT) {
-        const int pl = idx / (TX * TY), q = idx - pl * (TX * TY);
-        const int gx = x0 + (q % TX), gy = y0 + (q / TX);
-        if (gx < W && gy < H) a.zero_ptr[(size_t)pl * W * H + (size_t)gy * W + gx] = 0.f;
-      }
-    }
-    if (!LIST) {  // (the list pre-pass has already un-flagged it)
-      __syncthreads();   // every thread has read the flag
-      if (tid == 0 && a.flags_other && dirty) a.flags_other[tile] = 0;
-    }
-  }
-  const int slot = LIST ? wi : tile;  // row position of this tile's partial moments
-  if (LIST ? !(entry & 0x80000000u) : !tile_active(a, tile % a.tiles_x, tile / a.tiles_x, 2 * R, TX, TY)) {
-    if (tid == 0) {
-      if (tail) {
-        st_sc1(a.partials + (size_t)0 * a.nblk + slot, 0.0);
-        st_sc1(a.partials + (size_t)1 * a.nblk + slot, 0.0);
-      } else {
-        a.partials[(size_t)0 * a.nblk + slot] = 0.0;
-        a.partials[(size_t)1 * a.nblk + slot] = 0.0;
-      }
-    }
+  const TileWork w = tile_begin<TX, TY, LIST>(a, wi);
+  const int x0 = w.x0, y0 = w.y0;
+  tile_clear_partner<TX, TY, NT, LIST>(a, w);
+  if (!tile_in_reach<TX, TY, LIST>(a, w, 2 * R)) {
+    tile_store_moments<kZeros>(a, w.slot, 0.0, 0.0);
     continue;
   }
   // coefficient rows: every row of M at least 2r away from the border is the same 4r+1-tap kernel (wave-uniform loads);
@@ -1474,15 +1397,7 @@ __global__ __launch_bounds__(kAdjThreads) __attribute__((amdgpu_waves_per_eu(8, 
 #pragma unroll
     for (int i = 0; i < NTAP; i++) mx[i] = row[i];
   }
-  for (int idx = tid; idx < AW * AH; idx += NT) {
-    const int ly = idx / AW, lx = idx - ly * AW;
-    const int gx = reflect101(x0 + lx - 2 * R, W), gy = reflect101(y0 + ly - 2 * R, H);
-    const size_t off = (size_t)gy * W + gx;
-    float v = a.src_a[off];
-    if (a.src_b) v = v + a.src_b[off];
-    if (a.igp) v = a.igp[off] * alpha + v;
-    bufA[idx] = v;  // (beyond the image: the reflected value for G_x; M's rows carry zeros there)
-  }
+  tile_load_composed<NT>(a, alpha, x0, y0, 2 * R, AW, AH, bufA);  // (beyond the image: the reflected value for G_x; M's rows carry zeros there)
   __syncthreads();
 #pragma unroll
   for (int h = 0; h < 2; h++) {  // row pass: raw rows ty and ty + TY, output column tx
@@ -1498,12 +1413,7 @@ __global__ __launch_bounds__(kAdjThreads) __attribute__((amdgpu_waves_per_eu(8, 
 #pragma unroll
       for (int i = 1; i < NTAP; i++) m = __builtin_fma((double)mx[i], (double)in[i], m);  // (not an oracle-ordered sum: fused)
       bufM[ly * TX + tx] = (float)m;
-      if (ly >= R && ly < R + GH) {  // forward row pass, same op order as image_moments
-        float s = taps[0] * in[R];
-#pragma unroll
-        for (int j = 1; j <= 2 * R; j++) s += taps[j] * in[R + j];
-        bufG[(ly - R) * TX + tx] = s;
-      }
+      if (ly >= R && ly < R + GH) bufG[(ly - R) * TX + tx] = blur_row<R>(taps, R, in + R);  // forward row pass
     }
   }
   float my[NTAP];
@@ -1518,10 +1428,7 @@ __global__ __launch_bounds__(kAdjThreads) __attribute__((amdgpu_waves_per_eu(8, 
   {
     const int gx = x0 + tx, gy = y0 + ty;
     if (gx < W && gy < H) {
-      const float *T = bufG + (ty + R) * TX + tx;
-      float s = taps[R] * T[0];
-#pragma unroll
-      for (int t = 1; t <= R; t++) s += taps[R + t] * (T[t * TX] + T[-t * TX]);
+      const float s = blur_col<R>(taps, R, bufG + (ty + R) * TX + tx, TX);
       sI = (double)s;
       sII = (double)s * (double)s;
       if (a.out_blur0) a.out_blur0[(size_t)gy * W + gx] = s;
@@ -1535,19 +1442,7 @@ __global__ __launch_bounds__(kAdjThreads) __attribute__((amdgpu_waves_per_eu(8, 
   {
     double t0, t1;
     block_sum2(sI, sII, red, NT / 64, t0, t1);
-    if (tid == 0) {
-      if (TAIL == 3) {  // accumulator rows: read by every workgroup of the gradient pass queued behind this launch
-        double *row = a.macc + (size_t)(slot % kTailShards) * 16;
-        if (t0 != 0.0) __hip_atomic_fetch_add(row, t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (t1 != 0.0) __hip_atomic_fetch_add(row + 1, t1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      } else if (tail) {  // write-through: the last-arriving workgroup of this launch reads them
-        st_sc1(a.partials + (size_t)0 * a.nblk + slot, t0);
-        st_sc1(a.partials + (size_t)1 * a.nblk + slot, t1);
-      } else {
-        a.partials[(size_t)0 * a.nblk + slot] = t0;
-        a.partials[(size_t)1 * a.nblk + slot] = t1;
-      }
-    }
+    tile_store_moments<kStore>(a, w.slot, t0, t1);
   }
   }  // work loop
   if (tail && tail_arrive(a.tail, (int)gridDim.x, (int)blockIdx.x, fin_sm)) finalize_body<NT, TAIL == 2>(a.tail.fin, fin_sm);
@@ -1574,41 +1469,14 @@ __global__ __launch_bounds__(kAdjThreads) void image_adjoint2g_kernel(ImgAdjArgs
   const float alpha = a.alpha ? (float)(*a.alpha) : 0.f;
   const int n_work = LIST ? (int)(*a.tile_count) : 0;
   for (int wi = blockIdx.x, once = 1; LIST ? (wi < n_work) : (once != 0); wi += gridDim.x, once = 0) {
-  const unsigned entry = LIST ? a.tile_list[wi] : (unsigned)wi;
-  const int tile = (int)(entry & 0x3fffffffu);
-  const int x0 = (tile % a.tiles_x) * TX, y0 = (tile / a.tiles_x) * TY;
-  if (LIST) __syncthreads();  // LDS of the previous tile is free
-  if (a.zero_ptr) {  // clear this tile of the other accumulation buffer (ping-pong: no memset launch next time)
-    const bool dirty = LIST ? (entry & 0x40000000u) != 0 : (!a.flags_other || a.flags_other[tile] != 0);
-    if (dirty) {
-      for (int idx = tid; idx < TX * TY * a.zero_planes; idx += NT) {
-        const int pl = idx / (TX * TY), q = idx - pl * (TX * TY);
-        const int gx = x0 + (q % TX), gy = y0 + (q / TX);
-        if (gx < W && gy < H) a.zero_ptr[(size_t)pl * W * H + (size_t)gy * W + gx] = 0.f;
-      }
-    }
-    if (!LIST) {
-      __syncthreads();
-      if (tid == 0 && a.flags_other && dirty) a.flags_other[tile] = 0;
-    }
-  }
-  const int slot = LIST ? wi : tile;
-  if (LIST ? !(entry & 0x80000000u) : !tile_active(a, tile % a.tiles_x, tile / a.tiles_x, 2 * r, TX, TY)) {
-    if (tid == 0) {
-      a.partials[(size_t)0 * a.nblk + slot] = 0.0;
-      a.partials[(size_t)1 * a.nblk + slot] = 0.0;
-    }
+  const TileWork w = tile_begin<TX, TY, LIST>(a, wi);
+  const int x0 = w.x0, y0 = w.y0;
+  tile_clear_partner<TX, TY, NT, LIST>(a, w);
+  if (!tile_in_reach<TX, TY, LIST>(a, w, 2 * r)) {
+    tile_store_moments<kMomentsPlain>(a, w.slot, 0.0, 0.0);
     continue;
   }
-  for (int idx = tid; idx < AW * AH; idx += NT) {
-    const int ly = idx / AW, lx = idx - ly * AW;
-    const int gx = reflect101(x0 + lx - 2 * r, W), gy = reflect101(y0 + ly - 2 * r, H);
-    const size_t off = (size_t)gy * W + gx;
-    float v = a.src_a[off];
-    if (a.src_b) v = v + a.src_b[off];
-    if (a.igp) v = a.igp[off] * alpha + v;
-    bufA[idx] = v;
-  }
+  tile_load_composed<NT>(a, alpha, x0, y0, 2 * r, AW, AH, bufA);
   __syncthreads();
   {
     const bool interior = x0 >= 2 * r && x0 + TX - 1 <= W - 1 - 2 * r;
@@ -1618,11 +1486,7 @@ __global__ __launch_bounds__(kAdjThreads) void image_adjoint2g_kernel(ImgAdjArgs
       double m = 0.0;
       for (int i = 0; i < ntap; i++) m = __builtin_fma((double)mrow[i], (double)S[i], m);
       bufM[ly * TX + tx] = (float)m;
-      if (ly >= r && ly < r + GH) {  // forward row pass, same op order as image_moments
-        float sacc = a.taps[0] * S[r];
-        for (int j = 1; j <= 2 * r; j++) sacc += a.taps[j] * S[r + j];
-        bufG[(ly - r) * TX + tx] = sacc;
-      }
+      if (ly >= r && ly < r + GH) bufG[(ly - r) * TX + tx] = blur_row<-1>(a.taps, r, S + r);  // forward row pass (taps read through the caches)
     }
   }
   __syncthreads();
@@ -1630,9 +1494,7 @@ __global__ __launch_bounds__(kAdjThreads) void image_adjoint2g_kernel(ImgAdjArgs
   {
     const int gx = x0 + tx, gy = y0 + ty;
     if (gx < W && gy < H) {
-      const float *T = bufG + (ty + r) * TX + tx;
-      float sacc = a.taps[r] * T[0];
-      for (int t = 1; t <= r; t++) sacc += a.taps[r + t] * (T[t * TX] + T[-t * TX]);
+      const float sacc = blur_col<-1>(a.taps, r, bufG + (ty + r) * TX + tx, TX);
       sI = (double)sacc;
       sII = (double)sacc * (double)sacc;
       if (a.out_blur0) a.out_blur0[(size_t)gy * W + gx] = sacc;
@@ -1647,10 +1509,7 @@ __global__ __launch_bounds__(kAdjThreads) void image_adjoint2g_kernel(ImgAdjArgs
   {
     double t0, t1;
     block_sum2(sI, sII, red, NT / 64, t0, t1);
-    if (tid == 0) {
-      a.partials[(size_t)0 * a.nblk + slot] = t0;
-      a.partials[(size_t)1 * a.nblk + slot] = t1;
-    }
+    tile_store_moments<kMomentsPlain>(a, w.slot, t0, t1);
   }
   }  // work loop
 }
@@ -2561,7 +2420,7 @@ __global__ __launch_bounds__(kAdjThreads) void image_adjoint_sobel_kernel(ImgAdj
   const ImgArgs &a = g.img;
   const int r = (R >= 0) ? R : a.r;
   const int W = a.W, H = a.H;
-  float taps[2 * kMaxRadius + 1];
+  float taps[2 * kMaxRadius + 1];  // (register copy, local: cmx_imagephases.hpp)
 #pragma unroll
   for (int j = 0; j < 2 * kMaxRadius + 1; j++) taps[j] = (R < 0 || j <= 2 * R) ? a.taps[j] : 0.f;
   const int aw = TX + 4 * r + 4, ah = TY + 4 * r + 4;  // raw: tile + 2r+2
@@ -2577,51 +2436,27 @@ __global__ __launch_bounds__(kAdjThreads) void image_adjoint_sobel_kernel(ImgAdj
   float *bufH = bufB;   // hw x hh <= bw x bh  (B is dead after the Sobel phase)
   float *bufT = bufA;   // TX x hh <= aw x ah  (gx is dead after the Sobel^T phase)
   const int tid = threadIdx.x;
-  const int tile = (int)blockIdx.x;
-  const int x0 = (tile % a.tiles_x) * TX, y0 = (tile / a.tiles_x) * TY;
-  if (a.zero_ptr) {  // clear this tile of the other accumulation buffer (ping-pong: no memset launch next time)
-    const bool dirty = !a.flags_other || a.flags_other[tile] != 0;
-    if (dirty) {
-      for (int idx = tid; idx < TX * TY * a.zero_planes; idx += NT) {
-        const int pl = idx / (TX * TY), q = idx - pl * (TX * TY);
-        const int gx = x0 + (q % TX), gy = y0 + (q / TX);
-        if (gx < W && gy < H) a.zero_ptr[(size_t)pl * W * H + (size_t)gy * W + gx] = 0.f;
-      }
-    }
-    __syncthreads();  // every thread has read the flag
-    if (tid == 0 && a.flags_other && dirty) a.flags_other[tile] = 0;
-  }
+  const TileWork w = tile_begin<TX, TY, false>(a, (int)blockIdx.x);  // one tile per workgroup
+  const int tile = w.tile, x0 = w.x0, y0 = w.y0;
+  tile_clear_partner<TX, TY, NT, false>(a, w);
   // nothing non-zero within 2r+2 of this tile: B, gx, gy and Jt vanish on it, and no vote cell lies in it
-  if (!tile_active(a, tile % a.tiles_x, tile / a.tiles_x, 2 * r + 2, TX, TY)) {
-    if (tid == 0) {
-      a.partials[(size_t)0 * a.nblk + tile] = 0.0;
-      a.partials[(size_t)1 * a.nblk + tile] = 0.0;
-    }
+  if (!tile_in_reach<TX, TY, false>(a, w, 2 * r + 2)) {
+    tile_store_moments<kMomentsPlain>(a, tile, 0.0, 0.0);
     return;
   }
 
-  for (int idx = tid; idx < aw * ah; idx += NT) {
+  for (int idx = tid; idx < aw * ah; idx += NT) {  // tile_load_composed, local: the front end's single vote plane, halo 2r+2
     const int ly = idx / aw, lx = idx - ly * aw;
     const int gx = reflect101(x0 + lx - 2 * r - 2, W), gy = reflect101(y0 + ly - 2 * r - 2, H);
     bufA[idx] = a.src_a[(size_t)gy * W + gx];
   }
   __syncthreads();
-  for (int idx = tid; idx < bw * ah; idx += NT) {  // forward row pass (same op order as image_moments)
-    const int ly = idx / bw, lx = idx - ly * bw;
-    const float *S = bufA + ly * aw + lx;
-    float s = taps[0] * S[0];
-#pragma unroll
-    for (int j = 1; j <= 2 * r; j++) s += taps[j] * S[j];
-    bufR[idx] = s;
-  }
+  tile_blur_rows<R, NT>(taps, r, bufA, aw, bufR, bw, ah);
   __syncthreads();
   double sB = 0, sG = 0;
   for (int idx = tid; idx < bw * bh; idx += NT) {  // forward column pass -> B on tile + r+2
     const int ly = idx / bw, lx = idx - ly * bw;
-    const float *T = bufR + (ly + r) * bw + lx;
-    float s = taps[r] * T[0];
-#pragma unroll
-    for (int t = 1; t <= r; t++) s += taps[r + t] * (T[t * bw] + T[-t * bw]);
+    const float s = blur_col<R>(taps, r, bufR + (ly + r) * bw + lx, bw);
     bufB[idx] = s;
     const int gx = x0 + lx - r - 2, gy = y0 + ly - r - 2;
     if (gx >= x0 && gx < x0 + TX && gx < W && gy >= y0 && gy < y0 + TY && gy < H) sB += (double)s;
@@ -2652,10 +2487,7 @@ __global__ __launch_bounds__(kAdjThreads) void image_adjoint_sobel_kernel(ImgAdj
   {
     double t0, t1;
     block_sum2(sB, sG, red, NT / 64, t0, t1);  // (its barriers also publish gx, gy)
-    if (tid == 0) {
-      a.partials[(size_t)0 * a.nblk + tile] = t0;
-      a.partials[(size_t)1 * a.nblk + tile] = t1;
-    }
+    tile_store_moments<kMomentsPlain>(a, tile, t0, t1);
   }
   __syncthreads();
   for (int idx = tid; idx < hw * hh; idx += NT) {  // Hs = Sx^T gx + Sy^T gy on tile + r, reflected taps folded (see above)
@@ -2678,7 +2510,7 @@ __global__ __launch_bounds__(kAdjThreads) void image_adjoint_sobel_kernel(ImgAdj
     bufH[idx] = s;
   }
   __syncthreads();
-  for (int idx = tid; idx < TX * hh; idx += NT) {  // G^T row pass: zero-padded conv + folded reflections
+  for (int idx = tid; idx < TX * hh; idx += NT) {  // G^T row pass: zero-padded conv + folded reflections (local: cmx_imagephases.hpp)
     const int ly = idx / TX, lx = idx - ly * TX;
     const float *S = bufH + ly * hw + lx;
     float s = taps[0] * S[0];

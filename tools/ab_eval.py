@@ -2,6 +2,7 @@
 back end (config 3), for a list of option settings.  Usage on the GPU box:
     python tools/ab_eval.py [fe|be|both] [key=value ...]     keys: tail, spin, reuse (ints); events=N; reps=N;
                                                              tailhost=1: CMX_OPT_TAIL_FINALIZE 1 against 4, three times each
+                                                             nofuse=1: CMX_OPT_FUSED_IMAGE 0 on every variant
 Prints one line per variant: ms per fdf, ms per cost-only evaluation, kernel-class times (HIP events, separate pass)."""
 import os
 import sys
@@ -99,6 +100,8 @@ def main():
         variants = [("fold=0", {_lib.OPT_FOLD_BATCH: 0}), ("fold=1", {_lib.OPT_FOLD_BATCH: 1})] * 2
     if "det" in kv:
         variants = [("deterministic=0", {_lib.OPT_DETERMINISTIC: 0}), ("deterministic=1", {_lib.OPT_DETERMINISTIC: 1})]
+    if "nofuse" in kv:  # every variant with the image pass as its own launch (image_adjoint2<4>), whatever key chose the variants
+        variants = [(name + " fused=0", {**opts, _lib.OPT_FUSED_IMAGE: 0}) for name, opts in variants]
     for kind in kinds:
         run(kind, kv.get("events"), kv.get("reps", 300 if kind == "fe" else 100), variants)
 
