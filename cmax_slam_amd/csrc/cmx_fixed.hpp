@@ -27,6 +27,27 @@ __device__ __forceinline__ void vote4_global_fix(fix_t *img, int W, int xx, int 
   atomicAdd(q + W + 1, to_fix(dx * dy));
 }
 
+// The two votes with a temporal weight and a sign (the voxel grids of a reconstruction): every bilinear product of vote4_global,
+// formed the same way, times wt, negated when neg -- s * (wt * wb) in fp32.  The fixed-point form converts the magnitude and
+// negates the integer: two's complement, so the cell is read back as SIGNED.
+__device__ __forceinline__ void vote4_global_w(float *img, int W, int xx, int yy, float dx, float dy, float wt, bool neg) {
+  float *q = img + (size_t)yy * W + xx;
+  const float m0 = wt * ((1.f - dx) * (1.f - dy)), m1 = wt * (dx * (1.f - dy)), m2 = wt * ((1.f - dx) * dy), m3 = wt * (dx * dy);
+  atomic_add_f32(q, neg ? -m0 : m0);
+  atomic_add_f32(q + 1, neg ? -m1 : m1);
+  atomic_add_f32(q + W, neg ? -m2 : m2);
+  atomic_add_f32(q + W + 1, neg ? -m3 : m3);
+}
+__device__ __forceinline__ void vote4_global_fix_w(fix_t *img, int W, int xx, int yy, float dx, float dy, float wt, bool neg) {
+  fix_t *q = img + (size_t)yy * W + xx;
+  const fix_t m0 = to_fix(wt * ((1.f - dx) * (1.f - dy))), m1 = to_fix(wt * (dx * (1.f - dy)));
+  const fix_t m2 = to_fix(wt * ((1.f - dx) * dy)), m3 = to_fix(wt * (dx * dy));
+  atomicAdd(q, neg ? 0ull - m0 : m0);
+  atomicAdd(q + 1, neg ? 0ull - m1 : m1);
+  atomicAdd(q + W, neg ? 0ull - m2 : m2);
+  atomicAdd(q + W + 1, neg ? 0ull - m3 : m3);
+}
+
 // The same vote into a workgroup's LDS window (kBinWindow^2 cells, row stride kBinStride).  LDS accumulators are 64-bit fixed point
 // (2^-30 units), not fp32: on gfx950 ds_add_f32 retires ONE lane at a time (193 G lane-atomics/s for any address pattern) while
 // ds_add_u64 runs at 1.7 T/s (tools/microbench/lds_atomics.hip).  Integer adds also commute, so a window's sum does not depend on

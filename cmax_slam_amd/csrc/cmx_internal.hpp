@@ -494,6 +494,28 @@ struct ReconViewArgs {
   unsigned long long *n_voted;     // [n_views] events that voted into each view
 };
 void launch_recon_view_votes(const ReconViewArgs &g, hipStream_t s);
+// voxel grids (cmx_backend_recon_voxel_*): the vote loop of launch_recon_view_votes with G grids of n_bins planes as its targets.
+// A grid is a view plus the scale of its bin axis; an event votes into every grid whose range holds its OWN timestamp -- ev_t, read
+// at the index its packed word is read at -- with the bilinear weights of the view vote times the triangular weight of each of
+// its two neighbouring bins, negated for an OFF event of a signed set (polarity as in launch_recon_votes_pol: ev.pol, or bit 31 of
+// the word).  planes / fixed hold n_grids * n_bins planes of Wv x Hv, grid-major; the fixed-point cells are two's complement.
+struct ReconVoxelDev {       // one grid as the kernel reads it: 17 eight-byte words
+  ReconViewDev v;
+  double scale;              // (n_bins - 1) / (t_hi - t_lo)
+};
+struct ReconVoxelArgs {
+  ReconArgs ev;
+  const long long *ev_t;           // the events' own timestamps, indexed as ev.xy is
+  const ReconVoxelDev *grids;      // [n_grids]
+  const ReconViewRange *ranges;    // [n_grids]
+  int n_grids, Wv, Hv, n_bins;
+  int is_signed;                   // 0: every event votes +1 and polarity is not read
+  float *planes;                   // [n_grids][n_bins][Hv * Wv]: fp32 atomics ...
+  unsigned long long *fixed;       // ... or, when set, 64-bit integer adds into the 2^-30 fixed-point twins
+  unsigned long long *n_voted;     // [n_grids] events that voted into each grid (once per event, not per bin)
+};
+void launch_recon_voxel_votes(const ReconVoxelArgs &g, hipStream_t s);
+void launch_recon_fixed_to_float_signed(const unsigned long long *fixed, float *plane, size_t n, hipStream_t s);  // two's complement cells
 // bound events (cmx_backend_recon_bind_from / _eval_bound): the batch poses of a spline of any knot count as a table in global
 // memory (recon_pose<N>, one thread per batch: a.batch_t, a.nb) -- what the tile sort (launch_count_sort with poseR = the table)
 // and the vote kernel below read -- and the vote pass over the tile-sorted events: one workgroup per chunk, votes into a

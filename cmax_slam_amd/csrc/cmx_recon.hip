@@ -10,6 +10,8 @@
 //                   without the old / new split).  No pose table in global memory, no tile sort, no second launch.
 //                   POL (cmx_backend_recon_pol_add*): the same walk, the same cell and weights, but the four adds go to the ON or
 //                   the OFF plane by the event's polarity, and the voting events are counted per plane.
+//   recon_view_votes / recon_voxel_votes   the same walk with the planes of M pinhole views, or the bins of G voxel grids, as the
+//                   targets of the votes (further down, with their own descriptions)
 //   recon_fixed_to_float   deterministic mode: the 2^-30 fixed-point plane as fp32, leaving it as it is (accumulation goes on)
 #include "../../include/cmax_hip.h"
 #include "cmx_internal.hpp"
@@ -172,6 +174,18 @@ void launch_recon_votes_pol(const ReconArgs &a, hipStream_t s) {
 constexpr int kReconMaxViews = 4096;  // (cmx_backend_recon_view_begin refuses more: the list of a workgroup holds any subset)
 static_assert(sizeof(ReconViewDev) == 128 && sizeof(ReconViewRange) == 16, "view entries are copied word by word");
 
+// a world ray in one view (shared with the voxel grids): turned into the camera and projected, and the vote test -- in floating
+// point, before any conversion: a NaN fails it, and only values inside the plane are ever cast
+struct ReconViewHit { double u, w; bool ok; };
+__device__ __forceinline__ ReconViewHit recon_view_project(const ReconViewDev &V, double rx, double ry, double rz, double u_hi, double w_hi) {
+  double x, y, z;
+  be_rotate<false>(V.Rt, rx, ry, rz, x, y, z);
+  const double iz = 1.0 / z;
+  const double u = V.fx * (x * iz) + V.cx;
+  const double w = V.fy * (y * iz) + V.cy;
+  return ReconViewHit{u, w, z > 0.0 && u >= 1.0 && u < u_hi && w >= 1.0 && w < w_hi};
+}
+
 template <int N, bool FIXED>
 __global__ __launch_bounds__(kReconThreads) void recon_view_votes_kernel(const ReconViewArgs g) {
   constexpr int kWords = sizeof(ReconViewDev) / 8;
@@ -245,15 +259,10 @@ __global__ __launch_bounds__(kReconThreads) void recon_view_votes_kernel(const R
       for (int k = 0; k < nl; k++) {
         const ReconViewDev &V = sh_view[k];  // (one address for all lanes: LDS broadcasts)
         if (tb < V.t_lo || tb >= V.t_hi) continue;
-        double x, y, z;
-        be_rotate<false>(V.Rt, rx, ry, rz, x, y, z);
-        const double iz = 1.0 / z;
-        const double u = V.fx * (x * iz) + V.cx;
-        const double w = V.fy * (y * iz) + V.cy;
-        // the vote test in floating point, before any conversion: a NaN fails it, and only values inside the plane are cast
-        if (z > 0.0 && u >= 1.0 && u < u_hi && w >= 1.0 && w < w_hi) {
-          const int xx = (int)u, yy = (int)w;
-          const float dx = (float)(u - xx), dy = (float)(w - yy);
+        const ReconViewHit p = recon_view_project(V, rx, ry, rz, u_hi, w_hi);
+        if (p.ok) {
+          const int xx = (int)p.u, yy = (int)p.w;
+          const float dx = (float)(p.u - xx), dy = (float)(p.w - yy);
           const size_t at = (size_t)V.index * np;
           if (FIXED) vote4_global_fix(g.fixed + at, g.Wv, xx, yy, dx, dy);
           else vote4_global(g.planes + at, g.Wv, xx, yy, dx, dy);
@@ -280,6 +289,153 @@ void launch_recon_view_votes(const ReconViewArgs &g, hipStream_t s) {
   } else {
     if (g.fixed) hipLaunchKernelGGL((recon_view_votes_kernel<4, true>), gr, b, 0, s, g);
     else hipLaunchKernelGGL((recon_view_votes_kernel<4, false>), gr, b, 0, s, g);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- voxel grids
+// recon_voxel_votes   cmx_backend_recon_voxel_add*: recon_view_votes with G grids of n_bins planes as the targets and the event's OWN
+//                timestamp as what decides membership and weight.  The same run structure: batch poses into LDS; beside them the
+//                lanes take the minimum and maximum of the run's event times (the per-event stream ev_t, read at the index of the
+//                packed word), and the ONE scan of the table of grid ranges lists the grids that meet that span -- not the span of
+//                the batch times: a batch of 5000 events spans many bins and several grids.  Listed grids are taken
+//                kReconViewChunk at a time, 136-byte entries in LDS; the world ray is formed once per event and chunk, and for
+//                every grid of the chunk with t_lo <= t_i < t_hi: recon_view_project (the view vote's own projection and test), its
+//                cell and weights, tau = (t_i - t_lo) * scale in fp64, b0 = min((int)tau, n_bins - 2), f = (float)(tau - b0), and the
+//                four bilinear adds times 1 - f into bin b0 and times f into bin b0 + 1 (n_bins == 1: one bin, weight 1), negated
+//                for an OFF event of a signed set.  A bin whose weight is zero is skipped: it would add zeros.  Votes go to
+//                global memory: the two active bins of a grid are two planes, which no LDS window holds.
+static_assert(sizeof(ReconVoxelDev) == 136, "grid entries are copied word by word");
+
+template <int N, bool FIXED>
+__global__ __launch_bounds__(kReconThreads) void recon_voxel_votes_kernel(const ReconVoxelArgs g) {
+  constexpr int kWords = sizeof(ReconVoxelDev) / 8;
+  static_assert(kReconViewChunk * kWords <= kReconThreads, "one lane per word of a chunk");
+  __shared__ double sh_R[(kReconMaxRun + 2) * 9];
+  __shared__ ReconVoxelDev sh_grid[kReconViewChunk];
+  __shared__ unsigned sh_cnt[kReconViewChunk];
+  __shared__ unsigned short sh_match[kReconMaxViews];
+  __shared__ unsigned sh_nmatch;
+  __shared__ long long sh_tmin, sh_tmax;
+  const ReconArgs &a = g.ev;
+  const int tid = threadIdx.x;
+  const int e0 = blockIdx.x * a.run;  // (the grid covers [0, n): e0 < n)
+  const int e1 = (a.n - e0 > a.run) ? e0 + a.run : a.n;
+  const int b0 = e0 / a.per_batch;
+  int nbw = (e1 - 1) / a.per_batch - b0 + 1;
+  if (nbw > kReconMaxRun + 2) nbw = kReconMaxRun + 2;  // (cannot happen with run = recon_run(per_batch))
+  if (tid == 0) { sh_nmatch = 0; sh_tmin = 0x7fffffffffffffffLL; sh_tmax = -0x7fffffffffffffffLL - 1; }
+  __syncthreads();
+  for (int j = tid; j < nbw; j += kReconThreads) {
+    const int b = b0 + j < a.nb ? b0 + j : a.nb - 1;
+    recon_pose<N>(a, a.batch_t[b], sh_R + 9 * j);
+  }
+  // the span of the run's EVENT times: every event is looked at, so the list below holds for any order of the events
+  long long tmin = 0x7fffffffffffffffLL, tmax = -0x7fffffffffffffffLL - 1;
+  for (int i = e0 + tid; i < e1; i += kReconThreads) {
+    const int b = i / a.per_batch;
+    const size_t src = a.stride ? (size_t)b * a.B + (size_t)(i - b * a.per_batch) * a.stride : (size_t)i;
+    const long long t = g.ev_t[src];
+    tmin = t < tmin ? t : tmin;
+    tmax = t > tmax ? t : tmax;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const long long lo = __shfl_down(tmin, off, 64), hi = __shfl_down(tmax, off, 64);
+    tmin = lo < tmin ? lo : tmin;
+    tmax = hi > tmax ? hi : tmax;
+  }
+  if ((tid & 63) == 0) { atomicMin(&sh_tmin, tmin); atomicMax(&sh_tmax, tmax); }
+  __syncthreads();
+  tmin = sh_tmin; tmax = sh_tmax;
+  for (int v = tid; v < g.n_grids; v += kReconThreads) {
+    const ReconViewRange r = g.ranges[v];
+    if (r.t_lo <= tmax && r.t_hi > tmin) {
+      const unsigned pos = atomicAdd(&sh_nmatch, 1u);
+      if (pos < (unsigned)kReconMaxViews) sh_match[pos] = (unsigned short)v;
+    }
+  }
+  __syncthreads();
+  int nmatch = (int)sh_nmatch;
+  nmatch = nmatch < kReconMaxViews ? nmatch : kReconMaxViews;
+  const double u_hi = (double)(g.Wv - 2), w_hi = (double)(g.Hv - 2);
+  const size_t np = (size_t)g.Hv * g.Wv;
+  const int nbins = g.n_bins;
+  for (int c0 = 0; c0 < nmatch; c0 += kReconViewChunk) {  // (uniform: nmatch is the workgroup's)
+    const int nl = nmatch - c0 < kReconViewChunk ? nmatch - c0 : kReconViewChunk;
+    if (tid < nl * kWords) {
+      const int k = tid / kWords, wd = tid - k * kWords;
+      reinterpret_cast<long long *>(sh_grid)[tid] = reinterpret_cast<const long long *>(g.grids + sh_match[c0 + k])[wd];
+    }
+    if (tid < kReconViewChunk) sh_cnt[tid] = 0;
+    __syncthreads();
+    int cur = -1;
+    double R[9];
+    for (int i = e0 + tid; i < e1; i += kReconThreads) {
+      const int b = i / a.per_batch;
+      int j = b - b0;
+      j = j < nbw ? j : nbw - 1;
+      if (j != cur) {
+#pragma unroll
+        for (int c = 0; c < 9; c++) R[c] = sh_R[9 * j + c];
+        cur = j;
+      }
+      // sampling restarts at every batch start: packed slot k of batch b is raw event b * B + k * stride (recon_votes_kernel)
+      const size_t src = a.stride ? (size_t)b * a.B + (size_t)(i - b * a.per_batch) * a.stride : (size_t)i;
+      const uint32_t word = a.xy[src];
+      const long long ti = g.ev_t[src];
+      const uint32_t e = word & 0x7fffffffu;
+      // a signed set: the store's byte (a.pol is a kernel argument: uniform), read beside the word, or the word's own bit 31
+      const bool neg = g.is_signed && !(a.pol ? a.pol[src] != 0 : (word >> 31) != 0);
+      const int ex = e & 0xffff, ey = e >> 16;
+      double v0, v1, v2, rx, ry, rz;
+      load_bearing(a.cam, ex, ey, v0, v1, v2);
+      be_rotate<false>(R, v0, v1, v2, rx, ry, rz);
+      for (int k = 0; k < nl; k++) {
+        const ReconVoxelDev &G = sh_grid[k];  // (one address for all lanes: LDS broadcasts)
+        if (ti < G.v.t_lo || ti >= G.v.t_hi) continue;
+        const ReconViewHit p = recon_view_project(G.v, rx, ry, rz, u_hi, w_hi);
+        if (!p.ok) continue;
+        const int xx = (int)p.u, yy = (int)p.w;
+        const float dx = (float)(p.u - xx), dy = (float)(p.w - yy);
+        int bin = 0;
+        float w0 = 1.f, w1 = 0.f;
+        if (nbins >= 2) {
+          const double tau = (double)(ti - G.v.t_lo) * G.scale;  // (0 <= tau < n_bins - 1, up to its rounding: the cast is safe)
+          bin = (int)tau;
+          bin = bin < nbins - 2 ? bin : nbins - 2;
+          w1 = (float)(tau - bin);
+          w0 = 1.f - w1;
+        }
+        const size_t at = ((size_t)G.v.index * nbins + bin) * np;
+        if (FIXED) {
+          if (w0 != 0.f) vote4_global_fix_w(g.fixed + at, g.Wv, xx, yy, dx, dy, w0, neg);
+          if (w1 != 0.f) vote4_global_fix_w(g.fixed + at + np, g.Wv, xx, yy, dx, dy, w1, neg);
+        } else {
+          if (w0 != 0.f) vote4_global_w(g.planes + at, g.Wv, xx, yy, dx, dy, w0, neg);
+          if (w1 != 0.f) vote4_global_w(g.planes + at + np, g.Wv, xx, yy, dx, dy, w1, neg);
+        }
+        atomicAdd(&sh_cnt[k], 1u);
+      }
+    }
+    __syncthreads();
+    if (tid < nl) {  // (the lane that zeroes the counter of the next chunk)
+      const unsigned cnt = sh_cnt[tid];
+      if (cnt) atomicAdd(g.n_voted + sh_grid[tid].v.index, (unsigned long long)cnt);
+    }
+    __syncthreads();  // (the next chunk's entries overwrite sh_grid)
+  }
+}
+
+void launch_recon_voxel_votes(const ReconVoxelArgs &g, hipStream_t s) {
+  const ReconArgs &a = g.ev;
+  if (a.n <= 0 || a.nb <= 0 || g.n_grids <= 0) return;
+  const dim3 gr((unsigned)(((long long)a.n + a.run - 1) / a.run)), b(kReconThreads);  // (a.n <= 2^30: cmx_reconstruct.cpp)
+  if (a.order == 2) {
+    if (g.fixed) hipLaunchKernelGGL((recon_voxel_votes_kernel<2, true>), gr, b, 0, s, g);
+    else hipLaunchKernelGGL((recon_voxel_votes_kernel<2, false>), gr, b, 0, s, g);
+  } else {
+    if (g.fixed) hipLaunchKernelGGL((recon_voxel_votes_kernel<4, true>), gr, b, 0, s, g);
+    else hipLaunchKernelGGL((recon_voxel_votes_kernel<4, false>), gr, b, 0, s, g);
   }
 }
 
@@ -493,6 +649,17 @@ void launch_recon_fixed_to_float(const unsigned long long *fixed, float *plane, 
   size_t blocks = (n + 1023) / 1024;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(recon_fixed_to_float_kernel, dim3((unsigned)blocks), dim3(256), 0, s, fixed, plane, n);
+}
+// ... of cells that hold signed sums in two's complement (the voxel grids)
+__global__ __launch_bounds__(256) void recon_fixed_to_float_signed_kernel(const fix_t *fixed, float *plane, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+    plane[i] = (float)((double)(long long)fixed[i] * kFixInv);
+}
+void launch_recon_fixed_to_float_signed(const unsigned long long *fixed, float *plane, size_t n, hipStream_t s) {
+  if (n == 0) return;
+  size_t blocks = (n + 1023) / 1024;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(recon_fixed_to_float_signed_kernel, dim3((unsigned)blocks), dim3(256), 0, s, fixed, plane, n);
 }
 
 // ---------------------------------------------------------------------------------------------- contrast and gradient

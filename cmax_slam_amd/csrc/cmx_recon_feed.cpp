@@ -6,6 +6,7 @@
 //   warp*      the per-event export: where EVERY event handed in lands under the knots the reconstruction holds now
 //   pol_add*   add*'s vote loop into the ON / OFF planes of the signed polarity map
 //   view_add*  add*'s vote loop into the planes of the pinhole views
+//   voxel_add* add*'s vote loop into the bins of the voxel grids, by every event's own timestamp and polarity
 // Host arrays (SoA, or the host's own records) are packed slice by slice into two slots of pinned memory and uploaded on the copy
 // stream while the slice before runs; a range of an event store is read in place, its batch times formed on the device.
 #include "cmx_recon_state.hpp"
@@ -39,11 +40,13 @@ int validate_store_times(cmx_ctx *c, ReconState *r, const int64_t *d_t, int64_t 
   return CMX_OK;
 }
 
-static int slot_ensure(cmx_ctx *c, ReconSlot &s, size_t n_xy, size_t n_bt) {
+static int slot_ensure(cmx_ctx *c, ReconSlot &s, size_t n_xy, size_t n_bt, bool with_time) {
   int rc = ensure_pinned(c, s.h_xy, s.h_xy_cap, n_xy);
   if (!rc) rc = ensure(c, s.d_xy, s.xy_cap, n_xy);
   if (!rc) rc = ensure_pinned(c, s.h_bt, s.h_bt_cap, n_bt);
   if (!rc) rc = ensure(c, s.d_bt, s.bt_cap, n_bt);
+  if (!rc && with_time) rc = ensure_pinned(c, s.h_t, s.h_t_cap, n_xy);
+  if (!rc && with_time) rc = ensure(c, s.d_t, s.t_cap, n_xy);
   return rc;
 }
 
@@ -64,6 +67,7 @@ struct FedSlice : FeedSlice {
                                       // store's own from ev_first on, to be read in place
   const long long *d_bt = nullptr;    // its batch times
   long long lone_t = 0;               // every_event: the time of the call's lone trailing event
+  const long long *d_t = nullptr;     // with_time: its events' own timestamps, indexed as d_xy is
 };
 
 // The batch plan of the n events of src, then validation of EVERYTHING -- a call that fails adds nothing: every batch time (host:
@@ -72,9 +76,12 @@ struct FedSlice : FeedSlice {
 // uploaded while the kernels of slice k run.  Store sources: the batch times of the slice into slot[0]'s table; a single slice finds
 // there what the validation pass has just written.  From the first slice on only a runtime error (CMX_ERR_HIP) can end the call,
 // and slices queued before it have run.  Returns after the context's stream has run dry, the slots idle either way.
-// with_pol (pol_add*, host sources): the packed words carry the events' polarity in bit 31.
+// with_pol (pol_add*, signed voxel_add*; host sources): the packed words carry the events' polarity in bit 31.
+// with_time (voxel_add*, never with every_event): the slice also carries its events' own timestamps -- host sources: one int64 per
+// packed event, written by the packing pass beside the word into the same slot and uploaded with it; store: its own array in place.
 template <typename OnSlice>
-static int feed(cmx_ctx *c, ReconState *r, const EventSource &src, bool every_event, bool with_pol, BatchPlan *plan, OnSlice on_slice) {
+static int feed(cmx_ctx *c, ReconState *r, const EventSource &src, bool every_event, bool with_pol, bool with_time, BatchPlan *plan,
+                OnSlice on_slice) {
   const bool store = src.on_device();
   const int64_t n = src.n;
   const int B = r->B;
@@ -111,28 +118,32 @@ static int feed(cmx_ctx *c, ReconState *r, const EventSource &src, bool every_ev
         }
         f.d_xy = src.d_xy + f.ev_first;
         f.d_bt = s0.d_bt;
+        f.d_t = reinterpret_cast<const long long *>(src.d_t + f.ev_first);
       } else {
         const int64_t n_xy = every_event ? f.ev_n : f.n;
         if (s.busy) { HIP_TRY(c, hipEventSynchronize(s.done)); s.busy = false; }  // its previous slice has been consumed
-        rc = slot_ensure(c, s, (size_t)n_xy, (size_t)nbs);
+        rc = slot_ensure(c, s, (size_t)n_xy, (size_t)nbs, with_time);
         if (rc) return rc;
         uint32_t *xy = s.h_xy;
         long long *bt = s.h_bt;
+        int64_t *ts = with_time ? s.h_t : nullptr;
         src.view([&](const auto &v) {  // (validated above: neither pass finds anything)
           if (nbs > 0) batch_times(v, n, B, f.b_lo, f.b_hi, nullptr, [&](int64_t b, long long tb) { bt[b - f.b_lo] = tb; });
           const auto vs = v.from(f.ev_first);
           const int rate = every_event ? 1 : r->rate;
-          unsigned outside = with_pol ? pack_events<false, true>(vs, n - f.ev_first, nbs, B, rate, (unsigned)c->W, (unsigned)c->H, 0, xy)
-                                      : pack_events<false>(vs, n - f.ev_first, nbs, B, rate, (unsigned)c->W, (unsigned)c->H, 0, xy);
+          unsigned outside = with_pol ? pack_events<false, true>(vs, n - f.ev_first, nbs, B, rate, (unsigned)c->W, (unsigned)c->H, 0, xy, ts)
+                                      : pack_events<false>(vs, n - f.ev_first, nbs, B, rate, (unsigned)c->W, (unsigned)c->H, 0, xy, ts);
           if (f.lone) xy[f.ev_n - 1] = pack_word<false>(vs, f.ev_n - 1, (unsigned)c->W, (unsigned)c->H, 0, outside);
           return outside;
         });
         HIP_TRY(c, hipMemcpyAsync(s.d_xy, xy, (size_t)n_xy * sizeof(uint32_t), hipMemcpyHostToDevice, r->copy_stream));
         if (nbs > 0) HIP_TRY(c, hipMemcpyAsync(s.d_bt, bt, (size_t)nbs * sizeof(long long), hipMemcpyHostToDevice, r->copy_stream));
+        if (ts) HIP_TRY(c, hipMemcpyAsync(s.d_t, ts, (size_t)n_xy * sizeof(int64_t), hipMemcpyHostToDevice, r->copy_stream));
         HIP_TRY(c, hipEventRecord(s.up, r->copy_stream));
         HIP_TRY(c, hipStreamWaitEvent(c->stream, s.up, 0));
         f.d_xy = s.d_xy;
         f.d_bt = s.d_bt;
+        f.d_t = reinterpret_cast<const long long *>(s.d_t);
       }
       rc = on_slice(f);
       if (rc) return rc;
@@ -160,7 +171,7 @@ int recon_add_source(cmx_ctx *c, const EventSource &src, bool grad) {
   ReconGatherArgs ga = recon_gather_args(c, r);
   ReconArgs &a = ga.ev;
   BatchPlan p;
-  rc = feed(c, r, src, false, false, &p, [&](const FedSlice &s) {
+  rc = feed(c, r, src, false, false, false, &p, [&](const FedSlice &s) {
     a.xy = s.d_xy; a.stride = src.on_device() ? r->rate : 0;  // (the store's events in place: the sampling is an index map)
     a.batch_t = s.d_bt; a.nb = s.b_hi - s.b_lo;
     a.n = (int)s.n;
@@ -217,7 +228,7 @@ static int recon_pol_add_source(cmx_ctx *c, const EventSource &src) {
   a.fixed = r->d_pol_fixed;
   a.n_inside = r->d_pol_inside;
   BatchPlan p;
-  return feed(c, r, src, false, !src.on_device(), &p, [&](const FedSlice &s) {
+  return feed(c, r, src, false, !src.on_device(), false, &p, [&](const FedSlice &s) {
     a.xy = s.d_xy; a.stride = src.on_device() ? r->rate : 0;
     a.pol = src.on_device() ? src.d_pol + s.ev_first : nullptr;
     a.batch_t = s.d_bt; a.nb = s.b_hi - s.b_lo;
@@ -278,7 +289,7 @@ static int recon_view_add_source(cmx_ctx *c, const EventSource &src) {
   g.n_voted = r->d_vvoted;
   ReconArgs &a = g.ev;
   BatchPlan p;
-  return feed(c, r, src, false, false, &p, [&](const FedSlice &s) {
+  return feed(c, r, src, false, false, false, &p, [&](const FedSlice &s) {
     a.xy = s.d_xy; a.stride = src.on_device() ? r->rate : 0;
     a.batch_t = s.d_bt; a.nb = s.b_hi - s.b_lo;
     a.n = (int)s.n;
@@ -304,6 +315,73 @@ int cmx_backend_recon_view_add_aos(cmx_ctx *c, int64_t n, const void *events, co
 }
 int cmx_backend_recon_view_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
   return recon_view_add_entry(c, [&](EventSource *src) { return store_source(c, e, first, count, src); });
+}
+
+// ---- voxel_add*: add*'s vote pass with the bins of the voxel grids as its targets.  As view_add*: nothing of the
+// reconstruction but the knots is read, nothing but the grid planes and their counters is written.  Beside the packed word every
+// sampled event brings its own timestamp (feed: with_time); a signed set reads polarity as pol_add* does -- bit 31 of the word on
+// the host paths, the store's byte array -- an unsigned set reads none and packs none.
+static int recon_voxel_add_source(cmx_ctx *c, const EventSource &src) {
+  ReconState *r = c->recon;
+  int rc = feed_checks(c, src);
+  if (rc) return rc;
+  ReconVoxelArgs g{};
+  g.ev = recon_args(c, r);
+  g.ev.plane = nullptr; g.ev.fixed = nullptr; g.ev.n_inside = nullptr;
+  g.grids = r->d_grids; g.ranges = r->d_xranges;
+  g.n_grids = r->n_grids; g.Wv = r->Wx; g.Hv = r->Hx; g.n_bins = r->n_bins;
+  g.is_signed = r->vox_signed ? 1 : 0;
+  g.planes = r->d_xplanes;
+  g.fixed = r->d_xfixed;
+  g.n_voted = r->d_xvoted;
+  ReconArgs &a = g.ev;
+  BatchPlan p;
+  return feed(c, r, src, false, r->vox_signed && !src.on_device(), true, &p, [&](const FedSlice &s) {
+    a.xy = s.d_xy; a.stride = src.on_device() ? r->rate : 0;
+    a.pol = r->vox_signed && src.on_device() ? src.d_pol + s.ev_first : nullptr;
+    a.batch_t = s.d_bt; a.nb = s.b_hi - s.b_lo;
+    a.n = (int)s.n;
+    g.ev_t = s.d_t;
+    launch_recon_voxel_votes(g, c->stream);
+    return (int)CMX_OK;
+  });
+}
+template <typename MakeSource>
+static int recon_voxel_add_entry(cmx_ctx *c, MakeSource make) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (!c->recon->d_grids) return fail(c, CMX_ERR_STATE, "cmx_backend_recon_voxel_begin has not succeeded");
+  EventSource src;
+  rc = make(&src);
+  if (rc) return rc;
+  return recon_voxel_add_source(c, src);
+}
+int cmx_backend_recon_voxel_add(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, const uint8_t *pol) {
+  return recon_voxel_add_entry(c, [&](EventSource *src) {
+    if (c->recon->vox_signed && !pol) return fail(c, CMX_ERR_INVALID_ARG, "null polarity array for a signed voxel set");
+    *src = EventSource::arrays(n, x, y, t_ns);
+    src->soa.p = pol;
+    return (int)CMX_OK;
+  });
+}
+int cmx_backend_recon_voxel_add_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout, size_t off_polarity) {
+  return recon_voxel_add_entry(c, [&](EventSource *src) {
+    const int rc = make_aos(c, n, events, layout, src);
+    if (rc) return rc;
+    if (!c->recon->vox_signed) return (int)CMX_OK;  // (polarity is neither needed nor read)
+    if (off_polarity >= layout->stride) return fail(c, CMX_ERR_INVALID_ARG, "record layout: polarity outside the %zu-byte record", layout->stride);
+    src->aos.op = off_polarity;
+    return (int)CMX_OK;
+  });
+}
+int cmx_backend_recon_voxel_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
+  return recon_voxel_add_entry(c, [&](EventSource *src) {
+    const int rc = store_source(c, e, first, count, src);
+    if (rc) return rc;
+    if (c->recon->vox_signed && e->size > 0 && !e->has_pol)
+      return fail(c, CMX_ERR_STATE, "the voxel set is signed and the event store holds no polarity (cmx_events_push_pol)");
+    return (int)CMX_OK;
+  });
 }
 
 // ---- warp*: ALL events of a slice reach the kernel (the host paths pack at rate 1, the store is read in place), the true rate only
@@ -349,7 +427,7 @@ static int recon_warp_source(cmx_ctx *c, const EventSource &src, int format, voi
     return CMX_OK;
   };
   BatchPlan p;
-  rc = feed(c, r, src, true, false, &p, [&](const FedSlice &s) -> int {
+  rc = feed(c, r, src, true, false, false, &p, [&](const FedSlice &s) -> int {
     g.ev.xy = s.d_xy;
     g.ev.batch_t = s.d_bt; g.ev.nb = s.b_hi - s.b_lo;
     g.ev.n = (int)s.ev_n;

@@ -1,7 +1,9 @@
 // cmx_recon_state.hpp -- what the three sources of cmx_backend_recon_* share: the state a reconstruction keeps (cmx_ctx::recon) and
 // the helpers every one of them goes through.
-//   cmx_reconstruct.cpp  life cycle (begin, restart, extend, end), contrast / grad_get / eval_from, get / render, the view set
-//   cmx_recon_feed.cpp   one walk over the events handed in, in slices of whole batches: add*, grad_add*, warp*, pol_add*, view_add*
+//   cmx_reconstruct.cpp  life cycle (begin, restart, extend, end), contrast / grad_get / eval_from, get / render, the view set, the
+//                        voxel set
+//   cmx_recon_feed.cpp   one walk over the events handed in, in slices of whole batches: add*, grad_add*, warp*, pol_add*, view_add*,
+//                        voxel_add*
 //   cmx_recon_bound.cpp  events bound once and evaluated many times: bind / eval_bound, the frozen head, append / advance /
 //                        release, the hooks of cmx_backend_recon_solve
 // Kernels: cmx_recon.hip.
@@ -12,19 +14,23 @@
 // kept at or below 2^30, far from the wrap.
 constexpr int kMaxSliceEvents = 1 << 30;
 
-// Input staging of one slice.  The host paths hold packed events and batch times in pinned memory and on the device; the store
+// Input staging of one slice.  The host paths hold packed events and batch times (voxel_add*: and the packed events' own timestamps)
+// in pinned memory and on the device; the store
 // paths read the store's events in place and form the batch times on the device, so they use slot[0]'s device table alone.
 struct ReconSlot {
   uint32_t *h_xy = nullptr, *d_xy = nullptr;
   long long *h_bt = nullptr, *d_bt = nullptr;
-  size_t h_xy_cap = 0, xy_cap = 0, h_bt_cap = 0, bt_cap = 0;
+  int64_t *h_t = nullptr, *d_t = nullptr;  // the packed events' own timestamps, beside the words (voxel_add* alone)
+  size_t h_xy_cap = 0, xy_cap = 0, h_bt_cap = 0, bt_cap = 0, h_t_cap = 0, t_cap = 0;
   hipEvent_t up = nullptr, done = nullptr;  // upload complete (copy stream) / the slice's kernels complete (context stream)
   bool busy = false;
   void release() {
     if (h_xy) (void)hipHostFree(h_xy);
     if (h_bt) (void)hipHostFree(h_bt);
+    if (h_t) (void)hipHostFree(h_t);
     (void)hipFree(d_xy);
     (void)hipFree(d_bt);
+    (void)hipFree(d_t);
     if (up) (void)hipEventDestroy(up);
     if (done) (void)hipEventDestroy(done);
     *this = ReconSlot{};
@@ -196,7 +202,16 @@ struct ReconState {
   float *d_vplanes = nullptr;                  // [n_views][Hv * Wv] (default mode), or the fp32 view of d_vfixed made by view_get / view_render
   unsigned long long *d_vfixed = nullptr;      // deterministic mode: their 2^-30 fixed-point twins
   unsigned long long *d_vvoted = nullptr;      // [n_views] events that voted into each view
-  int64_t host_waits = 0;                // times a host thread has waited for the device in this reconstruction's calls
+  // ---- voxel grids (cmx_backend_recon_voxel_*): G grids of n_bins planes each, the reconstruction's own beside the
+  // view set: made by voxel_begin, cleared by restart and voxel_reset, freed by voxel_end, begin and end
+  int n_grids = 0, n_bins = 0, Wx = 0, Hx = 0; // n_grids == 0: no voxel set
+  bool vox_signed = false;
+  ReconVoxelDev *d_grids = nullptr;            // [n_grids]
+  ReconViewRange *d_xranges = nullptr;         // [n_grids]
+  float *d_xplanes = nullptr;                  // [n_grids][n_bins][Hx * Wx] (default mode), or the fp32 view of d_xfixed made by voxel_get
+  unsigned long long *d_xfixed = nullptr;      // deterministic mode: their 2^-30 fixed-point twins, two's complement
+  unsigned long long *d_xvoted = nullptr;      // [n_grids] events that voted into each grid
+  int64_t host_waits = 0;               // times a host thread has waited for the device in this reconstruction's calls
   // everything above that owns memory, a stream or an event (the streams idle: recon_release has waited for them)
   void release() {
     if (copy_stream) (void)hipStreamDestroy(copy_stream);
@@ -205,7 +220,7 @@ struct ReconState {
     for (ReconWarpSlot &s : wslot) s.release();
     void *dev[] = {d_knots, d_delta, d_plane, d_fixed, d_inside, d_err, d_cx, d_cy, d_tflags, d_tile_list, d_tile_count, d_partials,
                    d_cm, d_jt, d_gsum, d_voted, d_rows, d_row_win, d_app_xy, d_app_t, d_pol, d_pol_fixed, d_pol_inside,
-                   d_views, d_vranges, d_vplanes, d_vfixed, d_vvoted};
+                   d_views, d_vranges, d_vplanes, d_vfixed, d_vvoted, d_grids, d_xranges, d_xplanes, d_xfixed, d_xvoted};
     for (void *p : dev) (void)hipFree(p);
     bnd.release();
     frozen.release();
@@ -245,6 +260,8 @@ int recon_pol_ensure(cmx_ctx *c, ReconState *r);
 int recon_pol_clear(cmx_ctx *c, ReconState *r);
 // the view planes and their counters zeroed, where a view set exists (queued)
 int recon_view_clear(cmx_ctx *c, ReconState *r);
+// the voxel planes and their counters zeroed, where a voxel set exists (queued)
+int recon_voxel_clear(cmx_ctx *c, ReconState *r);
 
 // ---- cmx_recon_feed.cpp
 // one slice of the gradient pass, as g.ev describes it; deterministic mode: the workgroups' rows, then their sum in workgroup order

@@ -7,7 +7,8 @@
 // window path -- per batch one 3-vector through the 3 x 3N spline Jacobian, so nothing grows with the knot count
 // but the 2 x 3K sums -- and the plane's way out (get, render); the same for the ON / OFF planes of the signed polarity map
 // (pol_get, pol_render, pol_reset) and for the planes of a set of pinhole views (view_begin, view_get, view_render,
-// view_reset, view_end).  Events bound once and evaluated many times, the frozen head, the
+// view_reset, view_end) and for the bins of a set of voxel grids (voxel_begin, voxel_get, voxel_get_device, voxel_reset,
+// voxel_end).  Events bound once and evaluated many times, the frozen head, the
 // growing binding and the native solve's hooks: cmx_recon_bound.cpp.
 // Kernels: cmx_recon.hip.
 #include "cmx_recon_state.hpp"
@@ -190,6 +191,8 @@ int cmx_backend_recon_restart(cmx_ctx *c, const double *knots_xyzw) {
   rc = recon_pol_clear(c, c->recon);  // (... nor what the polarity planes hold)
   if (rc) return rc;
   rc = recon_view_clear(c, c->recon);  // (... nor the view planes; the views themselves stay)
+  if (rc) return rc;
+  rc = recon_voxel_clear(c, c->recon);  // (... nor the voxel planes; the grids themselves stay)
   if (rc) return rc;
   return recon_start_over(c, c->recon, knots_xyzw);
 }
@@ -551,6 +554,25 @@ static int recon_view_enter(cmx_ctx *c) {
   return CMX_OK;
 }
 
+// the argument rules of ONE view (or voxel grid) and its entry as the kernels read it: R(quat)^T from the normalised quaternion
+static int recon_view_entry(cmx_ctx *c, const cmx_recon_view &v, int i, ReconViewDev *out) {
+  const double *q = v.quat_xyzw;
+  const double nrm = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  if (!std::isfinite(nrm) || !(nrm > 0.0)) return fail(c, CMX_ERR_INVALID_ARG, "view %d: the quaternion has no direction", i);
+  if (!std::isfinite(v.fx) || !std::isfinite(v.fy) || !(v.fx > 0.0) || !(v.fy > 0.0))
+    return fail(c, CMX_ERR_INVALID_ARG, "view %d: fx, fy must be finite and > 0", i);
+  if (!std::isfinite(v.cx) || !std::isfinite(v.cy)) return fail(c, CMX_ERR_INVALID_ARG, "view %d: cx, cy must be finite", i);
+  if (v.t_lo_ns >= v.t_hi_ns) return fail(c, CMX_ERR_INVALID_ARG, "view %d: empty time range", i);
+  const Mat3 R = q_to_R(Quat{q[0] / nrm, q[1] / nrm, q[2] / nrm, q[3] / nrm});
+  ReconViewDev &d = *out;
+  for (int a = 0; a < 3; a++)
+    for (int b = 0; b < 3; b++) d.Rt[3 * a + b] = R.m[3 * b + a];
+  d.fx = v.fx; d.fy = v.fy; d.cx = v.cx; d.cy = v.cy;
+  d.t_lo = (long long)v.t_lo_ns; d.t_hi = (long long)v.t_hi_ns;
+  d.index = i;
+  return CMX_OK;
+}
+
 int cmx_backend_recon_view_begin(cmx_ctx *c, int Wv, int Hv, int n_views, const cmx_recon_view *views) {
   int rc = recon_enter(c, true);
   if (rc) return rc;
@@ -561,22 +583,9 @@ int cmx_backend_recon_view_begin(cmx_ctx *c, int Wv, int Hv, int n_views, const 
   std::vector<ReconViewDev> dev((size_t)n_views);
   std::vector<ReconViewRange> ranges((size_t)n_views);
   for (int i = 0; i < n_views; i++) {
-    const cmx_recon_view &v = views[i];
-    const double *q = v.quat_xyzw;
-    const double nrm = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    if (!std::isfinite(nrm) || !(nrm > 0.0)) return fail(c, CMX_ERR_INVALID_ARG, "view %d: the quaternion has no direction", i);
-    if (!std::isfinite(v.fx) || !std::isfinite(v.fy) || !(v.fx > 0.0) || !(v.fy > 0.0))
-      return fail(c, CMX_ERR_INVALID_ARG, "view %d: fx, fy must be finite and > 0", i);
-    if (!std::isfinite(v.cx) || !std::isfinite(v.cy)) return fail(c, CMX_ERR_INVALID_ARG, "view %d: cx, cy must be finite", i);
-    if (v.t_lo_ns >= v.t_hi_ns) return fail(c, CMX_ERR_INVALID_ARG, "view %d: empty time range", i);
-    const Mat3 R = q_to_R(Quat{q[0] / nrm, q[1] / nrm, q[2] / nrm, q[3] / nrm});
-    ReconViewDev &d = dev[(size_t)i];
-    for (int a = 0; a < 3; a++)
-      for (int b = 0; b < 3; b++) d.Rt[3 * a + b] = R.m[3 * b + a];
-    d.fx = v.fx; d.fy = v.fy; d.cx = v.cx; d.cy = v.cy;
-    d.t_lo = (long long)v.t_lo_ns; d.t_hi = (long long)v.t_hi_ns;
-    d.index = i;
-    ranges[(size_t)i] = ReconViewRange{d.t_lo, d.t_hi};
+    rc = recon_view_entry(c, views[i], i, &dev[(size_t)i]);
+    if (rc) return rc;
+    ranges[(size_t)i] = ReconViewRange{dev[(size_t)i].t_lo, dev[(size_t)i].t_hi};
   }
   ReconState *r = c->recon;
   recon_view_free(c, r);  // a second begin starts over
@@ -661,4 +670,127 @@ int cmx_backend_recon_view_render(cmx_ctx *c, int view, double gamma, unsigned c
   launch_display_range(plane, nullptr, np, c->d_disp_range, c->stream);
   launch_display_map(plane, np, (float)gamma, false, c->d_disp_range, c->d_disp, c->stream);
   return display_deliver(c, np, out);
+}
+
+// ---- voxel grids: the set of grids cmx_backend_recon_voxel_add* (cmx_recon_feed.cpp) votes into, and its planes' way out.  A grid is
+// a view with a bin axis over its time range; the planes are grid-major, n_bins to a grid.
+static void recon_voxel_free(cmx_ctx *c, ReconState *r) {
+  if (!r->d_grids) return;
+  (void)hipStreamSynchronize(c->stream);  // (a vote pass queued earlier may still write the planes)
+  void *dev[] = {r->d_grids, r->d_xranges, r->d_xplanes, r->d_xfixed, r->d_xvoted};
+  for (void *p : dev) (void)hipFree(p);
+  r->d_grids = nullptr; r->d_xranges = nullptr; r->d_xplanes = nullptr; r->d_xfixed = nullptr; r->d_xvoted = nullptr;
+  r->n_grids = r->n_bins = r->Wx = r->Hx = 0;
+  r->vox_signed = false;
+}
+
+int recon_voxel_clear(cmx_ctx *c, ReconState *r) {
+  if (!r->d_grids) return CMX_OK;
+  const size_t np = (size_t)r->n_grids * r->n_bins * r->Wx * r->Hx;
+  HIP_TRY(c, hipMemsetAsync(r->d_xplanes, 0, np * sizeof(float), c->stream));
+  if (r->d_xfixed) HIP_TRY(c, hipMemsetAsync(r->d_xfixed, 0, np * sizeof(unsigned long long), c->stream));
+  HIP_TRY(c, hipMemsetAsync(r->d_xvoted, 0, (size_t)r->n_grids * sizeof(unsigned long long), c->stream));
+  return CMX_OK;
+}
+
+static int recon_voxel_enter(cmx_ctx *c) {
+  const int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (!c->recon->d_grids) return fail(c, CMX_ERR_STATE, "cmx_backend_recon_voxel_begin has not succeeded");
+  return CMX_OK;
+}
+
+int cmx_backend_recon_voxel_begin(cmx_ctx *c, int Wv, int Hv, int n_bins, int signed_polarity, int n_grids, const cmx_recon_view *grids) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (Wv < 4 || Wv > 8192 || Hv < 4 || Hv > 8192) return fail(c, CMX_ERR_INVALID_ARG, "grid size %d x %d outside [4, 8192]", Wv, Hv);
+  if (n_bins < 1 || n_bins > 64) return fail(c, CMX_ERR_INVALID_ARG, "n_bins=%d outside [1, 64]", n_bins);
+  if (n_grids < 1 || (long long)n_grids * n_bins > 4096)
+    return fail(c, CMX_ERR_INVALID_ARG, "%d grids of %d bins: n_grids * n_bins outside [1, 4096]", n_grids, n_bins);
+  if ((long long)n_grids * n_bins * Wv * Hv > (1LL << 28))
+    return fail(c, CMX_ERR_INVALID_ARG, "%d grids of %d bins of %d x %d: more than 2^28 cells", n_grids, n_bins, Wv, Hv);
+  if (!grids) return fail(c, CMX_ERR_INVALID_ARG, "null grid array");
+  std::vector<ReconVoxelDev> dev((size_t)n_grids);
+  std::vector<ReconViewRange> ranges((size_t)n_grids);
+  for (int i = 0; i < n_grids; i++) {
+    ReconVoxelDev &d = dev[(size_t)i];
+    rc = recon_view_entry(c, grids[i], i, &d.v);
+    if (rc) return rc;
+    // t_lo < t_hi: their difference as an unsigned number is exact, whatever the two are -- no signed overflow.  The bin axis needs
+    // a finite span: beyond 2^53 ns the fp64 image of (t - t_lo) is no longer exact, so "all time" is refused
+    const uint64_t span = (uint64_t)grids[i].t_hi_ns - (uint64_t)grids[i].t_lo_ns;
+    if (span > (1ull << 53)) return fail(c, CMX_ERR_INVALID_ARG, "grid %d: time range longer than 2^53 ns (the bin axis needs a finite span)", i);
+    d.scale = (double)(n_bins - 1) / (double)span;
+    ranges[(size_t)i] = ReconViewRange{d.v.t_lo, d.v.t_hi};
+  }
+  ReconState *r = c->recon;
+  recon_voxel_free(c, r);  // a second begin starts over
+  const size_t np = (size_t)n_grids * n_bins * Wv * Hv;
+  ReconVoxelDev *d_grids = nullptr;
+  ReconViewRange *d_ranges = nullptr;
+  float *planes = nullptr;
+  unsigned long long *fixed = nullptr, *voted = nullptr;
+  hipError_t e = hipMalloc((void **)&d_grids, dev.size() * sizeof(ReconVoxelDev));
+  if (e == hipSuccess) e = hipMalloc((void **)&d_ranges, ranges.size() * sizeof(ReconViewRange));
+  if (e == hipSuccess) e = hipMalloc((void **)&planes, np * sizeof(float));
+  if (e == hipSuccess && r->deterministic) e = hipMalloc((void **)&fixed, np * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMalloc((void **)&voted, (size_t)n_grids * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMemcpy(d_grids, dev.data(), dev.size() * sizeof(ReconVoxelDev), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_ranges, ranges.data(), ranges.size() * sizeof(ReconViewRange), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {  // (all of it or none: d_grids says whether a voxel set exists)
+    (void)hipFree(d_grids); (void)hipFree(d_ranges); (void)hipFree(planes); (void)hipFree(fixed); (void)hipFree(voted);
+    return fail(c, CMX_ERR_HIP, "allocating %d grids of %d bins of %d x %d: %s", n_grids, n_bins, Wv, Hv, hipGetErrorString(e));
+  }
+  r->d_grids = d_grids; r->d_xranges = d_ranges; r->d_xplanes = planes; r->d_xfixed = fixed; r->d_xvoted = voted;
+  r->n_grids = n_grids; r->n_bins = n_bins; r->Wx = Wv; r->Hx = Hv;
+  r->vox_signed = signed_polarity != 0;
+  rc = recon_voxel_clear(c, r);
+  if (rc) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return CMX_OK;
+}
+
+int cmx_backend_recon_voxel_reset(cmx_ctx *c) {
+  int rc = recon_voxel_enter(c);
+  if (rc) return rc;
+  rc = recon_voxel_clear(c, c->recon);
+  if (rc) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return CMX_OK;
+}
+
+int cmx_backend_recon_voxel_end(cmx_ctx *c) {
+  const int rc = recon_enter(c, true);
+  if (rc) return rc;
+  recon_voxel_free(c, c->recon);  // (no voxel set: nothing to free, not an error)
+  return CMX_OK;
+}
+
+// grids [first, first + count) as fp32 on the device, wherever `out` is (host: get; the context's device: get_device), and their
+// counters; in deterministic mode the current fixed-point sums, read as signed and converted first (they stay: votes may follow)
+static int recon_voxel_deliver(cmx_ctx *c, int first_grid, int count, float *out, hipMemcpyKind kind, int64_t *n_voted) {
+  int rc = recon_voxel_enter(c);
+  if (rc) return rc;
+  ReconState *r = c->recon;
+  if (first_grid < 0 || count < 0 || first_grid > r->n_grids || count > r->n_grids - first_grid)
+    return fail(c, CMX_ERR_INVALID_ARG, "grids [%d, %d + %d) outside the %d of the set", first_grid, first_grid, count, r->n_grids);
+  if (count == 0) return CMX_OK;
+  const size_t ng = (size_t)r->n_bins * r->Wx * r->Hx, at = (size_t)first_grid * ng, n = (size_t)count * ng;
+  if (out) {
+    if (r->d_xfixed) launch_recon_fixed_to_float_signed(r->d_xfixed + at, r->d_xplanes + at, n, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out, r->d_xplanes + at, n * sizeof(float), kind, c->stream));
+  }
+  if (n_voted) HIP_TRY(c, hipMemcpyAsync(n_voted, r->d_xvoted + first_grid, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return CMX_OK;
+}
+int cmx_backend_recon_voxel_get(cmx_ctx *c, int first_grid, int count, float *out, int64_t *n_voted) {
+  return recon_voxel_deliver(c, first_grid, count, out, hipMemcpyDeviceToHost, n_voted);
+}
+int cmx_backend_recon_voxel_get_device(cmx_ctx *c, int first_grid, int count, float *d_out) {
+  const int rc = recon_voxel_enter(c);
+  if (rc) return rc;
+  if (count > 0 && !d_out) return fail(c, CMX_ERR_INVALID_ARG, "null device output");
+  return recon_voxel_deliver(c, first_grid, count, d_out, hipMemcpyDeviceToDevice, nullptr);
 }

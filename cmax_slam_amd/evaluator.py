@@ -649,6 +649,7 @@ class BackendEvaluator(_Evaluator):
         k = _c(knots_xyzw, np.float64).reshape(-1, 4)
         self._recon_K = k.shape[0]
         self._view_shape = None  # (begin frees a view set)
+        self._voxel_shape = None  # (... and a voxel set)
         self._ck(self._L.cmx_backend_recon_begin(self._ctx, int(order), k.shape[0], _dp(k), int(start_ns), int(dt_ns),
                                                  int(event_batch_size), int(event_sample_rate)))
 
@@ -809,6 +810,71 @@ class BackendEvaluator(_Evaluator):
     def reconstruct_view_end(self):
         self._ck(self._L.cmx_backend_recon_view_end(self._ctx))
         self._view_shape = None
+
+    # --- voxel grids: the discretised, polarity-signed event volume of the same vote loop (cmx_backend_recon_voxel_*)
+    _voxel_shape = None  # (n_grids, n_bins, Hv, Wv) of the last reconstruct_voxel_begin
+    _voxel_signed = True
+
+    def reconstruct_voxel_begin(self, grids, Wv, Hv, n_bins, signed=True):
+        """Attach voxel grids to the open reconstruction and zero their (n_bins, Hv, Wv) volumes.  grids: _lib.ReconView structures
+        or tuples (quat_xyzw, fx, fy, cx, cy, t_lo_ns, t_hi_ns) with a finite time range -- see trajectory.voxel_grids.  signed:
+        OFF events vote -1; otherwise every event votes +1 and polarity is never read."""
+        gs = [g if isinstance(g, _lib.ReconView) else _lib.recon_view(*g) for g in grids]
+        arr = (_lib.ReconView * max(len(gs), 1))(*gs)
+        self._voxel_shape = None
+        self._ck(self._L.cmx_backend_recon_voxel_begin(self._ctx, int(Wv), int(Hv), int(n_bins), int(bool(signed)), len(gs), arr))
+        self._voxel_shape = (len(gs), int(n_bins), int(Hv), int(Wv))
+        self._voxel_signed = bool(signed)
+
+    def reconstruct_voxel_add(self, x, y, t_ns, polarity=None):
+        """reconstruct_add's vote loop over exactly these events: every sampled event is warped once into the world frame and
+        voted, by its OWN timestamp, into the two neighbouring bins of every grid whose range holds it.  polarity (one value per
+        event, nonzero / positive = ON) is needed for a signed set and ignored by an unsigned one."""
+        x, y, t = _c(x, np.uint16), _c(y, np.uint16), _c(t_ns, np.int64)
+        p = _pol_bytes(polarity) if polarity is not None and self._voxel_signed else None
+        if not (len(x) == len(y) == len(t)) or (p is not None and len(p) != len(x)):
+            raise ValueError("x, y, t_ns, polarity must have equal length")
+        self._ck(self._L.cmx_backend_recon_voxel_add(self._ctx, len(x), x.ctypes.data_as(c_u16p), y.ctypes.data_as(c_u16p),
+                                                     t.ctypes.data_as(c_i64p), p.ctypes.data_as(_lib.c_u8p) if p is not None else None))
+
+    def reconstruct_voxel_add_aos(self, events, polarity_field="polarity"):
+        """The same from a structured array of records with fields x, y, sec, nsec and a one-byte polarity field."""
+        ev = np.ascontiguousarray(events)
+        lay = _lib.aos_layout_of(ev)
+        off = _pol_offset(ev, polarity_field) if self._voxel_signed else 0
+        self._ck(self._L.cmx_backend_recon_voxel_add_aos(self._ctx, len(ev), ev.ctypes.data_as(C.c_void_p), C.byref(lay), off))
+
+    def reconstruct_voxel_add_from(self, store, first, count):
+        """The same over events_[first, first+count) of an EventStore (with polarity, EventStore.push(..., polarity=), for a
+        signed set)."""
+        self._ck(self._L.cmx_backend_recon_voxel_add_from(self._ctx, store._h, int(first), int(count)))
+
+    def reconstruct_voxel_get(self, first=0, count=None, with_counts=False, out=None):
+        """(count, n_bins, Hv, Wv) fp32 volumes of grids [first, first+count) [, int64 events that voted into each].  out: an object
+        with data_ptr() -- a contiguous float32 torch tensor of that many elements on the context's device: the volumes are written
+        straight into it, nothing crosses the host, and out is returned in the array's place.  The call runs on the context's stream
+        and returns when out is complete; work of the caller's that still writes the tensor on another stream must be finished."""
+        n, nb, Hv, Wv = self._voxel_shape or (0, 0, 0, 0)
+        count = n - int(first) if count is None else int(count)
+        shape = (max(count, 0), nb, Hv, Wv)
+        cnt = np.zeros(shape[0], np.int64)
+        if out is not None:
+            self._ck(self._L.cmx_backend_recon_voxel_get_device(self._ctx, int(first), count, out.data_ptr()))
+            if with_counts:
+                self._ck(self._L.cmx_backend_recon_voxel_get(self._ctx, int(first), count, None, cnt.ctypes.data_as(c_i64p)))
+            return (out, cnt) if with_counts else out
+        vol = np.empty(shape, np.float32)
+        self._ck(self._L.cmx_backend_recon_voxel_get(self._ctx, int(first), count, vol.ctypes.data_as(c_fp),
+                                                     cnt.ctypes.data_as(c_i64p) if with_counts else None))
+        return (vol, cnt) if with_counts else vol
+
+    def reconstruct_voxel_reset(self):
+        """Clear the voxel volumes and their counters (after the knots have moved); the grids stay."""
+        self._ck(self._L.cmx_backend_recon_voxel_reset(self._ctx))
+
+    def reconstruct_voxel_end(self):
+        self._ck(self._L.cmx_backend_recon_voxel_end(self._ctx))
+        self._voxel_shape = None
 
     def reconstruct_get(self, with_counts=False):
         """The (Hp, Wp) fp32 plane [, events the sampling selected so far, events that voted so far]."""

@@ -146,6 +146,19 @@ def crop_view(quat_xyzw, fov_deg, Wv, Hv, t_range_ns=ALL_TIME_NS):
     return _lib.recon_view(quat_xyzw, f, f, 0.5 * (Wv - 1), 0.5 * (Hv - 1), t_range_ns[0], t_range_ns[1])
 
 
+def voxel_grids(order, knots, start_ns, dt_ns, period_ns, intrinsics, exposure_ns=None, t_beg_ns=None, t_end_ns=None):
+    """The grid list of BackendEvaluator.reconstruct_voxel_begin: frame_views' list, one grid per slice of period_ns, oriented by the
+    spline's pose at the slice centre.  A grid's bins divide its time range, so the range must be finite: one longer than 2^53 ns
+    (ALL_TIME_NS, say, passed as t_beg_ns / t_end_ns or as the exposure) is refused here as the library refuses it."""
+    n_knots = len(np.asarray(knots, np.float64).reshape(-1, 4))
+    t_beg = int(start_ns) if t_beg_ns is None else int(t_beg_ns)
+    t_end = int(start_ns) + (n_knots - int(order) + 1) * int(dt_ns) if t_end_ns is None else int(t_end_ns)
+    for span in (t_end - t_beg, int(period_ns) if exposure_ns is None else int(exposure_ns)):
+        if span > 2 ** 53:
+            raise ValueError("a voxel grid needs a finite time range: at most 2^53 ns")
+    return frame_views(order, knots, start_ns, dt_ns, period_ns, intrinsics, exposure_ns, t_beg_ns, t_end_ns)
+
+
 def _sec(t_ns):
     """ros::Time::toSec()"""
     return float(t_ns // 1000000000) + 1e-9 * float(t_ns % 1000000000)

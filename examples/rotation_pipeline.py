@@ -184,7 +184,7 @@ def reconstruct_panorama(be, traj, x, y, t, prm, store=None, knots=None):
 
 def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefix=None, reconstruct=False, refine_global=False,
                  refine_bound=False, refine_native=False, freeze_head=None, refine_online=None, online_free=8, export_warped=None,
-                 polarity_map=None, frames=None, frame_ms=20.0, crop=None):
+                 polarity_map=None, frames=None, frame_ms=20.0, crop=None, voxels=None, voxel_ms=20.0, voxel_bins=5):
     """stream: synth.EventStream (or anything with x, y, t_ns, W, H, fx, fy, cx, cy, lut).  Returns a dict.
     display_prefix: write the final panorama with the last pose's FOV and the last packet's local-IWE pair there.
     reconstruct: after the last window, re-warp all events along the whole refined trajectory (res["recon"]; with
@@ -207,8 +207,13 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
     frame_ms milliseconds with the sensor's size and intrinsics and the spline's pose at the slice centre
     (trajectory.frame_views, BackendEvaluator.reconstruct_view_*) -- written as PREFIX_0000.pgm ...; res["frames"] = (planes, counts).
     crop = PREFIX (implies reconstruct): one zoomed view of all events around the last pose, a quarter of the sensor's field of
-    view on CROP_SIZE pixels (trajectory.crop_view), written as PREFIX.pgm; res["crop"] = (plane, count)."""
-    reconstruct = reconstruct or export_warped is not None or polarity_map is not None or frames is not None or crop is not None
+    view on CROP_SIZE pixels (trajectory.crop_view), written as PREFIX.pgm; res["crop"] = (plane, count).
+    voxels = PATH (implies reconstruct): the motion-compensated, polarity-signed voxel grids of the final trajectory -- one grid of
+    voxel_bins time bins per voxel_ms milliseconds, with the sensor's size and intrinsics and the spline's pose at the slice centre
+    (trajectory.voxel_grids, BackendEvaluator.reconstruct_voxel_*) -- written as one .npy of shape (G, B, H, W), the input format of
+    event-based networks; res["voxels"] = (volumes, counts).  Polarities as for polarity_map."""
+    reconstruct = (reconstruct or export_warped is not None or polarity_map is not None or frames is not None or crop is not None
+                   or voxels is not None)
     prm = prm or Params()
     x, y, t = stream.x, stream.y, stream.t_ns
     n_total = len(t)
@@ -220,13 +225,13 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
         fe.set_deterministic(True)
         be.set_deterministic(True)
     pol = None
-    if polarity_map is not None:
+    if polarity_map is not None or voxels is not None:
         pol = getattr(stream, "polarity", None)
         pol = np.random.default_rng(POLARITY_SEED).integers(0, 2, n_total).astype(np.uint8) if pol is None else np.asarray(pol)
     store = None
     if use_event_store:
         store = evaluator.EventStore(stream.W, stream.H, n_total)
-        store.push(x, y, t, polarity=pol)  # (with polarity: a byte array beside the events, which nothing but reconstruct_pol_add_from reads)
+        store.push(x, y, t, polarity=pol)  # (with polarity: a byte array beside the events, which nothing but reconstruct_pol_add_from and reconstruct_voxel_add_from read)
 
     # ------------------------------------------------------------------ front end: packets (pushEvent)
     dt_av = _dur_ns(prm.dt_ang_vel)
@@ -469,6 +474,25 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
             if log:
                 log("crop: %d events within %.1f degrees around the last pose on %d x %d -> %s.pgm" %
                     (int(counts[0]), fov, CROP_SIZE[0], CROP_SIZE[1], crop))
+        if voxels is not None:  # the signed event volume a network reads: grids of voxel_ms x voxel_bins seen by the sensor itself
+            t0 = time.perf_counter()
+            grids = trajectory.voxel_grids(traj.order, knots_rec, traj.t_beg_ns, traj.dt_ns, int(round(voxel_ms * 1e6)),
+                                           (stream.fx, stream.fy, stream.cx, stream.cy), t_beg_ns=int(t[i_rec]),
+                                           t_end_ns=int(t[i_rec + n_rec - 1]) + 1)
+            be.reconstruct_voxel_begin(grids, stream.W, stream.H, voxel_bins, signed=True)
+            if store is not None:
+                be.reconstruct_voxel_add_from(store, i_rec, n_rec)
+            else:
+                be.reconstruct_voxel_add(x[i_rec:i_rec + n_rec], y[i_rec:i_rec + n_rec], t[i_rec:i_rec + n_rec], pol[i_rec:i_rec + n_rec])
+            volumes, counts = be.reconstruct_voxel_get(with_counts=True)
+            be.reconstruct_voxel_end()
+            res["voxels"] = (volumes, counts)
+            path = voxels if voxels.endswith(".npy") else voxels + ".npy"
+            np.save(path, volumes)
+            if log:
+                log("voxels: %d grids of %.3g ms x %d bins, %d to %d events each, in %.2f ms -> %s %s" %
+                    (len(grids), voxel_ms, voxel_bins, int(counts.min()), int(counts.max()), (time.perf_counter() - t0) * 1e3, path,
+                     volumes.shape))
         be.reconstruct_end()
     return res
 
@@ -541,6 +565,11 @@ def main():
     ap.add_argument("--crop", metavar="PREFIX", default=None,
                     help="after the reconstruction, write one zoomed view of all events around the last pose as PREFIX.pgm "
                          "(implies --reconstruct)")
+    ap.add_argument("--voxels", metavar="PATH", default=None,
+                    help="after the reconstruction, write the motion-compensated, polarity-signed voxel grids of the final trajectory "
+                         "as ONE .npy of shape (G, B, H, W) (implies --reconstruct; polarities as for --polarity-map)")
+    ap.add_argument("--voxel-ms", type=float, metavar="MS", default=20.0, help="with --voxels: the time range of a grid in milliseconds")
+    ap.add_argument("--voxel-bins", type=int, metavar="B", default=5, help="with --voxels: time bins per grid, 1 to 64")
     ap.add_argument("--refine-global", action="store_true",
                     help="after the last window, one bundle adjustment over the whole trajectory (--reconstruct then uses its result)")
     ap.add_argument("--refine-bound", action="store_true",
@@ -560,6 +589,8 @@ def main():
         ap.error("--refine-online takes a stride > 0 and --online-free at least 1")
     if not a.frame_ms > 0:
         ap.error("--frame-ms must be > 0")
+    if not a.voxel_ms > 0 or not 1 <= a.voxel_bins <= 64:
+        ap.error("--voxel-ms must be > 0 and --voxel-bins in [1, 64]")
     stream = synth.event_stream(a.rate, a.seconds, 240, 180, 200.0, 200.0, 119.5, 89.5, omega_mean=(0.2, 1.8, 0.3),
                                 omega_amp=(1.0, 0.8, 1.0))
     prm = Params()
@@ -569,7 +600,8 @@ def main():
     res = run_pipeline(stream, prm, use_event_store=not a.host_events, log=print, display_prefix=a.display, reconstruct=a.reconstruct,
                        refine_global=a.refine_global or a.refine_native, refine_bound=a.refine_bound, refine_native=a.refine_native,
                        freeze_head=a.freeze_head, refine_online=a.refine_online, online_free=a.online_free, export_warped=a.export_warped,
-                       polarity_map=a.polarity_map, frames=a.frames, frame_ms=a.frame_ms, crop=a.crop)
+                       polarity_map=a.polarity_map, frames=a.frames, frame_ms=a.frame_ms, crop=a.crop, voxels=a.voxels, voxel_ms=a.voxel_ms,
+                       voxel_bins=a.voxel_bins)
     wall = time.perf_counter() - t0
     m = evaluate_against_truth(stream, res)
     print("%.2f s of events (%d) processed in %.2f s wall" % (a.seconds, len(stream.x), wall))

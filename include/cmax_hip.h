@@ -477,6 +477,63 @@ int cmx_backend_recon_view_get(cmx_ctx *ctx, int first_view, int count, float *p
 int cmx_backend_recon_view_render(cmx_ctx *ctx, int view, double gamma, unsigned char *out /* Hv*Wv mono8 */);
 int cmx_backend_recon_view_reset(cmx_ctx *ctx);
 int cmx_backend_recon_view_end(cmx_ctx *ctx);
+/* Voxel grids: the discretised event volume event-based networks read, motion-compensated.  A set of G grids is attached to an open
+ * reconstruction; a grid is a cmx_recon_view -- orientation, intrinsics, [t_lo_ns, t_hi_ns) -- with n_bins time bins over its range
+ * (trajectory.frame_views' output can be passed as it is).  One vote pass warps every sampled event ONCE into the world frame and
+ * spreads it over four pixels bilinearly and over its two neighbouring bins with triangular weights, signed by polarity.
+ *     recon_voxel_begin(grids)   recon_voxel_add*(events, polarity) ...   recon_voxel_get / _get_device (any number of times)
+ *     [recon_voxel_reset]   recon_voxel_end
+ *   voxel_begin  needs an open reconstruction.  Copies the grids to the device as view_begin copies views, allocates
+ *              n_grids * n_bins fp32 planes of Wv x Hv (and their 2^-30 fixed-point twins when CMX_OPT_DETERMINISTIC was 1 at
+ *              recon_begin) and zeroes them and one vote counter per grid.  A second voxel_begin starts over.
+ *              CMX_ERR_INVALID_ARG: every rule of view_begin (Wv or Hv outside [4, 8192]; a quaternion that is zero or not finite;
+ *              fx or fy not finite or <= 0; cx or cy not finite; t_lo_ns >= t_hi_ns); n_bins outside [1, 64]; n_grids * n_bins
+ *              outside [1, 4096]; n_grids * n_bins * Wv * Hv > 2^28; t_hi_ns - t_lo_ns above 2^53 (the difference is formed without
+ *              signed overflow).  The bin axis needs a FINITE span -- beyond 2^53 ns the fp64 image of t - t_lo is not exact -- so a
+ *              range that stands for all time (trajectory.ALL_TIME_NS, crop_view's default) is refused here although view_begin
+ *              takes it.  Ranges may overlap, nest or leave gaps.
+ *   voxel_add* ONE call = the vote loop of add* over exactly the events handed in -- the same batches, batch times and batch poses,
+ *              sampling restarting at every batch start, the lone trailing event skipped, the same validation and status codes,
+ *              complete before the first vote: a call that fails validation adds nothing.  Per sampled event i, in fp64 unless
+ *              stated otherwise:
+ *                  ray_w = R_batch * bearing                      (the vote kernels' own function, the pose at the BATCH time)
+ *                  for every grid with t_lo_ns <= t_i < t_hi_ns   (t_i the event's OWN timestamp, compared as integers):
+ *                      projection, vote test, cell (xx, yy) and fp32 dx, dy exactly as in view_add* above
+ *                      n_bins >= 2:  scale = (double)(n_bins - 1) / (double)(t_hi_ns - t_lo_ns)   (formed once, on the host)
+ *                                    tau = (double)(t_i - t_lo_ns) * scale,   b0 = min((int)tau, n_bins - 2),   f = (float)(tau - b0)
+ *                                    bin b0 gets wt = 1.f - f, bin b0 + 1 gets wt = f
+ *                      n_bins == 1:  the one bin gets wt = 1.f
+ *                      each of the four cells of such a bin receives  s * (wt * wb)  in fp32, wb the fp32 bilinear product of add*
+ *                      ((1-dx)(1-dy), dx(1-dy), (1-dx)dy, dx dy);  s = +1 always when signed_polarity == 0 (polarity is then
+ *                      neither needed nor read), otherwise +1 for polarity != 0 and -1 for any other value
+ *                      one count for the grid: an event counts once, not once per bin
+ *              Deterministic mode: each magnitude is converted, to_fix(wt * wb), negated as an integer for s = -1 and added as a
+ *              64-bit integer into the fixed-point twin; the cells are two's complement and are read as SIGNED.  A bin whose wt is
+ *              zero may be skipped: that changes no sum.
+ *              Polarity: pol[i] (one byte per event; NULL is allowed only when signed_polarity == 0), the byte at off_polarity of
+ *              record i (not looked at for an unsigned set), or the store's own.
+ *   voxel_get  out[g][b][yy][xx] fp32, contiguous: count * n_bins planes of Wv x Hv for grids [first_grid, first_grid + count), or
+ *              NULL; n_voted = count counters or NULL.  CMX_ERR_INVALID_ARG when the range leaves the set.  Accumulation may continue.
+ *   voxel_get_device  the same planes into a device pointer on the context's device (e.g. a torch tensor): nothing crosses the host.
+ *              Runs on the context's stream and returns when d_out is complete.
+ *   voxel_reset  clears the planes and the counters and keeps the grids.   voxel_end frees the set (without a set: CMX_OK).
+ *   state      as for the views: the calls read the knots the reconstruction holds NOW and nothing else of it, and write only the
+ *              grid planes and their counters.  recon_begin and recon_end free the set; restart and voxel_reset clear it; EVERY
+ *              other call leaves it alone.  A view set and a voxel set may be open at the same time.
+ *   status     CMX_ERR_STATE before recon_begin, before voxel_begin (add*, get*, reset), on a group handle, and for add_from on a
+ *              store without polarity when the set is signed; CMX_ERR_INVALID_ARG for pol == NULL with a signed set.
+ * Deterministic mode: every cell is a sum of integers -- bitwise identical from run to run, for any slicing at batch multiples,
+ * through the three ingest paths, and whatever other grids are in the set.  Otherwise votes are fp32 atomics. */
+int cmx_backend_recon_voxel_begin(cmx_ctx *ctx, int Wv, int Hv, int n_bins, int signed_polarity, int n_grids, const cmx_recon_view *grids);
+int cmx_backend_recon_voxel_add(cmx_ctx *ctx, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns,
+                                const uint8_t *pol /* n bytes; may be NULL only when signed_polarity == 0 */);
+int cmx_backend_recon_voxel_add_aos(cmx_ctx *ctx, int64_t n, const void *events, const cmx_aos_layout *layout, size_t off_polarity);
+int cmx_backend_recon_voxel_add_from(cmx_ctx *ctx, const cmx_events *ev, int64_t first, int64_t count);
+int cmx_backend_recon_voxel_get(cmx_ctx *ctx, int first_grid, int count, float *out /* count*n_bins*Hv*Wv or NULL */,
+                                int64_t *n_voted /* count or NULL */);
+int cmx_backend_recon_voxel_get_device(cmx_ctx *ctx, int first_grid, int count, float *d_out /* device pointer on the context's device */);
+int cmx_backend_recon_voxel_reset(cmx_ctx *ctx);
+int cmx_backend_recon_voxel_end(cmx_ctx *ctx);
 /* Whole-trajectory contrast and its gradient with respect to a LEFT increment of every control pose, on top of an open
  * reconstruction -- the evaluation one bundle adjustment over the whole recording needs, for a spline of any knot count:
  *     recon_begin   recon_add*(events) ...   recon_contrast(want_grad)   recon_grad_add*(the same events) ...   recon_grad_get
