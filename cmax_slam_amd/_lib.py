@@ -169,6 +169,16 @@ SYMBOLS = {
     "cmx_backend_recon_voxel_get_device": (C.c_int, [ctx_p, C.c_int, C.c_int, C.c_void_p]),
     "cmx_backend_recon_voxel_reset": (C.c_int, [ctx_p]),
     "cmx_backend_recon_voxel_end": (C.c_int, [ctx_p]),
+    "cmx_backend_recon_surface_begin": (C.c_int, [ctx_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ReconView)]),
+    "cmx_backend_recon_surface_add": (C.c_int, [ctx_p, C.c_int64, c_u16p, c_u16p, c_i64p, c_u8p]),
+    "cmx_backend_recon_surface_add_aos": (C.c_int, [ctx_p, C.c_int64, C.c_void_p, C.POINTER(AosLayout), C.c_size_t]),
+    "cmx_backend_recon_surface_add_from": (C.c_int, [ctx_p, C.c_void_p, C.c_int64, C.c_int64]),
+    "cmx_backend_recon_surface_get": (C.c_int, [ctx_p, C.c_int, C.c_int, c_i64p, c_i64p]),
+    "cmx_backend_recon_surface_get_device": (C.c_int, [ctx_p, C.c_int, C.c_int, C.c_void_p]),
+    "cmx_backend_recon_surface_decay": (C.c_int, [ctx_p, C.c_int, C.c_int, c_i64p, C.c_double, c_fp]),
+    "cmx_backend_recon_surface_decay_device": (C.c_int, [ctx_p, C.c_int, C.c_int, c_i64p, C.c_double, C.c_void_p]),
+    "cmx_backend_recon_surface_reset": (C.c_int, [ctx_p]),
+    "cmx_backend_recon_surface_end": (C.c_int, [ctx_p]),
     "cmx_backend_recon_get": (C.c_int, [ctx_p, c_fp, c_i64p, c_i64p]),
     "cmx_backend_recon_render": (C.c_int, [ctx_p, C.c_double, c_dp, C.POINTER(C.c_uint8)]),
     "cmx_backend_recon_end": (C.c_int, [ctx_p]),

@@ -516,6 +516,28 @@ struct ReconVoxelArgs {
 };
 void launch_recon_voxel_votes(const ReconVoxelArgs &g, hipStream_t s);
 void launch_recon_fixed_to_float_signed(const unsigned long long *fixed, float *plane, size_t n, hipStream_t s);  // two's complement cells
+// time surfaces (cmx_backend_recon_surface_*): the vote loop of launch_recon_voxel_votes with S surfaces of C channels as its targets.
+// A surface is a view; an event votes into every surface whose range holds its OWN timestamp -- ev_t, indexed as ev.xy is -- and the
+// vote is ONE signed 64-bit integer max of that timestamp at the NEAREST pixel of the projection, in channel 1 for an OFF event of a
+// by-polarity set (polarity as in launch_recon_votes_pol: ev.pol, or bit 31 of the word) and in channel 0 otherwise.  A max commutes
+// and is idempotent: the cells are bitwise reproducible in every mode and there is no fixed-point form.
+constexpr long long kReconSurfaceEmpty = -0x7fffffffffffffffLL - 1;  // a cell no event has reached (never a vote: surface_begin refuses it as t_lo)
+struct ReconSurfaceArgs {
+  ReconArgs ev;
+  const long long *ev_t;           // the events' own timestamps, indexed as ev.xy is
+  const ReconViewDev *surfaces;    // [n_surfaces]
+  const ReconViewRange *ranges;    // [n_surfaces]
+  int n_surfaces, Wv, Hv;
+  int by_polarity;                 // 0: one channel and polarity is not read
+  long long *cells;                // [n_surfaces][by_polarity ? 2 : 1][Hv * Wv]
+  unsigned long long *n_voted;     // [n_surfaces] events that voted into each surface
+};
+void launch_recon_surface_votes(const ReconSurfaceArgs &g, hipStream_t s);
+void launch_recon_surface_fill(long long *cells, size_t n, hipStream_t s);  // every cell = kReconSurfaceEmpty (no byte memset writes that)
+// `count` surfaces of per_surface cells: out = 0 for an empty cell, 1 for T >= t_ref, else (float)exp(-(double)(uint64_t)(t_ref - T) /
+// tau_ns); the t_ref of surface k is t_ref[k] or, without t_ref, ranges[k].t_hi (all pointers on the device, at the first surface)
+void launch_recon_surface_decay(const long long *cells, const ReconViewRange *ranges, const long long *t_ref, size_t per_surface, int count,
+                                double tau_ns, float *out, hipStream_t s);
 // bound events (cmx_backend_recon_bind_from / _eval_bound): the batch poses of a spline of any knot count as a table in global
 // memory (recon_pose<N>, one thread per batch: a.batch_t, a.nb) -- what the tile sort (launch_count_sort with poseR = the table)
 // and the vote kernel below read -- and the vote pass over the tile-sorted events: one workgroup per chunk, votes into a

@@ -12,6 +12,8 @@
 //                   the OFF plane by the event's polarity, and the voting events are counted per plane.
 //   recon_view_votes / recon_voxel_votes   the same walk with the planes of M pinhole views, or the bins of G voxel grids, as the
 //                   targets of the votes (further down, with their own descriptions)
+//   recon_surface_votes   the same walk again with the cells of S time surfaces as the targets: one 64-bit integer max per vote;
+//                   recon_surface_fill and recon_surface_decay beside it
 //   recon_fixed_to_float   deterministic mode: the 2^-30 fixed-point plane as fp32, leaving it as it is (accumulation goes on)
 #include "../../include/cmax_hip.h"
 #include "cmx_internal.hpp"
@@ -437,6 +439,165 @@ void launch_recon_voxel_votes(const ReconVoxelArgs &g, hipStream_t s) {
     if (g.fixed) hipLaunchKernelGGL((recon_voxel_votes_kernel<4, true>), gr, b, 0, s, g);
     else hipLaunchKernelGGL((recon_voxel_votes_kernel<4, false>), gr, b, 0, s, g);
   }
+}
+
+// ---------------------------------------------------------------------------------------------- time surfaces
+// recon_surface_votes   cmx_backend_recon_surface_add*: recon_voxel_votes with S surfaces of one or two channels as the targets.  The
+//                same run structure: batch poses into LDS; the span of the run's EVENT times by wave reduction and one LDS atomic
+//                per wave; ONE scan of the table of ranges lists the surfaces that meet that span; listed surfaces are taken
+//                kReconViewChunk at a time, 128-byte view entries in LDS; the world ray is formed once per event and chunk, and
+//                for every surface of the chunk with t_lo <= t_i < t_hi: recon_view_project (the view vote's own projection and
+//                test), the NEAREST pixel (int)(u + 0.5), (int)(w + 0.5) -- inside the plane because of the test -- and ONE signed
+//                64-bit atomic max of t_i there, in channel 1 for an OFF event of a by-polarity set and in channel 0 otherwise.
+//                The result of the max is not read.  No fixed-point form: a max of integers commutes and is idempotent.
+template <int N>
+__global__ __launch_bounds__(kReconThreads) void recon_surface_votes_kernel(const ReconSurfaceArgs g) {
+  constexpr int kWords = sizeof(ReconViewDev) / 8;
+  static_assert(kReconViewChunk * kWords <= kReconThreads, "one lane per word of a chunk");
+  __shared__ double sh_R[(kReconMaxRun + 2) * 9];
+  __shared__ ReconViewDev sh_view[kReconViewChunk];
+  __shared__ unsigned sh_cnt[kReconViewChunk];
+  __shared__ unsigned short sh_match[kReconMaxViews];
+  __shared__ unsigned sh_nmatch;
+  __shared__ long long sh_tmin, sh_tmax;
+  const ReconArgs &a = g.ev;
+  const int tid = threadIdx.x;
+  const int e0 = blockIdx.x * a.run;  // (the grid covers [0, n): e0 < n)
+  const int e1 = (a.n - e0 > a.run) ? e0 + a.run : a.n;
+  const int b0 = e0 / a.per_batch;
+  int nbw = (e1 - 1) / a.per_batch - b0 + 1;
+  if (nbw > kReconMaxRun + 2) nbw = kReconMaxRun + 2;  // (cannot happen with run = recon_run(per_batch))
+  if (tid == 0) { sh_nmatch = 0; sh_tmin = 0x7fffffffffffffffLL; sh_tmax = kReconSurfaceEmpty; }
+  __syncthreads();
+  for (int j = tid; j < nbw; j += kReconThreads) {
+    const int b = b0 + j < a.nb ? b0 + j : a.nb - 1;
+    recon_pose<N>(a, a.batch_t[b], sh_R + 9 * j);
+  }
+  // the span of the run's EVENT times: every event is looked at, so the list below holds for any order of the events
+  long long tmin = 0x7fffffffffffffffLL, tmax = kReconSurfaceEmpty;
+  for (int i = e0 + tid; i < e1; i += kReconThreads) {
+    const int b = i / a.per_batch;
+    const size_t src = a.stride ? (size_t)b * a.B + (size_t)(i - b * a.per_batch) * a.stride : (size_t)i;
+    const long long t = g.ev_t[src];
+    tmin = t < tmin ? t : tmin;
+    tmax = t > tmax ? t : tmax;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const long long lo = __shfl_down(tmin, off, 64), hi = __shfl_down(tmax, off, 64);
+    tmin = lo < tmin ? lo : tmin;
+    tmax = hi > tmax ? hi : tmax;
+  }
+  if ((tid & 63) == 0) { atomicMin(&sh_tmin, tmin); atomicMax(&sh_tmax, tmax); }
+  __syncthreads();
+  tmin = sh_tmin; tmax = sh_tmax;
+  for (int v = tid; v < g.n_surfaces; v += kReconThreads) {
+    const ReconViewRange r = g.ranges[v];
+    if (r.t_lo <= tmax && r.t_hi > tmin) {
+      const unsigned pos = atomicAdd(&sh_nmatch, 1u);
+      if (pos < (unsigned)kReconMaxViews) sh_match[pos] = (unsigned short)v;
+    }
+  }
+  __syncthreads();
+  int nmatch = (int)sh_nmatch;
+  nmatch = nmatch < kReconMaxViews ? nmatch : kReconMaxViews;
+  const double u_hi = (double)(g.Wv - 2), w_hi = (double)(g.Hv - 2);
+  const size_t np = (size_t)g.Hv * g.Wv;
+  const size_t per_surface = g.by_polarity ? 2 * np : np;
+  for (int c0 = 0; c0 < nmatch; c0 += kReconViewChunk) {  // (uniform: nmatch is the workgroup's)
+    const int nl = nmatch - c0 < kReconViewChunk ? nmatch - c0 : kReconViewChunk;
+    if (tid < nl * kWords) {
+      const int k = tid / kWords, wd = tid - k * kWords;
+      reinterpret_cast<long long *>(sh_view)[tid] = reinterpret_cast<const long long *>(g.surfaces + sh_match[c0 + k])[wd];
+    }
+    if (tid < kReconViewChunk) sh_cnt[tid] = 0;
+    __syncthreads();
+    int cur = -1;
+    double R[9];
+    for (int i = e0 + tid; i < e1; i += kReconThreads) {
+      const int b = i / a.per_batch;
+      int j = b - b0;
+      j = j < nbw ? j : nbw - 1;
+      if (j != cur) {
+#pragma unroll
+        for (int c = 0; c < 9; c++) R[c] = sh_R[9 * j + c];
+        cur = j;
+      }
+      // sampling restarts at every batch start: packed slot k of batch b is raw event b * B + k * stride (recon_votes_kernel)
+      const size_t src = a.stride ? (size_t)b * a.B + (size_t)(i - b * a.per_batch) * a.stride : (size_t)i;
+      const uint32_t word = a.xy[src];
+      const long long ti = g.ev_t[src];
+      const uint32_t e = word & 0x7fffffffu;
+      // a by-polarity set: the store's byte (a.pol is a kernel argument: uniform), read beside the word, or the word's own bit 31
+      const bool off = g.by_polarity && !(a.pol ? a.pol[src] != 0 : (word >> 31) != 0);
+      const int ex = e & 0xffff, ey = e >> 16;
+      double v0, v1, v2, rx, ry, rz;
+      load_bearing(a.cam, ex, ey, v0, v1, v2);
+      be_rotate<false>(R, v0, v1, v2, rx, ry, rz);
+      for (int k = 0; k < nl; k++) {
+        const ReconViewDev &V = sh_view[k];  // (one address for all lanes: LDS broadcasts)
+        if (ti < V.t_lo || ti >= V.t_hi) continue;
+        const ReconViewHit p = recon_view_project(V, rx, ry, rz, u_hi, w_hi);
+        if (!p.ok) continue;
+        const int cx = (int)(p.u + 0.5), cy = (int)(p.w + 0.5);  // (1 <= cx <= Wv - 2 and 1 <= cy <= Hv - 2: the test above)
+        long long *cell = g.cells + (size_t)V.index * per_surface + (off ? np : 0) + (size_t)cy * g.Wv + cx;
+        atomicMax(cell, ti);
+        atomicAdd(&sh_cnt[k], 1u);
+      }
+    }
+    __syncthreads();
+    if (tid < nl) {  // (the lane that zeroes the counter of the next chunk)
+      const unsigned cnt = sh_cnt[tid];
+      if (cnt) atomicAdd(g.n_voted + sh_view[tid].index, (unsigned long long)cnt);
+    }
+    __syncthreads();  // (the next chunk's entries overwrite sh_view)
+  }
+}
+
+void launch_recon_surface_votes(const ReconSurfaceArgs &g, hipStream_t s) {
+  const ReconArgs &a = g.ev;
+  if (a.n <= 0 || a.nb <= 0 || g.n_surfaces <= 0) return;
+  const dim3 gr((unsigned)(((long long)a.n + a.run - 1) / a.run)), b(kReconThreads);  // (a.n <= 2^30: cmx_reconstruct.cpp)
+  if (a.order == 2) hipLaunchKernelGGL((recon_surface_votes_kernel<2>), gr, b, 0, s, g);
+  else hipLaunchKernelGGL((recon_surface_votes_kernel<4>), gr, b, 0, s, g);
+}
+
+// every cell = "no event yet": INT64_MIN, a pattern no byte memset writes (surface_begin, surface_reset, restart)
+__global__ __launch_bounds__(256) void recon_surface_fill_kernel(long long *cells, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) cells[i] = kReconSurfaceEmpty;
+}
+void launch_recon_surface_fill(long long *cells, size_t n, hipStream_t s) {
+  if (n == 0) return;
+  size_t blocks = (n + 1023) / 1024;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(recon_surface_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, s, cells, n);
+}
+
+// the surfaces read through an exponential decay, one cell per lane (8-byte load, 4-byte store): 0 for an empty cell, 1 at or behind
+// the reference time, else exp(-(t_ref - T) / tau) -- the difference as an unsigned number: t_ref > T there, so it is exact whatever
+// the two are -- with the quotient and the exponential in fp64, rounded once to fp32
+__global__ __launch_bounds__(256) void recon_surface_decay_kernel(const long long *cells, const ReconViewRange *ranges, const long long *t_ref,
+                                                                  size_t per_surface, double tau_ns, float *out) {
+  const size_t k = blockIdx.y;  // the surface: its reference time is the workgroup's
+  const long long tr = t_ref ? t_ref[k] : ranges[k].t_hi;
+  cells += k * per_surface;
+  out += k * per_surface;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < per_surface; i += (size_t)gridDim.x * 256) {
+    const long long T = cells[i];
+    float v;
+    if (T == kReconSurfaceEmpty) v = 0.f;
+    else if (T >= tr) v = 1.f;
+    else v = (float)exp(-((double)((unsigned long long)tr - (unsigned long long)T) / tau_ns));
+    out[i] = v;
+  }
+}
+void launch_recon_surface_decay(const long long *cells, const ReconViewRange *ranges, const long long *t_ref, size_t per_surface, int count,
+                                double tau_ns, float *out, hipStream_t s) {
+  if (per_surface == 0 || count <= 0) return;
+  size_t blocks = (per_surface + 255) / 256;  // one cell per lane, up to 1024 workgroups to a surface (count <= 4096: grid.y)
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(recon_surface_decay_kernel, dim3((unsigned)blocks, (unsigned)count), dim3(256), 0, s, cells, ranges, t_ref, per_surface,
+                     tau_ns, out);
 }
 
 // ---------------------------------------------------------------------------------------------- per-event export

@@ -7,6 +7,7 @@
 //   pol_add*   add*'s vote loop into the ON / OFF planes of the signed polarity map
 //   view_add*  add*'s vote loop into the planes of the pinhole views
 //   voxel_add* add*'s vote loop into the bins of the voxel grids, by every event's own timestamp and polarity
+//   surface_add*  add*'s vote loop into the cells of the time surfaces: the latest timestamp per pixel and polarity
 // Host arrays (SoA, or the host's own records) are packed slice by slice into two slots of pinned memory and uploaded on the copy
 // stream while the slice before runs; a range of an event store is read in place, its batch times formed on the device.
 #include "cmx_recon_state.hpp"
@@ -76,8 +77,8 @@ struct FedSlice : FeedSlice {
 // uploaded while the kernels of slice k run.  Store sources: the batch times of the slice into slot[0]'s table; a single slice finds
 // there what the validation pass has just written.  From the first slice on only a runtime error (CMX_ERR_HIP) can end the call,
 // and slices queued before it have run.  Returns after the context's stream has run dry, the slots idle either way.
-// with_pol (pol_add*, signed voxel_add*; host sources): the packed words carry the events' polarity in bit 31.
-// with_time (voxel_add*, never with every_event): the slice also carries its events' own timestamps -- host sources: one int64 per
+// with_pol (pol_add*, signed voxel_add*, by-polarity surface_add*; host sources): the packed words carry the events' polarity in bit 31.
+// with_time (voxel_add*, surface_add*; never with every_event): the slice also carries its events' own timestamps -- host sources: one int64 per
 // packed event, written by the packing pass beside the word into the same slot and uploaded with it; store: its own array in place.
 template <typename OnSlice>
 static int feed(cmx_ctx *c, ReconState *r, const EventSource &src, bool every_event, bool with_pol, bool with_time, BatchPlan *plan,
@@ -380,6 +381,72 @@ int cmx_backend_recon_voxel_add_from(cmx_ctx *c, const cmx_events *e, int64_t fi
     if (rc) return rc;
     if (c->recon->vox_signed && e->size > 0 && !e->has_pol)
       return fail(c, CMX_ERR_STATE, "the voxel set is signed and the event store holds no polarity (cmx_events_push_pol)");
+    return (int)CMX_OK;
+  });
+}
+
+// ---- surface_add*: add*'s vote pass with the cells of the time surfaces as its targets.  As voxel_add*: nothing of the
+// reconstruction but the knots is read, nothing but the surface cells and their counters is written; every sampled event brings its
+// own timestamp (feed: with_time), and a by-polarity set reads polarity as pol_add* does -- bit 31 of the word on the host paths, the
+// store's byte array -- while a merged set reads none and packs none.
+static int recon_surface_add_source(cmx_ctx *c, const EventSource &src) {
+  ReconState *r = c->recon;
+  int rc = feed_checks(c, src);
+  if (rc) return rc;
+  ReconSurfaceArgs g{};
+  g.ev = recon_args(c, r);
+  g.ev.plane = nullptr; g.ev.fixed = nullptr; g.ev.n_inside = nullptr;
+  g.surfaces = r->d_surfaces; g.ranges = r->d_sranges;
+  g.n_surfaces = r->n_surfaces; g.Wv = r->Ws; g.Hv = r->Hs;
+  g.by_polarity = r->surf_by_pol ? 1 : 0;
+  g.cells = r->d_scells;
+  g.n_voted = r->d_svoted;
+  ReconArgs &a = g.ev;
+  BatchPlan p;
+  return feed(c, r, src, false, r->surf_by_pol && !src.on_device(), true, &p, [&](const FedSlice &s) {
+    a.xy = s.d_xy; a.stride = src.on_device() ? r->rate : 0;
+    a.pol = r->surf_by_pol && src.on_device() ? src.d_pol + s.ev_first : nullptr;
+    a.batch_t = s.d_bt; a.nb = s.b_hi - s.b_lo;
+    a.n = (int)s.n;
+    g.ev_t = s.d_t;
+    launch_recon_surface_votes(g, c->stream);
+    return (int)CMX_OK;
+  });
+}
+template <typename MakeSource>
+static int recon_surface_add_entry(cmx_ctx *c, MakeSource make) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (!c->recon->d_surfaces) return fail(c, CMX_ERR_STATE, "cmx_backend_recon_surface_begin has not succeeded");
+  EventSource src;
+  rc = make(&src);
+  if (rc) return rc;
+  return recon_surface_add_source(c, src);
+}
+int cmx_backend_recon_surface_add(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, const uint8_t *pol) {
+  return recon_surface_add_entry(c, [&](EventSource *src) {
+    if (c->recon->surf_by_pol && !pol) return fail(c, CMX_ERR_INVALID_ARG, "null polarity array for a by-polarity surface set");
+    *src = EventSource::arrays(n, x, y, t_ns);
+    src->soa.p = pol;
+    return (int)CMX_OK;
+  });
+}
+int cmx_backend_recon_surface_add_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout, size_t off_polarity) {
+  return recon_surface_add_entry(c, [&](EventSource *src) {
+    const int rc = make_aos(c, n, events, layout, src);
+    if (rc) return rc;
+    if (!c->recon->surf_by_pol) return (int)CMX_OK;  // (polarity is neither needed nor read)
+    if (off_polarity >= layout->stride) return fail(c, CMX_ERR_INVALID_ARG, "record layout: polarity outside the %zu-byte record", layout->stride);
+    src->aos.op = off_polarity;
+    return (int)CMX_OK;
+  });
+}
+int cmx_backend_recon_surface_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
+  return recon_surface_add_entry(c, [&](EventSource *src) {
+    const int rc = store_source(c, e, first, count, src);
+    if (rc) return rc;
+    if (c->recon->surf_by_pol && e->size > 0 && !e->has_pol)
+      return fail(c, CMX_ERR_STATE, "the surface set is by polarity and the event store holds no polarity (cmx_events_push_pol)");
     return (int)CMX_OK;
   });
 }

@@ -1,9 +1,9 @@
 // cmx_recon_state.hpp -- what the three sources of cmx_backend_recon_* share: the state a reconstruction keeps (cmx_ctx::recon) and
 // the helpers every one of them goes through.
 //   cmx_reconstruct.cpp  life cycle (begin, restart, extend, end), contrast / grad_get / eval_from, get / render, the view set, the
-//                        voxel set
+//                        voxel set, the surface set
 //   cmx_recon_feed.cpp   one walk over the events handed in, in slices of whole batches: add*, grad_add*, warp*, pol_add*, view_add*,
-//                        voxel_add*
+//                        voxel_add*, surface_add*
 //   cmx_recon_bound.cpp  events bound once and evaluated many times: bind / eval_bound, the frozen head, append / advance /
 //                        release, the hooks of cmx_backend_recon_solve
 // Kernels: cmx_recon.hip.
@@ -14,13 +14,13 @@
 // kept at or below 2^30, far from the wrap.
 constexpr int kMaxSliceEvents = 1 << 30;
 
-// Input staging of one slice.  The host paths hold packed events and batch times (voxel_add*: and the packed events' own timestamps)
+// Input staging of one slice.  The host paths hold packed events and batch times (voxel_add*, surface_add*: and the packed events' own timestamps)
 // in pinned memory and on the device; the store
 // paths read the store's events in place and form the batch times on the device, so they use slot[0]'s device table alone.
 struct ReconSlot {
   uint32_t *h_xy = nullptr, *d_xy = nullptr;
   long long *h_bt = nullptr, *d_bt = nullptr;
-  int64_t *h_t = nullptr, *d_t = nullptr;  // the packed events' own timestamps, beside the words (voxel_add* alone)
+  int64_t *h_t = nullptr, *d_t = nullptr;  // the packed events' own timestamps, beside the words (voxel_add*, surface_add*)
   size_t h_xy_cap = 0, xy_cap = 0, h_bt_cap = 0, bt_cap = 0, h_t_cap = 0, t_cap = 0;
   hipEvent_t up = nullptr, done = nullptr;  // upload complete (copy stream) / the slice's kernels complete (context stream)
   bool busy = false;
@@ -211,6 +211,17 @@ struct ReconState {
   float *d_xplanes = nullptr;                  // [n_grids][n_bins][Hx * Wx] (default mode), or the fp32 view of d_xfixed made by voxel_get
   unsigned long long *d_xfixed = nullptr;      // deterministic mode: their 2^-30 fixed-point twins, two's complement
   unsigned long long *d_xvoted = nullptr;      // [n_grids] events that voted into each grid
+  // ---- time surfaces (cmx_backend_recon_surface_*): S surfaces of C channels each, the reconstruction's own beside the
+  // view and voxel sets: made by surface_begin, cleared (to INT64_MIN) by restart and surface_reset, freed by surface_end, begin and end
+  int n_surfaces = 0, Ws = 0, Hs = 0;          // n_surfaces == 0: no surface set
+  bool surf_by_pol = false;                    // two channels, ON then OFF; otherwise one and polarity is never read
+  ReconViewDev *d_surfaces = nullptr;          // [n_surfaces]
+  ReconViewRange *d_sranges = nullptr;         // [n_surfaces]
+  long long *d_scells = nullptr;               // [n_surfaces][C][Hs * Ws] the latest timestamp voted into each cell, or INT64_MIN
+  unsigned long long *d_svoted = nullptr;      // [n_surfaces] events that voted into each surface
+  long long *d_stref = nullptr;                // [n_surfaces] the reference times of a surface_decay call that names them
+  float *d_sdecay = nullptr;                   // surface_decay (host output): the decayed cells on their way out, grown on demand
+  size_t sdecay_cap = 0;
   int64_t host_waits = 0;               // times a host thread has waited for the device in this reconstruction's calls
   // everything above that owns memory, a stream or an event (the streams idle: recon_release has waited for them)
   void release() {
@@ -220,7 +231,8 @@ struct ReconState {
     for (ReconWarpSlot &s : wslot) s.release();
     void *dev[] = {d_knots, d_delta, d_plane, d_fixed, d_inside, d_err, d_cx, d_cy, d_tflags, d_tile_list, d_tile_count, d_partials,
                    d_cm, d_jt, d_gsum, d_voted, d_rows, d_row_win, d_app_xy, d_app_t, d_pol, d_pol_fixed, d_pol_inside,
-                   d_views, d_vranges, d_vplanes, d_vfixed, d_vvoted, d_grids, d_xranges, d_xplanes, d_xfixed, d_xvoted};
+                   d_views, d_vranges, d_vplanes, d_vfixed, d_vvoted, d_grids, d_xranges, d_xplanes, d_xfixed, d_xvoted,
+                   d_surfaces, d_sranges, d_scells, d_svoted, d_stref, d_sdecay};
     for (void *p : dev) (void)hipFree(p);
     bnd.release();
     frozen.release();
@@ -262,6 +274,8 @@ int recon_pol_clear(cmx_ctx *c, ReconState *r);
 int recon_view_clear(cmx_ctx *c, ReconState *r);
 // the voxel planes and their counters zeroed, where a voxel set exists (queued)
 int recon_voxel_clear(cmx_ctx *c, ReconState *r);
+// the surface cells filled with INT64_MIN and their counters zeroed, where a surface set exists (queued)
+int recon_surface_clear(cmx_ctx *c, ReconState *r);
 
 // ---- cmx_recon_feed.cpp
 // one slice of the gradient pass, as g.ev describes it; deterministic mode: the workgroups' rows, then their sum in workgroup order

@@ -8,7 +8,8 @@
 // but the 2 x 3K sums -- and the plane's way out (get, render); the same for the ON / OFF planes of the signed polarity map
 // (pol_get, pol_render, pol_reset) and for the planes of a set of pinhole views (view_begin, view_get, view_render,
 // view_reset, view_end) and for the bins of a set of voxel grids (voxel_begin, voxel_get, voxel_get_device, voxel_reset,
-// voxel_end).  Events bound once and evaluated many times, the frozen head, the
+// voxel_end) and for the cells of a set of time surfaces (surface_begin, surface_get, surface_get_device, surface_decay,
+// surface_decay_device, surface_reset, surface_end).  Events bound once and evaluated many times, the frozen head, the
 // growing binding and the native solve's hooks: cmx_recon_bound.cpp.
 // Kernels: cmx_recon.hip.
 #include "cmx_recon_state.hpp"
@@ -193,6 +194,8 @@ int cmx_backend_recon_restart(cmx_ctx *c, const double *knots_xyzw) {
   rc = recon_view_clear(c, c->recon);  // (... nor the view planes; the views themselves stay)
   if (rc) return rc;
   rc = recon_voxel_clear(c, c->recon);  // (... nor the voxel planes; the grids themselves stay)
+  if (rc) return rc;
+  rc = recon_surface_clear(c, c->recon);  // (... nor the time surfaces, which go back to empty; the surfaces themselves stay)
   if (rc) return rc;
   return recon_start_over(c, c->recon, knots_xyzw);
 }
@@ -793,4 +796,171 @@ int cmx_backend_recon_voxel_get_device(cmx_ctx *c, int first_grid, int count, fl
   if (rc) return rc;
   if (count > 0 && !d_out) return fail(c, CMX_ERR_INVALID_ARG, "null device output");
   return recon_voxel_deliver(c, first_grid, count, d_out, hipMemcpyDeviceToDevice, nullptr);
+}
+
+// ---- time surfaces: the set of surfaces cmx_backend_recon_surface_add* (cmx_recon_feed.cpp) votes into, and its cells' way out -- as
+// they are (get, get_device: absolute nanoseconds, INT64_MIN where no event landed) or through an exponential decay (decay,
+// decay_device).  A surface is a view; the cells are surface-major, C = 1 or 2 channels to a surface, ON before OFF.
+static void recon_surface_free(cmx_ctx *c, ReconState *r) {
+  if (!r->d_surfaces) return;
+  (void)hipStreamSynchronize(c->stream);  // (a vote pass queued earlier may still write the cells)
+  void *dev[] = {r->d_surfaces, r->d_sranges, r->d_scells, r->d_svoted, r->d_stref, r->d_sdecay};
+  for (void *p : dev) (void)hipFree(p);
+  r->d_surfaces = nullptr; r->d_sranges = nullptr; r->d_scells = nullptr; r->d_svoted = nullptr; r->d_stref = nullptr;
+  r->d_sdecay = nullptr; r->sdecay_cap = 0;
+  r->n_surfaces = r->Ws = r->Hs = 0;
+  r->surf_by_pol = false;
+}
+
+static size_t recon_surface_cells(const ReconState *r) { return (size_t)(r->surf_by_pol ? 2 : 1) * r->Ws * r->Hs; }  // of ONE surface
+
+int recon_surface_clear(cmx_ctx *c, ReconState *r) {
+  if (!r->d_surfaces) return CMX_OK;
+  launch_recon_surface_fill(r->d_scells, (size_t)r->n_surfaces * recon_surface_cells(r), c->stream);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemsetAsync(r->d_svoted, 0, (size_t)r->n_surfaces * sizeof(unsigned long long), c->stream));
+  return CMX_OK;
+}
+
+static int recon_surface_enter(cmx_ctx *c) {
+  const int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (!c->recon->d_surfaces) return fail(c, CMX_ERR_STATE, "cmx_backend_recon_surface_begin has not succeeded");
+  return CMX_OK;
+}
+
+int cmx_backend_recon_surface_begin(cmx_ctx *c, int Wv, int Hv, int by_polarity, int n_surfaces, const cmx_recon_view *surfaces) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (Wv < 4 || Wv > 8192 || Hv < 4 || Hv > 8192) return fail(c, CMX_ERR_INVALID_ARG, "surface size %d x %d outside [4, 8192]", Wv, Hv);
+  if (n_surfaces < 1 || n_surfaces > 4096) return fail(c, CMX_ERR_INVALID_ARG, "n_surfaces=%d outside [1, 4096]", n_surfaces);
+  const int C = by_polarity ? 2 : 1;
+  if ((long long)n_surfaces * C * Wv * Hv > (1LL << 28))
+    return fail(c, CMX_ERR_INVALID_ARG, "%d surfaces of %d channels of %d x %d: more than 2^28 cells", n_surfaces, C, Wv, Hv);
+  if (!surfaces) return fail(c, CMX_ERR_INVALID_ARG, "null surface array");
+  std::vector<ReconViewDev> dev((size_t)n_surfaces);
+  std::vector<ReconViewRange> ranges((size_t)n_surfaces);
+  for (int i = 0; i < n_surfaces; i++) {
+    rc = recon_view_entry(c, surfaces[i], i, &dev[(size_t)i]);
+    if (rc) return rc;
+    // INT64_MIN marks a cell no event has reached; a range that starts there could hold an event with that timestamp
+    if (surfaces[i].t_lo_ns == INT64_MIN) return fail(c, CMX_ERR_INVALID_ARG, "surface %d: t_lo_ns is INT64_MIN, the empty marker", i);
+    ranges[(size_t)i] = ReconViewRange{dev[(size_t)i].t_lo, dev[(size_t)i].t_hi};
+  }
+  ReconState *r = c->recon;
+  recon_surface_free(c, r);  // a second begin starts over
+  const size_t nc = (size_t)n_surfaces * C * Wv * Hv;
+  ReconViewDev *d_surfaces = nullptr;
+  ReconViewRange *d_ranges = nullptr;
+  long long *cells = nullptr, *tref = nullptr;
+  unsigned long long *voted = nullptr;
+  hipError_t e = hipMalloc((void **)&d_surfaces, dev.size() * sizeof(ReconViewDev));
+  if (e == hipSuccess) e = hipMalloc((void **)&d_ranges, ranges.size() * sizeof(ReconViewRange));
+  if (e == hipSuccess) e = hipMalloc((void **)&cells, nc * sizeof(long long));
+  if (e == hipSuccess) e = hipMalloc((void **)&voted, (size_t)n_surfaces * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMalloc((void **)&tref, (size_t)n_surfaces * sizeof(long long));
+  if (e == hipSuccess) e = hipMemcpy(d_surfaces, dev.data(), dev.size() * sizeof(ReconViewDev), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_ranges, ranges.data(), ranges.size() * sizeof(ReconViewRange), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {  // (all of it or none: d_surfaces says whether a surface set exists)
+    (void)hipFree(d_surfaces); (void)hipFree(d_ranges); (void)hipFree(cells); (void)hipFree(voted); (void)hipFree(tref);
+    return fail(c, CMX_ERR_HIP, "allocating %d surfaces of %d channels of %d x %d: %s", n_surfaces, C, Wv, Hv, hipGetErrorString(e));
+  }
+  r->d_surfaces = d_surfaces; r->d_sranges = d_ranges; r->d_scells = cells; r->d_svoted = voted; r->d_stref = tref;
+  r->n_surfaces = n_surfaces; r->Ws = Wv; r->Hs = Hv;
+  r->surf_by_pol = by_polarity != 0;
+  rc = recon_surface_clear(c, r);
+  if (rc) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return CMX_OK;
+}
+
+int cmx_backend_recon_surface_reset(cmx_ctx *c) {
+  int rc = recon_surface_enter(c);
+  if (rc) return rc;
+  rc = recon_surface_clear(c, c->recon);
+  if (rc) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return CMX_OK;
+}
+
+int cmx_backend_recon_surface_end(cmx_ctx *c) {
+  const int rc = recon_enter(c, true);
+  if (rc) return rc;
+  recon_surface_free(c, c->recon);  // (no surface set: nothing to free, not an error)
+  return CMX_OK;
+}
+
+// the common front door of get* and decay*: a surface set, and a range inside it
+static int recon_surface_range(cmx_ctx *c, int first, int count) {
+  const int rc = recon_surface_enter(c);
+  if (rc) return rc;
+  const ReconState *r = c->recon;
+  if (first < 0 || count < 0 || first > r->n_surfaces || count > r->n_surfaces - first)
+    return fail(c, CMX_ERR_INVALID_ARG, "surfaces [%d, %d + %d) outside the %d of the set", first, first, count, r->n_surfaces);
+  return CMX_OK;
+}
+
+// surfaces [first, first + count) as int64 wherever `cells` is (host: get; the context's device: get_device), and their counters
+static int recon_surface_deliver(cmx_ctx *c, int first, int count, int64_t *cells, hipMemcpyKind kind, int64_t *n_voted) {
+  const int rc = recon_surface_range(c, first, count);
+  if (rc) return rc;
+  if (count == 0) return CMX_OK;
+  ReconState *r = c->recon;
+  const size_t per = recon_surface_cells(r);
+  if (cells) HIP_TRY(c, hipMemcpyAsync(cells, r->d_scells + (size_t)first * per, (size_t)count * per * sizeof(int64_t), kind, c->stream));
+  if (n_voted) HIP_TRY(c, hipMemcpyAsync(n_voted, r->d_svoted + first, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return CMX_OK;
+}
+int cmx_backend_recon_surface_get(cmx_ctx *c, int first, int count, int64_t *cells, int64_t *n_voted) {
+  return recon_surface_deliver(c, first, count, cells, hipMemcpyDeviceToHost, n_voted);
+}
+int cmx_backend_recon_surface_get_device(cmx_ctx *c, int first, int count, int64_t *d_cells) {
+  const int rc = recon_surface_enter(c);
+  if (rc) return rc;
+  if (count > 0 && !d_cells) return fail(c, CMX_ERR_INVALID_ARG, "null device output");
+  return recon_surface_deliver(c, first, count, d_cells, hipMemcpyDeviceToDevice, nullptr);
+}
+
+// one decay pass over surfaces [first, first + count) into d_out on the device, queued; t_ref_ns (host, count values) or NULL: every
+// surface's own t_hi
+static int recon_surface_decay_queue(cmx_ctx *c, int first, int count, const int64_t *t_ref_ns, double tau_ns, float *d_out) {
+  ReconState *r = c->recon;
+  const long long *d_tref = nullptr;
+  if (t_ref_ns) {  // (pageable memory: the copy has read it when the call returns)
+    HIP_TRY(c, hipMemcpyAsync(r->d_stref, t_ref_ns, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    d_tref = r->d_stref;
+  }
+  launch_recon_surface_decay(r->d_scells + (size_t)first * recon_surface_cells(r), r->d_sranges + first, d_tref, recon_surface_cells(r),
+                             count, tau_ns, d_out, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return CMX_OK;
+}
+static int recon_surface_decay_checks(cmx_ctx *c, int first, int count, double tau_ns, const void *out) {
+  const int rc = recon_surface_range(c, first, count);
+  if (rc) return rc;
+  if (!std::isfinite(tau_ns) || !(tau_ns > 0.0)) return fail(c, CMX_ERR_INVALID_ARG, "tau_ns must be finite and > 0");
+  if (count > 0 && !out) return fail(c, CMX_ERR_INVALID_ARG, "null output");
+  return CMX_OK;
+}
+int cmx_backend_recon_surface_decay_device(cmx_ctx *c, int first, int count, const int64_t *t_ref_ns, double tau_ns, float *d_out) {
+  int rc = recon_surface_decay_checks(c, first, count, tau_ns, d_out);
+  if (rc || count == 0) return rc;
+  rc = recon_surface_decay_queue(c, first, count, t_ref_ns, tau_ns, d_out);
+  if (rc) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return CMX_OK;
+}
+int cmx_backend_recon_surface_decay(cmx_ctx *c, int first, int count, const int64_t *t_ref_ns, double tau_ns, float *out) {
+  int rc = recon_surface_decay_checks(c, first, count, tau_ns, out);
+  if (rc || count == 0) return rc;
+  ReconState *r = c->recon;
+  const size_t n = (size_t)count * recon_surface_cells(r);
+  rc = ensure(c, r->d_sdecay, r->sdecay_cap, n);  // (the decayed cells exist nowhere else: the set holds timestamps)
+  if (rc) return rc;
+  rc = recon_surface_decay_queue(c, first, count, t_ref_ns, tau_ns, r->d_sdecay);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(out, r->d_sdecay, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return CMX_OK;
 }

@@ -650,6 +650,7 @@ class BackendEvaluator(_Evaluator):
         self._recon_K = k.shape[0]
         self._view_shape = None  # (begin frees a view set)
         self._voxel_shape = None  # (... and a voxel set)
+        self._surface_shape = None  # (... and a surface set)
         self._ck(self._L.cmx_backend_recon_begin(self._ctx, int(order), k.shape[0], _dp(k), int(start_ns), int(dt_ns),
                                                  int(event_batch_size), int(event_sample_rate)))
 
@@ -875,6 +876,91 @@ class BackendEvaluator(_Evaluator):
     def reconstruct_voxel_end(self):
         self._ck(self._L.cmx_backend_recon_voxel_end(self._ctx))
         self._voxel_shape = None
+
+    # --- time surfaces: the latest event per pixel and polarity of the same vote loop (cmx_backend_recon_surface_*)
+    _surface_shape = None  # (n_surfaces, C, Hv, Wv) of the last reconstruct_surface_begin
+    _surface_by_polarity = True
+
+    def reconstruct_surface_begin(self, surfaces, Wv, Hv, by_polarity=True):
+        """Attach time surfaces to the open reconstruction, every cell empty (trajectory.SURFACE_EMPTY).  surfaces: _lib.ReconView
+        structures or tuples (quat_xyzw, fx, fy, cx, cy, t_lo_ns, t_hi_ns) -- trajectory.frame_views' or crop_view's output as it
+        is; a range over all time is accepted.  by_polarity: two channels, ON then OFF; otherwise one, and polarity is never read."""
+        vs = [v if isinstance(v, _lib.ReconView) else _lib.recon_view(*v) for v in surfaces]
+        arr = (_lib.ReconView * max(len(vs), 1))(*vs)
+        self._surface_shape = None
+        self._ck(self._L.cmx_backend_recon_surface_begin(self._ctx, int(Wv), int(Hv), int(bool(by_polarity)), len(vs), arr))
+        self._surface_shape = (len(vs), 2 if by_polarity else 1, int(Hv), int(Wv))
+        self._surface_by_polarity = bool(by_polarity)
+
+    def reconstruct_surface_add(self, x, y, t_ns, polarity=None):
+        """reconstruct_add's vote loop over exactly these events: every sampled event is warped once into the world frame and its OWN
+        timestamp is kept, where it is the latest, at the nearest pixel of every surface whose range holds it.  polarity (one value
+        per event, nonzero / positive = ON) is needed for a by-polarity set and ignored by a merged one."""
+        x, y, t = _c(x, np.uint16), _c(y, np.uint16), _c(t_ns, np.int64)
+        p = _pol_bytes(polarity) if polarity is not None and self._surface_by_polarity else None
+        if not (len(x) == len(y) == len(t)) or (p is not None and len(p) != len(x)):
+            raise ValueError("x, y, t_ns, polarity must have equal length")
+        self._ck(self._L.cmx_backend_recon_surface_add(self._ctx, len(x), x.ctypes.data_as(c_u16p), y.ctypes.data_as(c_u16p),
+                                                       t.ctypes.data_as(c_i64p), p.ctypes.data_as(_lib.c_u8p) if p is not None else None))
+
+    def reconstruct_surface_add_aos(self, events, polarity_field="polarity"):
+        """The same from a structured array of records with fields x, y, sec, nsec and a one-byte polarity field."""
+        ev = np.ascontiguousarray(events)
+        lay = _lib.aos_layout_of(ev)
+        off = _pol_offset(ev, polarity_field) if self._surface_by_polarity else 0
+        self._ck(self._L.cmx_backend_recon_surface_add_aos(self._ctx, len(ev), ev.ctypes.data_as(C.c_void_p), C.byref(lay), off))
+
+    def reconstruct_surface_add_from(self, store, first, count):
+        """The same over events_[first, first+count) of an EventStore (with polarity, EventStore.push(..., polarity=), for a
+        by-polarity set)."""
+        self._ck(self._L.cmx_backend_recon_surface_add_from(self._ctx, store._h, int(first), int(count)))
+
+    def _surface_range(self, first, count):
+        n, C_, Hv, Wv = self._surface_shape or (0, 0, 0, 0)
+        count = n - int(first) if count is None else int(count)
+        return count, (max(count, 0), C_, Hv, Wv)
+
+    def reconstruct_surface_get(self, first=0, count=None, with_counts=False, out=None):
+        """(count, C, Hv, Wv) int64 timestamps of surfaces [first, first+count) in absolute nanoseconds, trajectory.SURFACE_EMPTY
+        where no event landed [, int64 events that voted into each].  out: an object with data_ptr() -- a contiguous int64 torch
+        tensor of that many elements on the context's device: the cells are written straight into it, nothing crosses the host,
+        and out is returned in the array's place.  The call runs on the context's stream and returns when out is complete; work of
+        the caller's that still writes the tensor on another stream must be finished."""
+        count, shape = self._surface_range(first, count)
+        cnt = np.zeros(shape[0], np.int64)
+        if out is not None:
+            self._ck(self._L.cmx_backend_recon_surface_get_device(self._ctx, int(first), count, out.data_ptr()))
+            if with_counts:
+                self._ck(self._L.cmx_backend_recon_surface_get(self._ctx, int(first), count, None, cnt.ctypes.data_as(c_i64p)))
+            return (out, cnt) if with_counts else out
+        cells = np.empty(shape, np.int64)
+        self._ck(self._L.cmx_backend_recon_surface_get(self._ctx, int(first), count, cells.ctypes.data_as(c_i64p),
+                                                       cnt.ctypes.data_as(c_i64p) if with_counts else None))
+        return (cells, cnt) if with_counts else cells
+
+    def reconstruct_surface_decay(self, tau_ns, t_ref_ns=None, first=0, count=None, out=None):
+        """(count, C, Hv, Wv) fp32: the surfaces read through exp(-(t_ref - T) / tau_ns) in one device pass -- 0 where no event
+        landed, 1 where T >= t_ref.  t_ref_ns: one reference time per surface of the range (or one for all); None: every surface's
+        own t_hi.  out: a contiguous float32 torch tensor on the context's device, as in reconstruct_surface_get."""
+        count, shape = self._surface_range(first, count)
+        ref = None
+        if t_ref_ns is not None:
+            ref = np.ascontiguousarray(np.broadcast_to(np.asarray(t_ref_ns, np.int64), (shape[0],)))
+        ref_p = ref.ctypes.data_as(c_i64p) if ref is not None else None
+        if out is not None:
+            self._ck(self._L.cmx_backend_recon_surface_decay_device(self._ctx, int(first), count, ref_p, float(tau_ns), out.data_ptr()))
+            return out
+        res = np.empty(shape, np.float32)
+        self._ck(self._L.cmx_backend_recon_surface_decay(self._ctx, int(first), count, ref_p, float(tau_ns), res.ctypes.data_as(c_fp)))
+        return res
+
+    def reconstruct_surface_reset(self):
+        """Set every cell back to empty and the counters to zero (after the knots have moved); the surfaces stay."""
+        self._ck(self._L.cmx_backend_recon_surface_reset(self._ctx))
+
+    def reconstruct_surface_end(self):
+        self._ck(self._L.cmx_backend_recon_surface_end(self._ctx))
+        self._surface_shape = None
 
     def reconstruct_get(self, with_counts=False):
         """The (Hp, Wp) fp32 plane [, events the sampling selected so far, events that voted so far]."""

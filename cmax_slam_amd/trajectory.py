@@ -134,6 +134,8 @@ def frame_views(order, knots, start_ns, dt_ns, period_ns, intrinsics, exposure_n
 
 
 ALL_TIME_NS = (-2 ** 62, 2 ** 62)
+# what a cell of a time surface holds when no event has reached it (BackendEvaluator.reconstruct_surface_get): INT64_MIN
+SURFACE_EMPTY = -2 ** 63
 
 
 def crop_view(quat_xyzw, fov_deg, Wv, Hv, t_range_ns=ALL_TIME_NS):

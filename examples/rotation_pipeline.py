@@ -184,7 +184,8 @@ def reconstruct_panorama(be, traj, x, y, t, prm, store=None, knots=None):
 
 def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefix=None, reconstruct=False, refine_global=False,
                  refine_bound=False, refine_native=False, freeze_head=None, refine_online=None, online_free=8, export_warped=None,
-                 polarity_map=None, frames=None, frame_ms=20.0, crop=None, voxels=None, voxel_ms=20.0, voxel_bins=5):
+                 polarity_map=None, frames=None, frame_ms=20.0, crop=None, voxels=None, voxel_ms=20.0, voxel_bins=5,
+                 time_surfaces=None, surface_ms=20.0, surface_tau_ms=None):
     """stream: synth.EventStream (or anything with x, y, t_ns, W, H, fx, fy, cx, cy, lut).  Returns a dict.
     display_prefix: write the final panorama with the last pose's FOV and the last packet's local-IWE pair there.
     reconstruct: after the last window, re-warp all events along the whole refined trajectory (res["recon"]; with
@@ -211,9 +212,14 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
     voxels = PATH (implies reconstruct): the motion-compensated, polarity-signed voxel grids of the final trajectory -- one grid of
     voxel_bins time bins per voxel_ms milliseconds, with the sensor's size and intrinsics and the spline's pose at the slice centre
     (trajectory.voxel_grids, BackendEvaluator.reconstruct_voxel_*) -- written as one .npy of shape (G, B, H, W), the input format of
-    event-based networks; res["voxels"] = (volumes, counts).  Polarities as for polarity_map."""
+    event-based networks; res["voxels"] = (volumes, counts).  Polarities as for polarity_map.
+    time_surfaces = PATH (implies reconstruct): the motion-compensated time surfaces of the final trajectory -- per surface_ms
+    milliseconds one surface with the sensor's size and intrinsics and the spline's pose at the slice centre (trajectory.frame_views,
+    BackendEvaluator.reconstruct_surface_*), ON and OFF channels, read through exp(-(t_hi - T) / tau) at its own t_hi with tau =
+    surface_tau_ms (default: surface_ms) -- written as one .npy of shape (S, 2, H, W) fp32; res["time_surfaces"] = (decayed, counts).
+    Polarities as for polarity_map."""
     reconstruct = (reconstruct or export_warped is not None or polarity_map is not None or frames is not None or crop is not None
-                   or voxels is not None)
+                   or voxels is not None or time_surfaces is not None)
     prm = prm or Params()
     x, y, t = stream.x, stream.y, stream.t_ns
     n_total = len(t)
@@ -225,13 +231,14 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
         fe.set_deterministic(True)
         be.set_deterministic(True)
     pol = None
-    if polarity_map is not None or voxels is not None:
+    if polarity_map is not None or voxels is not None or time_surfaces is not None:
         pol = getattr(stream, "polarity", None)
         pol = np.random.default_rng(POLARITY_SEED).integers(0, 2, n_total).astype(np.uint8) if pol is None else np.asarray(pol)
     store = None
     if use_event_store:
         store = evaluator.EventStore(stream.W, stream.H, n_total)
-        store.push(x, y, t, polarity=pol)  # (with polarity: a byte array beside the events, which nothing but reconstruct_pol_add_from and reconstruct_voxel_add_from read)
+        store.push(x, y, t, polarity=pol)  # (with polarity: a byte array beside the events, which nothing but reconstruct_pol_add_from, reconstruct_voxel_add_from and
+        # reconstruct_surface_add_from read)
 
     # ------------------------------------------------------------------ front end: packets (pushEvent)
     dt_av = _dur_ns(prm.dt_ang_vel)
@@ -493,6 +500,27 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
                 log("voxels: %d grids of %.3g ms x %d bins, %d to %d events each, in %.2f ms -> %s %s" %
                     (len(grids), voxel_ms, voxel_bins, int(counts.min()), int(counts.max()), (time.perf_counter() - t0) * 1e3, path,
                      volumes.shape))
+        if time_surfaces is not None:  # when every scene point last fired, per polarity: one surface per surface_ms, decayed at its end
+            t0 = time.perf_counter()
+            views = trajectory.frame_views(traj.order, knots_rec, traj.t_beg_ns, traj.dt_ns, int(round(surface_ms * 1e6)),
+                                           (stream.fx, stream.fy, stream.cx, stream.cy), t_beg_ns=int(t[i_rec]),
+                                           t_end_ns=int(t[i_rec + n_rec - 1]) + 1)
+            tau_ms = surface_ms if surface_tau_ms is None else surface_tau_ms
+            be.reconstruct_surface_begin(views, stream.W, stream.H, by_polarity=True)
+            if store is not None:
+                be.reconstruct_surface_add_from(store, i_rec, n_rec)
+            else:
+                be.reconstruct_surface_add(x[i_rec:i_rec + n_rec], y[i_rec:i_rec + n_rec], t[i_rec:i_rec + n_rec], pol[i_rec:i_rec + n_rec])
+            decayed = be.reconstruct_surface_decay(tau_ms * 1e6)
+            counts = be.reconstruct_surface_get(0, len(views), with_counts=True)[1]
+            be.reconstruct_surface_end()
+            res["time_surfaces"] = (decayed, counts)
+            path = time_surfaces if time_surfaces.endswith(".npy") else time_surfaces + ".npy"
+            np.save(path, decayed)
+            if log:
+                log("time surfaces: %d of %.3g ms, tau %.3g ms, %d to %d events each, in %.2f ms -> %s %s" %
+                    (len(views), surface_ms, tau_ms, int(counts.min()), int(counts.max()), (time.perf_counter() - t0) * 1e3, path,
+                     decayed.shape))
         be.reconstruct_end()
     return res
 
@@ -570,6 +598,13 @@ def main():
                          "as ONE .npy of shape (G, B, H, W) (implies --reconstruct; polarities as for --polarity-map)")
     ap.add_argument("--voxel-ms", type=float, metavar="MS", default=20.0, help="with --voxels: the time range of a grid in milliseconds")
     ap.add_argument("--voxel-bins", type=int, metavar="B", default=5, help="with --voxels: time bins per grid, 1 to 64")
+    ap.add_argument("--time-surfaces", metavar="PATH", default=None,
+                    help="after the reconstruction, write the motion-compensated time surfaces of the final trajectory, decayed at "
+                         "each surface's own end, as ONE .npy of shape (S, 2, H, W) fp32 (implies --reconstruct; polarities as for "
+                         "--polarity-map)")
+    ap.add_argument("--surface-ms", type=float, metavar="MS", default=20.0, help="with --time-surfaces: the time range of a surface in milliseconds")
+    ap.add_argument("--surface-tau-ms", type=float, metavar="MS", default=None,
+                    help="with --time-surfaces: the decay constant in milliseconds (default: --surface-ms)")
     ap.add_argument("--refine-global", action="store_true",
                     help="after the last window, one bundle adjustment over the whole trajectory (--reconstruct then uses its result)")
     ap.add_argument("--refine-bound", action="store_true",
@@ -591,6 +626,8 @@ def main():
         ap.error("--frame-ms must be > 0")
     if not a.voxel_ms > 0 or not 1 <= a.voxel_bins <= 64:
         ap.error("--voxel-ms must be > 0 and --voxel-bins in [1, 64]")
+    if not a.surface_ms > 0 or (a.surface_tau_ms is not None and not a.surface_tau_ms > 0):
+        ap.error("--surface-ms and --surface-tau-ms must be > 0")
     stream = synth.event_stream(a.rate, a.seconds, 240, 180, 200.0, 200.0, 119.5, 89.5, omega_mean=(0.2, 1.8, 0.3),
                                 omega_amp=(1.0, 0.8, 1.0))
     prm = Params()
@@ -601,7 +638,7 @@ def main():
                        refine_global=a.refine_global or a.refine_native, refine_bound=a.refine_bound, refine_native=a.refine_native,
                        freeze_head=a.freeze_head, refine_online=a.refine_online, online_free=a.online_free, export_warped=a.export_warped,
                        polarity_map=a.polarity_map, frames=a.frames, frame_ms=a.frame_ms, crop=a.crop, voxels=a.voxels, voxel_ms=a.voxel_ms,
-                       voxel_bins=a.voxel_bins)
+                       voxel_bins=a.voxel_bins, time_surfaces=a.time_surfaces, surface_ms=a.surface_ms, surface_tau_ms=a.surface_tau_ms)
     wall = time.perf_counter() - t0
     m = evaluate_against_truth(stream, res)
     print("%.2f s of events (%d) processed in %.2f s wall" % (a.seconds, len(stream.x), wall))

@@ -534,6 +534,79 @@ int cmx_backend_recon_voxel_get(cmx_ctx *ctx, int first_grid, int count, float *
 int cmx_backend_recon_voxel_get_device(cmx_ctx *ctx, int first_grid, int count, float *d_out /* device pointer on the context's device */);
 int cmx_backend_recon_voxel_reset(cmx_ctx *ctx);
 int cmx_backend_recon_voxel_end(cmx_ctx *ctx);
+/* Time surfaces (surfaces of active events), motion-compensated: for every pixel the timestamp of the most recent event that landed
+ * there, per polarity -- what corner detectors, HATS / TORE-style descriptors and network front ends read, usually through an
+ * exponential decay.  A set of S surfaces is attached to an open reconstruction; a surface is a cmx_recon_view -- orientation,
+ * intrinsics, [t_lo_ns, t_hi_ns) -- and trajectory.frame_views' and crop_view's output can be passed as it is.
+ *     recon_surface_begin(surfaces)   recon_surface_add*(events, polarity) ...   recon_surface_get / _get_device / _decay /
+ *     _decay_device (any number of times)   [recon_surface_reset]   recon_surface_end
+ *   layout     C = by_polarity ? 2 : 1 channels; cells[s][c][yy][xx], contiguous.  Channel 0 is ON (polarity != 0), channel 1 is
+ *              OFF -- the order of pol_get's arguments.  With by_polarity == 0 there is one channel and polarity is neither needed
+ *              nor read.
+ *   surface_begin  needs an open reconstruction.  Validates everything, then allocates all or nothing: the surfaces on the device as
+ *              view_begin copies views, n_surfaces * C planes of Wv x Hv int64 cells, every one set to INT64_MIN ("no event"), and
+ *              one vote counter per surface.  A second surface_begin starts over.
+ *              CMX_ERR_INVALID_ARG: every rule of view_begin (Wv or Hv outside [4, 8192]; a quaternion that is zero or not finite;
+ *              fx or fy not finite or <= 0; cx or cy not finite; t_lo_ns >= t_hi_ns); n_surfaces outside [1, 4096];
+ *              n_surfaces * C * Wv * Hv > 2^28 (cells of 8 bytes: 2 GB, the footprint of a view set's fixed-point twins);
+ *              t_lo_ns == INT64_MIN (the empty marker can then never be a vote).  A range that stands for all time
+ *              (trajectory.ALL_TIME_NS, crop_view's default) is ACCEPTED, as view_begin accepts it and voxel_begin does not: a
+ *              surface has no bin axis.  Ranges may overlap, nest or leave gaps.
+ *   surface_add*  ONE call = the vote loop of add* over exactly the events handed in -- the same batches, batch times and batch
+ *              poses, sampling restarting at every batch start, the lone trailing event skipped, the same validation and status
+ *              codes, complete before the first vote: a call that fails validation adds nothing.  Per sampled event i, in fp64:
+ *                  ray_w = R_batch * bearing                        (the vote kernels' own function, the pose at the BATCH time)
+ *                  for every surface with t_lo_ns <= t_i < t_hi_ns  (t_i the event's OWN timestamp, compared as integers -- the
+ *                                                                    voxel rule):
+ *                      projection and vote test exactly as in view_add* above  (v.z > 0 && 1 <= u < Wv-2 && 1 <= w < Hv-2, in
+ *                          floating point before any conversion)
+ *                      cx = (int)(u + 0.5),  cy = (int)(w + 0.5)    (the NEAREST pixel; inside the plane because of the test)
+ *                      c  = by_polarity && polarity == 0 ? 1 : 0
+ *                      cells[s][c][cy][cx] = max(cells[s][c][cy][cx], t_i)   as a signed 64-bit integer
+ *                      one count for the surface
+ *              Polarity: pol[i] (one byte per event; NULL is allowed only when by_polarity == 0), the byte at off_polarity of record
+ *              i (not looked at for a merged set), or the store's own.
+ *   surface_get  cells = count * C planes of Wv x Hv int64 for surfaces [first, first + count), or NULL: absolute nanoseconds, and
+ *              INT64_MIN in a cell no event reached; n_voted = count counters (events: one per event and surface) or NULL.
+ *              CMX_ERR_INVALID_ARG when the range leaves the set.  Accumulation may continue.
+ *   surface_get_device  the same cells into a device pointer on the context's device (e.g. a torch int64 tensor): nothing crosses the
+ *              host.  Runs on the context's stream and returns when d_cells is complete.
+ *   surface_decay / _decay_device  one device pass writes fp32 in the layout above, to the host (staged through device memory of the
+ *              set's own) or to a device pointer on the context's device.  With t_ref of surface s = t_ref_ns[s - first], or that
+ *              surface's t_hi_ns when t_ref_ns is NULL (a host array in both forms), and T the cell:
+ *                  T == INT64_MIN   ->  0.0f
+ *                  T >= t_ref       ->  1.0f
+ *                  otherwise        ->  (float)exp(-((double)(uint64_t)(t_ref - T) / tau_ns))
+ *              the difference formed without signed overflow, quotient and exp in fp64, rounded once.  Results below FLT_MIN may be
+ *              flushed to zero or left denormal.  CMX_ERR_INVALID_ARG: tau_ns not finite or <= 0; a range outside the set; a null
+ *              output with count > 0.  The cells stay as they are.
+ *   surface_reset  sets every cell back to INT64_MIN and the counters to zero and keeps the surfaces.   surface_end frees the set
+ *              (without a set: CMX_OK).
+ *   state      as for the views and the voxel grids: the calls read the knots the reconstruction holds NOW and nothing else of it,
+ *              and write only the surface cells and their counters.  recon_begin and recon_end free the set; restart and
+ *              surface_reset clear it to empty; EVERY other call leaves it alone.  A view set, a voxel set and a surface set may be
+ *              open together.  The calls work with a gradient pass open, with events bound, after freeze_head and after
+ *              release_head.
+ *   status     CMX_ERR_STATE before recon_begin, before surface_begin (add*, get*, decay*, reset), on a group handle, and for
+ *              add_from on a store without polarity when the set is by polarity; CMX_ERR_INVALID_ARG for pol == NULL with a
+ *              by-polarity set and for off_polarity outside the record.
+ * Reproducibility: a cell is a maximum of integers, which commutes and is idempotent -- bitwise identical from run to run, through
+ * the three ingest paths, for any slicing at batch multiples, for the calls of a split IN ANY ORDER, and whatever other surfaces are
+ * in the set, with CMX_OPT_DETERMINISTIC 0 or 1: the option changes nothing here and there is no fixed-point twin. */
+int cmx_backend_recon_surface_begin(cmx_ctx *ctx, int Wv, int Hv, int by_polarity, int n_surfaces, const cmx_recon_view *surfaces);
+int cmx_backend_recon_surface_add(cmx_ctx *ctx, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns,
+                                  const uint8_t *pol /* n bytes; may be NULL only when by_polarity == 0 */);
+int cmx_backend_recon_surface_add_aos(cmx_ctx *ctx, int64_t n, const void *events, const cmx_aos_layout *layout, size_t off_polarity);
+int cmx_backend_recon_surface_add_from(cmx_ctx *ctx, const cmx_events *ev, int64_t first, int64_t count);
+int cmx_backend_recon_surface_get(cmx_ctx *ctx, int first, int count, int64_t *cells /* count*C*Hv*Wv or NULL */,
+                                  int64_t *n_voted /* count or NULL */);
+int cmx_backend_recon_surface_get_device(cmx_ctx *ctx, int first, int count, int64_t *d_cells /* device pointer on the context's device */);
+int cmx_backend_recon_surface_decay(cmx_ctx *ctx, int first, int count, const int64_t *t_ref_ns /* count, or NULL */, double tau_ns,
+                                    float *out /* count*C*Hv*Wv */);
+int cmx_backend_recon_surface_decay_device(cmx_ctx *ctx, int first, int count, const int64_t *t_ref_ns /* host: count, or NULL */,
+                                           double tau_ns, float *d_out /* device pointer on the context's device */);
+int cmx_backend_recon_surface_reset(cmx_ctx *ctx);
+int cmx_backend_recon_surface_end(cmx_ctx *ctx);
 /* Whole-trajectory contrast and its gradient with respect to a LEFT increment of every control pose, on top of an open
  * reconstruction -- the evaluation one bundle adjustment over the whole recording needs, for a spline of any knot count:
  *     recon_begin   recon_add*(events) ...   recon_contrast(want_grad)   recon_grad_add*(the same events) ...   recon_grad_get
