@@ -470,67 +470,61 @@ struct ReconWarpArgs {
   int vec;                   // xy_out is aligned for one 16- / 8-byte pair store per lane
 };
 void launch_recon_warp(const ReconWarpArgs &g, hipStream_t s);
-// pinhole views (cmx_backend_recon_view_*): the vote loop of launch_recon_votes with M virtual pinhole cameras as its targets.  An
-// event's world ray is formed once and voted into every view whose time range holds its batch time; planes / fixed hold n_views
-// planes of Wv x Hv, n_voted one counter per view.  ev.plane / ev.fixed / ev.n_inside / ev.pol are not used.
-struct ReconViewDev {        // one view as the kernel reads it: 16 eight-byte words
+// target sets (cmx_backend_recon_view_* / _voxel_* / _surface_*): the vote loop of launch_recon_votes with the n targets of a set --
+// virtual pinhole cameras with a time range each -- as its targets.  An event's world ray is formed once and voted into every
+// target whose range holds its time.  What the three kinds of set share is ReconSetArgs; each adds a small tail of its own.
+// ev.plane / ev.fixed / ev.n_inside are not used (ev.pol: by the sets that read polarity, as in launch_recon_votes_pol).
+struct ReconViewDev {        // one target as the kernel reads it: 16 eight-byte words
   double Rt[9];              // R(quat)^T, row-major: ray_cam = Rt ray_world
   double fx, fy, cx, cy;
-  long long t_lo, t_hi;      // votes of the batches with t_lo <= batch time < t_hi
-  long long index;           // of the view in the set: its plane and its counter
+  long long t_lo, t_hi;      // votes of the events (views: of the batches) with t_lo <= time < t_hi
+  long long index;           // of the target in the set: its planes and its counter
 };
 struct ReconViewRange { long long t_lo, t_hi; };  // the same range in a table of its own: what a workgroup scans
-// views a workgroup holds in LDS at a time; more that meet its run are taken chunk by chunk.  A run of 2048 events meets one or two
-// frames of a video, three when the exposure is twice the period; every view beyond that costs its projection anyway, next to which
+// targets a workgroup holds in LDS at a time; more that meet its run are taken chunk by chunk.  A run of 2048 events meets one or two
+// frames of a video, three when the exposure is twice the period; every target beyond that costs its projection anyway, next to which
 // the chunk's two barriers and the re-read bearing are small
 constexpr int kReconViewChunk = 3;
-struct ReconViewArgs {
+struct ReconSetArgs {
   ReconArgs ev;
-  const ReconViewDev *views;       // [n_views]
-  const ReconViewRange *ranges;    // [n_views]
-  int n_views, Wv, Hv;
-  float *planes;                   // [n_views][Hv * Wv]: fp32 atomics ...
+  const long long *ev_t;           // the events' own timestamps, indexed as ev.xy is (voxel grids, surfaces; views: not read)
+  const void *entries;             // [n] the set's entry type: ReconViewDev (views, surfaces) or ReconVoxelDev
+  const ReconViewRange *ranges;    // [n]
+  int n, Wv, Hv;
+  unsigned long long *n_voted;     // [n] events that voted into each target (once per event, whatever the cells it touched)
+};
+// pinhole views: an event votes into every view whose range holds its BATCH time, with the four bilinear adds of the panorama vote
+struct ReconViewArgs {
+  ReconSetArgs set;
+  float *planes;                   // [n][Hv * Wv]: fp32 atomics ...
   unsigned long long *fixed;       // ... or, when set, 64-bit integer adds into the 2^-30 fixed-point twins
-  unsigned long long *n_voted;     // [n_views] events that voted into each view
 };
 void launch_recon_view_votes(const ReconViewArgs &g, hipStream_t s);
-// voxel grids (cmx_backend_recon_voxel_*): the vote loop of launch_recon_view_votes with G grids of n_bins planes as its targets.
-// A grid is a view plus the scale of its bin axis; an event votes into every grid whose range holds its OWN timestamp -- ev_t, read
-// at the index its packed word is read at -- with the bilinear weights of the view vote times the triangular weight of each of
-// its two neighbouring bins, negated for an OFF event of a signed set (polarity as in launch_recon_votes_pol: ev.pol, or bit 31 of
-// the word).  planes / fixed hold n_grids * n_bins planes of Wv x Hv, grid-major; the fixed-point cells are two's complement.
+// voxel grids: a grid is a view plus the scale of its bin axis; an event votes into every grid whose range holds its OWN timestamp
+// with the bilinear weights of the view vote times the triangular weight of each of its two neighbouring bins, negated for an OFF
+// event of a signed set.  planes / fixed hold n * n_bins planes of Wv x Hv, grid-major; the fixed-point cells are two's complement.
 struct ReconVoxelDev {       // one grid as the kernel reads it: 17 eight-byte words
   ReconViewDev v;
   double scale;              // (n_bins - 1) / (t_hi - t_lo)
 };
 struct ReconVoxelArgs {
-  ReconArgs ev;
-  const long long *ev_t;           // the events' own timestamps, indexed as ev.xy is
-  const ReconVoxelDev *grids;      // [n_grids]
-  const ReconViewRange *ranges;    // [n_grids]
-  int n_grids, Wv, Hv, n_bins;
-  int is_signed;                   // 0: every event votes +1 and polarity is not read
-  float *planes;                   // [n_grids][n_bins][Hv * Wv]: fp32 atomics ...
+  ReconSetArgs set;
+  float *planes;                   // [n][n_bins][Hv * Wv]: fp32 atomics ...
   unsigned long long *fixed;       // ... or, when set, 64-bit integer adds into the 2^-30 fixed-point twins
-  unsigned long long *n_voted;     // [n_grids] events that voted into each grid (once per event, not per bin)
+  int n_bins;
+  int is_signed;                   // 0: every event votes +1 and polarity is not read
 };
 void launch_recon_voxel_votes(const ReconVoxelArgs &g, hipStream_t s);
 void launch_recon_fixed_to_float_signed(const unsigned long long *fixed, float *plane, size_t n, hipStream_t s);  // two's complement cells
-// time surfaces (cmx_backend_recon_surface_*): the vote loop of launch_recon_voxel_votes with S surfaces of C channels as its targets.
-// A surface is a view; an event votes into every surface whose range holds its OWN timestamp -- ev_t, indexed as ev.xy is -- and the
-// vote is ONE signed 64-bit integer max of that timestamp at the NEAREST pixel of the projection, in channel 1 for an OFF event of a
-// by-polarity set (polarity as in launch_recon_votes_pol: ev.pol, or bit 31 of the word) and in channel 0 otherwise.  A max commutes
-// and is idempotent: the cells are bitwise reproducible in every mode and there is no fixed-point form.
+// time surfaces: a surface is a view; an event votes into every surface whose range holds its OWN timestamp, and the vote is ONE
+// signed 64-bit integer max of that timestamp at the NEAREST pixel of the projection, in channel 1 for an OFF event of a by-polarity
+// set and in channel 0 otherwise.  A max commutes and is idempotent: the cells are bitwise reproducible in every mode and there is
+// no fixed-point form.
 constexpr long long kReconSurfaceEmpty = -0x7fffffffffffffffLL - 1;  // a cell no event has reached (never a vote: surface_begin refuses it as t_lo)
 struct ReconSurfaceArgs {
-  ReconArgs ev;
-  const long long *ev_t;           // the events' own timestamps, indexed as ev.xy is
-  const ReconViewDev *surfaces;    // [n_surfaces]
-  const ReconViewRange *ranges;    // [n_surfaces]
-  int n_surfaces, Wv, Hv;
+  ReconSetArgs set;
+  long long *cells;                // [n][by_polarity ? 2 : 1][Hv * Wv]
   int by_polarity;                 // 0: one channel and polarity is not read
-  long long *cells;                // [n_surfaces][by_polarity ? 2 : 1][Hv * Wv]
-  unsigned long long *n_voted;     // [n_surfaces] events that voted into each surface
 };
 void launch_recon_surface_votes(const ReconSurfaceArgs &g, hipStream_t s);
 void launch_recon_surface_fill(long long *cells, size_t n, hipStream_t s);  // every cell = kReconSurfaceEmpty (no byte memset writes that)

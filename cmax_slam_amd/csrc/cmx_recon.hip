@@ -10,10 +10,10 @@
 //                   without the old / new split).  No pose table in global memory, no tile sort, no second launch.
 //                   POL (cmx_backend_recon_pol_add*): the same walk, the same cell and weights, but the four adds go to the ON or
 //                   the OFF plane by the event's polarity, and the voting events are counted per plane.
-//   recon_view_votes / recon_voxel_votes   the same walk with the planes of M pinhole views, or the bins of G voxel grids, as the
-//                   targets of the votes (further down, with their own descriptions)
-//   recon_surface_votes   the same walk again with the cells of S time surfaces as the targets: one 64-bit integer max per vote;
-//                   recon_surface_fill and recon_surface_decay beside it
+//   recon_set_votes   the same walk with the targets of a set as the targets of the votes -- the planes of M pinhole views
+//                   (recon_view_votes), the bins of G voxel grids (recon_voxel_votes), the cells of S time surfaces
+//                   (recon_surface_votes: one 64-bit integer max per vote) -- ONE skeleton, further down with its description, and
+//                   a Target per set; recon_surface_fill and recon_surface_decay beside it
 //   recon_fixed_to_float   deterministic mode: the 2^-30 fixed-point plane as fp32, leaving it as it is (accumulation goes on)
 #include "../../include/cmax_hip.h"
 #include "cmx_internal.hpp"
@@ -160,24 +160,33 @@ void launch_recon_votes_pol(const ReconArgs &a, hipStream_t s) {
   }
 }
 
-// ---------------------------------------------------------------------------------------------- pinhole views
-// recon_view_votes   cmx_backend_recon_view_add*: the run structure of recon_votes -- the first lanes evaluate the run's batch poses into
-//                LDS, and keep the batch times beside them -- with M virtual pinhole cameras as the targets of the votes.  After the
-//                barrier the workgroup scans the table of view ranges ONCE, 16 bytes per view and lane, and lists the views whose
-//                [t_lo, t_hi) meets the span of its batch times; the per-event cost therefore depends on the views a run meets
-//                (one or two for disjoint frames), not on n_views.  The listed views are taken kReconViewChunk at a time: their
-//                128-byte entries (R^T, intrinsics, range, index) are copied into LDS, one barrier, then all lanes walk the run's
-//                events: the world ray R_batch * bearing is formed once per event and chunk (be_rotate, the vote kernel's own
-//                function on the vote kernel's own pose), and for every view of the chunk that holds the batch time it is turned
-//                into the camera, projected, tested in floating point and voted with the four bilinear adds of vote4_global /
-//                vote4_global_fix into that view's plane.  A run that meets more views than a chunk holds walks its events again
-//                for the next chunk (the bearing and the pose are re-read; the votes of a view do not depend on the chunking).
-//                Votes per view are counted in LDS and leave by one global atomic per listed view and workgroup.
-constexpr int kReconMaxViews = 4096;  // (cmx_backend_recon_view_begin refuses more: the list of a workgroup holds any subset)
-static_assert(sizeof(ReconViewDev) == 128 && sizeof(ReconViewRange) == 16, "view entries are copied word by word");
+// ---------------------------------------------------------------------------------------------- target sets: views, voxel grids, surfaces
+// recon_set_votes   cmx_backend_recon_view_add* / _voxel_add* / _surface_add*: the run structure of recon_votes -- the first lanes
+//                evaluate the run's batch poses into LDS -- with the n targets of a set, virtual pinhole cameras with a time range
+//                each, as the targets of the votes.  Beside the poses the workgroup forms the span [tmin, tmax] of its run's times:
+//                of the batch times, kept in LDS, for a set that votes by batch time, or of the EVENT times (the per-event stream
+//                ev_t, read at the index of the packed word; every event is looked at, so the span holds for any order of the
+//                events -- and a batch of 5000 events spans several targets) by wave reduction and one LDS atomic per wave.  After
+//                the barrier the workgroup scans the table of ranges ONCE, 16 bytes per target and lane, and lists the targets whose
+//                [t_lo, t_hi) meets that span; the per-event cost therefore depends on the targets a run meets (one or two for
+//                disjoint frames), not on n.  The listed targets are taken kReconViewChunk at a time: their entries (R^T,
+//                intrinsics, range, index, and what the set adds) are copied into LDS word by word, one barrier, then all lanes walk
+//                the run's events: the world ray R_batch * bearing is formed once per event and chunk (be_rotate, the vote kernel's
+//                own function on the vote kernel's own pose), and for every target of the chunk that holds the time it is turned
+//                into the camera, projected, tested in floating point (recon_view_project) and voted as the set's Target says.  A
+//                run that meets more targets than a chunk holds walks its events again for the next chunk (the bearing and the pose
+//                are re-read; the votes of a target do not depend on the chunking).  Votes per target are counted in LDS and leave
+//                by one global atomic per listed target and workgroup.
+//                What a Target supplies: Args (ReconSetArgs and its tail) and Entry (whole 8-byte words, its view first);
+//                kEventSpan (span and membership by ev_t, not by batch time); reads_polarity (whether the event's polarity is
+//                looked at: the store's byte, or bit 31 of the word); vote (one hit).  What stays per set, once, here: a workgroup's
+//                list holds any subset of kReconMaxViews targets (the begin calls refuse more); an entry is 128 or 136 bytes and a
+//                chunk of them has at most one word per lane.
+constexpr int kReconMaxViews = 4096;
+static_assert(sizeof(ReconViewDev) == 128 && sizeof(ReconVoxelDev) == 136 && sizeof(ReconViewRange) == 16, "set entries are copied word by word");
 
-// a world ray in one view (shared with the voxel grids): turned into the camera and projected, and the vote test -- in floating
-// point, before any conversion: a NaN fails it, and only values inside the plane are ever cast
+// a world ray in one view: turned into the camera and projected, and the vote test -- in floating point, before any conversion: a
+// NaN fails it, and only values inside the plane are ever cast
 struct ReconViewHit { double u, w; bool ok; };
 __device__ __forceinline__ ReconViewHit recon_view_project(const ReconViewDev &V, double rx, double ry, double rz, double u_hi, double w_hi) {
   double x, y, z;
@@ -188,17 +197,90 @@ __device__ __forceinline__ ReconViewHit recon_view_project(const ReconViewDev &V
   return ReconViewHit{u, w, z > 0.0 && u >= 1.0 && u < u_hi && w >= 1.0 && w < w_hi};
 }
 
-template <int N, bool FIXED>
-__global__ __launch_bounds__(kReconThreads) void recon_view_votes_kernel(const ReconViewArgs g) {
-  constexpr int kWords = sizeof(ReconViewDev) / 8;
+// pinhole views: the four bilinear adds of vote4_global / vote4_global_fix into the view's plane
+template <bool FIXED>
+struct ReconViewTarget {
+  using Args = ReconViewArgs;
+  using Entry = ReconViewDev;
+  static constexpr bool kEventSpan = false;
+  static __device__ __forceinline__ const ReconViewDev &view(const Entry &V) { return V; }
+  static __device__ __forceinline__ bool reads_polarity(const Args &) { return false; }
+  static __device__ __forceinline__ void vote(const Args &g, const Entry &V, const ReconViewHit &p, long long, bool, size_t np) {
+    const int xx = (int)p.u, yy = (int)p.w;
+    const float dx = (float)(p.u - xx), dy = (float)(p.w - yy);
+    const size_t at = (size_t)V.index * np;
+    if (FIXED) vote4_global_fix(g.fixed + at, g.set.Wv, xx, yy, dx, dy);
+    else vote4_global(g.planes + at, g.set.Wv, xx, yy, dx, dy);
+  }
+};
+
+// voxel grids: the view vote's cell and weights, tau = (t_i - t_lo) * scale in fp64, b0 = min((int)tau, n_bins - 2),
+// f = (float)(tau - b0), and the four bilinear adds times 1 - f into bin b0 and times f into bin b0 + 1 (n_bins == 1: one bin, weight
+// 1), negated for an OFF event of a signed set.  A bin whose weight is zero is skipped: it would add zeros.  Votes go to global
+// memory: the two active bins of a grid are two planes, which no LDS window holds.
+template <bool FIXED>
+struct ReconVoxelTarget {
+  using Args = ReconVoxelArgs;
+  using Entry = ReconVoxelDev;
+  static constexpr bool kEventSpan = true;
+  static __device__ __forceinline__ const ReconViewDev &view(const Entry &G) { return G.v; }
+  static __device__ __forceinline__ bool reads_polarity(const Args &g) { return g.is_signed != 0; }
+  static __device__ __forceinline__ void vote(const Args &g, const Entry &G, const ReconViewHit &p, long long ti, bool neg, size_t np) {
+    const int xx = (int)p.u, yy = (int)p.w;
+    const float dx = (float)(p.u - xx), dy = (float)(p.w - yy);
+    const int nbins = g.n_bins;
+    int bin = 0;
+    float w0 = 1.f, w1 = 0.f;
+    if (nbins >= 2) {
+      const double tau = (double)(ti - G.v.t_lo) * G.scale;  // (0 <= tau < n_bins - 1, up to its rounding: the cast is safe)
+      bin = (int)tau;
+      bin = bin < nbins - 2 ? bin : nbins - 2;
+      w1 = (float)(tau - bin);
+      w0 = 1.f - w1;
+    }
+    const size_t at = ((size_t)G.v.index * nbins + bin) * np;
+    if (FIXED) {
+      if (w0 != 0.f) vote4_global_fix_w(g.fixed + at, g.set.Wv, xx, yy, dx, dy, w0, neg);
+      if (w1 != 0.f) vote4_global_fix_w(g.fixed + at + np, g.set.Wv, xx, yy, dx, dy, w1, neg);
+    } else {
+      if (w0 != 0.f) vote4_global_w(g.planes + at, g.set.Wv, xx, yy, dx, dy, w0, neg);
+      if (w1 != 0.f) vote4_global_w(g.planes + at + np, g.set.Wv, xx, yy, dx, dy, w1, neg);
+    }
+  }
+};
+
+// time surfaces: the NEAREST pixel (int)(u + 0.5), (int)(w + 0.5) -- inside the plane because of the test -- and ONE signed 64-bit
+// atomic max of t_i there, in channel 1 for an OFF event of a by-polarity set and in channel 0 otherwise.  The result of the max is
+// not read.  No fixed-point form: a max of integers commutes and is idempotent.
+struct ReconSurfaceTarget {
+  using Args = ReconSurfaceArgs;
+  using Entry = ReconViewDev;
+  static constexpr bool kEventSpan = true;
+  static __device__ __forceinline__ const ReconViewDev &view(const Entry &V) { return V; }
+  static __device__ __forceinline__ bool reads_polarity(const Args &g) { return g.by_polarity != 0; }
+  static __device__ __forceinline__ void vote(const Args &g, const Entry &V, const ReconViewHit &p, long long ti, bool off, size_t np) {
+    const int cx = (int)(p.u + 0.5), cy = (int)(p.w + 0.5);  // (1 <= cx <= Wv - 2 and 1 <= cy <= Hv - 2: the test of the projection)
+    const size_t per_surface = g.by_polarity ? 2 * np : np;
+    long long *cell = g.cells + (size_t)V.index * per_surface + (off ? np : 0) + (size_t)cy * g.set.Wv + cx;
+    atomicMax(cell, ti);
+  }
+};
+
+template <int N, class Target>
+__device__ __forceinline__ void recon_set_votes(const typename Target::Args &g) {
+  using Entry = typename Target::Entry;
+  constexpr bool kEventSpan = Target::kEventSpan;
+  constexpr int kWords = sizeof(Entry) / 8;
+  static_assert(kReconViewChunk * kWords <= kReconThreads, "one lane per word of a chunk");
   __shared__ double sh_R[(kReconMaxRun + 2) * 9];
-  __shared__ long long sh_bt[kReconMaxRun + 2];
-  __shared__ ReconViewDev sh_view[kReconViewChunk];
+  __shared__ long long sh_bt[kReconMaxRun + 2];  // (batch-time sets alone: the event-time form never names it, and it is not allocated)
+  __shared__ Entry sh_entry[kReconViewChunk];
   __shared__ unsigned sh_cnt[kReconViewChunk];
   __shared__ unsigned short sh_match[kReconMaxViews];
   __shared__ unsigned sh_nmatch;
   __shared__ long long sh_tmin, sh_tmax;
-  const ReconArgs &a = g.ev;
+  const ReconSetArgs &st = g.set;
+  const ReconArgs &a = st.ev;
   const int tid = threadIdx.x;
   const int e0 = blockIdx.x * a.run;  // (the grid covers [0, n): e0 < n)
   const int e1 = (a.n - e0 > a.run) ? e0 + a.run : a.n;
@@ -211,146 +293,34 @@ __global__ __launch_bounds__(kReconThreads) void recon_view_votes_kernel(const R
     const int b = b0 + j < a.nb ? b0 + j : a.nb - 1;
     const long long t = a.batch_t[b];
     recon_pose<N>(a, t, sh_R + 9 * j);
-    sh_bt[j] = t;
-    atomicMin(&sh_tmin, t);
-    atomicMax(&sh_tmax, t);
-  }
-  __syncthreads();
-  // the views that meet the run's batch times [tmin, tmax], in no particular order (integer sums and counts do not depend on it)
-  const long long tmin = sh_tmin, tmax = sh_tmax;
-  for (int v = tid; v < g.n_views; v += kReconThreads) {
-    const ReconViewRange r = g.ranges[v];
-    if (r.t_lo <= tmax && r.t_hi > tmin) {
-      const unsigned pos = atomicAdd(&sh_nmatch, 1u);
-      if (pos < (unsigned)kReconMaxViews) sh_match[pos] = (unsigned short)v;
+    if constexpr (!kEventSpan) {
+      sh_bt[j] = t;
+      atomicMin(&sh_tmin, t);
+      atomicMax(&sh_tmax, t);
     }
   }
-  __syncthreads();
-  int nmatch = (int)sh_nmatch;
-  nmatch = nmatch < kReconMaxViews ? nmatch : kReconMaxViews;
-  const double u_hi = (double)(g.Wv - 2), w_hi = (double)(g.Hv - 2);
-  const size_t np = (size_t)g.Hv * g.Wv;
-  for (int c0 = 0; c0 < nmatch; c0 += kReconViewChunk) {  // (uniform: nmatch is the workgroup's)
-    const int nl = nmatch - c0 < kReconViewChunk ? nmatch - c0 : kReconViewChunk;
-    if (tid < nl * kWords) {
-      const int k = tid / kWords, wd = tid - k * kWords;
-      reinterpret_cast<long long *>(sh_view)[tid] = reinterpret_cast<const long long *>(g.views + sh_match[c0 + k])[wd];
-    }
-    if (tid < kReconViewChunk) sh_cnt[tid] = 0;
-    __syncthreads();
-    int cur = -1;
-    double R[9];
-    long long tb = 0;
-    for (int i = e0 + tid; i < e1; i += kReconThreads) {
-      const int b = i / a.per_batch;
-      int j = b - b0;
-      j = j < nbw ? j : nbw - 1;
-      if (j != cur) {
-#pragma unroll
-        for (int c = 0; c < 9; c++) R[c] = sh_R[9 * j + c];
-        tb = sh_bt[j];
-        cur = j;
-      }
-      // sampling restarts at every batch start: packed slot k of batch b is raw event b * B + k * stride (recon_votes_kernel)
-      const size_t src = a.stride ? (size_t)b * a.B + (size_t)(i - b * a.per_batch) * a.stride : (size_t)i;
-      const uint32_t e = a.xy[src] & 0x7fffffffu;
-      const int ex = e & 0xffff, ey = e >> 16;
-      double v0, v1, v2, rx, ry, rz;
-      load_bearing(a.cam, ex, ey, v0, v1, v2);
-      be_rotate<false>(R, v0, v1, v2, rx, ry, rz);
-      for (int k = 0; k < nl; k++) {
-        const ReconViewDev &V = sh_view[k];  // (one address for all lanes: LDS broadcasts)
-        if (tb < V.t_lo || tb >= V.t_hi) continue;
-        const ReconViewHit p = recon_view_project(V, rx, ry, rz, u_hi, w_hi);
-        if (p.ok) {
-          const int xx = (int)p.u, yy = (int)p.w;
-          const float dx = (float)(p.u - xx), dy = (float)(p.w - yy);
-          const size_t at = (size_t)V.index * np;
-          if (FIXED) vote4_global_fix(g.fixed + at, g.Wv, xx, yy, dx, dy);
-          else vote4_global(g.planes + at, g.Wv, xx, yy, dx, dy);
-          atomicAdd(&sh_cnt[k], 1u);
-        }
-      }
-    }
-    __syncthreads();
-    if (tid < nl) {  // (the lane that zeroes the counter of the next chunk)
-      const unsigned cnt = sh_cnt[tid];
-      if (cnt) atomicAdd(g.n_voted + sh_view[tid].index, (unsigned long long)cnt);
-    }
-    __syncthreads();  // (the next chunk's entries overwrite sh_view)
-  }
-}
-
-void launch_recon_view_votes(const ReconViewArgs &g, hipStream_t s) {
-  const ReconArgs &a = g.ev;
-  if (a.n <= 0 || a.nb <= 0 || g.n_views <= 0) return;
-  const dim3 gr((unsigned)(((long long)a.n + a.run - 1) / a.run)), b(kReconThreads);  // (a.n <= 2^30: cmx_reconstruct.cpp)
-  if (a.order == 2) {
-    if (g.fixed) hipLaunchKernelGGL((recon_view_votes_kernel<2, true>), gr, b, 0, s, g);
-    else hipLaunchKernelGGL((recon_view_votes_kernel<2, false>), gr, b, 0, s, g);
-  } else {
-    if (g.fixed) hipLaunchKernelGGL((recon_view_votes_kernel<4, true>), gr, b, 0, s, g);
-    else hipLaunchKernelGGL((recon_view_votes_kernel<4, false>), gr, b, 0, s, g);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------- voxel grids
-// recon_voxel_votes   cmx_backend_recon_voxel_add*: recon_view_votes with G grids of n_bins planes as the targets and the event's OWN
-//                timestamp as what decides membership and weight.  The same run structure: batch poses into LDS; beside them the
-//                lanes take the minimum and maximum of the run's event times (the per-event stream ev_t, read at the index of the
-//                packed word), and the ONE scan of the table of grid ranges lists the grids that meet that span -- not the span of
-//                the batch times: a batch of 5000 events spans many bins and several grids.  Listed grids are taken
-//                kReconViewChunk at a time, 136-byte entries in LDS; the world ray is formed once per event and chunk, and for
-//                every grid of the chunk with t_lo <= t_i < t_hi: recon_view_project (the view vote's own projection and test), its
-//                cell and weights, tau = (t_i - t_lo) * scale in fp64, b0 = min((int)tau, n_bins - 2), f = (float)(tau - b0), and the
-//                four bilinear adds times 1 - f into bin b0 and times f into bin b0 + 1 (n_bins == 1: one bin, weight 1), negated
-//                for an OFF event of a signed set.  A bin whose weight is zero is skipped: it would add zeros.  Votes go to
-//                global memory: the two active bins of a grid are two planes, which no LDS window holds.
-static_assert(sizeof(ReconVoxelDev) == 136, "grid entries are copied word by word");
-
-template <int N, bool FIXED>
-__global__ __launch_bounds__(kReconThreads) void recon_voxel_votes_kernel(const ReconVoxelArgs g) {
-  constexpr int kWords = sizeof(ReconVoxelDev) / 8;
-  static_assert(kReconViewChunk * kWords <= kReconThreads, "one lane per word of a chunk");
-  __shared__ double sh_R[(kReconMaxRun + 2) * 9];
-  __shared__ ReconVoxelDev sh_grid[kReconViewChunk];
-  __shared__ unsigned sh_cnt[kReconViewChunk];
-  __shared__ unsigned short sh_match[kReconMaxViews];
-  __shared__ unsigned sh_nmatch;
-  __shared__ long long sh_tmin, sh_tmax;
-  const ReconArgs &a = g.ev;
-  const int tid = threadIdx.x;
-  const int e0 = blockIdx.x * a.run;  // (the grid covers [0, n): e0 < n)
-  const int e1 = (a.n - e0 > a.run) ? e0 + a.run : a.n;
-  const int b0 = e0 / a.per_batch;
-  int nbw = (e1 - 1) / a.per_batch - b0 + 1;
-  if (nbw > kReconMaxRun + 2) nbw = kReconMaxRun + 2;  // (cannot happen with run = recon_run(per_batch))
-  if (tid == 0) { sh_nmatch = 0; sh_tmin = 0x7fffffffffffffffLL; sh_tmax = -0x7fffffffffffffffLL - 1; }
-  __syncthreads();
-  for (int j = tid; j < nbw; j += kReconThreads) {
-    const int b = b0 + j < a.nb ? b0 + j : a.nb - 1;
-    recon_pose<N>(a, a.batch_t[b], sh_R + 9 * j);
-  }
-  // the span of the run's EVENT times: every event is looked at, so the list below holds for any order of the events
   long long tmin = 0x7fffffffffffffffLL, tmax = -0x7fffffffffffffffLL - 1;
-  for (int i = e0 + tid; i < e1; i += kReconThreads) {
-    const int b = i / a.per_batch;
-    const size_t src = a.stride ? (size_t)b * a.B + (size_t)(i - b * a.per_batch) * a.stride : (size_t)i;
-    const long long t = g.ev_t[src];
-    tmin = t < tmin ? t : tmin;
-    tmax = t > tmax ? t : tmax;
-  }
+  if constexpr (kEventSpan) {
+    for (int i = e0 + tid; i < e1; i += kReconThreads) {
+      const int b = i / a.per_batch;
+      const size_t src = a.stride ? (size_t)b * a.B + (size_t)(i - b * a.per_batch) * a.stride : (size_t)i;
+      const long long t = st.ev_t[src];
+      tmin = t < tmin ? t : tmin;
+      tmax = t > tmax ? t : tmax;
+    }
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const long long lo = __shfl_down(tmin, off, 64), hi = __shfl_down(tmax, off, 64);
-    tmin = lo < tmin ? lo : tmin;
-    tmax = hi > tmax ? hi : tmax;
+    for (int off = 32; off > 0; off >>= 1) {
+      const long long lo = __shfl_down(tmin, off, 64), hi = __shfl_down(tmax, off, 64);
+      tmin = lo < tmin ? lo : tmin;
+      tmax = hi > tmax ? hi : tmax;
+    }
+    if ((tid & 63) == 0) { atomicMin(&sh_tmin, tmin); atomicMax(&sh_tmax, tmax); }
   }
-  if ((tid & 63) == 0) { atomicMin(&sh_tmin, tmin); atomicMax(&sh_tmax, tmax); }
   __syncthreads();
+  // the targets that meet the run's span [tmin, tmax], in no particular order (integer sums, maxima and counts do not depend on it)
   tmin = sh_tmin; tmax = sh_tmax;
-  for (int v = tid; v < g.n_grids; v += kReconThreads) {
-    const ReconViewRange r = g.ranges[v];
+  for (int v = tid; v < st.n; v += kReconThreads) {
+    const ReconViewRange r = st.ranges[v];
     if (r.t_lo <= tmax && r.t_hi > tmin) {
       const unsigned pos = atomicAdd(&sh_nmatch, 1u);
       if (pos < (unsigned)kReconMaxViews) sh_match[pos] = (unsigned short)v;
@@ -359,19 +329,19 @@ __global__ __launch_bounds__(kReconThreads) void recon_voxel_votes_kernel(const 
   __syncthreads();
   int nmatch = (int)sh_nmatch;
   nmatch = nmatch < kReconMaxViews ? nmatch : kReconMaxViews;
-  const double u_hi = (double)(g.Wv - 2), w_hi = (double)(g.Hv - 2);
-  const size_t np = (size_t)g.Hv * g.Wv;
-  const int nbins = g.n_bins;
+  const double u_hi = (double)(st.Wv - 2), w_hi = (double)(st.Hv - 2);
+  const size_t np = (size_t)st.Hv * st.Wv;
   for (int c0 = 0; c0 < nmatch; c0 += kReconViewChunk) {  // (uniform: nmatch is the workgroup's)
     const int nl = nmatch - c0 < kReconViewChunk ? nmatch - c0 : kReconViewChunk;
     if (tid < nl * kWords) {
       const int k = tid / kWords, wd = tid - k * kWords;
-      reinterpret_cast<long long *>(sh_grid)[tid] = reinterpret_cast<const long long *>(g.grids + sh_match[c0 + k])[wd];
+      reinterpret_cast<long long *>(sh_entry)[tid] = reinterpret_cast<const long long *>(static_cast<const Entry *>(st.entries) + sh_match[c0 + k])[wd];
     }
     if (tid < kReconViewChunk) sh_cnt[tid] = 0;
     __syncthreads();
     int cur = -1;
     double R[9];
+    long long ti = 0;
     for (int i = e0 + tid; i < e1; i += kReconThreads) {
       const int b = i / a.per_batch;
       int j = b - b0;
@@ -379,187 +349,65 @@ __global__ __launch_bounds__(kReconThreads) void recon_voxel_votes_kernel(const 
       if (j != cur) {
 #pragma unroll
         for (int c = 0; c < 9; c++) R[c] = sh_R[9 * j + c];
+        if constexpr (!kEventSpan) ti = sh_bt[j];
         cur = j;
       }
       // sampling restarts at every batch start: packed slot k of batch b is raw event b * B + k * stride (recon_votes_kernel)
       const size_t src = a.stride ? (size_t)b * a.B + (size_t)(i - b * a.per_batch) * a.stride : (size_t)i;
       const uint32_t word = a.xy[src];
-      const long long ti = g.ev_t[src];
+      if constexpr (kEventSpan) ti = st.ev_t[src];
       const uint32_t e = word & 0x7fffffffu;
-      // a signed set: the store's byte (a.pol is a kernel argument: uniform), read beside the word, or the word's own bit 31
-      const bool neg = g.is_signed && !(a.pol ? a.pol[src] != 0 : (word >> 31) != 0);
+      // OFF, where the set looks: the store's byte (a.pol is a kernel argument: uniform), read beside the word, or the word's own bit 31
+      const bool off = Target::reads_polarity(g) && !(a.pol ? a.pol[src] != 0 : (word >> 31) != 0);
       const int ex = e & 0xffff, ey = e >> 16;
       double v0, v1, v2, rx, ry, rz;
       load_bearing(a.cam, ex, ey, v0, v1, v2);
       be_rotate<false>(R, v0, v1, v2, rx, ry, rz);
       for (int k = 0; k < nl; k++) {
-        const ReconVoxelDev &G = sh_grid[k];  // (one address for all lanes: LDS broadcasts)
-        if (ti < G.v.t_lo || ti >= G.v.t_hi) continue;
-        const ReconViewHit p = recon_view_project(G.v, rx, ry, rz, u_hi, w_hi);
-        if (!p.ok) continue;
-        const int xx = (int)p.u, yy = (int)p.w;
-        const float dx = (float)(p.u - xx), dy = (float)(p.w - yy);
-        int bin = 0;
-        float w0 = 1.f, w1 = 0.f;
-        if (nbins >= 2) {
-          const double tau = (double)(ti - G.v.t_lo) * G.scale;  // (0 <= tau < n_bins - 1, up to its rounding: the cast is safe)
-          bin = (int)tau;
-          bin = bin < nbins - 2 ? bin : nbins - 2;
-          w1 = (float)(tau - bin);
-          w0 = 1.f - w1;
-        }
-        const size_t at = ((size_t)G.v.index * nbins + bin) * np;
-        if (FIXED) {
-          if (w0 != 0.f) vote4_global_fix_w(g.fixed + at, g.Wv, xx, yy, dx, dy, w0, neg);
-          if (w1 != 0.f) vote4_global_fix_w(g.fixed + at + np, g.Wv, xx, yy, dx, dy, w1, neg);
-        } else {
-          if (w0 != 0.f) vote4_global_w(g.planes + at, g.Wv, xx, yy, dx, dy, w0, neg);
-          if (w1 != 0.f) vote4_global_w(g.planes + at + np, g.Wv, xx, yy, dx, dy, w1, neg);
-        }
-        atomicAdd(&sh_cnt[k], 1u);
-      }
-    }
-    __syncthreads();
-    if (tid < nl) {  // (the lane that zeroes the counter of the next chunk)
-      const unsigned cnt = sh_cnt[tid];
-      if (cnt) atomicAdd(g.n_voted + sh_grid[tid].v.index, (unsigned long long)cnt);
-    }
-    __syncthreads();  // (the next chunk's entries overwrite sh_grid)
-  }
-}
-
-void launch_recon_voxel_votes(const ReconVoxelArgs &g, hipStream_t s) {
-  const ReconArgs &a = g.ev;
-  if (a.n <= 0 || a.nb <= 0 || g.n_grids <= 0) return;
-  const dim3 gr((unsigned)(((long long)a.n + a.run - 1) / a.run)), b(kReconThreads);  // (a.n <= 2^30: cmx_reconstruct.cpp)
-  if (a.order == 2) {
-    if (g.fixed) hipLaunchKernelGGL((recon_voxel_votes_kernel<2, true>), gr, b, 0, s, g);
-    else hipLaunchKernelGGL((recon_voxel_votes_kernel<2, false>), gr, b, 0, s, g);
-  } else {
-    if (g.fixed) hipLaunchKernelGGL((recon_voxel_votes_kernel<4, true>), gr, b, 0, s, g);
-    else hipLaunchKernelGGL((recon_voxel_votes_kernel<4, false>), gr, b, 0, s, g);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------- time surfaces
-// recon_surface_votes   cmx_backend_recon_surface_add*: recon_voxel_votes with S surfaces of one or two channels as the targets.  The
-//                same run structure: batch poses into LDS; the span of the run's EVENT times by wave reduction and one LDS atomic
-//                per wave; ONE scan of the table of ranges lists the surfaces that meet that span; listed surfaces are taken
-//                kReconViewChunk at a time, 128-byte view entries in LDS; the world ray is formed once per event and chunk, and
-//                for every surface of the chunk with t_lo <= t_i < t_hi: recon_view_project (the view vote's own projection and
-//                test), the NEAREST pixel (int)(u + 0.5), (int)(w + 0.5) -- inside the plane because of the test -- and ONE signed
-//                64-bit atomic max of t_i there, in channel 1 for an OFF event of a by-polarity set and in channel 0 otherwise.
-//                The result of the max is not read.  No fixed-point form: a max of integers commutes and is idempotent.
-template <int N>
-__global__ __launch_bounds__(kReconThreads) void recon_surface_votes_kernel(const ReconSurfaceArgs g) {
-  constexpr int kWords = sizeof(ReconViewDev) / 8;
-  static_assert(kReconViewChunk * kWords <= kReconThreads, "one lane per word of a chunk");
-  __shared__ double sh_R[(kReconMaxRun + 2) * 9];
-  __shared__ ReconViewDev sh_view[kReconViewChunk];
-  __shared__ unsigned sh_cnt[kReconViewChunk];
-  __shared__ unsigned short sh_match[kReconMaxViews];
-  __shared__ unsigned sh_nmatch;
-  __shared__ long long sh_tmin, sh_tmax;
-  const ReconArgs &a = g.ev;
-  const int tid = threadIdx.x;
-  const int e0 = blockIdx.x * a.run;  // (the grid covers [0, n): e0 < n)
-  const int e1 = (a.n - e0 > a.run) ? e0 + a.run : a.n;
-  const int b0 = e0 / a.per_batch;
-  int nbw = (e1 - 1) / a.per_batch - b0 + 1;
-  if (nbw > kReconMaxRun + 2) nbw = kReconMaxRun + 2;  // (cannot happen with run = recon_run(per_batch))
-  if (tid == 0) { sh_nmatch = 0; sh_tmin = 0x7fffffffffffffffLL; sh_tmax = kReconSurfaceEmpty; }
-  __syncthreads();
-  for (int j = tid; j < nbw; j += kReconThreads) {
-    const int b = b0 + j < a.nb ? b0 + j : a.nb - 1;
-    recon_pose<N>(a, a.batch_t[b], sh_R + 9 * j);
-  }
-  // the span of the run's EVENT times: every event is looked at, so the list below holds for any order of the events
-  long long tmin = 0x7fffffffffffffffLL, tmax = kReconSurfaceEmpty;
-  for (int i = e0 + tid; i < e1; i += kReconThreads) {
-    const int b = i / a.per_batch;
-    const size_t src = a.stride ? (size_t)b * a.B + (size_t)(i - b * a.per_batch) * a.stride : (size_t)i;
-    const long long t = g.ev_t[src];
-    tmin = t < tmin ? t : tmin;
-    tmax = t > tmax ? t : tmax;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const long long lo = __shfl_down(tmin, off, 64), hi = __shfl_down(tmax, off, 64);
-    tmin = lo < tmin ? lo : tmin;
-    tmax = hi > tmax ? hi : tmax;
-  }
-  if ((tid & 63) == 0) { atomicMin(&sh_tmin, tmin); atomicMax(&sh_tmax, tmax); }
-  __syncthreads();
-  tmin = sh_tmin; tmax = sh_tmax;
-  for (int v = tid; v < g.n_surfaces; v += kReconThreads) {
-    const ReconViewRange r = g.ranges[v];
-    if (r.t_lo <= tmax && r.t_hi > tmin) {
-      const unsigned pos = atomicAdd(&sh_nmatch, 1u);
-      if (pos < (unsigned)kReconMaxViews) sh_match[pos] = (unsigned short)v;
-    }
-  }
-  __syncthreads();
-  int nmatch = (int)sh_nmatch;
-  nmatch = nmatch < kReconMaxViews ? nmatch : kReconMaxViews;
-  const double u_hi = (double)(g.Wv - 2), w_hi = (double)(g.Hv - 2);
-  const size_t np = (size_t)g.Hv * g.Wv;
-  const size_t per_surface = g.by_polarity ? 2 * np : np;
-  for (int c0 = 0; c0 < nmatch; c0 += kReconViewChunk) {  // (uniform: nmatch is the workgroup's)
-    const int nl = nmatch - c0 < kReconViewChunk ? nmatch - c0 : kReconViewChunk;
-    if (tid < nl * kWords) {
-      const int k = tid / kWords, wd = tid - k * kWords;
-      reinterpret_cast<long long *>(sh_view)[tid] = reinterpret_cast<const long long *>(g.surfaces + sh_match[c0 + k])[wd];
-    }
-    if (tid < kReconViewChunk) sh_cnt[tid] = 0;
-    __syncthreads();
-    int cur = -1;
-    double R[9];
-    for (int i = e0 + tid; i < e1; i += kReconThreads) {
-      const int b = i / a.per_batch;
-      int j = b - b0;
-      j = j < nbw ? j : nbw - 1;
-      if (j != cur) {
-#pragma unroll
-        for (int c = 0; c < 9; c++) R[c] = sh_R[9 * j + c];
-        cur = j;
-      }
-      // sampling restarts at every batch start: packed slot k of batch b is raw event b * B + k * stride (recon_votes_kernel)
-      const size_t src = a.stride ? (size_t)b * a.B + (size_t)(i - b * a.per_batch) * a.stride : (size_t)i;
-      const uint32_t word = a.xy[src];
-      const long long ti = g.ev_t[src];
-      const uint32_t e = word & 0x7fffffffu;
-      // a by-polarity set: the store's byte (a.pol is a kernel argument: uniform), read beside the word, or the word's own bit 31
-      const bool off = g.by_polarity && !(a.pol ? a.pol[src] != 0 : (word >> 31) != 0);
-      const int ex = e & 0xffff, ey = e >> 16;
-      double v0, v1, v2, rx, ry, rz;
-      load_bearing(a.cam, ex, ey, v0, v1, v2);
-      be_rotate<false>(R, v0, v1, v2, rx, ry, rz);
-      for (int k = 0; k < nl; k++) {
-        const ReconViewDev &V = sh_view[k];  // (one address for all lanes: LDS broadcasts)
+        const Entry &E = sh_entry[k];  // (one address for all lanes: LDS broadcasts)
+        const ReconViewDev &V = Target::view(E);
         if (ti < V.t_lo || ti >= V.t_hi) continue;
         const ReconViewHit p = recon_view_project(V, rx, ry, rz, u_hi, w_hi);
         if (!p.ok) continue;
-        const int cx = (int)(p.u + 0.5), cy = (int)(p.w + 0.5);  // (1 <= cx <= Wv - 2 and 1 <= cy <= Hv - 2: the test above)
-        long long *cell = g.cells + (size_t)V.index * per_surface + (off ? np : 0) + (size_t)cy * g.Wv + cx;
-        atomicMax(cell, ti);
+        Target::vote(g, E, p, ti, off, np);
         atomicAdd(&sh_cnt[k], 1u);
       }
     }
     __syncthreads();
     if (tid < nl) {  // (the lane that zeroes the counter of the next chunk)
       const unsigned cnt = sh_cnt[tid];
-      if (cnt) atomicAdd(g.n_voted + sh_view[tid].index, (unsigned long long)cnt);
+      if (cnt) atomicAdd(st.n_voted + Target::view(sh_entry[tid]).index, (unsigned long long)cnt);
     }
-    __syncthreads();  // (the next chunk's entries overwrite sh_view)
+    __syncthreads();  // (the next chunk's entries overwrite sh_entry)
   }
 }
 
-void launch_recon_surface_votes(const ReconSurfaceArgs &g, hipStream_t s) {
-  const ReconArgs &a = g.ev;
-  if (a.n <= 0 || a.nb <= 0 || g.n_surfaces <= 0) return;
+// the kernels: the skeleton with each set's Target (their names are those the three sets have always had)
+template <int N, bool FIXED>
+__global__ __launch_bounds__(kReconThreads) void recon_view_votes_kernel(const ReconViewArgs g) { recon_set_votes<N, ReconViewTarget<FIXED>>(g); }
+template <int N, bool FIXED>
+__global__ __launch_bounds__(kReconThreads) void recon_voxel_votes_kernel(const ReconVoxelArgs g) { recon_set_votes<N, ReconVoxelTarget<FIXED>>(g); }
+template <int N>
+__global__ __launch_bounds__(kReconThreads) void recon_surface_votes_kernel(const ReconSurfaceArgs g) { recon_set_votes<N, ReconSurfaceTarget>(g); }
+
+// the grid of a slice, and the kernel of the spline's order
+template <class Args>
+static void launch_recon_set_votes(const Args &g, void (*order2)(Args), void (*order4)(Args), hipStream_t s) {
+  const ReconArgs &a = g.set.ev;
+  if (a.n <= 0 || a.nb <= 0 || g.set.n <= 0) return;
   const dim3 gr((unsigned)(((long long)a.n + a.run - 1) / a.run)), b(kReconThreads);  // (a.n <= 2^30: cmx_reconstruct.cpp)
-  if (a.order == 2) hipLaunchKernelGGL((recon_surface_votes_kernel<2>), gr, b, 0, s, g);
-  else hipLaunchKernelGGL((recon_surface_votes_kernel<4>), gr, b, 0, s, g);
+  hipLaunchKernelGGL(a.order == 2 ? order2 : order4, gr, b, 0, s, g);
+}
+void launch_recon_view_votes(const ReconViewArgs &g, hipStream_t s) {
+  if (g.fixed) launch_recon_set_votes(g, recon_view_votes_kernel<2, true>, recon_view_votes_kernel<4, true>, s);
+  else launch_recon_set_votes(g, recon_view_votes_kernel<2, false>, recon_view_votes_kernel<4, false>, s);
+}
+void launch_recon_voxel_votes(const ReconVoxelArgs &g, hipStream_t s) {
+  if (g.fixed) launch_recon_set_votes(g, recon_voxel_votes_kernel<2, true>, recon_voxel_votes_kernel<4, true>, s);
+  else launch_recon_set_votes(g, recon_voxel_votes_kernel<2, false>, recon_voxel_votes_kernel<4, false>, s);
+}
+void launch_recon_surface_votes(const ReconSurfaceArgs &g, hipStream_t s) {
+  launch_recon_set_votes(g, recon_surface_votes_kernel<2>, recon_surface_votes_kernel<4>, s);
 }
 
 // every cell = "no event yet": INT64_MIN, a pattern no byte memset writes (surface_begin, surface_reset, restart)

@@ -273,182 +273,106 @@ int cmx_backend_recon_pol_add_from(cmx_ctx *c, const cmx_events *e, int64_t firs
   });
 }
 
-// ---- view_add*: add*'s vote pass with the planes of the pinhole views as its targets.  As pol_add*: nothing of the
-// reconstruction but the knots is read, nothing but the view planes and their counters is written, an open gradient pass stays open.
-// The packed words are those of add*.
-static int recon_view_add_source(cmx_ctx *c, const EventSource &src) {
+// ---- view_add*, voxel_add*, surface_add*: add*'s vote pass with the targets of a set as its targets.  As pol_add*:
+// nothing of the reconstruction but the knots is read, nothing but the set's planes or cells and its counters is written, an open
+// gradient pass stays open.  The packed words are those of add*; for the sets that vote by the event's OWN timestamp (voxel grids,
+// surfaces) every sampled event brings it beside the word (feed: with_time), and a set that reads polarity (a signed voxel set, a
+// by-polarity surface set) reads it as pol_add* does -- bit 31 of the word on the host paths, the store's byte array -- while any
+// other set reads none and packs none.
+static int recon_set_add_source(cmx_ctx *c, const EventSource &src, ReconTargetSet ReconState::*which) {
   ReconState *r = c->recon;
+  const ReconTargetSet &t = r->*which;
   int rc = feed_checks(c, src);
   if (rc) return rc;
-  ReconViewArgs g{};
+  ReconSetArgs g{};
   g.ev = recon_args(c, r);
   g.ev.plane = nullptr; g.ev.fixed = nullptr; g.ev.n_inside = nullptr;
-  g.views = r->d_views; g.ranges = r->d_vranges;
-  g.n_views = r->n_views; g.Wv = r->Wv; g.Hv = r->Hv;
-  g.planes = r->d_vplanes;
-  g.fixed = r->d_vfixed;
-  g.n_voted = r->d_vvoted;
+  g.entries = t.d_entries; g.ranges = t.d_ranges;
+  g.n = t.n; g.Wv = t.W; g.Hv = t.H;
+  g.n_voted = t.d_voted;
   ReconArgs &a = g.ev;
+  const bool with_time = &t != &r->views;
   BatchPlan p;
-  return feed(c, r, src, false, false, false, &p, [&](const FedSlice &s) {
+  return feed(c, r, src, false, t.polarity && !src.on_device(), with_time, &p, [&](const FedSlice &s) {
     a.xy = s.d_xy; a.stride = src.on_device() ? r->rate : 0;
+    a.pol = t.polarity && src.on_device() ? src.d_pol + s.ev_first : nullptr;
     a.batch_t = s.d_bt; a.nb = s.b_hi - s.b_lo;
     a.n = (int)s.n;
-    launch_recon_view_votes(g, c->stream);
+    g.ev_t = with_time ? s.d_t : nullptr;
+    if (&t == &r->views) launch_recon_view_votes(ReconViewArgs{g, t.d_planes, t.d_fixed}, c->stream);
+    else if (&t == &r->voxels) launch_recon_voxel_votes(ReconVoxelArgs{g, t.d_planes, t.d_fixed, t.per, t.polarity ? 1 : 0}, c->stream);
+    else launch_recon_surface_votes(ReconSurfaceArgs{g, t.d_cells, t.polarity ? 1 : 0}, c->stream);
     return (int)CMX_OK;
   });
 }
+// the front door of the nine entry points: the set, the call's own way to its source -- told whether the set reads polarity, and
+// so whether the source must bring it -- then the pass
 template <typename MakeSource>
-static int recon_view_add_entry(cmx_ctx *c, MakeSource make) {
-  int rc = recon_enter(c, true);
+static int recon_set_add_entry(cmx_ctx *c, ReconTargetSet ReconState::*which, MakeSource make) {
+  int rc = recon_set_enter(c, which);
   if (rc) return rc;
-  if (!c->recon->d_views) return fail(c, CMX_ERR_STATE, "cmx_backend_recon_view_begin has not succeeded");
   EventSource src;
-  rc = make(&src);
+  rc = make(&src, (c->recon->*which).polarity);
   if (rc) return rc;
-  return recon_view_add_source(c, src);
+  return recon_set_add_source(c, src, which);
+}
+// the three forms of a source and the polarity that comes with each; kind / why: a set that reads polarity, as the message about a
+// source without it puts it ("signed voxel", "voxel set is signed")
+static int recon_set_add(cmx_ctx *c, ReconTargetSet ReconState::*which, const char *kind, int64_t n, const uint16_t *x, const uint16_t *y,
+                         const int64_t *t_ns, const uint8_t *pol) {
+  return recon_set_add_entry(c, which, [&](EventSource *src, bool reads_pol) {
+    if (reads_pol && !pol) return fail(c, CMX_ERR_INVALID_ARG, "null polarity array for a %s set", kind);
+    *src = EventSource::arrays(n, x, y, t_ns);
+    src->soa.p = pol;
+    return (int)CMX_OK;
+  });
+}
+static int recon_set_add_aos(cmx_ctx *c, ReconTargetSet ReconState::*which, int64_t n, const void *events, const cmx_aos_layout *layout,
+                             size_t off_polarity) {
+  return recon_set_add_entry(c, which, [&](EventSource *src, bool reads_pol) {
+    const int rc = make_aos(c, n, events, layout, src);
+    if (rc) return rc;
+    if (!reads_pol) return (int)CMX_OK;  // (polarity is neither needed nor read)
+    if (off_polarity >= layout->stride) return fail(c, CMX_ERR_INVALID_ARG, "record layout: polarity outside the %zu-byte record", layout->stride);
+    src->aos.op = off_polarity;
+    return (int)CMX_OK;
+  });
+}
+static int recon_set_add_from(cmx_ctx *c, ReconTargetSet ReconState::*which, const char *why, const cmx_events *e, int64_t first, int64_t count) {
+  return recon_set_add_entry(c, which, [&](EventSource *src, bool reads_pol) {
+    const int rc = store_source(c, e, first, count, src);
+    if (rc) return rc;
+    if (reads_pol && e->size > 0 && !e->has_pol)
+      return fail(c, CMX_ERR_STATE, "the %s and the event store holds no polarity (cmx_events_push_pol)", why);
+    return (int)CMX_OK;
+  });
 }
 int cmx_backend_recon_view_add(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns) {
-  return recon_view_add_entry(c, [&](EventSource *src) { *src = EventSource::arrays(n, x, y, t_ns); return (int)CMX_OK; });
+  return recon_set_add(c, &ReconState::views, "", n, x, y, t_ns, nullptr);
 }
 int cmx_backend_recon_view_add_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout) {
-  return recon_view_add_entry(c, [&](EventSource *src) { return make_aos(c, n, events, layout, src); });
+  return recon_set_add_aos(c, &ReconState::views, n, events, layout, 0);
 }
 int cmx_backend_recon_view_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
-  return recon_view_add_entry(c, [&](EventSource *src) { return store_source(c, e, first, count, src); });
-}
-
-// ---- voxel_add*: add*'s vote pass with the bins of the voxel grids as its targets.  As view_add*: nothing of the
-// reconstruction but the knots is read, nothing but the grid planes and their counters is written.  Beside the packed word every
-// sampled event brings its own timestamp (feed: with_time); a signed set reads polarity as pol_add* does -- bit 31 of the word on
-// the host paths, the store's byte array -- an unsigned set reads none and packs none.
-static int recon_voxel_add_source(cmx_ctx *c, const EventSource &src) {
-  ReconState *r = c->recon;
-  int rc = feed_checks(c, src);
-  if (rc) return rc;
-  ReconVoxelArgs g{};
-  g.ev = recon_args(c, r);
-  g.ev.plane = nullptr; g.ev.fixed = nullptr; g.ev.n_inside = nullptr;
-  g.grids = r->d_grids; g.ranges = r->d_xranges;
-  g.n_grids = r->n_grids; g.Wv = r->Wx; g.Hv = r->Hx; g.n_bins = r->n_bins;
-  g.is_signed = r->vox_signed ? 1 : 0;
-  g.planes = r->d_xplanes;
-  g.fixed = r->d_xfixed;
-  g.n_voted = r->d_xvoted;
-  ReconArgs &a = g.ev;
-  BatchPlan p;
-  return feed(c, r, src, false, r->vox_signed && !src.on_device(), true, &p, [&](const FedSlice &s) {
-    a.xy = s.d_xy; a.stride = src.on_device() ? r->rate : 0;
-    a.pol = r->vox_signed && src.on_device() ? src.d_pol + s.ev_first : nullptr;
-    a.batch_t = s.d_bt; a.nb = s.b_hi - s.b_lo;
-    a.n = (int)s.n;
-    g.ev_t = s.d_t;
-    launch_recon_voxel_votes(g, c->stream);
-    return (int)CMX_OK;
-  });
-}
-template <typename MakeSource>
-static int recon_voxel_add_entry(cmx_ctx *c, MakeSource make) {
-  int rc = recon_enter(c, true);
-  if (rc) return rc;
-  if (!c->recon->d_grids) return fail(c, CMX_ERR_STATE, "cmx_backend_recon_voxel_begin has not succeeded");
-  EventSource src;
-  rc = make(&src);
-  if (rc) return rc;
-  return recon_voxel_add_source(c, src);
+  return recon_set_add_from(c, &ReconState::views, "", e, first, count);
 }
 int cmx_backend_recon_voxel_add(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, const uint8_t *pol) {
-  return recon_voxel_add_entry(c, [&](EventSource *src) {
-    if (c->recon->vox_signed && !pol) return fail(c, CMX_ERR_INVALID_ARG, "null polarity array for a signed voxel set");
-    *src = EventSource::arrays(n, x, y, t_ns);
-    src->soa.p = pol;
-    return (int)CMX_OK;
-  });
+  return recon_set_add(c, &ReconState::voxels, "signed voxel", n, x, y, t_ns, pol);
 }
 int cmx_backend_recon_voxel_add_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout, size_t off_polarity) {
-  return recon_voxel_add_entry(c, [&](EventSource *src) {
-    const int rc = make_aos(c, n, events, layout, src);
-    if (rc) return rc;
-    if (!c->recon->vox_signed) return (int)CMX_OK;  // (polarity is neither needed nor read)
-    if (off_polarity >= layout->stride) return fail(c, CMX_ERR_INVALID_ARG, "record layout: polarity outside the %zu-byte record", layout->stride);
-    src->aos.op = off_polarity;
-    return (int)CMX_OK;
-  });
+  return recon_set_add_aos(c, &ReconState::voxels, n, events, layout, off_polarity);
 }
 int cmx_backend_recon_voxel_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
-  return recon_voxel_add_entry(c, [&](EventSource *src) {
-    const int rc = store_source(c, e, first, count, src);
-    if (rc) return rc;
-    if (c->recon->vox_signed && e->size > 0 && !e->has_pol)
-      return fail(c, CMX_ERR_STATE, "the voxel set is signed and the event store holds no polarity (cmx_events_push_pol)");
-    return (int)CMX_OK;
-  });
-}
-
-// ---- surface_add*: add*'s vote pass with the cells of the time surfaces as its targets.  As voxel_add*: nothing of the
-// reconstruction but the knots is read, nothing but the surface cells and their counters is written; every sampled event brings its
-// own timestamp (feed: with_time), and a by-polarity set reads polarity as pol_add* does -- bit 31 of the word on the host paths, the
-// store's byte array -- while a merged set reads none and packs none.
-static int recon_surface_add_source(cmx_ctx *c, const EventSource &src) {
-  ReconState *r = c->recon;
-  int rc = feed_checks(c, src);
-  if (rc) return rc;
-  ReconSurfaceArgs g{};
-  g.ev = recon_args(c, r);
-  g.ev.plane = nullptr; g.ev.fixed = nullptr; g.ev.n_inside = nullptr;
-  g.surfaces = r->d_surfaces; g.ranges = r->d_sranges;
-  g.n_surfaces = r->n_surfaces; g.Wv = r->Ws; g.Hv = r->Hs;
-  g.by_polarity = r->surf_by_pol ? 1 : 0;
-  g.cells = r->d_scells;
-  g.n_voted = r->d_svoted;
-  ReconArgs &a = g.ev;
-  BatchPlan p;
-  return feed(c, r, src, false, r->surf_by_pol && !src.on_device(), true, &p, [&](const FedSlice &s) {
-    a.xy = s.d_xy; a.stride = src.on_device() ? r->rate : 0;
-    a.pol = r->surf_by_pol && src.on_device() ? src.d_pol + s.ev_first : nullptr;
-    a.batch_t = s.d_bt; a.nb = s.b_hi - s.b_lo;
-    a.n = (int)s.n;
-    g.ev_t = s.d_t;
-    launch_recon_surface_votes(g, c->stream);
-    return (int)CMX_OK;
-  });
-}
-template <typename MakeSource>
-static int recon_surface_add_entry(cmx_ctx *c, MakeSource make) {
-  int rc = recon_enter(c, true);
-  if (rc) return rc;
-  if (!c->recon->d_surfaces) return fail(c, CMX_ERR_STATE, "cmx_backend_recon_surface_begin has not succeeded");
-  EventSource src;
-  rc = make(&src);
-  if (rc) return rc;
-  return recon_surface_add_source(c, src);
+  return recon_set_add_from(c, &ReconState::voxels, "voxel set is signed", e, first, count);
 }
 int cmx_backend_recon_surface_add(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, const uint8_t *pol) {
-  return recon_surface_add_entry(c, [&](EventSource *src) {
-    if (c->recon->surf_by_pol && !pol) return fail(c, CMX_ERR_INVALID_ARG, "null polarity array for a by-polarity surface set");
-    *src = EventSource::arrays(n, x, y, t_ns);
-    src->soa.p = pol;
-    return (int)CMX_OK;
-  });
+  return recon_set_add(c, &ReconState::surfaces, "by-polarity surface", n, x, y, t_ns, pol);
 }
 int cmx_backend_recon_surface_add_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout, size_t off_polarity) {
-  return recon_surface_add_entry(c, [&](EventSource *src) {
-    const int rc = make_aos(c, n, events, layout, src);
-    if (rc) return rc;
-    if (!c->recon->surf_by_pol) return (int)CMX_OK;  // (polarity is neither needed nor read)
-    if (off_polarity >= layout->stride) return fail(c, CMX_ERR_INVALID_ARG, "record layout: polarity outside the %zu-byte record", layout->stride);
-    src->aos.op = off_polarity;
-    return (int)CMX_OK;
-  });
+  return recon_set_add_aos(c, &ReconState::surfaces, n, events, layout, off_polarity);
 }
 int cmx_backend_recon_surface_add_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count) {
-  return recon_surface_add_entry(c, [&](EventSource *src) {
-    const int rc = store_source(c, e, first, count, src);
-    if (rc) return rc;
-    if (c->recon->surf_by_pol && e->size > 0 && !e->has_pol)
-      return fail(c, CMX_ERR_STATE, "the surface set is by polarity and the event store holds no polarity (cmx_events_push_pol)");
-    return (int)CMX_OK;
-  });
+  return recon_set_add_from(c, &ReconState::surfaces, "surface set is by polarity", e, first, count);
 }
 
 // ---- warp*: ALL events of a slice reach the kernel (the host paths pack at rate 1, the store is read in place), the true rate only

@@ -1,9 +1,9 @@
 // cmx_recon_state.hpp -- what the three sources of cmx_backend_recon_* share: the state a reconstruction keeps (cmx_ctx::recon) and
 // the helpers every one of them goes through.
-//   cmx_reconstruct.cpp  life cycle (begin, restart, extend, end), contrast / grad_get / eval_from, get / render, the view set, the
-//                        voxel set, the surface set
-//   cmx_recon_feed.cpp   one walk over the events handed in, in slices of whole batches: add*, grad_add*, warp*, pol_add*, view_add*,
-//                        voxel_add*, surface_add*
+//   cmx_reconstruct.cpp  life cycle (begin, restart, extend, end), contrast / grad_get / eval_from, get / render, and the three target
+//                        sets (views, voxel grids, time surfaces) through ONE ReconTargetSet: begin, reset, end, get*, render, decay
+//   cmx_recon_feed.cpp   one walk over the events handed in, in slices of whole batches: add*, grad_add*, warp*, pol_add*, and
+//                        view_add* / voxel_add* / surface_add* through one recon_set_add_source
 //   cmx_recon_bound.cpp  events bound once and evaluated many times: bind / eval_bound, the frozen head, append / advance /
 //                        release, the hooks of cmx_backend_recon_solve
 // Kernels: cmx_recon.hip.
@@ -145,6 +145,30 @@ struct ReconSolve {
 
 typedef double ReconRows[2 * 3 * kReconWindow];  // one row of window sums (ReconGatherArgs::rows)
 
+// One set of vote targets beside the panorama -- pinhole views, voxel grids or time surfaces: n virtual cameras
+// with a time range each, and what their votes land in.  The reconstruction's own: made by cmx_backend_recon_<api>_begin, cleared
+// by restart and _reset, freed by _end, begin and end; nothing but <api>_add* writes it and nothing but <api>_get* / render /
+// decay reads it.
+struct ReconTargetSet {
+  const char *noun, *api;                      // "view" / "grid" / "surface" in the error texts; the <api> of the calls' names
+  bool timestamps;                             // the targets hold int64 timestamps (d_cells), not vote sums (d_planes, d_fixed)
+  int n = 0, W = 0, H = 0;                     // n == 0: no set
+  int per = 1;                                 // planes of W x H per target: 1 (views), n_bins (grids), channels (surfaces)
+  bool polarity = false;                       // a signed voxel set / a by-polarity surface set: the events' polarity is read
+  void *d_entries = nullptr;                   // [n] ReconViewDev (views, surfaces) or ReconVoxelDev; says whether the set exists
+  ReconViewRange *d_ranges = nullptr;          // [n] the time ranges alone: what a vote workgroup scans
+  float *d_planes = nullptr;                   // [n][per][H * W] (default mode), or the fp32 view of d_fixed made by get / render
+  unsigned long long *d_fixed = nullptr;       // deterministic mode: their 2^-30 fixed-point twins (voxel grids: two's complement)
+  long long *d_cells = nullptr;                // [n][per][H * W] the latest timestamp voted into each cell, or INT64_MIN
+  unsigned long long *d_voted = nullptr;       // [n] events that voted into each target
+  size_t cells_per_target() const { return (size_t)per * W * H; }
+  void release() {
+    void *dev[] = {d_entries, d_ranges, d_planes, d_fixed, d_cells, d_voted};
+    for (void *p : dev) (void)hipFree(p);
+    *this = ReconTargetSet{noun, api, timestamps};
+  }
+};
+
 struct ReconState {
   KnotSupport sup;
   int B = 0, rate = 0, per_batch = 0;
@@ -194,33 +218,11 @@ struct ReconState {
   float *d_pol = nullptr;                      // [2][Hp * Wp] ON then OFF (default mode), or the fp32 view of d_pol_fixed made by pol_get / pol_render
   unsigned long long *d_pol_fixed = nullptr;   // deterministic mode: their 2^-30 fixed-point twins
   unsigned long long *d_pol_inside = nullptr;  // [2] events that voted into the ON / the OFF plane
-  // ---- pinhole views (cmx_backend_recon_view_*): M virtual cameras and their planes, the reconstruction's own:
-  // made by view_begin, cleared by restart and view_reset, freed by view_end, begin and end; nothing else reads or writes them
-  int n_views = 0, Wv = 0, Hv = 0;             // n_views == 0: no view set
-  ReconViewDev *d_views = nullptr;             // [n_views]
-  ReconViewRange *d_vranges = nullptr;         // [n_views] the time ranges alone: what a vote workgroup scans
-  float *d_vplanes = nullptr;                  // [n_views][Hv * Wv] (default mode), or the fp32 view of d_vfixed made by view_get / view_render
-  unsigned long long *d_vfixed = nullptr;      // deterministic mode: their 2^-30 fixed-point twins
-  unsigned long long *d_vvoted = nullptr;      // [n_views] events that voted into each view
-  // ---- voxel grids (cmx_backend_recon_voxel_*): G grids of n_bins planes each, the reconstruction's own beside the
-  // view set: made by voxel_begin, cleared by restart and voxel_reset, freed by voxel_end, begin and end
-  int n_grids = 0, n_bins = 0, Wx = 0, Hx = 0; // n_grids == 0: no voxel set
-  bool vox_signed = false;
-  ReconVoxelDev *d_grids = nullptr;            // [n_grids]
-  ReconViewRange *d_xranges = nullptr;         // [n_grids]
-  float *d_xplanes = nullptr;                  // [n_grids][n_bins][Hx * Wx] (default mode), or the fp32 view of d_xfixed made by voxel_get
-  unsigned long long *d_xfixed = nullptr;      // deterministic mode: their 2^-30 fixed-point twins, two's complement
-  unsigned long long *d_xvoted = nullptr;      // [n_grids] events that voted into each grid
-  // ---- time surfaces (cmx_backend_recon_surface_*): S surfaces of C channels each, the reconstruction's own beside the
-  // view and voxel sets: made by surface_begin, cleared (to INT64_MIN) by restart and surface_reset, freed by surface_end, begin and end
-  int n_surfaces = 0, Ws = 0, Hs = 0;          // n_surfaces == 0: no surface set
-  bool surf_by_pol = false;                    // two channels, ON then OFF; otherwise one and polarity is never read
-  ReconViewDev *d_surfaces = nullptr;          // [n_surfaces]
-  ReconViewRange *d_sranges = nullptr;         // [n_surfaces]
-  long long *d_scells = nullptr;               // [n_surfaces][C][Hs * Ws] the latest timestamp voted into each cell, or INT64_MIN
-  unsigned long long *d_svoted = nullptr;      // [n_surfaces] events that voted into each surface
-  long long *d_stref = nullptr;                // [n_surfaces] the reference times of a surface_decay call that names them
-  float *d_sdecay = nullptr;                   // surface_decay (host output): the decayed cells on their way out, grown on demand
+  // ---- target sets: pinhole views (cmx_backend_recon_view_*), voxel grids (_voxel_*), time surfaces (_surface_*)
+  ReconTargetSet views{"view", "view", false}, voxels{"grid", "voxel", false}, surfaces{"surface", "surface", true};
+  // the surface set's own, for surface_decay: freed with it
+  long long *d_stref = nullptr;                // [surfaces.n] the reference times of a call that names them
+  float *d_sdecay = nullptr;                   // (host output) the decayed cells on their way out, grown on demand
   size_t sdecay_cap = 0;
   int64_t host_waits = 0;               // times a host thread has waited for the device in this reconstruction's calls
   // everything above that owns memory, a stream or an event (the streams idle: recon_release has waited for them)
@@ -230,10 +232,9 @@ struct ReconState {
     for (ReconSlot &s : slot) s.release();
     for (ReconWarpSlot &s : wslot) s.release();
     void *dev[] = {d_knots, d_delta, d_plane, d_fixed, d_inside, d_err, d_cx, d_cy, d_tflags, d_tile_list, d_tile_count, d_partials,
-                   d_cm, d_jt, d_gsum, d_voted, d_rows, d_row_win, d_app_xy, d_app_t, d_pol, d_pol_fixed, d_pol_inside,
-                   d_views, d_vranges, d_vplanes, d_vfixed, d_vvoted, d_grids, d_xranges, d_xplanes, d_xfixed, d_xvoted,
-                   d_surfaces, d_sranges, d_scells, d_svoted, d_stref, d_sdecay};
+                   d_cm, d_jt, d_gsum, d_voted, d_rows, d_row_win, d_app_xy, d_app_t, d_pol, d_pol_fixed, d_pol_inside, d_stref, d_sdecay};
     for (void *p : dev) (void)hipFree(p);
+    for (ReconTargetSet *t : {&views, &voxels, &surfaces}) t->release();
     bnd.release();
     frozen.release();
     solve.release();
@@ -270,12 +271,10 @@ int recon_grad_precheck(cmx_ctx *c, ReconState *r, double sigma);
 // the polarity planes and their two counters: allocated (and zeroed) at the first pol_add*; zeroed, where they exist (queued)
 int recon_pol_ensure(cmx_ctx *c, ReconState *r);
 int recon_pol_clear(cmx_ctx *c, ReconState *r);
-// the view planes and their counters zeroed, where a view set exists (queued)
-int recon_view_clear(cmx_ctx *c, ReconState *r);
-// the voxel planes and their counters zeroed, where a voxel set exists (queued)
-int recon_voxel_clear(cmx_ctx *c, ReconState *r);
-// the surface cells filled with INT64_MIN and their counters zeroed, where a surface set exists (queued)
-int recon_surface_clear(cmx_ctx *c, ReconState *r);
+// a target set's planes (or cells: back to INT64_MIN) and its counters cleared, where the set exists (queued)
+int recon_set_clear(cmx_ctx *c, ReconTargetSet *t);
+// the front door of every call that needs the set: recon_enter, and the set's _begin has succeeded
+int recon_set_enter(cmx_ctx *c, ReconTargetSet ReconState::*which);
 
 // ---- cmx_recon_feed.cpp
 // one slice of the gradient pass, as g.ev describes it; deterministic mode: the workgroups' rows, then their sum in workgroup order

@@ -191,12 +191,11 @@ int cmx_backend_recon_restart(cmx_ctx *c, const double *knots_xyzw) {
   frozen_drop(c, c->recon);  // (new knots: what the frozen batches voted no longer holds)
   rc = recon_pol_clear(c, c->recon);  // (... nor what the polarity planes hold)
   if (rc) return rc;
-  rc = recon_view_clear(c, c->recon);  // (... nor the view planes; the views themselves stay)
-  if (rc) return rc;
-  rc = recon_voxel_clear(c, c->recon);  // (... nor the voxel planes; the grids themselves stay)
-  if (rc) return rc;
-  rc = recon_surface_clear(c, c->recon);  // (... nor the time surfaces, which go back to empty; the surfaces themselves stay)
-  if (rc) return rc;
+  ReconState *r = c->recon;
+  for (ReconTargetSet *t : {&r->views, &r->voxels, &r->surfaces}) {  // (... nor the sets' planes and cells; the targets themselves stay)
+    rc = recon_set_clear(c, t);
+    if (rc) return rc;
+  }
   return recon_start_over(c, c->recon, knots_xyzw);
 }
 
@@ -531,33 +530,68 @@ int cmx_backend_recon_pol_render(cmx_ctx *c, double gamma, int mode, unsigned ch
   return display_deliver(c, bytes, out);
 }
 
-// ---- pinhole views: the set of virtual cameras cmx_backend_recon_view_add* (cmx_recon_feed.cpp) votes into, and its planes' way out
-static void recon_view_free(cmx_ctx *c, ReconState *r) {
-  if (!r->d_views) return;
-  (void)hipStreamSynchronize(c->stream);  // (a vote pass queued earlier may still write the planes)
-  void *dev[] = {r->d_views, r->d_vranges, r->d_vplanes, r->d_vfixed, r->d_vvoted};
-  for (void *p : dev) (void)hipFree(p);
-  r->d_views = nullptr; r->d_vranges = nullptr; r->d_vplanes = nullptr; r->d_vfixed = nullptr; r->d_vvoted = nullptr;
-  r->n_views = r->Wv = r->Hv = 0;
+// ---- target sets: the pinhole views, voxel grids and time surfaces that cmx_backend_recon_view_add* / _voxel_add* / _surface_add*
+// (cmx_recon_feed.cpp) vote into, and their contents' way out.  One ReconTargetSet each and one copy of everything they share; a
+// call names its set by member (&ReconState::views ...), since the reconstruction may not exist yet when it does.
+static void recon_set_free(cmx_ctx *c, ReconState *r, ReconTargetSet *t) {
+  if (!t->d_entries) return;
+  (void)hipStreamSynchronize(c->stream);  // (a vote pass queued earlier may still write the planes or cells)
+  t->release();
+  if (t == &r->surfaces) {
+    (void)hipFree(r->d_stref); (void)hipFree(r->d_sdecay);
+    r->d_stref = nullptr; r->d_sdecay = nullptr; r->sdecay_cap = 0;
+  }
 }
 
-int recon_view_clear(cmx_ctx *c, ReconState *r) {
-  if (!r->d_views) return CMX_OK;
-  const size_t np = (size_t)r->n_views * r->Wv * r->Hv;
-  HIP_TRY(c, hipMemsetAsync(r->d_vplanes, 0, np * sizeof(float), c->stream));
-  if (r->d_vfixed) HIP_TRY(c, hipMemsetAsync(r->d_vfixed, 0, np * sizeof(unsigned long long), c->stream));
-  HIP_TRY(c, hipMemsetAsync(r->d_vvoted, 0, (size_t)r->n_views * sizeof(unsigned long long), c->stream));
+int recon_set_clear(cmx_ctx *c, ReconTargetSet *t) {
+  if (!t->d_entries) return CMX_OK;
+  const size_t nc = (size_t)t->n * t->cells_per_target();
+  if (t->timestamps) {  // every cell = "no event yet": INT64_MIN, a pattern no byte memset writes
+    launch_recon_surface_fill(t->d_cells, nc, c->stream);
+    HIP_TRY(c, hipGetLastError());
+  } else {
+    HIP_TRY(c, hipMemsetAsync(t->d_planes, 0, nc * sizeof(float), c->stream));
+    if (t->d_fixed) HIP_TRY(c, hipMemsetAsync(t->d_fixed, 0, nc * sizeof(unsigned long long), c->stream));
+  }
+  HIP_TRY(c, hipMemsetAsync(t->d_voted, 0, (size_t)t->n * sizeof(unsigned long long), c->stream));
   return CMX_OK;
 }
 
-static int recon_view_enter(cmx_ctx *c) {
+int recon_set_enter(cmx_ctx *c, ReconTargetSet ReconState::*which) {
   const int rc = recon_enter(c, true);
   if (rc) return rc;
-  if (!c->recon->d_views) return fail(c, CMX_ERR_STATE, "cmx_backend_recon_view_begin has not succeeded");
+  const ReconTargetSet &t = c->recon->*which;
+  if (!t.d_entries) return fail(c, CMX_ERR_STATE, "cmx_backend_recon_%s_begin has not succeeded", t.api);
   return CMX_OK;
 }
 
-// the argument rules of ONE view (or voxel grid) and its entry as the kernels read it: R(quat)^T from the normalised quaternion
+// the common front door of get*, render and decay*: the set, and a range of targets inside it
+static int recon_set_range(cmx_ctx *c, ReconTargetSet ReconState::*which, int first, int count) {
+  const int rc = recon_set_enter(c, which);
+  if (rc) return rc;
+  const ReconTargetSet &t = c->recon->*which;
+  if (first < 0 || count < 0 || first > t.n || count > t.n - first)
+    return fail(c, CMX_ERR_INVALID_ARG, "%ss [%d, %d + %d) outside the %d of the set", t.noun, first, first, count, t.n);
+  return CMX_OK;
+}
+
+static int recon_set_reset(cmx_ctx *c, ReconTargetSet ReconState::*which) {
+  int rc = recon_set_enter(c, which);
+  if (rc) return rc;
+  rc = recon_set_clear(c, &(c->recon->*which));
+  if (rc) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return CMX_OK;
+}
+
+static int recon_set_end(cmx_ctx *c, ReconTargetSet ReconState::*which) {
+  const int rc = recon_enter(c, true);
+  if (rc) return rc;
+  recon_set_free(c, c->recon, &(c->recon->*which));  // (no set: nothing to free, not an error)
+  return CMX_OK;
+}
+
+// the argument rules of ONE target and its entry as the kernels read it: R(quat)^T from the normalised quaternion
 static int recon_view_entry(cmx_ctx *c, const cmx_recon_view &v, int i, ReconViewDev *out) {
   const double *q = v.quat_xyzw;
   const double nrm = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
@@ -576,368 +610,192 @@ static int recon_view_entry(cmx_ctx *c, const cmx_recon_view &v, int i, ReconVie
   return CMX_OK;
 }
 
-int cmx_backend_recon_view_begin(cmx_ctx *c, int Wv, int Hv, int n_views, const cmx_recon_view *views) {
+// What a _begin call asks for.  Entry: the set's entry type, a ReconViewDev or a struct that starts with one.  limits: the set's own
+// rules on n and per, checked after the size and before the cell count; extra: its own rule on target i and whatever its entry adds,
+// after recon_view_entry.  `what` names the request in the two messages that speak of all of it.
+template <typename Entry, typename Limits, typename Extra>
+static int recon_set_begin(cmx_ctx *c, ReconTargetSet ReconState::*which, int W, int H, int n, int per, bool polarity, const cmx_recon_view *targets,
+                           const char *what, Limits limits, Extra extra) {
   int rc = recon_enter(c, true);
   if (rc) return rc;
-  if (Wv < 4 || Wv > 8192 || Hv < 4 || Hv > 8192) return fail(c, CMX_ERR_INVALID_ARG, "view size %d x %d outside [4, 8192]", Wv, Hv);
-  if (n_views < 1 || n_views > 4096) return fail(c, CMX_ERR_INVALID_ARG, "n_views=%d outside [1, 4096]", n_views);
-  if ((long long)n_views * Wv * Hv > (1LL << 28)) return fail(c, CMX_ERR_INVALID_ARG, "%d views of %d x %d: more than 2^28 cells", n_views, Wv, Hv);
-  if (!views) return fail(c, CMX_ERR_INVALID_ARG, "null view array");
-  std::vector<ReconViewDev> dev((size_t)n_views);
-  std::vector<ReconViewRange> ranges((size_t)n_views);
-  for (int i = 0; i < n_views; i++) {
-    rc = recon_view_entry(c, views[i], i, &dev[(size_t)i]);
+  ReconState *r = c->recon;
+  ReconTargetSet *t = &(r->*which);
+  if (W < 4 || W > 8192 || H < 4 || H > 8192) return fail(c, CMX_ERR_INVALID_ARG, "%s size %d x %d outside [4, 8192]", t->noun, W, H);
+  rc = limits();
+  if (rc) return rc;
+  if ((long long)n * per * W * H > (1LL << 28)) return fail(c, CMX_ERR_INVALID_ARG, "%s: more than 2^28 cells", what);
+  if (!targets) return fail(c, CMX_ERR_INVALID_ARG, "null %s array", t->noun);
+  std::vector<Entry> dev((size_t)n);
+  std::vector<ReconViewRange> ranges((size_t)n);
+  for (int i = 0; i < n; i++) {
+    ReconViewDev *v = reinterpret_cast<ReconViewDev *>(&dev[(size_t)i]);
+    rc = recon_view_entry(c, targets[i], i, v);
+    if (!rc) rc = extra(i, targets[i], &dev[(size_t)i]);
     if (rc) return rc;
-    ranges[(size_t)i] = ReconViewRange{dev[(size_t)i].t_lo, dev[(size_t)i].t_hi};
+    ranges[(size_t)i] = ReconViewRange{v->t_lo, v->t_hi};
   }
-  ReconState *r = c->recon;
-  recon_view_free(c, r);  // a second begin starts over
-  const size_t np = (size_t)n_views * Wv * Hv;
-  ReconViewDev *d_views = nullptr;
-  ReconViewRange *d_ranges = nullptr;
-  float *planes = nullptr;
-  unsigned long long *fixed = nullptr, *voted = nullptr;
-  hipError_t e = hipMalloc((void **)&d_views, dev.size() * sizeof(ReconViewDev));
-  if (e == hipSuccess) e = hipMalloc((void **)&d_ranges, ranges.size() * sizeof(ReconViewRange));
-  if (e == hipSuccess) e = hipMalloc((void **)&planes, np * sizeof(float));
-  if (e == hipSuccess && r->deterministic) e = hipMalloc((void **)&fixed, np * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMalloc((void **)&voted, (size_t)n_views * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMemcpy(d_views, dev.data(), dev.size() * sizeof(ReconViewDev), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_ranges, ranges.data(), ranges.size() * sizeof(ReconViewRange), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {  // (all of it or none: d_views says whether a view set exists)
-    (void)hipFree(d_views); (void)hipFree(d_ranges); (void)hipFree(planes); (void)hipFree(fixed); (void)hipFree(voted);
-    return fail(c, CMX_ERR_HIP, "allocating %d views of %d x %d: %s", n_views, Wv, Hv, hipGetErrorString(e));
+  recon_set_free(c, r, t);  // a second begin starts over
+  ReconTargetSet s{t->noun, t->api, t->timestamps};
+  const size_t nc = (size_t)n * per * W * H;
+  hipError_t e = hipMalloc(&s.d_entries, dev.size() * sizeof(Entry));
+  if (e == hipSuccess) e = hipMalloc((void **)&s.d_ranges, ranges.size() * sizeof(ReconViewRange));
+  if (e == hipSuccess && s.timestamps) e = hipMalloc((void **)&s.d_cells, nc * sizeof(long long));
+  if (e == hipSuccess && !s.timestamps) e = hipMalloc((void **)&s.d_planes, nc * sizeof(float));
+  if (e == hipSuccess && !s.timestamps && r->deterministic) e = hipMalloc((void **)&s.d_fixed, nc * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMalloc((void **)&s.d_voted, (size_t)n * sizeof(unsigned long long));
+  if (e == hipSuccess && t == &r->surfaces) e = hipMalloc((void **)&r->d_stref, (size_t)n * sizeof(long long));
+  if (e == hipSuccess) e = hipMemcpy(s.d_entries, dev.data(), dev.size() * sizeof(Entry), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(s.d_ranges, ranges.data(), ranges.size() * sizeof(ReconViewRange), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {  // (all of it or none: d_entries says whether the set exists)
+    s.release();
+    if (t == &r->surfaces) { (void)hipFree(r->d_stref); r->d_stref = nullptr; }
+    return fail(c, CMX_ERR_HIP, "allocating %s: %s", what, hipGetErrorString(e));
   }
-  r->d_views = d_views; r->d_vranges = d_ranges; r->d_vplanes = planes; r->d_vfixed = fixed; r->d_vvoted = voted;
-  r->n_views = n_views; r->Wv = Wv; r->Hv = Hv;
-  rc = recon_view_clear(c, r);
+  s.n = n; s.W = W; s.H = H; s.per = per; s.polarity = polarity;
+  *t = s;
+  rc = recon_set_clear(c, t);
   if (rc) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return CMX_OK;
 }
 
-int cmx_backend_recon_view_reset(cmx_ctx *c) {
-  int rc = recon_view_enter(c);
-  if (rc) return rc;
-  rc = recon_view_clear(c, c->recon);
-  if (rc) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return CMX_OK;
+// targets [first, first + count) wherever `out` is (host: get; the context's device: get_device) and their counters: the timestamps as
+// they are, or the vote sums as fp32 -- in deterministic mode the current fixed-point sums, converted first (they stay: votes may follow)
+typedef void (*ReconFixedToFloat)(const unsigned long long *fixed, float *plane, size_t n, hipStream_t s);
+static void recon_set_refresh(cmx_ctx *c, ReconTargetSet &t, int first, int count, ReconFixedToFloat convert) {
+  const size_t per = t.cells_per_target();
+  if (t.d_fixed) convert(t.d_fixed + (size_t)first * per, t.d_planes + (size_t)first * per, (size_t)count * per, c->stream);
 }
-
-int cmx_backend_recon_view_end(cmx_ctx *c) {
-  const int rc = recon_enter(c, true);
-  if (rc) return rc;
-  recon_view_free(c, c->recon);  // (no view set: nothing to free, not an error)
-  return CMX_OK;
-}
-
-// views [first, first + count) as fp32 on the device: in deterministic mode the current fixed-point sums, converted (they stay)
-static void recon_view_refresh(cmx_ctx *c, ReconState *r, int first, int count) {
-  const size_t np = (size_t)r->Wv * r->Hv;
-  if (r->d_vfixed) launch_recon_fixed_to_float(r->d_vfixed + (size_t)first * np, r->d_vplanes + (size_t)first * np, (size_t)count * np, c->stream);
-}
-
-int cmx_backend_recon_view_get(cmx_ctx *c, int first_view, int count, float *planes, int64_t *n_voted) {
-  int rc = recon_view_enter(c);
-  if (rc) return rc;
-  ReconState *r = c->recon;
-  if (first_view < 0 || count < 0 || first_view > r->n_views || count > r->n_views - first_view)
-    return fail(c, CMX_ERR_INVALID_ARG, "views [%d, %d + %d) outside the %d of the set", first_view, first_view, count, r->n_views);
-  if (count == 0) return CMX_OK;
-  const size_t np = (size_t)r->Wv * r->Hv;
+static int recon_set_deliver(cmx_ctx *c, ReconTargetSet ReconState::*which, int first, int count, void *out, ReconFixedToFloat convert,
+                             hipMemcpyKind kind, int64_t *n_voted) {
+  const int rc = recon_set_range(c, which, first, count);
+  if (rc || count == 0) return rc;
+  ReconTargetSet &t = c->recon->*which;
+  const size_t per = t.cells_per_target();
   static_assert(sizeof(int64_t) == sizeof(unsigned long long), "the counters travel as they are");
-  if (planes) {
-    recon_view_refresh(c, r, first_view, count);
+  if (out && t.timestamps) HIP_TRY(c, hipMemcpyAsync(out, t.d_cells + (size_t)first * per, (size_t)count * per * sizeof(int64_t), kind, c->stream));
+  if (out && !t.timestamps) {
+    recon_set_refresh(c, t, first, count, convert);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(planes, r->d_vplanes + (size_t)first_view * np, (size_t)count * np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out, t.d_planes + (size_t)first * per, (size_t)count * per * sizeof(float), kind, c->stream));
   }
-  if (n_voted) HIP_TRY(c, hipMemcpyAsync(n_voted, r->d_vvoted + first_view, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  if (n_voted) HIP_TRY(c, hipMemcpyAsync(n_voted, t.d_voted + first, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return CMX_OK;
+}
+// ... into memory of the context's device
+static int recon_set_deliver_device(cmx_ctx *c, ReconTargetSet ReconState::*which, int first, int count, void *d_out, ReconFixedToFloat convert) {
+  const int rc = recon_set_enter(c, which);
+  if (rc) return rc;
+  if (count > 0 && !d_out) return fail(c, CMX_ERR_INVALID_ARG, "null device output");
+  return recon_set_deliver(c, which, first, count, d_out, convert, hipMemcpyDeviceToDevice, nullptr);
+}
+
+// ---- pinhole views
+int cmx_backend_recon_view_begin(cmx_ctx *c, int Wv, int Hv, int n_views, const cmx_recon_view *views) {
+  char what[96];
+  snprintf(what, sizeof(what), "%d views of %d x %d", n_views, Wv, Hv);
+  return recon_set_begin<ReconViewDev>(
+      c, &ReconState::views, Wv, Hv, n_views, 1, false, views, what,
+      [&] { return n_views < 1 || n_views > 4096 ? fail(c, CMX_ERR_INVALID_ARG, "n_views=%d outside [1, 4096]", n_views) : (int)CMX_OK; },
+      [](int, const cmx_recon_view &, ReconViewDev *) { return (int)CMX_OK; });
+}
+int cmx_backend_recon_view_reset(cmx_ctx *c) { return recon_set_reset(c, &ReconState::views); }
+int cmx_backend_recon_view_end(cmx_ctx *c) { return recon_set_end(c, &ReconState::views); }
+int cmx_backend_recon_view_get(cmx_ctx *c, int first_view, int count, float *planes, int64_t *n_voted) {
+  return recon_set_deliver(c, &ReconState::views, first_view, count, planes, launch_recon_fixed_to_float, hipMemcpyDeviceToHost, n_voted);
 }
 
 // cmx_backend_recon_render's tone map, without the outline, on one view's plane
 int cmx_backend_recon_view_render(cmx_ctx *c, int view, double gamma, unsigned char *out) {
-  int rc = recon_view_enter(c);
+  int rc = recon_set_enter(c, &ReconState::views);
   if (rc) return rc;
-  ReconState *r = c->recon;
-  if (view < 0 || view >= r->n_views) return fail(c, CMX_ERR_INVALID_ARG, "view %d outside the %d of the set", view, r->n_views);
+  ReconTargetSet &t = c->recon->views;
+  if (view < 0 || view >= t.n) return fail(c, CMX_ERR_INVALID_ARG, "view %d outside the %d of the set", view, t.n);
   if (!out) return fail(c, CMX_ERR_INVALID_ARG, "null output buffer");
   if (!std::isfinite(gamma) || !(gamma > 0.0)) return fail(c, CMX_ERR_INVALID_ARG, "gamma must be finite and > 0");
-  const size_t np = (size_t)r->Wv * r->Hv;
+  const size_t np = t.cells_per_target();
   rc = display_begin(c, np);
   if (rc) return rc;
-  recon_view_refresh(c, r, view, 1);
-  const float *plane = r->d_vplanes + (size_t)view * np;
+  recon_set_refresh(c, t, view, 1, launch_recon_fixed_to_float);
+  const float *plane = t.d_planes + (size_t)view * np;
   launch_display_range(plane, nullptr, np, c->d_disp_range, c->stream);
   launch_display_map(plane, np, (float)gamma, false, c->d_disp_range, c->d_disp, c->stream);
   return display_deliver(c, np, out);
 }
 
-// ---- voxel grids: the set of grids cmx_backend_recon_voxel_add* (cmx_recon_feed.cpp) votes into, and its planes' way out.  A grid is
-// a view with a bin axis over its time range; the planes are grid-major, n_bins to a grid.
-static void recon_voxel_free(cmx_ctx *c, ReconState *r) {
-  if (!r->d_grids) return;
-  (void)hipStreamSynchronize(c->stream);  // (a vote pass queued earlier may still write the planes)
-  void *dev[] = {r->d_grids, r->d_xranges, r->d_xplanes, r->d_xfixed, r->d_xvoted};
-  for (void *p : dev) (void)hipFree(p);
-  r->d_grids = nullptr; r->d_xranges = nullptr; r->d_xplanes = nullptr; r->d_xfixed = nullptr; r->d_xvoted = nullptr;
-  r->n_grids = r->n_bins = r->Wx = r->Hx = 0;
-  r->vox_signed = false;
-}
-
-int recon_voxel_clear(cmx_ctx *c, ReconState *r) {
-  if (!r->d_grids) return CMX_OK;
-  const size_t np = (size_t)r->n_grids * r->n_bins * r->Wx * r->Hx;
-  HIP_TRY(c, hipMemsetAsync(r->d_xplanes, 0, np * sizeof(float), c->stream));
-  if (r->d_xfixed) HIP_TRY(c, hipMemsetAsync(r->d_xfixed, 0, np * sizeof(unsigned long long), c->stream));
-  HIP_TRY(c, hipMemsetAsync(r->d_xvoted, 0, (size_t)r->n_grids * sizeof(unsigned long long), c->stream));
-  return CMX_OK;
-}
-
-static int recon_voxel_enter(cmx_ctx *c) {
-  const int rc = recon_enter(c, true);
-  if (rc) return rc;
-  if (!c->recon->d_grids) return fail(c, CMX_ERR_STATE, "cmx_backend_recon_voxel_begin has not succeeded");
-  return CMX_OK;
-}
-
+// ---- voxel grids: a grid is a view with a bin axis over its time range; the planes are grid-major, n_bins to a grid, and their
+// fixed-point twins hold signed sums
 int cmx_backend_recon_voxel_begin(cmx_ctx *c, int Wv, int Hv, int n_bins, int signed_polarity, int n_grids, const cmx_recon_view *grids) {
-  int rc = recon_enter(c, true);
-  if (rc) return rc;
-  if (Wv < 4 || Wv > 8192 || Hv < 4 || Hv > 8192) return fail(c, CMX_ERR_INVALID_ARG, "grid size %d x %d outside [4, 8192]", Wv, Hv);
-  if (n_bins < 1 || n_bins > 64) return fail(c, CMX_ERR_INVALID_ARG, "n_bins=%d outside [1, 64]", n_bins);
-  if (n_grids < 1 || (long long)n_grids * n_bins > 4096)
-    return fail(c, CMX_ERR_INVALID_ARG, "%d grids of %d bins: n_grids * n_bins outside [1, 4096]", n_grids, n_bins);
-  if ((long long)n_grids * n_bins * Wv * Hv > (1LL << 28))
-    return fail(c, CMX_ERR_INVALID_ARG, "%d grids of %d bins of %d x %d: more than 2^28 cells", n_grids, n_bins, Wv, Hv);
-  if (!grids) return fail(c, CMX_ERR_INVALID_ARG, "null grid array");
-  std::vector<ReconVoxelDev> dev((size_t)n_grids);
-  std::vector<ReconViewRange> ranges((size_t)n_grids);
-  for (int i = 0; i < n_grids; i++) {
-    ReconVoxelDev &d = dev[(size_t)i];
-    rc = recon_view_entry(c, grids[i], i, &d.v);
-    if (rc) return rc;
-    // t_lo < t_hi: their difference as an unsigned number is exact, whatever the two are -- no signed overflow.  The bin axis needs
-    // a finite span: beyond 2^53 ns the fp64 image of (t - t_lo) is no longer exact, so "all time" is refused
-    const uint64_t span = (uint64_t)grids[i].t_hi_ns - (uint64_t)grids[i].t_lo_ns;
-    if (span > (1ull << 53)) return fail(c, CMX_ERR_INVALID_ARG, "grid %d: time range longer than 2^53 ns (the bin axis needs a finite span)", i);
-    d.scale = (double)(n_bins - 1) / (double)span;
-    ranges[(size_t)i] = ReconViewRange{d.v.t_lo, d.v.t_hi};
-  }
-  ReconState *r = c->recon;
-  recon_voxel_free(c, r);  // a second begin starts over
-  const size_t np = (size_t)n_grids * n_bins * Wv * Hv;
-  ReconVoxelDev *d_grids = nullptr;
-  ReconViewRange *d_ranges = nullptr;
-  float *planes = nullptr;
-  unsigned long long *fixed = nullptr, *voted = nullptr;
-  hipError_t e = hipMalloc((void **)&d_grids, dev.size() * sizeof(ReconVoxelDev));
-  if (e == hipSuccess) e = hipMalloc((void **)&d_ranges, ranges.size() * sizeof(ReconViewRange));
-  if (e == hipSuccess) e = hipMalloc((void **)&planes, np * sizeof(float));
-  if (e == hipSuccess && r->deterministic) e = hipMalloc((void **)&fixed, np * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMalloc((void **)&voted, (size_t)n_grids * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMemcpy(d_grids, dev.data(), dev.size() * sizeof(ReconVoxelDev), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_ranges, ranges.data(), ranges.size() * sizeof(ReconViewRange), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {  // (all of it or none: d_grids says whether a voxel set exists)
-    (void)hipFree(d_grids); (void)hipFree(d_ranges); (void)hipFree(planes); (void)hipFree(fixed); (void)hipFree(voted);
-    return fail(c, CMX_ERR_HIP, "allocating %d grids of %d bins of %d x %d: %s", n_grids, n_bins, Wv, Hv, hipGetErrorString(e));
-  }
-  r->d_grids = d_grids; r->d_xranges = d_ranges; r->d_xplanes = planes; r->d_xfixed = fixed; r->d_xvoted = voted;
-  r->n_grids = n_grids; r->n_bins = n_bins; r->Wx = Wv; r->Hx = Hv;
-  r->vox_signed = signed_polarity != 0;
-  rc = recon_voxel_clear(c, r);
-  if (rc) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return CMX_OK;
+  char what[96];
+  snprintf(what, sizeof(what), "%d grids of %d bins of %d x %d", n_grids, n_bins, Wv, Hv);
+  return recon_set_begin<ReconVoxelDev>(
+      c, &ReconState::voxels, Wv, Hv, n_grids, n_bins, signed_polarity != 0, grids, what,
+      [&] {
+        if (n_bins < 1 || n_bins > 64) return fail(c, CMX_ERR_INVALID_ARG, "n_bins=%d outside [1, 64]", n_bins);
+        if (n_grids < 1 || (long long)n_grids * n_bins > 4096)
+          return fail(c, CMX_ERR_INVALID_ARG, "%d grids of %d bins: n_grids * n_bins outside [1, 4096]", n_grids, n_bins);
+        return (int)CMX_OK;
+      },
+      [&](int i, const cmx_recon_view &g, ReconVoxelDev *d) {
+        // t_lo < t_hi: their difference as an unsigned number is exact, whatever the two are -- no signed overflow.  The bin axis needs
+        // a finite span: beyond 2^53 ns the fp64 image of (t - t_lo) is no longer exact, so "all time" is refused
+        const uint64_t span = (uint64_t)g.t_hi_ns - (uint64_t)g.t_lo_ns;
+        if (span > (1ull << 53)) return fail(c, CMX_ERR_INVALID_ARG, "grid %d: time range longer than 2^53 ns (the bin axis needs a finite span)", i);
+        d->scale = (double)(n_bins - 1) / (double)span;
+        return (int)CMX_OK;
+      });
 }
-
-int cmx_backend_recon_voxel_reset(cmx_ctx *c) {
-  int rc = recon_voxel_enter(c);
-  if (rc) return rc;
-  rc = recon_voxel_clear(c, c->recon);
-  if (rc) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return CMX_OK;
-}
-
-int cmx_backend_recon_voxel_end(cmx_ctx *c) {
-  const int rc = recon_enter(c, true);
-  if (rc) return rc;
-  recon_voxel_free(c, c->recon);  // (no voxel set: nothing to free, not an error)
-  return CMX_OK;
-}
-
-// grids [first, first + count) as fp32 on the device, wherever `out` is (host: get; the context's device: get_device), and their
-// counters; in deterministic mode the current fixed-point sums, read as signed and converted first (they stay: votes may follow)
-static int recon_voxel_deliver(cmx_ctx *c, int first_grid, int count, float *out, hipMemcpyKind kind, int64_t *n_voted) {
-  int rc = recon_voxel_enter(c);
-  if (rc) return rc;
-  ReconState *r = c->recon;
-  if (first_grid < 0 || count < 0 || first_grid > r->n_grids || count > r->n_grids - first_grid)
-    return fail(c, CMX_ERR_INVALID_ARG, "grids [%d, %d + %d) outside the %d of the set", first_grid, first_grid, count, r->n_grids);
-  if (count == 0) return CMX_OK;
-  const size_t ng = (size_t)r->n_bins * r->Wx * r->Hx, at = (size_t)first_grid * ng, n = (size_t)count * ng;
-  if (out) {
-    if (r->d_xfixed) launch_recon_fixed_to_float_signed(r->d_xfixed + at, r->d_xplanes + at, n, c->stream);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(out, r->d_xplanes + at, n * sizeof(float), kind, c->stream));
-  }
-  if (n_voted) HIP_TRY(c, hipMemcpyAsync(n_voted, r->d_xvoted + first_grid, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return CMX_OK;
-}
+int cmx_backend_recon_voxel_reset(cmx_ctx *c) { return recon_set_reset(c, &ReconState::voxels); }
+int cmx_backend_recon_voxel_end(cmx_ctx *c) { return recon_set_end(c, &ReconState::voxels); }
 int cmx_backend_recon_voxel_get(cmx_ctx *c, int first_grid, int count, float *out, int64_t *n_voted) {
-  return recon_voxel_deliver(c, first_grid, count, out, hipMemcpyDeviceToHost, n_voted);
+  return recon_set_deliver(c, &ReconState::voxels, first_grid, count, out, launch_recon_fixed_to_float_signed, hipMemcpyDeviceToHost, n_voted);
 }
 int cmx_backend_recon_voxel_get_device(cmx_ctx *c, int first_grid, int count, float *d_out) {
-  const int rc = recon_voxel_enter(c);
-  if (rc) return rc;
-  if (count > 0 && !d_out) return fail(c, CMX_ERR_INVALID_ARG, "null device output");
-  return recon_voxel_deliver(c, first_grid, count, d_out, hipMemcpyDeviceToDevice, nullptr);
+  return recon_set_deliver_device(c, &ReconState::voxels, first_grid, count, d_out, launch_recon_fixed_to_float_signed);
 }
 
-// ---- time surfaces: the set of surfaces cmx_backend_recon_surface_add* (cmx_recon_feed.cpp) votes into, and its cells' way out -- as
-// they are (get, get_device: absolute nanoseconds, INT64_MIN where no event landed) or through an exponential decay (decay,
-// decay_device).  A surface is a view; the cells are surface-major, C = 1 or 2 channels to a surface, ON before OFF.
-static void recon_surface_free(cmx_ctx *c, ReconState *r) {
-  if (!r->d_surfaces) return;
-  (void)hipStreamSynchronize(c->stream);  // (a vote pass queued earlier may still write the cells)
-  void *dev[] = {r->d_surfaces, r->d_sranges, r->d_scells, r->d_svoted, r->d_stref, r->d_sdecay};
-  for (void *p : dev) (void)hipFree(p);
-  r->d_surfaces = nullptr; r->d_sranges = nullptr; r->d_scells = nullptr; r->d_svoted = nullptr; r->d_stref = nullptr;
-  r->d_sdecay = nullptr; r->sdecay_cap = 0;
-  r->n_surfaces = r->Ws = r->Hs = 0;
-  r->surf_by_pol = false;
-}
-
-static size_t recon_surface_cells(const ReconState *r) { return (size_t)(r->surf_by_pol ? 2 : 1) * r->Ws * r->Hs; }  // of ONE surface
-
-int recon_surface_clear(cmx_ctx *c, ReconState *r) {
-  if (!r->d_surfaces) return CMX_OK;
-  launch_recon_surface_fill(r->d_scells, (size_t)r->n_surfaces * recon_surface_cells(r), c->stream);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemsetAsync(r->d_svoted, 0, (size_t)r->n_surfaces * sizeof(unsigned long long), c->stream));
-  return CMX_OK;
-}
-
-static int recon_surface_enter(cmx_ctx *c) {
-  const int rc = recon_enter(c, true);
-  if (rc) return rc;
-  if (!c->recon->d_surfaces) return fail(c, CMX_ERR_STATE, "cmx_backend_recon_surface_begin has not succeeded");
-  return CMX_OK;
-}
-
+// ---- time surfaces: a surface is a view; the cells are surface-major, C = 1 or 2 channels to a surface, ON before OFF, and leave as
+// they are (get, get_device: absolute nanoseconds, INT64_MIN where no event landed) or through an exponential decay (decay, decay_device)
 int cmx_backend_recon_surface_begin(cmx_ctx *c, int Wv, int Hv, int by_polarity, int n_surfaces, const cmx_recon_view *surfaces) {
-  int rc = recon_enter(c, true);
-  if (rc) return rc;
-  if (Wv < 4 || Wv > 8192 || Hv < 4 || Hv > 8192) return fail(c, CMX_ERR_INVALID_ARG, "surface size %d x %d outside [4, 8192]", Wv, Hv);
-  if (n_surfaces < 1 || n_surfaces > 4096) return fail(c, CMX_ERR_INVALID_ARG, "n_surfaces=%d outside [1, 4096]", n_surfaces);
   const int C = by_polarity ? 2 : 1;
-  if ((long long)n_surfaces * C * Wv * Hv > (1LL << 28))
-    return fail(c, CMX_ERR_INVALID_ARG, "%d surfaces of %d channels of %d x %d: more than 2^28 cells", n_surfaces, C, Wv, Hv);
-  if (!surfaces) return fail(c, CMX_ERR_INVALID_ARG, "null surface array");
-  std::vector<ReconViewDev> dev((size_t)n_surfaces);
-  std::vector<ReconViewRange> ranges((size_t)n_surfaces);
-  for (int i = 0; i < n_surfaces; i++) {
-    rc = recon_view_entry(c, surfaces[i], i, &dev[(size_t)i]);
-    if (rc) return rc;
-    // INT64_MIN marks a cell no event has reached; a range that starts there could hold an event with that timestamp
-    if (surfaces[i].t_lo_ns == INT64_MIN) return fail(c, CMX_ERR_INVALID_ARG, "surface %d: t_lo_ns is INT64_MIN, the empty marker", i);
-    ranges[(size_t)i] = ReconViewRange{dev[(size_t)i].t_lo, dev[(size_t)i].t_hi};
-  }
-  ReconState *r = c->recon;
-  recon_surface_free(c, r);  // a second begin starts over
-  const size_t nc = (size_t)n_surfaces * C * Wv * Hv;
-  ReconViewDev *d_surfaces = nullptr;
-  ReconViewRange *d_ranges = nullptr;
-  long long *cells = nullptr, *tref = nullptr;
-  unsigned long long *voted = nullptr;
-  hipError_t e = hipMalloc((void **)&d_surfaces, dev.size() * sizeof(ReconViewDev));
-  if (e == hipSuccess) e = hipMalloc((void **)&d_ranges, ranges.size() * sizeof(ReconViewRange));
-  if (e == hipSuccess) e = hipMalloc((void **)&cells, nc * sizeof(long long));
-  if (e == hipSuccess) e = hipMalloc((void **)&voted, (size_t)n_surfaces * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMalloc((void **)&tref, (size_t)n_surfaces * sizeof(long long));
-  if (e == hipSuccess) e = hipMemcpy(d_surfaces, dev.data(), dev.size() * sizeof(ReconViewDev), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_ranges, ranges.data(), ranges.size() * sizeof(ReconViewRange), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {  // (all of it or none: d_surfaces says whether a surface set exists)
-    (void)hipFree(d_surfaces); (void)hipFree(d_ranges); (void)hipFree(cells); (void)hipFree(voted); (void)hipFree(tref);
-    return fail(c, CMX_ERR_HIP, "allocating %d surfaces of %d channels of %d x %d: %s", n_surfaces, C, Wv, Hv, hipGetErrorString(e));
-  }
-  r->d_surfaces = d_surfaces; r->d_sranges = d_ranges; r->d_scells = cells; r->d_svoted = voted; r->d_stref = tref;
-  r->n_surfaces = n_surfaces; r->Ws = Wv; r->Hs = Hv;
-  r->surf_by_pol = by_polarity != 0;
-  rc = recon_surface_clear(c, r);
-  if (rc) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return CMX_OK;
+  char what[96];
+  snprintf(what, sizeof(what), "%d surfaces of %d channels of %d x %d", n_surfaces, C, Wv, Hv);
+  return recon_set_begin<ReconViewDev>(
+      c, &ReconState::surfaces, Wv, Hv, n_surfaces, C, by_polarity != 0, surfaces, what,
+      [&] { return n_surfaces < 1 || n_surfaces > 4096 ? fail(c, CMX_ERR_INVALID_ARG, "n_surfaces=%d outside [1, 4096]", n_surfaces) : (int)CMX_OK; },
+      [&](int i, const cmx_recon_view &s, ReconViewDev *) {
+        // INT64_MIN marks a cell no event has reached; a range that starts there could hold an event with that timestamp
+        if (s.t_lo_ns == INT64_MIN) return fail(c, CMX_ERR_INVALID_ARG, "surface %d: t_lo_ns is INT64_MIN, the empty marker", i);
+        return (int)CMX_OK;
+      });
 }
-
-int cmx_backend_recon_surface_reset(cmx_ctx *c) {
-  int rc = recon_surface_enter(c);
-  if (rc) return rc;
-  rc = recon_surface_clear(c, c->recon);
-  if (rc) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return CMX_OK;
-}
-
-int cmx_backend_recon_surface_end(cmx_ctx *c) {
-  const int rc = recon_enter(c, true);
-  if (rc) return rc;
-  recon_surface_free(c, c->recon);  // (no surface set: nothing to free, not an error)
-  return CMX_OK;
-}
-
-// the common front door of get* and decay*: a surface set, and a range inside it
-static int recon_surface_range(cmx_ctx *c, int first, int count) {
-  const int rc = recon_surface_enter(c);
-  if (rc) return rc;
-  const ReconState *r = c->recon;
-  if (first < 0 || count < 0 || first > r->n_surfaces || count > r->n_surfaces - first)
-    return fail(c, CMX_ERR_INVALID_ARG, "surfaces [%d, %d + %d) outside the %d of the set", first, first, count, r->n_surfaces);
-  return CMX_OK;
-}
-
-// surfaces [first, first + count) as int64 wherever `cells` is (host: get; the context's device: get_device), and their counters
-static int recon_surface_deliver(cmx_ctx *c, int first, int count, int64_t *cells, hipMemcpyKind kind, int64_t *n_voted) {
-  const int rc = recon_surface_range(c, first, count);
-  if (rc) return rc;
-  if (count == 0) return CMX_OK;
-  ReconState *r = c->recon;
-  const size_t per = recon_surface_cells(r);
-  if (cells) HIP_TRY(c, hipMemcpyAsync(cells, r->d_scells + (size_t)first * per, (size_t)count * per * sizeof(int64_t), kind, c->stream));
-  if (n_voted) HIP_TRY(c, hipMemcpyAsync(n_voted, r->d_svoted + first, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return CMX_OK;
-}
+int cmx_backend_recon_surface_reset(cmx_ctx *c) { return recon_set_reset(c, &ReconState::surfaces); }
+int cmx_backend_recon_surface_end(cmx_ctx *c) { return recon_set_end(c, &ReconState::surfaces); }
 int cmx_backend_recon_surface_get(cmx_ctx *c, int first, int count, int64_t *cells, int64_t *n_voted) {
-  return recon_surface_deliver(c, first, count, cells, hipMemcpyDeviceToHost, n_voted);
+  return recon_set_deliver(c, &ReconState::surfaces, first, count, cells, nullptr, hipMemcpyDeviceToHost, n_voted);
 }
 int cmx_backend_recon_surface_get_device(cmx_ctx *c, int first, int count, int64_t *d_cells) {
-  const int rc = recon_surface_enter(c);
-  if (rc) return rc;
-  if (count > 0 && !d_cells) return fail(c, CMX_ERR_INVALID_ARG, "null device output");
-  return recon_surface_deliver(c, first, count, d_cells, hipMemcpyDeviceToDevice, nullptr);
+  return recon_set_deliver_device(c, &ReconState::surfaces, first, count, d_cells, nullptr);
 }
 
 // one decay pass over surfaces [first, first + count) into d_out on the device, queued; t_ref_ns (host, count values) or NULL: every
 // surface's own t_hi
 static int recon_surface_decay_queue(cmx_ctx *c, int first, int count, const int64_t *t_ref_ns, double tau_ns, float *d_out) {
   ReconState *r = c->recon;
+  const ReconTargetSet &t = r->surfaces;
   const long long *d_tref = nullptr;
   if (t_ref_ns) {  // (pageable memory: the copy has read it when the call returns)
     HIP_TRY(c, hipMemcpyAsync(r->d_stref, t_ref_ns, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     d_tref = r->d_stref;
   }
-  launch_recon_surface_decay(r->d_scells + (size_t)first * recon_surface_cells(r), r->d_sranges + first, d_tref, recon_surface_cells(r),
-                             count, tau_ns, d_out, c->stream);
+  launch_recon_surface_decay(t.d_cells + (size_t)first * t.cells_per_target(), t.d_ranges + first, d_tref, t.cells_per_target(), count, tau_ns,
+                             d_out, c->stream);
   HIP_TRY(c, hipGetLastError());
   return CMX_OK;
 }
 static int recon_surface_decay_checks(cmx_ctx *c, int first, int count, double tau_ns, const void *out) {
-  const int rc = recon_surface_range(c, first, count);
+  const int rc = recon_set_range(c, &ReconState::surfaces, first, count);
   if (rc) return rc;
   if (!std::isfinite(tau_ns) || !(tau_ns > 0.0)) return fail(c, CMX_ERR_INVALID_ARG, "tau_ns must be finite and > 0");
   if (count > 0 && !out) return fail(c, CMX_ERR_INVALID_ARG, "null output");
@@ -955,7 +813,7 @@ int cmx_backend_recon_surface_decay(cmx_ctx *c, int first, int count, const int6
   int rc = recon_surface_decay_checks(c, first, count, tau_ns, out);
   if (rc || count == 0) return rc;
   ReconState *r = c->recon;
-  const size_t n = (size_t)count * recon_surface_cells(r);
+  const size_t n = (size_t)count * r->surfaces.cells_per_target();
   rc = ensure(c, r->d_sdecay, r->sdecay_cap, n);  // (the decayed cells exist nowhere else: the set holds timestamps)
   if (rc) return rc;
   rc = recon_surface_decay_queue(c, first, count, t_ref_ns, tau_ns, r->d_sdecay);

@@ -756,32 +756,69 @@ class BackendEvaluator(_Evaluator):
         """Clear the ON / OFF planes and their counters (after the knots have moved); nothing else changes."""
         self._ck(self._L.cmx_backend_recon_pol_reset(self._ctx))
 
+    # --- target sets: what the view, voxel and surface calls below share
+    @staticmethod
+    def _set_targets(targets):
+        """(n, the ReconView array of a *_begin call) from _lib.ReconView structures or the tuples _lib.recon_view takes."""
+        vs = [v if isinstance(v, _lib.ReconView) else _lib.recon_view(*v) for v in targets]
+        return len(vs), (_lib.ReconView * max(len(vs), 1))(*vs)
+
+    def _set_add(self, fn, x, y, t_ns, *pol):
+        """fn(ctx, n, x, y, t_ns[, polarity]).  pol = (polarity, whether the set reads it) for the calls that take one."""
+        x, y, t = _c(x, np.uint16), _c(y, np.uint16), _c(t_ns, np.int64)
+        p = _pol_bytes(pol[0]) if pol and pol[0] is not None and pol[1] else None
+        if not (len(x) == len(y) == len(t)) or (p is not None and len(p) != len(x)):
+            raise ValueError("x, y, t_ns%s must have equal length" % (", polarity" if pol else ""))
+        tail = (p.ctypes.data_as(_lib.c_u8p) if p is not None else None,) if pol else ()
+        self._ck(fn(self._ctx, len(x), x.ctypes.data_as(c_u16p), y.ctypes.data_as(c_u16p), t.ctypes.data_as(c_i64p), *tail))
+
+    def _set_add_aos(self, fn, events, *pol):
+        """fn(ctx, n, records, layout[, polarity offset]).  pol = (polarity field, whether the set reads it)."""
+        ev = np.ascontiguousarray(events)
+        lay = _lib.aos_layout_of(ev)
+        tail = (_pol_offset(ev, pol[0]) if pol[1] else 0,) if pol else ()
+        self._ck(fn(self._ctx, len(ev), ev.ctypes.data_as(C.c_void_p), C.byref(lay), *tail))
+
+    @staticmethod
+    def _set_range(shape, first, count):
+        """(count, the array shape of targets [first, first+count)) of a set of `shape` = (n, ...); count None: all from first."""
+        count = shape[0] - int(first) if count is None else int(count)
+        return count, (max(count, 0),) + tuple(shape[1:])
+
+    def _set_get(self, shape, dtype, get, get_device, first, count, with_counts, out):
+        """get(ctx, first, count, array | None, counters | None) into a new array of dtype, or get_device(ctx, first, count, pointer)
+        into out; with_counts: (that, the int64 events that voted into each target)."""
+        count, shape = self._set_range(shape, first, count)
+        cnt = np.zeros(shape[0], np.int64)
+        cnt_p = cnt.ctypes.data_as(c_i64p) if with_counts else None
+        if out is not None:
+            self._ck(get_device(self._ctx, int(first), count, out.data_ptr()))
+            if with_counts:
+                self._ck(get(self._ctx, int(first), count, None, cnt_p))
+            return (out, cnt) if with_counts else out
+        res = np.empty(shape, dtype)
+        self._ck(get(self._ctx, int(first), count, res.ctypes.data_as(c_fp if dtype == np.float32 else c_i64p), cnt_p))
+        return (res, cnt) if with_counts else res
+
     # --- pinhole views: motion-compensated frames and crops of the same vote loop (cmx_backend_recon_view_*)
     _view_shape = None  # (n_views, Hv, Wv) of the last reconstruct_view_begin
 
     def reconstruct_view_begin(self, views, Wv, Hv):
         """Attach virtual pinhole cameras to the open reconstruction and zero their (Hv, Wv) planes.  views: _lib.ReconView
         structures, or tuples (quat_xyzw, fx, fy, cx, cy, t_lo_ns, t_hi_ns) -- see trajectory.frame_views / crop_view."""
-        vs = [v if isinstance(v, _lib.ReconView) else _lib.recon_view(*v) for v in views]
-        arr = (_lib.ReconView * max(len(vs), 1))(*vs)
+        n, arr = self._set_targets(views)
         self._view_shape = None
-        self._ck(self._L.cmx_backend_recon_view_begin(self._ctx, int(Wv), int(Hv), len(vs), arr))
-        self._view_shape = (len(vs), int(Hv), int(Wv))
+        self._ck(self._L.cmx_backend_recon_view_begin(self._ctx, int(Wv), int(Hv), n, arr))
+        self._view_shape = (n, int(Hv), int(Wv))
 
     def reconstruct_view_add(self, x, y, t_ns):
         """reconstruct_add's vote loop over exactly these events: every sampled event is warped once into the world frame and
         voted into every view whose time range holds its batch time.  Nothing else of the reconstruction is read or written."""
-        x, y, t = _c(x, np.uint16), _c(y, np.uint16), _c(t_ns, np.int64)
-        if not (len(x) == len(y) == len(t)):
-            raise ValueError("x, y, t_ns must have equal length")
-        self._ck(self._L.cmx_backend_recon_view_add(self._ctx, len(x), x.ctypes.data_as(c_u16p), y.ctypes.data_as(c_u16p),
-                                                    t.ctypes.data_as(c_i64p)))
+        self._set_add(self._L.cmx_backend_recon_view_add, x, y, t_ns)
 
     def reconstruct_view_add_aos(self, events):
         """The same from a structured array of records with fields x, y, sec, nsec."""
-        ev = np.ascontiguousarray(events)
-        lay = _lib.aos_layout_of(ev)
-        self._ck(self._L.cmx_backend_recon_view_add_aos(self._ctx, len(ev), ev.ctypes.data_as(C.c_void_p), C.byref(lay)))
+        self._set_add_aos(self._L.cmx_backend_recon_view_add_aos, events)
 
     def reconstruct_view_add_from(self, store, first, count):
         """The same over events_[first, first+count) of a device-resident EventStore."""
@@ -789,13 +826,8 @@ class BackendEvaluator(_Evaluator):
 
     def reconstruct_view_get(self, first=0, count=None, with_counts=False):
         """(count, Hv, Wv) fp32 planes of views [first, first+count) [, int64 events that voted into each]."""
-        n, Hv, Wv = self._view_shape or (0, 0, 0)
-        count = n - int(first) if count is None else int(count)
-        shape = (max(count, 0), Hv, Wv)
-        out, cnt = np.empty(shape, np.float32), np.zeros(shape[0], np.int64)
-        self._ck(self._L.cmx_backend_recon_view_get(self._ctx, int(first), count, out.ctypes.data_as(c_fp),
-                                                    cnt.ctypes.data_as(c_i64p) if with_counts else None))
-        return (out, cnt) if with_counts else out
+        return self._set_get(self._view_shape or (0, 0, 0), np.float32, self._L.cmx_backend_recon_view_get, None, first, count,
+                             with_counts, None)
 
     def reconstruct_view_render(self, view, gamma=0.75):
         """reconstruct_render's tone map (no outline) on one view's plane: (Hv, Wv) uint8."""
@@ -820,30 +852,21 @@ class BackendEvaluator(_Evaluator):
         """Attach voxel grids to the open reconstruction and zero their (n_bins, Hv, Wv) volumes.  grids: _lib.ReconView structures
         or tuples (quat_xyzw, fx, fy, cx, cy, t_lo_ns, t_hi_ns) with a finite time range -- see trajectory.voxel_grids.  signed:
         OFF events vote -1; otherwise every event votes +1 and polarity is never read."""
-        gs = [g if isinstance(g, _lib.ReconView) else _lib.recon_view(*g) for g in grids]
-        arr = (_lib.ReconView * max(len(gs), 1))(*gs)
+        n, arr = self._set_targets(grids)
         self._voxel_shape = None
-        self._ck(self._L.cmx_backend_recon_voxel_begin(self._ctx, int(Wv), int(Hv), int(n_bins), int(bool(signed)), len(gs), arr))
-        self._voxel_shape = (len(gs), int(n_bins), int(Hv), int(Wv))
+        self._ck(self._L.cmx_backend_recon_voxel_begin(self._ctx, int(Wv), int(Hv), int(n_bins), int(bool(signed)), n, arr))
+        self._voxel_shape = (n, int(n_bins), int(Hv), int(Wv))
         self._voxel_signed = bool(signed)
 
     def reconstruct_voxel_add(self, x, y, t_ns, polarity=None):
         """reconstruct_add's vote loop over exactly these events: every sampled event is warped once into the world frame and
         voted, by its OWN timestamp, into the two neighbouring bins of every grid whose range holds it.  polarity (one value per
         event, nonzero / positive = ON) is needed for a signed set and ignored by an unsigned one."""
-        x, y, t = _c(x, np.uint16), _c(y, np.uint16), _c(t_ns, np.int64)
-        p = _pol_bytes(polarity) if polarity is not None and self._voxel_signed else None
-        if not (len(x) == len(y) == len(t)) or (p is not None and len(p) != len(x)):
-            raise ValueError("x, y, t_ns, polarity must have equal length")
-        self._ck(self._L.cmx_backend_recon_voxel_add(self._ctx, len(x), x.ctypes.data_as(c_u16p), y.ctypes.data_as(c_u16p),
-                                                     t.ctypes.data_as(c_i64p), p.ctypes.data_as(_lib.c_u8p) if p is not None else None))
+        self._set_add(self._L.cmx_backend_recon_voxel_add, x, y, t_ns, polarity, self._voxel_signed)
 
     def reconstruct_voxel_add_aos(self, events, polarity_field="polarity"):
         """The same from a structured array of records with fields x, y, sec, nsec and a one-byte polarity field."""
-        ev = np.ascontiguousarray(events)
-        lay = _lib.aos_layout_of(ev)
-        off = _pol_offset(ev, polarity_field) if self._voxel_signed else 0
-        self._ck(self._L.cmx_backend_recon_voxel_add_aos(self._ctx, len(ev), ev.ctypes.data_as(C.c_void_p), C.byref(lay), off))
+        self._set_add_aos(self._L.cmx_backend_recon_voxel_add_aos, events, polarity_field, self._voxel_signed)
 
     def reconstruct_voxel_add_from(self, store, first, count):
         """The same over events_[first, first+count) of an EventStore (with polarity, EventStore.push(..., polarity=), for a
@@ -855,19 +878,8 @@ class BackendEvaluator(_Evaluator):
         with data_ptr() -- a contiguous float32 torch tensor of that many elements on the context's device: the volumes are written
         straight into it, nothing crosses the host, and out is returned in the array's place.  The call runs on the context's stream
         and returns when out is complete; work of the caller's that still writes the tensor on another stream must be finished."""
-        n, nb, Hv, Wv = self._voxel_shape or (0, 0, 0, 0)
-        count = n - int(first) if count is None else int(count)
-        shape = (max(count, 0), nb, Hv, Wv)
-        cnt = np.zeros(shape[0], np.int64)
-        if out is not None:
-            self._ck(self._L.cmx_backend_recon_voxel_get_device(self._ctx, int(first), count, out.data_ptr()))
-            if with_counts:
-                self._ck(self._L.cmx_backend_recon_voxel_get(self._ctx, int(first), count, None, cnt.ctypes.data_as(c_i64p)))
-            return (out, cnt) if with_counts else out
-        vol = np.empty(shape, np.float32)
-        self._ck(self._L.cmx_backend_recon_voxel_get(self._ctx, int(first), count, vol.ctypes.data_as(c_fp),
-                                                     cnt.ctypes.data_as(c_i64p) if with_counts else None))
-        return (vol, cnt) if with_counts else vol
+        return self._set_get(self._voxel_shape or (0, 0, 0, 0), np.float32, self._L.cmx_backend_recon_voxel_get,
+                             self._L.cmx_backend_recon_voxel_get_device, first, count, with_counts, out)
 
     def reconstruct_voxel_reset(self):
         """Clear the voxel volumes and their counters (after the knots have moved); the grids stay."""
@@ -885,40 +897,26 @@ class BackendEvaluator(_Evaluator):
         """Attach time surfaces to the open reconstruction, every cell empty (trajectory.SURFACE_EMPTY).  surfaces: _lib.ReconView
         structures or tuples (quat_xyzw, fx, fy, cx, cy, t_lo_ns, t_hi_ns) -- trajectory.frame_views' or crop_view's output as it
         is; a range over all time is accepted.  by_polarity: two channels, ON then OFF; otherwise one, and polarity is never read."""
-        vs = [v if isinstance(v, _lib.ReconView) else _lib.recon_view(*v) for v in surfaces]
-        arr = (_lib.ReconView * max(len(vs), 1))(*vs)
+        n, arr = self._set_targets(surfaces)
         self._surface_shape = None
-        self._ck(self._L.cmx_backend_recon_surface_begin(self._ctx, int(Wv), int(Hv), int(bool(by_polarity)), len(vs), arr))
-        self._surface_shape = (len(vs), 2 if by_polarity else 1, int(Hv), int(Wv))
+        self._ck(self._L.cmx_backend_recon_surface_begin(self._ctx, int(Wv), int(Hv), int(bool(by_polarity)), n, arr))
+        self._surface_shape = (n, 2 if by_polarity else 1, int(Hv), int(Wv))
         self._surface_by_polarity = bool(by_polarity)
 
     def reconstruct_surface_add(self, x, y, t_ns, polarity=None):
         """reconstruct_add's vote loop over exactly these events: every sampled event is warped once into the world frame and its OWN
         timestamp is kept, where it is the latest, at the nearest pixel of every surface whose range holds it.  polarity (one value
         per event, nonzero / positive = ON) is needed for a by-polarity set and ignored by a merged one."""
-        x, y, t = _c(x, np.uint16), _c(y, np.uint16), _c(t_ns, np.int64)
-        p = _pol_bytes(polarity) if polarity is not None and self._surface_by_polarity else None
-        if not (len(x) == len(y) == len(t)) or (p is not None and len(p) != len(x)):
-            raise ValueError("x, y, t_ns, polarity must have equal length")
-        self._ck(self._L.cmx_backend_recon_surface_add(self._ctx, len(x), x.ctypes.data_as(c_u16p), y.ctypes.data_as(c_u16p),
-                                                       t.ctypes.data_as(c_i64p), p.ctypes.data_as(_lib.c_u8p) if p is not None else None))
+        self._set_add(self._L.cmx_backend_recon_surface_add, x, y, t_ns, polarity, self._surface_by_polarity)
 
     def reconstruct_surface_add_aos(self, events, polarity_field="polarity"):
         """The same from a structured array of records with fields x, y, sec, nsec and a one-byte polarity field."""
-        ev = np.ascontiguousarray(events)
-        lay = _lib.aos_layout_of(ev)
-        off = _pol_offset(ev, polarity_field) if self._surface_by_polarity else 0
-        self._ck(self._L.cmx_backend_recon_surface_add_aos(self._ctx, len(ev), ev.ctypes.data_as(C.c_void_p), C.byref(lay), off))
+        self._set_add_aos(self._L.cmx_backend_recon_surface_add_aos, events, polarity_field, self._surface_by_polarity)
 
     def reconstruct_surface_add_from(self, store, first, count):
         """The same over events_[first, first+count) of an EventStore (with polarity, EventStore.push(..., polarity=), for a
         by-polarity set)."""
         self._ck(self._L.cmx_backend_recon_surface_add_from(self._ctx, store._h, int(first), int(count)))
-
-    def _surface_range(self, first, count):
-        n, C_, Hv, Wv = self._surface_shape or (0, 0, 0, 0)
-        count = n - int(first) if count is None else int(count)
-        return count, (max(count, 0), C_, Hv, Wv)
 
     def reconstruct_surface_get(self, first=0, count=None, with_counts=False, out=None):
         """(count, C, Hv, Wv) int64 timestamps of surfaces [first, first+count) in absolute nanoseconds, trajectory.SURFACE_EMPTY
@@ -926,23 +924,14 @@ class BackendEvaluator(_Evaluator):
         tensor of that many elements on the context's device: the cells are written straight into it, nothing crosses the host,
         and out is returned in the array's place.  The call runs on the context's stream and returns when out is complete; work of
         the caller's that still writes the tensor on another stream must be finished."""
-        count, shape = self._surface_range(first, count)
-        cnt = np.zeros(shape[0], np.int64)
-        if out is not None:
-            self._ck(self._L.cmx_backend_recon_surface_get_device(self._ctx, int(first), count, out.data_ptr()))
-            if with_counts:
-                self._ck(self._L.cmx_backend_recon_surface_get(self._ctx, int(first), count, None, cnt.ctypes.data_as(c_i64p)))
-            return (out, cnt) if with_counts else out
-        cells = np.empty(shape, np.int64)
-        self._ck(self._L.cmx_backend_recon_surface_get(self._ctx, int(first), count, cells.ctypes.data_as(c_i64p),
-                                                       cnt.ctypes.data_as(c_i64p) if with_counts else None))
-        return (cells, cnt) if with_counts else cells
+        return self._set_get(self._surface_shape or (0, 0, 0, 0), np.int64, self._L.cmx_backend_recon_surface_get,
+                             self._L.cmx_backend_recon_surface_get_device, first, count, with_counts, out)
 
     def reconstruct_surface_decay(self, tau_ns, t_ref_ns=None, first=0, count=None, out=None):
         """(count, C, Hv, Wv) fp32: the surfaces read through exp(-(t_ref - T) / tau_ns) in one device pass -- 0 where no event
         landed, 1 where T >= t_ref.  t_ref_ns: one reference time per surface of the range (or one for all); None: every surface's
         own t_hi.  out: a contiguous float32 torch tensor on the context's device, as in reconstruct_surface_get."""
-        count, shape = self._surface_range(first, count)
+        count, shape = self._set_range(self._surface_shape or (0, 0, 0, 0), first, count)
         ref = None
         if t_ref_ns is not None:
             ref = np.ascontiguousarray(np.broadcast_to(np.asarray(t_ref_ns, np.int64), (shape[0],)))
