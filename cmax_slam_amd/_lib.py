@@ -147,6 +147,12 @@ SYMBOLS = {
     "cmx_backend_recon_warp_aos": (C.c_int, [ctx_p, C.c_int64, C.c_void_p, C.POINTER(AosLayout), C.c_int, C.c_void_p, C.c_void_p]),
     "cmx_backend_recon_warp_from": (C.c_int, [ctx_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "cmx_backend_recon_warp_from_device": (C.c_int, [ctx_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "cmx_backend_recon_score_open": (C.c_int, [ctx_p, C.c_double]),
+    "cmx_backend_recon_score_plane": (C.c_int, [ctx_p, c_fp]),
+    "cmx_backend_recon_score": (C.c_int, [ctx_p, C.c_int64, c_u16p, c_u16p, c_i64p, C.c_int, C.c_void_p, C.c_void_p]),
+    "cmx_backend_recon_score_aos": (C.c_int, [ctx_p, C.c_int64, C.c_void_p, C.POINTER(AosLayout), C.c_int, C.c_void_p, C.c_void_p]),
+    "cmx_backend_recon_score_from": (C.c_int, [ctx_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "cmx_backend_recon_score_from_device": (C.c_int, [ctx_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "cmx_backend_recon_pol_add": (C.c_int, [ctx_p, C.c_int64, c_u16p, c_u16p, c_i64p, c_u8p]),
     "cmx_backend_recon_pol_add_aos": (C.c_int, [ctx_p, C.c_int64, C.c_void_p, C.POINTER(AosLayout), C.c_size_t]),
     "cmx_backend_recon_pol_add_from": (C.c_int, [ctx_p, C.c_void_p, C.c_int64, C.c_int64]),

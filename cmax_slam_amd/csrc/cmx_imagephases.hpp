@@ -1,7 +1,8 @@
 // cmx_imagephases.hpp -- the tile phases shared by the image kernels of cmx_kernels.hip, ONE device-inline definition of each.
 // Two are those kernels' correctness contract: the operation order of the forward blur (blur_row / blur_col) and the clearing
 // and un-flagging of the ping-pong partner plane (tile_clear_partner).  tile_* functions are whole phases: every thread of the
-// workgroup calls them, and those that hold a barrier say so.  Included by cmx_kernels.hip only (st_sc1 is defined there).
+// workgroup calls them, and those that hold a barrier say so.  Included by cmx_kernels.hip (st_sc1 is defined there) and, for the
+// load and the Gaussian passes alone, by cmx_recon.hip (recon_smooth_kernel: no moments, so no st_sc1).
 // A helper is optimised on its own before it is inlined, so moving text here is not neutral; what therefore stays in the kernels
 // (tables and timings: profiles/image_phases_refactor.txt):
 //   * the register copy of the taps: as a function it grew image_adjoint2_kernel's scratch (36 -> 44, 28 -> 44, 44 -> 76 bytes);

@@ -470,6 +470,19 @@ struct ReconWarpArgs {
   int vec;                   // xy_out is aligned for one 16- / 8-byte pair store per lane
 };
 void launch_recon_warp(const ReconWarpArgs &g, hipStream_t s);
+// per-event support scores (cmx_backend_recon_score*): the export's walk (w: ev, rate, lone, lone_t, flags_out as above; xy_out, f32
+// and vec are not used) with the support plane S = G plane read back at the vote cell of every event, one float per event.
+struct ReconScoreArgs {
+  ReconWarpArgs w;
+  const float *S;            // [Hp * Wp] the support plane: d_support, or the count plane itself at sigma 0
+  float *score_out;          // [n]
+  int loo;                   // leave-one-out: events that voted (SAMPLED and INSIDE) have their own contribution subtracted
+  int r;                     // blur radius of S (0: S is the plane) and its taps: what the own contribution is made of
+  float taps[2 * kMaxRadius + 1];
+};
+void launch_recon_score(const ReconScoreArgs &g, hipStream_t s);
+// S = G plane (a.src_a, a.taps, a.r, a.flags_cur) on the tiles with a vote within r pixels; every other tile of `out` is left alone
+void launch_recon_smooth(const ImgArgs &a, float *out, hipStream_t s);
 // target sets (cmx_backend_recon_view_* / _voxel_* / _surface_*): the vote loop of launch_recon_votes with the n targets of a set --
 // virtual pinhole cameras with a time range each -- as its targets.  An event's world ray is formed once and voted into every
 // target whose range holds its time.  What the three kinds of set share is ReconSetArgs; each adds a small tail of its own.

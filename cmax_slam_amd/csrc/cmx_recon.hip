@@ -14,11 +14,14 @@
 //                   (recon_view_votes), the bins of G voxel grids (recon_voxel_votes), the cells of S time surfaces
 //                   (recon_surface_votes: one 64-bit integer max per vote) -- ONE skeleton, further down with its description, and
 //                   a Target per set; recon_surface_fill and recon_surface_decay beside it
+//   recon_smooth, recon_score   the way back from the map to the events (cmx_backend_recon_score*): S = G plane, and the export's walk
+//                   with S read at every event's vote cell -- further down with their description
 //   recon_fixed_to_float   deterministic mode: the 2^-30 fixed-point plane as fp32, leaving it as it is (accumulation goes on)
 #include "../../include/cmax_hip.h"
 #include "cmx_internal.hpp"
 #include "cmx_warp.hpp"
 #include "cmx_fixed.hpp"
+#include "cmx_imagephases.hpp"
 
 namespace cmx {
 
@@ -528,8 +531,151 @@ void launch_recon_warp(const ReconWarpArgs &g, hipStream_t s) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------- per-event support scores
+// recon_smooth   cmx_backend_recon_score_open at sigma > 0: S = G plane, one workgroup per 64 x 16 tile.  The phases of
+//                image_moments_kernel (cmx_kernels.hip) without its moments -- raw tile with a REFLECT_101 halo into LDS
+//                (tile_load_composed), row pass (tile_blur_rows), column pass in registers (blur_col): the operation order of the
+//                forward blur that cmx_imagephases.hpp states, so S holds the value the image pass forms.  A tile with no vote within
+//                r pixels (launch_tile_flags; tile_in_reach) is left alone: the host has zeroed S in front of the launch.
+// recon_score    cmx_backend_recon_score*: recon_warp_kernel's walk -- the run's batch poses into LDS, the lone trailing event's in a
+//                slot of its own, one barrier, one event per lane and step with load_bearing + be_warp_math<0, true> -- and then,
+//                for an event inside the plane, four loads from S around its vote cell and
+//                    score = ((w00 S[yy][xx] + w01 S[yy][xx+1]) + w10 S[yy+1][xx]) + w11 S[yy+1][xx+1]
+//                with the four weights of vote4_global, every product and every sum rounded on its own (no FMA): a host forms the
+//                same bits from S and the exported (px, py).  One 4-byte store per event, the flag byte of the export when asked
+//                for; no atomics, no LDS beyond the poses.  The loads are bound by memory latency, not by issue.
+//                Leave-one-out: an event that voted (SAMPLED and INSIDE) put w_c into its four cells, which S hands back as
+//                    self = sum_c sum_c' w_c w_c' Gx[x_c, x_c'] Gy[y_c, y_c'] = (wx^T Gx wx) (wy^T Gy wy),  wx = (1 - dx, dx), wy = (1 - dy, dy)
+//                with Gx[a, b] the entry of the REFLECT_101 filter matrix (output a, input b): the tap g(a - b) plus the tap that
+//                folds onto b at a border (score_fold: a panorama wider than 2r + 1 folds once).  The 2 x 2 blocks of an event
+//                away from the borders are (g(0), g(1); g(1), g(0)): it never calls score_fold.  sigma 0: self is
+//                ((w00^2 + w01^2) + w10^2) + w11^2.  One fp32 subtraction, no clamp: the plane is a sum of fp32 atomics, which
+//                the event's own four adds need not have reached exactly, so a score of -1e-7 is what was measured.
+template <int R>
+__global__ __launch_bounds__(kImgThreads) void recon_smooth_kernel(const ImgArgs a, float *out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smooth_smem[];
+  const int r = (R >= 0) ? R : a.r;
+  float taps[2 * kMaxRadius + 1];  // (register copy, local: cmx_imagephases.hpp)
+#pragma unroll
+  for (int j = 0; j < 2 * kMaxRadius + 1; j++) taps[j] = (R < 0 || j <= 2 * R) ? a.taps[j] : 0.f;
+  const int rawW = kTileX + 2 * r, rawH = kTileY + 2 * r;
+  float *raw = reinterpret_cast<float *>(smooth_smem);
+  float *rowb = raw + rawW * rawH;
+  const int tx = threadIdx.x & 63, tq = threadIdx.x >> 6;  // output column, row quad
+  const TileWork w = tile_begin<kTileX, kTileY, false>(a, (int)blockIdx.x);
+  if (!tile_in_reach<kTileX, kTileY, false>(a, w, r)) return;  // (workgroup-uniform) nothing within reach: S stays zero
+  tile_load_composed<kImgThreads>(a, 0.f, w.x0, w.y0, r, rawW, rawH, raw);
+  __syncthreads();
+  tile_blur_rows<R, kImgThreads>(taps, r, raw, rawW, rowb, kTileX, rawH);
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const float s = blur_col<R>(taps, r, rowb + (tq * 4 + j + r) * kTileX + tx, kTileX);
+    const int x = w.x0 + tx, y = w.y0 + tq * 4 + j;
+    if (x < a.W && y < a.H) out[(size_t)y * a.W + x] = s;
+  }
+}
+void launch_recon_smooth(const ImgArgs &a, float *out, hipStream_t s) {
+  const int rawW = kTileX + 2 * a.r, rawH = kTileY + 2 * a.r;
+  const size_t lds = sizeof(float) * ((size_t)rawW * rawH + (size_t)kTileX * rawH);
+  if (a.r == 4) hipLaunchKernelGGL(recon_smooth_kernel<4>, dim3(a.nblk), dim3(kImgThreads), lds, s, a, out);
+  else hipLaunchKernelGGL(recon_smooth_kernel<-1>, dim3(a.nblk), dim3(kImgThreads), lds, s, a, out);
+}
+
+// Gx[a, b] of the REFLECT_101 filter with these taps on a side of L > 2r + 1 cells, |a - b| <= 1 <= r: the tap of the offset, plus
+// the tap whose input position folds onto b at the left border (-b) or at the right one (2 (L - 1) - b)
+__device__ __forceinline__ float score_fold(const float *taps, int r, int L, int a, int b) {
+  float g = taps[r + b - a];
+  const int kl = r - a - b;                // a - r + kl == -b
+  if (kl >= 0 && b > 0) g = __fadd_rn(g, taps[kl]);
+  const int kr = 2 * (L - 1) - a - b + r;  // a - r + kr == 2 (L - 1) - b
+  if (kr <= 2 * r && b < L - 1) g = __fadd_rn(g, taps[kr]);
+  return g;
+}
+// w^T G w over the cells p, p + 1 of one axis, w = (1 - d, d)
+__device__ __forceinline__ float score_self_axis(const float *taps, int r, int L, int p, float d) {
+  const float w0 = 1.f - d, w1 = d;
+  float g00 = taps[r], g01 = taps[r + 1], g10 = g01, g11 = g00;
+  if (2 * p <= r || 2 * p + 2 >= 2 * (L - 1) - r) {  // a tap folds onto one of the two cells: a few events next to a border
+    g00 = score_fold(taps, r, L, p, p);
+    g01 = score_fold(taps, r, L, p, p + 1);
+    g10 = score_fold(taps, r, L, p + 1, p);
+    g11 = score_fold(taps, r, L, p + 1, p + 1);
+  }
+  const float a = __fmul_rn(__fmul_rn(w0, w0), g00), b = __fmul_rn(__fmul_rn(w0, w1), g01);
+  const float c = __fmul_rn(__fmul_rn(w1, w0), g10), e = __fmul_rn(__fmul_rn(w1, w1), g11);
+  return __fadd_rn(__fadd_rn(__fadd_rn(a, b), c), e);
+}
+
+template <int N>
+__global__ __launch_bounds__(kReconThreads) void recon_score_kernel(const ReconScoreArgs g) {
+  __shared__ double sh_R[(kReconMaxRun + 3) * 9];
+  const ReconArgs &a = g.w.ev;
+  const int tid = threadIdx.x;
+  const int e0 = blockIdx.x * a.run;  // (the grid covers [0, n): e0 < n)
+  const int e1 = (a.n - e0 > a.run) ? e0 + a.run : a.n;
+  const int nbe = a.n - g.w.lone;     // events of the slice that batches hold
+  const int eb1 = e1 < nbe ? e1 : nbe;
+  const int b0 = e0 / a.B;
+  int nbw = eb1 > e0 ? (eb1 - 1) / a.B - b0 + 1 : 0;
+  if (nbw > kReconMaxRun + 2) nbw = kReconMaxRun + 2;  // (cannot happen with run = recon_run(B))
+  const bool has_lone = g.w.lone && e1 == a.n;         // this workgroup holds the lone trailing event: pose slot nbw
+  for (int j = tid; j < nbw + (has_lone ? 1 : 0); j += kReconThreads) {
+    long long t = g.w.lone_t;
+    if (j < nbw) t = a.batch_t[b0 + j < a.nb ? b0 + j : a.nb - 1];
+    recon_pose<N>(a, t, sh_R + 9 * j);
+  }
+  __syncthreads();
+  const int Wp = a.cam.Wp;
+  int cur = -1;
+  double R[9];
+  for (int i = e0 + tid; i < e1; i += kReconThreads) {
+    const bool is_lone = i >= nbe;
+    const int b = i / a.B;
+    int j = b - b0;
+    j = is_lone ? nbw : (j < nbw ? j : nbw - 1);
+    if (j != cur) {
+#pragma unroll
+      for (int c = 0; c < 9; c++) R[c] = sh_R[9 * j + c];
+      cur = j;
+    }
+    const uint32_t e = a.xy[i] & 0x7fffffffu;
+    const int ex = e & 0xffff, ey = e >> 16;
+    double v0, v1, v2, pxy[2];
+    load_bearing(a.cam, ex, ey, v0, v1, v2);
+    const BeWarp w = be_warp_math<0, true>(a.cam, e, b, v0, v1, v2, R, pxy);
+    const bool sampled = !is_lone && (i - b * a.B) % g.w.rate == 0;
+    float score = 0.f;
+    if (w.ok) {  // 1 <= xx < Wp - 2 && 1 <= yy < Hp - 2: the four cells are inside the plane
+      const float *q = g.S + (size_t)w.yy * Wp + w.xx;
+      const float s00 = q[0], s01 = q[1], s10 = q[Wp], s11 = q[Wp + 1];
+      const float ux = 1.f - w.dx, uy = 1.f - w.dy;
+      const float w00 = __fmul_rn(ux, uy), w01 = __fmul_rn(w.dx, uy), w10 = __fmul_rn(ux, w.dy), w11 = __fmul_rn(w.dx, w.dy);
+      score = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(w00, s00), __fmul_rn(w01, s01)), __fmul_rn(w10, s10)), __fmul_rn(w11, s11));
+      if (g.loo && sampled) {  // the event voted: its own four adds, as S hands them back
+        float self;
+        if (g.r == 0)
+          self = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(w00, w00), __fmul_rn(w01, w01)), __fmul_rn(w10, w10)), __fmul_rn(w11, w11));
+        else
+          self = __fmul_rn(score_self_axis(g.taps, g.r, Wp, w.xx, w.dx), score_self_axis(g.taps, g.r, a.cam.Hp, w.yy, w.dy));
+        score = __fsub_rn(score, self);
+      }
+    }
+    g.score_out[i] = score;
+    if (g.w.flags_out) g.w.flags_out[i] = (unsigned char)((sampled ? CMX_WARP_SAMPLED : 0) | (w.ok ? CMX_WARP_INSIDE : 0));
+  }
+}
+
+void launch_recon_score(const ReconScoreArgs &g, hipStream_t s) {
+  const ReconArgs &a = g.w.ev;
+  if (a.n <= 0) return;
+  const dim3 gr((unsigned)(((long long)a.n + a.run - 1) / a.run)), b(kReconThreads);  // (a.n <= 2^30 + 1: cmx_reconstruct.cpp)
+  if (a.order == 2) hipLaunchKernelGGL(recon_score_kernel<2>, gr, b, 0, s, g);
+  else hipLaunchKernelGGL(recon_score_kernel<4>, gr, b, 0, s, g);
+}
+
 // ---------------------------------------------------------------------------------------------- bound events
-// recon_pose_table      the batch poses of an evaluation as a table in global memory: recon_pose<N> once per batch, the value the
+// recon_pose_table     the batch poses of an evaluation as a table in global memory: recon_pose<N> once per batch, the value the
 //                        votes kernel above forms in LDS, bit for bit (72 B per batch)
 // recon_votes_lds        the vote pass over events sorted by the destination tile of their vote (launch_count_sort /
 //                        launch_build_chunks with poseR = the table): be_splat_lds_kernel's structure with ONE plane and the

@@ -4,6 +4,7 @@
 //              events, into the reconstruction's plane
 //   grad_add*  the second pass over the same events, their share of the gradient sums
 //   warp*      the per-event export: where EVERY event handed in lands under the knots the reconstruction holds now
+//   score*     the export's walk with another sink: the support plane of the open score pass read at every event
 //   pol_add*   add*'s vote loop into the ON / OFF planes of the signed polarity map
 //   view_add*  add*'s vote loop into the planes of the pinhole views
 //   voxel_add* add*'s vote loop into the bins of the voxel grids, by every event's own timestamp and polarity
@@ -389,58 +390,44 @@ static int warp_slot_ensure(cmx_ctx *c, ReconState *r, ReconWarpSlot &s, size_t 
   return rc;
 }
 
-static int recon_warp_source(cmx_ctx *c, const EventSource &src, int format, void *xy_out, unsigned char *flags_out, bool dev_out) {
+// The walk of warp* and score*: one kernel per slice (launch(slice, d_out, d_flags): the sink's own), `elem` bytes of output per event
+// and one flag byte.  dev_out: straight into the caller's device pointers.  Host output: slice k into the staging of wslot[k & 1],
+// a copy on the download stream into its pinned twin, and from there into the caller's arrays by the host pool while slice k + 1 runs.
+template <typename Launch>
+static int recon_export_walk(cmx_ctx *c, const EventSource &src, size_t elem, void *out, unsigned char *flags_out, bool dev_out, Launch launch) {
   ReconState *r = c->recon;
-  int rc = feed_checks(c, src);
-  if (rc) return rc;
-  if (src.n > 0 && !xy_out) return fail(c, CMX_ERR_INVALID_ARG, "null coordinate output");
-  const bool f32 = format == CMX_WARP_F32;
-  const size_t pair = f32 ? 2 * sizeof(float) : 2 * sizeof(double);
-  ReconWarpArgs g{};
-  g.ev = recon_args(c, r);
-  g.ev.per_batch = r->B; g.ev.stride = 0;
-  g.ev.run = recon_run(r->B);
-  g.rate = r->rate;
-  g.f32 = f32 ? 1 : 0;
   struct Pending { ReconWarpSlot *o = nullptr; int64_t first = 0, count = 0; } pend;
   auto finish = [&](Pending &q) -> int {  // the download of a slice is complete: into the caller's arrays
     if (!q.o) return CMX_OK;
     HIP_TRY(c, hipEventSynchronize(q.o->down));
     const char *hx = reinterpret_cast<const char *>(q.o->h_xy);
     const unsigned char *hf = q.o->h_fl;
-    char *ox = static_cast<char *>(xy_out) + (size_t)q.first * pair;
+    char *ox = static_cast<char *>(out) + (size_t)q.first * elem;
     unsigned char *of = flags_out ? flags_out + q.first : nullptr;
     parallel_ranges(q.count, [=](int64_t a0, int64_t a1) {
-      memcpy(ox + (size_t)a0 * pair, hx + (size_t)a0 * pair, (size_t)(a1 - a0) * pair);
+      memcpy(ox + (size_t)a0 * elem, hx + (size_t)a0 * elem, (size_t)(a1 - a0) * elem);
       if (of) memcpy(of + a0, hf + a0, (size_t)(a1 - a0));
     });
     q.o = nullptr;
     return CMX_OK;
   };
   BatchPlan p;
-  rc = feed(c, r, src, true, false, false, &p, [&](const FedSlice &s) -> int {
-    g.ev.xy = s.d_xy;
-    g.ev.batch_t = s.d_bt; g.ev.nb = s.b_hi - s.b_lo;
-    g.ev.n = (int)s.ev_n;
-    g.lone = s.lone ? 1 : 0;
-    g.lone_t = s.lone_t;
+  int rc = feed(c, r, src, true, false, false, &p, [&](const FedSlice &s) -> int {
     ReconWarpSlot *o = nullptr;
-    if (dev_out) {
-      g.xy_out = static_cast<char *>(xy_out) + (size_t)s.ev_first * pair;
-      g.flags_out = flags_out ? flags_out + s.ev_first : nullptr;
-    } else {
+    void *d_out = static_cast<char *>(out) + (size_t)s.ev_first * elem;
+    unsigned char *d_fl = flags_out ? flags_out + s.ev_first : nullptr;
+    if (!dev_out) {
       o = &r->wslot[s.k & 1];  // (free: the slice before the last was finished while the last one ran)
       const int rc2 = warp_slot_ensure(c, r, *o, (size_t)s.ev_n);
       if (rc2) return rc2;
-      g.xy_out = o->d_xy;
-      g.flags_out = flags_out ? o->d_fl : nullptr;
+      d_out = o->d_xy;
+      d_fl = flags_out ? o->d_fl : nullptr;
     }
-    g.vec = (uintptr_t)g.xy_out % (f32 ? 8 : 16) == 0 ? 1 : 0;
-    launch_recon_warp(g, c->stream);
+    launch(s, d_out, d_fl);
     if (!o) return CMX_OK;
     HIP_TRY(c, hipEventRecord(o->kdone, c->stream));
     HIP_TRY(c, hipStreamWaitEvent(r->down_stream, o->kdone, 0));
-    HIP_TRY(c, hipMemcpyAsync(o->h_xy, o->d_xy, (size_t)s.ev_n * pair, hipMemcpyDeviceToHost, r->down_stream));
+    HIP_TRY(c, hipMemcpyAsync(o->h_xy, o->d_xy, (size_t)s.ev_n * elem, hipMemcpyDeviceToHost, r->down_stream));
     if (flags_out) HIP_TRY(c, hipMemcpyAsync(o->h_fl, o->d_fl, (size_t)s.ev_n, hipMemcpyDeviceToHost, r->down_stream));
     HIP_TRY(c, hipEventRecord(o->down, r->down_stream));
     const int rc2 = finish(pend);  // the slice before this one, while this one runs
@@ -451,6 +438,40 @@ static int recon_warp_source(cmx_ctx *c, const EventSource &src, int format, voi
   if (!rc) rc = finish(pend);
   if (rc && r->down_stream) (void)hipStreamSynchronize(r->down_stream);
   return rc;
+}
+// what both sinks' kernels read of a slice: ALL its raw events, one run of recon_run(B) of them per workgroup
+static ReconWarpArgs warp_args(const cmx_ctx *c, const ReconState *r) {
+  ReconWarpArgs g{};
+  g.ev = recon_args(c, r);
+  g.ev.per_batch = r->B; g.ev.stride = 0;
+  g.ev.run = recon_run(r->B);
+  g.rate = r->rate;
+  return g;
+}
+static void warp_slice(ReconWarpArgs &g, const FedSlice &s, unsigned char *d_flags) {
+  g.ev.xy = s.d_xy;
+  g.ev.batch_t = s.d_bt; g.ev.nb = s.b_hi - s.b_lo;
+  g.ev.n = (int)s.ev_n;
+  g.lone = s.lone ? 1 : 0;
+  g.lone_t = s.lone_t;
+  g.flags_out = d_flags;
+}
+
+static int recon_warp_source(cmx_ctx *c, const EventSource &src, int format, void *xy_out, unsigned char *flags_out, bool dev_out) {
+  ReconState *r = c->recon;
+  int rc = feed_checks(c, src);
+  if (rc) return rc;
+  if (src.n > 0 && !xy_out) return fail(c, CMX_ERR_INVALID_ARG, "null coordinate output");
+  const bool f32 = format == CMX_WARP_F32;
+  ReconWarpArgs g = warp_args(c, r);
+  g.f32 = f32 ? 1 : 0;
+  return recon_export_walk(c, src, f32 ? 2 * sizeof(float) : 2 * sizeof(double), xy_out, flags_out, dev_out,
+                           [&](const FedSlice &s, void *d_out, unsigned char *d_flags) {
+                             warp_slice(g, s, d_flags);
+                             g.xy_out = d_out;
+                             g.vec = (uintptr_t)g.xy_out % (f32 ? 8 : 16) == 0 ? 1 : 0;
+                             launch_recon_warp(g, c->stream);
+                           });
 }
 
 template <typename MakeSource>
@@ -479,4 +500,50 @@ int cmx_backend_recon_warp_from(cmx_ctx *c, const cmx_events *e, int64_t first, 
 int cmx_backend_recon_warp_from_device(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count, int format, void *d_xy_out,
                                        unsigned char *d_flags_out) {
   return recon_warp_entry(c, format, d_xy_out, d_flags_out, true, [&](EventSource *src) { return store_source(c, e, first, count, src); });
+}
+
+// ---- score*: the export's walk with the support plane of the open score pass read at every event's vote cell -- one float per
+// event, the export's flag byte.  Read-only on everything but the output staging: no recon_pass_enter, no counter, no plane.
+static int recon_score_source(cmx_ctx *c, const EventSource &src, int loo, float *score_out, unsigned char *flags_out, bool dev_out) {
+  ReconState *r = c->recon;
+  int rc = feed_checks(c, src);
+  if (rc) return rc;
+  if (src.n > 0 && !score_out) return fail(c, CMX_ERR_INVALID_ARG, "null score output");
+  ReconScoreArgs g{};
+  g.w = warp_args(c, r);
+  g.S = r->score_radius > 0 ? r->d_support : r->d_plane;
+  g.loo = loo ? 1 : 0;
+  g.r = r->score_radius;
+  memcpy(g.taps, r->score_taps, sizeof(g.taps));
+  return recon_export_walk(c, src, sizeof(float), score_out, flags_out, dev_out, [&](const FedSlice &s, void *d_out, unsigned char *d_flags) {
+    warp_slice(g.w, s, d_flags);
+    g.score_out = static_cast<float *>(d_out);
+    launch_recon_score(g, c->stream);
+  });
+}
+template <typename MakeSource>
+static int recon_score_entry(cmx_ctx *c, int loo, float *score_out, unsigned char *flags_out, bool dev_out, MakeSource make) {
+  int rc = recon_score_enter(c);
+  if (rc) return rc;
+  EventSource src;
+  rc = make(&src);
+  if (rc) return rc;
+  return recon_score_source(c, src, loo, score_out, flags_out, dev_out);
+}
+int cmx_backend_recon_score(cmx_ctx *c, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, int loo, float *score_out,
+                            unsigned char *flags_out) {
+  return recon_score_entry(c, loo, score_out, flags_out, false,
+                           [&](EventSource *src) { *src = EventSource::arrays(n, x, y, t_ns); return (int)CMX_OK; });
+}
+int cmx_backend_recon_score_aos(cmx_ctx *c, int64_t n, const void *events, const cmx_aos_layout *layout, int loo, float *score_out,
+                                unsigned char *flags_out) {
+  return recon_score_entry(c, loo, score_out, flags_out, false, [&](EventSource *src) { return make_aos(c, n, events, layout, src); });
+}
+int cmx_backend_recon_score_from(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count, int loo, float *score_out,
+                                 unsigned char *flags_out) {
+  return recon_score_entry(c, loo, score_out, flags_out, false, [&](EventSource *src) { return store_source(c, e, first, count, src); });
+}
+int cmx_backend_recon_score_from_device(cmx_ctx *c, const cmx_events *e, int64_t first, int64_t count, int loo, float *d_score_out,
+                                        unsigned char *d_flags_out) {
+  return recon_score_entry(c, loo, d_score_out, d_flags_out, true, [&](EventSource *src) { return store_source(c, e, first, count, src); });
 }

@@ -224,6 +224,13 @@ struct ReconState {
   long long *d_stref = nullptr;                // [surfaces.n] the reference times of a call that names them
   float *d_sdecay = nullptr;                   // (host output) the decayed cells on their way out, grown on demand
   size_t sdecay_cap = 0;
+  // ---- per-event support scores (cmx_backend_recon_score*): open from score_open until something changes the plane or
+  // the knots (recon_pass_enter, recon_start_over).  The taps are the pass's own copy: a contrast at another sigma rebuilds those
+  // above and leaves the pass open.
+  bool score_open = false;
+  int score_radius = 0;                        // 0: S is the count plane itself (d_plane, refreshed by score_open)
+  float score_taps[2 * kMaxRadius + 1] = {1.f};
+  float *d_support = nullptr;                  // [Hp * Wp] S = G plane, allocated at the first score_open with sigma > 0
   int64_t host_waits = 0;               // times a host thread has waited for the device in this reconstruction's calls
   // everything above that owns memory, a stream or an event (the streams idle: recon_release has waited for them)
   void release() {
@@ -232,7 +239,8 @@ struct ReconState {
     for (ReconSlot &s : slot) s.release();
     for (ReconWarpSlot &s : wslot) s.release();
     void *dev[] = {d_knots, d_delta, d_plane, d_fixed, d_inside, d_err, d_cx, d_cy, d_tflags, d_tile_list, d_tile_count, d_partials,
-                   d_cm, d_jt, d_gsum, d_voted, d_rows, d_row_win, d_app_xy, d_app_t, d_pol, d_pol_fixed, d_pol_inside, d_stref, d_sdecay};
+                   d_cm, d_jt, d_gsum, d_voted, d_rows, d_row_win, d_app_xy, d_app_t, d_pol, d_pol_fixed, d_pol_inside, d_stref, d_sdecay,
+                   d_support};
     for (void *p : dev) (void)hipFree(p);
     for (ReconTargetSet *t : {&views, &voxels, &surfaces}) t->release();
     bnd.release();
@@ -255,8 +263,10 @@ int recon_plan(cmx_ctx *c, const ReconState *r, int64_t n, BatchPlan *p, int *sl
 ReconArgs recon_args(const cmx_ctx *c, const ReconState *r);
 // the gradient pass's view of the same launch: the events and the spline of recon_args, Jt and the border factors, the sums
 ReconGatherArgs recon_gather_args(const cmx_ctx *c, const ReconState *r);
-// first thing of every pass over events: a vote pass closes an open gradient pass, a gradient pass needs one
+// first thing of every pass over events: a vote pass closes an open gradient pass (and an open score pass), a gradient pass needs one
 int recon_pass_enter(cmx_ctx *c, ReconState *r, bool grad);
+// the front door of score*: recon_enter, and a score pass is open
+int recon_score_enter(cmx_ctx *c);
 // knot values for the trajectory of begin; plane, counters and gradient state start over (from_base: from the frozen head's votes;
 // staged: the knots are in pinned memory that stays untouched until the caller's own wait)
 int recon_start_over(cmx_ctx *c, ReconState *r, const double *knots_xyzw, bool from_base = false, bool staged = false);

@@ -66,6 +66,7 @@ int recon_start_over(cmx_ctx *c, ReconState *r, const double *knots_xyzw, bool f
   const ReconFrozen &fz = r->frozen;
   const bool base = from_base && fz.num_fixed > 0;
   r->grad_open = false;
+  r->score_open = false;
   r->g_num_fixed = 0;
   r->n_sampled = base ? fz.sampled : 0;
   if (knots_xyzw) {
@@ -171,7 +172,7 @@ ReconGatherArgs recon_gather_args(const cmx_ctx *c, const ReconState *r) {
 }
 
 int recon_pass_enter(cmx_ctx *c, ReconState *r, bool grad) {
-  if (!grad) { r->grad_open = false; return CMX_OK; }
+  if (!grad) { r->grad_open = false; r->score_open = false; return CMX_OK; }  // (votes follow: Jt and S no longer belong to the plane)
   if (!r->grad_open) return fail(c, CMX_ERR_STATE, "no gradient pass is open (cmx_backend_recon_contrast with want_grad, and no add since)");
   return CMX_OK;
 }
@@ -266,6 +267,22 @@ int recon_grad_precheck(cmx_ctx *c, ReconState *r, double sigma) {
   return CMX_OK;
 }
 
+// the plane as an image pass reads it (its fp32 view refreshed), its tiles and their occupancy flags, queued
+static int recon_image_source(cmx_ctx *c, ReconState *r, ImgArgs &a) {
+  a.W = c->Wp; a.H = c->Hp;
+  a.src_a = r->d_plane;
+  a.P = 0;
+  a.tiles_x = (a.W + kTileX - 1) / kTileX;
+  a.tiles_y = (a.H + kTileY - 1) / kTileY;
+  a.nblk = a.tiles_x * a.tiles_y;
+  if (!r->d_tflags) HIP_TRY(c, hipMalloc((void **)&r->d_tflags, (size_t)a.nblk));
+  recon_refresh_plane(c, r);
+  HIP_TRY(c, hipMemsetAsync(r->d_tflags, 0, (size_t)a.nblk, c->stream));
+  launch_tile_flags(r->d_plane, a.W, a.H, r->d_tflags, c->stream);
+  a.flags_cur = r->d_tflags;
+  return CMX_OK;
+}
+
 // The image pass over the plane as accumulated so far: contrast of GaussianBlur(plane, sigma), and with want_grad
 // Jt = G^T (G plane) for the gradient pass it opens.  The plane is read only.
 // Everything of it up to the wait: queued on the stream, contrast and mean on their way into cm[2] (host memory that stays valid
@@ -275,18 +292,13 @@ int recon_contrast_queue(cmx_ctx *c, ReconState *r, double blur_sigma, int contr
   if (!std::isfinite(blur_sigma)) return fail(c, CMX_ERR_INVALID_ARG, "blur_sigma is not finite");
   int rc = want_grad ? recon_grad_precheck(c, r, blur_sigma) : recon_setup_blur(c, r, blur_sigma);
   if (rc) return rc;
-  const int W = c->Wp, H = c->Hp, rad = r->radius;
-  const size_t np = (size_t)W * H;
+  const int rad = r->radius;
+  const size_t np = (size_t)c->Wp * c->Hp;
   ImgAdjArgs ia{};
   ImgArgs &a = ia.img;
-  a.W = W; a.H = H; a.r = rad;
+  a.r = rad;
   memcpy(a.taps, r->taps, sizeof(a.taps));
-  a.src_a = r->d_plane;
-  a.P = 0;
-  a.tiles_x = (W + kTileX - 1) / kTileX;
-  a.tiles_y = (H + kTileY - 1) / kTileY;
-  a.nblk = a.tiles_x * a.tiles_y;
-  if (!r->d_tflags) HIP_TRY(c, hipMalloc((void **)&r->d_tflags, (size_t)a.nblk));
+  a.nblk = ((c->Wp + kTileX - 1) / kTileX) * ((c->Hp + kTileY - 1) / kTileY);
   if (!r->d_partials) HIP_TRY(c, hipMalloc((void **)&r->d_partials, 2 * (size_t)a.nblk * sizeof(double)));
   if (!r->d_cm) HIP_TRY(c, hipMalloc((void **)&r->d_cm, 2 * sizeof(double)));
   if (a.nblk > kTileListMin && !r->d_tile_list) {
@@ -301,10 +313,8 @@ int recon_contrast_queue(cmx_ctx *c, ReconState *r, double blur_sigma, int contr
     if (!r->d_gsum) HIP_TRY(c, hipMalloc((void **)&r->d_gsum, 2 * 3 * (size_t)r->sup.K * sizeof(double)));
     if (!r->d_voted) HIP_TRY(c, hipMalloc((void **)&r->d_voted, sizeof(unsigned long long)));
   }
-  recon_refresh_plane(c, r);
-  HIP_TRY(c, hipMemsetAsync(r->d_tflags, 0, (size_t)a.nblk, c->stream));
-  launch_tile_flags(r->d_plane, W, H, r->d_tflags, c->stream);
-  a.flags_cur = r->d_tflags;
+  rc = recon_image_source(c, r, a);
+  if (rc) return rc;
   a.partials = r->d_partials;
   if (r->d_tile_list) {  // tile order: the order the moment rows are summed in does not depend on the run
     launch_tile_list(a, want_grad ? 2 * rad : rad, r->d_tile_list, r->d_tile_count, r->d_tile_count + 1, /*ordered=*/true, c->stream);
@@ -400,6 +410,61 @@ int cmx_backend_recon_eval_from(cmx_ctx *c, const cmx_events *e, int64_t first, 
 // the plane as fp32 on the device: in deterministic mode the current fixed-point sums, converted (they stay: votes may follow)
 static void recon_refresh_plane(cmx_ctx *c, ReconState *r) {
   if (r->deterministic) launch_recon_fixed_to_float(r->d_fixed, r->d_plane, (size_t)c->Wp * c->Hp, c->stream);
+}
+
+// ---- per-event support scores: the pass that cmx_backend_recon_score* (cmx_recon_feed.cpp) reads.  score_open forms S = G plane from
+// the plane as it stands -- the fp32 view of the fixed-point plane in deterministic mode -- and the pass stays open until votes or
+// knots change (recon_pass_enter, recon_start_over).  sigma 0: S is the plane itself, which nothing writes while the pass is open.
+int cmx_backend_recon_score_open(cmx_ctx *c, double blur_sigma) {
+  int rc = recon_enter(c, true);
+  if (rc) return rc;
+  ReconState *r = c->recon;
+  if (!std::isfinite(blur_sigma)) return fail(c, CMX_ERR_INVALID_ARG, "blur_sigma is not finite");
+  rc = recon_setup_blur(c, r, blur_sigma);  // (as recon_contrast: an open gradient pass at another sigma is closed, one at this sigma stays)
+  if (rc) return rc;
+  const int rad = r->radius;
+  if (!(c->Wp > 2 * rad + 1 && c->Hp > 2 * rad + 1))  // (the own contribution of an event folds single reflections, as the adjoint gradient does)
+    return fail(c, CMX_ERR_INVALID_ARG, "panorama %d x %d too small for support scores at blur radius %d", c->Wp, c->Hp, rad);
+  const size_t np = (size_t)c->Wp * c->Hp;
+  r->score_open = false;  // (a call refused above leaves an open pass as it was: it has its own taps)
+  if (rad > 0) {
+    if (!r->d_support) HIP_TRY(c, hipMalloc((void **)&r->d_support, np * sizeof(float)));
+    ImgArgs a{};
+    a.r = rad;
+    memcpy(a.taps, r->taps, sizeof(a.taps));
+    rc = recon_image_source(c, r, a);
+    if (rc) return rc;
+    // S is read wherever ANY event lands, not only where votes lie: zero first, then the tiles with a vote within reach
+    HIP_TRY(c, hipMemsetAsync(r->d_support, 0, np * sizeof(float), c->stream));
+    launch_recon_smooth(a, r->d_support, c->stream);
+  } else {
+    recon_refresh_plane(c, r);
+  }
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, recon_wait(c, r));
+  r->score_radius = rad;
+  memcpy(r->score_taps, r->taps, sizeof(r->score_taps));
+  r->score_open = true;
+  return CMX_OK;
+}
+
+int recon_score_enter(cmx_ctx *c) {
+  const int rc = recon_enter(c, true);
+  if (rc) return rc;
+  if (!c->recon->score_open)
+    return fail(c, CMX_ERR_STATE, "no score pass is open (cmx_backend_recon_score_open, and nothing that changes the plane or the knots since)");
+  return CMX_OK;
+}
+
+int cmx_backend_recon_score_plane(cmx_ctx *c, float *S) {
+  int rc = recon_score_enter(c);
+  if (rc) return rc;
+  if (!S) return fail(c, CMX_ERR_INVALID_ARG, "null output");
+  ReconState *r = c->recon;
+  const float *src = r->score_radius > 0 ? r->d_support : r->d_plane;
+  HIP_TRY(c, hipMemcpyAsync(S, src, (size_t)c->Wp * c->Hp * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return CMX_OK;
 }
 
 int cmx_backend_recon_get(cmx_ctx *c, float *pano, int64_t *n_sampled, int64_t *n_inside) {

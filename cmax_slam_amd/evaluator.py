@@ -716,6 +716,53 @@ class BackendEvaluator(_Evaluator):
         self._ck(self._L.cmx_backend_recon_warp_from(self._ctx, store._h, int(first), int(count), fmt, xy.ctypes.data, fl.ctypes.data))
         return xy, fl
 
+    # --- per-event support scores: the panorama read back at every event (cmx_backend_recon_score*)
+    def reconstruct_score_open(self, sigma=0.0):
+        """Open a score pass: S = GaussianBlur(plane, sigma) of the plane as accumulated now (sigma 0: the plane itself).  It stays
+        open until something changes the plane or the knots (add, restart, extend, eval, solve, bind, freeze / advance_head)."""
+        self._ck(self._L.cmx_backend_recon_score_open(self._ctx, float(sigma)))
+
+    def reconstruct_score_plane(self):
+        """S of the open score pass, (Hp, Wp) float32."""
+        S = np.empty((self.Hp, self.Wp), np.float32)
+        self._ck(self._L.cmx_backend_recon_score_plane(self._ctx, S.ctypes.data_as(c_fp)))
+        return S
+
+    def reconstruct_score(self, x, y, t_ns, loo=True):
+        """(scores float32[n], flags uint8[n]) of exactly these events, in input order: S interpolated with the vote's own four
+        weights where the event lands (0 outside the plane), flags as reconstruct_warp.  loo: events that voted (flags == 3) have
+        their own contribution subtracted; no clamp at zero.  Reads only."""
+        x, y, t = _c(x, np.uint16), _c(y, np.uint16), _c(t_ns, np.int64)
+        if not (len(x) == len(y) == len(t)):
+            raise ValueError("x, y, t_ns must have equal length")
+        sc, fl = np.empty(len(x), np.float32), np.empty(len(x), np.uint8)
+        self._ck(self._L.cmx_backend_recon_score(self._ctx, len(x), x.ctypes.data_as(c_u16p), y.ctypes.data_as(c_u16p),
+                                                 t.ctypes.data_as(c_i64p), int(bool(loo)), sc.ctypes.data, fl.ctypes.data))
+        return sc, fl
+
+    def reconstruct_score_aos(self, events, loo=True):
+        """The same from a structured array of records with fields x, y, sec, nsec."""
+        ev = np.ascontiguousarray(events)
+        lay = _lib.aos_layout_of(ev)
+        sc, fl = np.empty(len(ev), np.float32), np.empty(len(ev), np.uint8)
+        self._ck(self._L.cmx_backend_recon_score_aos(self._ctx, len(ev), ev.ctypes.data_as(C.c_void_p), C.byref(lay), int(bool(loo)),
+                                                     sc.ctypes.data, fl.ctypes.data))
+        return sc, fl
+
+    def reconstruct_score_from(self, store, first, count, loo=True, out=None):
+        """The same over events_[first, first+count) of an EventStore.  out = (scores, flags_or_None), torch tensors on the context's
+        device (`count` float32, `count` bytes): the kernel writes straight into them, nothing crosses the host, and out is returned
+        (the stream rules of reconstruct_warp_from)."""
+        if out is not None:
+            sc, fl = out
+            self._ck(self._L.cmx_backend_recon_score_from_device(self._ctx, store._h, int(first), int(count), int(bool(loo)), sc.data_ptr(),
+                                                                 fl.data_ptr() if fl is not None else None))
+            return out
+        sc, fl = np.empty(int(count), np.float32), np.empty(int(count), np.uint8)
+        self._ck(self._L.cmx_backend_recon_score_from(self._ctx, store._h, int(first), int(count), int(bool(loo)), sc.ctypes.data,
+                                                      fl.ctypes.data))
+        return sc, fl
+
     # --- signed polarity map: ON / OFF planes of the same vote loop (cmx_backend_recon_pol_*)
     def reconstruct_pol_add(self, x, y, t_ns, polarity):
         """reconstruct_add's vote loop over exactly these events, into the ON plane (polarity nonzero) or the OFF plane.  The count

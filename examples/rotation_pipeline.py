@@ -185,7 +185,7 @@ def reconstruct_panorama(be, traj, x, y, t, prm, store=None, knots=None):
 def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefix=None, reconstruct=False, refine_global=False,
                  refine_bound=False, refine_native=False, freeze_head=None, refine_online=None, online_free=8, export_warped=None,
                  polarity_map=None, frames=None, frame_ms=20.0, crop=None, voxels=None, voxel_ms=20.0, voxel_bins=5,
-                 time_surfaces=None, surface_ms=20.0, surface_tau_ms=None):
+                 time_surfaces=None, surface_ms=20.0, surface_tau_ms=None, score_events=None, score_sigma=1.0):
     """stream: synth.EventStream (or anything with x, y, t_ns, W, H, fx, fy, cx, cy, lut).  Returns a dict.
     display_prefix: write the final panorama with the last pose's FOV and the last packet's local-IWE pair there.
     reconstruct: after the last window, re-warp all events along the whole refined trajectory (res["recon"]; with
@@ -217,8 +217,13 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
     milliseconds one surface with the sensor's size and intrinsics and the spline's pose at the slice centre (trajectory.frame_views,
     BackendEvaluator.reconstruct_surface_*), ON and OFF channels, read through exp(-(t_hi - T) / tau) at its own t_hi with tau =
     surface_tau_ms (default: surface_ms) -- written as one .npy of shape (S, 2, H, W) fp32; res["time_surfaces"] = (decayed, counts).
-    Polarities as for polarity_map."""
-    reconstruct = (reconstruct or export_warped is not None or polarity_map is not None or frames is not None or crop is not None
+    Polarities as for polarity_map.
+    score_events = PATH (implies reconstruct): the support score of every event of the reconstruction against the final panorama,
+    blurred with score_sigma (BackendEvaluator.reconstruct_score_*): the panorama read back where the event lands, an event that
+    voted without its own vote -- many companions on a sharp edge, none for noise and hot pixels.  Written to PATH.npz as score
+    (float32) and flags (as export_warped); res["scores"] = (score, flags).  The quartiles and the share of voting events with less
+    than one vote of support are logged; nothing is asserted."""
+    reconstruct = (reconstruct or score_events is not None or export_warped is not None or polarity_map is not None or frames is not None or crop is not None
                    or voxels is not None or time_surfaces is not None)
     prm = prm or Params()
     x, y, t = stream.x, stream.y, stream.t_ns
@@ -417,6 +422,20 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
             np.savez(export_warped + ".npz", xy=xy, flags=flags, index=index)
             if log:
                 log("export: %d events to %s.npz, %d of them voted" % (n_rec, export_warped, int(np.count_nonzero(flags == 3))))
+        if score_events is not None:  # (the same range in one call, right after the votes: the own contribution is the event's)
+            be.reconstruct_score_open(score_sigma)
+            if store is not None:
+                score, sflags = be.reconstruct_score_from(store, i_rec, n_rec, loo=True)
+            else:
+                score, sflags = be.reconstruct_score(x[i_rec:i_rec + n_rec], y[i_rec:i_rec + n_rec], t[i_rec:i_rec + n_rec], loo=True)
+            res["scores"] = (score, sflags)
+            np.savez(score_events + ".npz", score=score, flags=sflags)
+            if log:
+                voted = score[sflags == 3]
+                q = np.percentile(voted, [25, 50, 75]) if len(voted) else np.zeros(3)
+                log("scores: %d events to %s.npz at sigma %g; leave-one-out support of the %d voting events: quartiles %.2f / %.2f / %.2f, "
+                    "%.1f %% below one vote" % (n_rec, score_events, score_sigma, len(voted), q[0], q[1], q[2],
+                                                100.0 * float(np.mean(voted < 1.0)) if len(voted) else 0.0))
         if log:
             log("reconstruction: %d events along %d control poses in %.2f ms (%d sampled, %d voted)" %
                 (n_rec, traj.size(), (time.perf_counter() - t0) * 1e3, n_sampled, n_inside))
@@ -582,6 +601,11 @@ def main():
     ap.add_argument("--export-warped", metavar="PATH", default=None,
                     help="after the final refinement, write PATH.npz: the panorama coordinate (xy) and flags of every event warped along "
                          "the whole trajectory, and the events' indices (implies --reconstruct)")
+    ap.add_argument("--score-events", metavar="PATH", default=None,
+                    help="after the reconstruction (or any refine mode), write PATH.npz: the leave-one-out support score of every event "
+                         "against the final panorama (score) and its flags; prints the quartiles and the share of voting events with "
+                         "less than one vote of support (implies --reconstruct)")
+    ap.add_argument("--score-sigma", type=float, default=1.0, help="blur of the panorama the scores are read from (0: none)")
     ap.add_argument("--polarity-map", metavar="PREFIX", default=None,
                     help="after the reconstruction, write the signed panorama ON - OFF as PREFIX.pgm and PREFIX.ppm (implies "
                          "--reconstruct).  The synthetic stream has no brightness model: the polarities are drawn from a seeded "
@@ -638,7 +662,8 @@ def main():
                        refine_global=a.refine_global or a.refine_native, refine_bound=a.refine_bound, refine_native=a.refine_native,
                        freeze_head=a.freeze_head, refine_online=a.refine_online, online_free=a.online_free, export_warped=a.export_warped,
                        polarity_map=a.polarity_map, frames=a.frames, frame_ms=a.frame_ms, crop=a.crop, voxels=a.voxels, voxel_ms=a.voxel_ms,
-                       voxel_bins=a.voxel_bins, time_surfaces=a.time_surfaces, surface_ms=a.surface_ms, surface_tau_ms=a.surface_tau_ms)
+                       voxel_bins=a.voxel_bins, time_surfaces=a.time_surfaces, surface_ms=a.surface_ms, surface_tau_ms=a.surface_tau_ms,
+                       score_events=a.score_events, score_sigma=a.score_sigma)
     wall = time.perf_counter() - t0
     m = evaluate_against_truth(stream, res)
     print("%.2f s of events (%d) processed in %.2f s wall" % (a.seconds, len(stream.x), wall))

@@ -359,8 +359,9 @@ int cmx_backend_recon_get(cmx_ctx *ctx, float *pano /* Hp*Wp or NULL */, int64_t
 int cmx_backend_recon_render(cmx_ctx *ctx, double gamma, const double fov_quat_xyzw[4] /* or NULL */, unsigned char *out);
 int cmx_backend_recon_end(cmx_ctx *ctx);
 /* Per-event export: WHERE every event lands under the trajectory the reconstruction holds -- what a host needs for any product other
- * than the count panorama (a time surface, outlier flags; the signed polarity map and pinhole frames or crops have calls of their
- * own, cmx_backend_recon_pol_* and cmx_backend_recon_view_*): the export itself never reads polarity, the host joins the entries with whatever it kept.
+ * than the count panorama (the signed polarity map, pinhole frames or crops, voxel grids, time surfaces and support scores for
+ * outlier flags have calls of their own, cmx_backend_recon_pol_*, _view_*, _voxel_*, _surface_* and _score*): the export itself
+ * never reads polarity, the host joins the entries with whatever it kept.
  *   output   ONE entry per event handed in, sampled or not, in input order: xy_out[2i], xy_out[2i+1] = (px, py), flags_out[i]
  *            (flags_out may be NULL).  CMX_WARP_F64: 2 doubles per event; CMX_WARP_F32: 2 floats, (float)px and (float)py.
  *   poses    spline, batch size and sample rate are those of recon_begin / restart / extend; the knots are the ones the
@@ -395,6 +396,55 @@ int cmx_backend_recon_warp_from(cmx_ctx *ctx, const cmx_events *ev, int64_t firs
                                 unsigned char *flags_out);
 int cmx_backend_recon_warp_from_device(cmx_ctx *ctx, const cmx_events *ev, int64_t first, int64_t count, int format, void *d_xy_out,
                                        unsigned char *d_flags_out /* device pointers on the context's device */);
+/* Per-event support scores: the way back from the map to the events -- the motion-compensated image read at the place where an event
+ * lands, with or without the event's own vote.  Events on a sharp edge of the panorama have many companions, noise events and hot
+ * pixels have none: outlier flags, denoising, an input weight beside the voxel grids and time surfaces.  On an open reconstruction:
+ *     recon_add* ...   recon_score_open(sigma)   recon_score*(events, loo) (any number of times)   [recon_score_plane]
+ *   the plane   is the count panorama of recon_add* / eval_from / eval_bound as it stands at score_open.
+ *   S           the support plane: GaussianBlur(plane, blur_sigma) exactly as recon_contrast forms it (the same taps, REFLECT_101, the
+ *               same operation order); with blur_sigma == 0 the plane itself.  In deterministic mode S comes from the fp32 view of the
+ *               fixed-point plane (what recon_get returns).
+ *   score       event i is warped exactly as recon_warp* warps it: cell (xx, yy) = ((int)px, (int)py), fp32 fractions dx, dy, and the
+ *               four fp32 weights of the vote, each a single rounded product: w00 = (1-dx)(1-dy), w01 = dx(1-dy), w10 = (1-dx)dy,
+ *               w11 = dx dy.  If INSIDE,
+ *                   score_i = ((w00 S[yy][xx] + w01 S[yy][xx+1]) + w10 S[yy+1][xx]) + w11 S[yy+1][xx+1]
+ *               in fp32, every product and every sum rounded on its own, in this order, no FMA: a host reproduces it bit for bit
+ *               from recon_score_plane and the (px, py) of recon_warp*.  Otherwise 0.0f.
+ *   loo != 0    leave-one-out: an event with flags == 3 (SAMPLED | INSIDE) voted into the plane, and what S hands back of its own four
+ *               adds is subtracted, score_i - self_i in one fp32 subtraction:
+ *                   self_i = (sum_{j,j'} wx_j wx_j' Gx[xx+j, xx+j']) * (the same in y),   wx = (1-dx, dx), wy = (1-dy, dy)
+ *               with Gx[a, b] the entry of the 1-D REFLECT_101 filter matrix: the tap g(a-b) plus every tap that folds onto b at the
+ *               left or the right border.  blur_sigma == 0: self_i = ((w00^2 + w01^2) + w10^2) + w11^2.  Events that are not SAMPLED,
+ *               and the lone trailing event, did not vote: nothing is subtracted.  NO clamp at zero: in default mode the plane is a sum
+ *               of fp32 atomics, so a leave-one-out score of -1e-7 is honest; in deterministic mode |.| <= 2^-28 for an event alone
+ *               in its cells (2^-30 per vote, four cells).  The subtraction is right for events that DID vote into this plane: score
+ *               the events that were added, in the cuts they were added in.
+ *   score_open  takes the snapshot: S is formed from the plane as accumulated NOW.  Accepts every blur_sigma recon_contrast accepts
+ *               (CMX_ERR_INVALID_ARG: not finite, radius > 12) and needs Wp > 2r+1 && Hp > 2r+1 (CMX_ERR_INVALID_ARG: the own
+ *               contribution folds single reflections, as the adjoint gradient does).  The taps are those of recon_contrast: an open
+ *               gradient pass at ANOTHER sigma is closed exactly as recon_contrast(sigma) would close it, one at the same sigma is
+ *               left alone.  The pass stays open until something changes the plane or the knots: begin, restart, extend, every add*
+ *               that votes into the count plane, eval_from, eval_bound, solve, bind*, freeze_head, advance_head, end.  pol_add*,
+ *               view_*, voxel_*, surface_*, warp*, grad_add*, contrast, get and render do not close it.
+ *   score*      CMX_ERR_STATE without an open pass, before begin and on a group handle.  Otherwise everything of recon_warp*: one
+ *               float per event handed in, in input order; the same flags (flags_out may be NULL); the same batches and batch times;
+ *               the lone trailing event scored with the pose at its own time, its time validated against the spline; validation and
+ *               status codes complete before anything is written; n == 0 is valid, a NULL score_out with n > 0 is
+ *               CMX_ERR_INVALID_ARG; the internal slices and the double-buffered device staging -> pinned -> caller path of the host
+ *               outputs; _from_device writes straight into device pointers on the context's device.  Read-only on everything but S:
+ *               the plane, the counters, the knots, an open gradient pass, a binding, a frozen or released head, the target sets, the
+ *               window, IG and the exchange sets are untouched.  Works after release_head.
+ *   score_plane copies S out (tests, display).  CMX_ERR_STATE without an open pass. */
+int cmx_backend_recon_score_open(cmx_ctx *ctx, double blur_sigma);
+int cmx_backend_recon_score_plane(cmx_ctx *ctx, float *S /* Hp*Wp */);
+int cmx_backend_recon_score(cmx_ctx *ctx, int64_t n, const uint16_t *x, const uint16_t *y, const int64_t *t_ns, int loo, float *score_out,
+                            unsigned char *flags_out /* n bytes or NULL */);
+int cmx_backend_recon_score_aos(cmx_ctx *ctx, int64_t n, const void *events, const cmx_aos_layout *layout, int loo, float *score_out,
+                                unsigned char *flags_out);
+int cmx_backend_recon_score_from(cmx_ctx *ctx, const cmx_events *ev, int64_t first, int64_t count, int loo, float *score_out,
+                                 unsigned char *flags_out);
+int cmx_backend_recon_score_from_device(cmx_ctx *ctx, const cmx_events *ev, int64_t first, int64_t count, int loo, float *d_score_out,
+                                        unsigned char *d_flags_out /* device pointers on the context's device */);
 /* Signed polarity panorama: the ON and the OFF events of the recording as two planes, ON - OFF being the map that feeds intensity
  * reconstruction and the usual red / blue picture.  On an open reconstruction:
  *     recon_pol_add*(events, polarity) ...   recon_pol_get / recon_pol_render (any number of times)   [recon_pol_reset]
