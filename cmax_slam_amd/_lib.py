@@ -21,7 +21,7 @@ SCHED_BACKGROUND, SCHED_NORMAL, SCHED_URGENT = -1, 0, 1
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p)
 OPT_GRAD_MODE, OPT_SPLAT_MODE, OPT_REUSE_IMAGE, OPT_SPIN_WAIT, OPT_DETERMINISTIC, OPT_TAIL_FINALIZE = 1, 2, 3, 4, 5, 6
 OPT_COMPOSITE_IMAGE, OPT_FOLD_BATCH, OPT_GATED_DF, OPT_CHAIN_SOLVE, OPT_FUSED_IMAGE = 8, 9, 10, 11, 12
-DIAG_FORCE_CROSS_DEVICE, DIAG_RECON_SLICE_EVENTS = 1, 2  # cmx_diag_set keys (include/cmax_hip_diag.h)
+DIAG_FORCE_CROSS_DEVICE, DIAG_RECON_SLICE_EVENTS, DIAG_EVENTS_STAGE_SLICE = 1, 2, 3  # cmx_diag_set keys (include/cmax_hip_diag.h)
 DIAG_JT_EVAL, DIAG_JT_RECON = 0, 1  # cmx_diag_get_adjoint_plane: which
 WARP_F64, WARP_F32 = 0, 1  # cmx_backend_recon_warp*: output format
 WARP_SAMPLED, WARP_INSIDE = 1, 2  # ... and the flag bits
@@ -46,6 +46,11 @@ class AosLayout(C.Structure):  # cmx_aos_layout: record size + byte offsets of (
 class ReconView(C.Structure):  # cmx_recon_view: one virtual pinhole camera of cmx_backend_recon_view_begin
     _fields_ = [("quat_xyzw", C.c_double * 4), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
                 ("t_lo_ns", C.c_int64), ("t_hi_ns", C.c_int64)]
+
+
+class Select(C.Structure):  # cmx_select: the criteria of cmx_events_select* (size = sizeof; a NULL pointer = criterion not given)
+    _fields_ = [("size", C.c_size_t), ("keep", C.c_void_p), ("score", C.c_void_p), ("min_score", C.c_float), ("flags", C.c_void_p),
+                ("flags_mask", C.c_ubyte), ("flags_value", C.c_ubyte), ("pixel_keep", C.c_void_p)]
 
 
 def recon_view(quat_xyzw, fx, fy, cx, cy, t_lo_ns, t_hi_ns):
@@ -135,6 +140,11 @@ SYMBOLS = {
     "cmx_events_drop_before": (C.c_int, [C.c_void_p, C.c_int64]),
     "cmx_events_begin": (C.c_int64, [C.c_void_p]),
     "cmx_events_end": (C.c_int64, [C.c_void_p]),
+    "cmx_events_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(Select), c_i64p]),
+    "cmx_events_select_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(Select), c_i64p]),
+    "cmx_events_pixel_counts": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "cmx_events_pixel_counts_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "cmx_events_read": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, c_u16p, c_u16p, c_i64p, c_u8p]),
     "cmx_frontend_set_packet_from": (C.c_int, [ctx_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double,
                                                C.c_double, C.c_double, C.c_int, C.c_double, C.c_int]),
     "cmx_backend_set_window_from": (C.c_int, [ctx_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, c_dp, C.c_int64,

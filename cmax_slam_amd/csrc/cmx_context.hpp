@@ -344,6 +344,14 @@ struct cmx_events {
   size_t pol_stage_cap = 0;
   bool has_pol = false;      // the events held carry polarity: all of them or none (decided by the first push into an empty store)
   std::vector<int64_t> h_t;  // host mirror of the timestamps (per-batch pose times are formed on the host)
+  // scratch of cmx_events_select* with this store as the DESTINATION (its first replica's device; grown on demand)
+  unsigned long long *d_sel_ballot = nullptr;  // one word per 64 source events, whole tiles
+  unsigned *d_sel_counts = nullptr;            // kept events per tile
+  long long *d_sel_offsets = nullptr;          // their exclusive scan, and the total behind it
+  size_t sel_tiles_cap = 0;
+  int64_t *h_sel_total = nullptr;              // pinned: the total, read between the scan and the scatter
+  unsigned char *d_sel_in = nullptr;           // the host form's criteria arrays, uploaded
+  size_t sel_in_cap = 0;
   std::string err;
   const Replica *on(int dev) const {
     for (const Replica &r : rep)
@@ -515,6 +523,7 @@ int be_eval_one(cmx_ctx *c, const double *drotv, double *contrast, double *grad)
 // ---- whole-trajectory reconstruction: what the rest of the library sees of it (its own shared state and helpers:
 // cmx_recon_state.hpp).  cmx_reconstruct.cpp: life cycle, contrast, get / render; cmx_recon_feed.cpp: add*, grad_add*, warp*;
 // cmx_recon_bound.cpp: the binding, its frozen head, the solve's hooks
+int events_diag_stage_slice(int n);  // CMX_DIAG_EVENTS_STAGE_SLICE (cmax_hip_diag.h)
 int recon_diag_slice_events(int n);  // CMX_DIAG_RECON_SLICE_EVENTS (cmax_hip_diag.h)
 void recon_release(cmx_ctx *c);  // frees whatever a reconstruction holds (cmx_backend_recon_end, cmx_destroy)
 // cmx_recon_bound.cpp -- cmx_backend_recon_solve (cmx_solver.cpp) around the bound evaluation: begin validates everything before anything changes, sets

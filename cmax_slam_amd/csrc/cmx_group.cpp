@@ -550,6 +550,7 @@ static int group_connect(cmx_group *g, cmx_ctx *leader, const int *devices, int 
 static std::atomic<int> g_diag_force_cross_device{0};
 int cmx_diag_set(int key, int value) {
   if (key == CMX_DIAG_RECON_SLICE_EVENTS) return recon_diag_slice_events(value);
+  if (key == CMX_DIAG_EVENTS_STAGE_SLICE) return events_diag_stage_slice(value);
   if (key != CMX_DIAG_FORCE_CROSS_DEVICE) return CMX_ERR_INVALID_ARG;
   g_diag_force_cross_device.store(value != 0 ? 1 : 0, std::memory_order_relaxed);
   return CMX_OK;

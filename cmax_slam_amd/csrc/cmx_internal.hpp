@@ -596,6 +596,37 @@ void launch_mark_visited(const BeSplatArgs &cam, const double R[9], int sensor_h
 void launch_interleave3(const float *planes, float *out, int npix, hipStream_t s);
 size_t image_lds_bytes(int r);
 
+// event store (cmx_select.hip): stable compaction of n events of one store behind the events of another, in three launches on one
+// stream -- mark (predicate, one ballot word per 64 events, one count per tile), scan (tile counts -> 64-bit offsets,
+// offsets[ntiles] = the total), scatter -- and the per-pixel histogram.  The host reads the total between scan and scatter and
+// launches the scatter only when everything fits.
+constexpr int kSelTile = 4096;         // events per workgroup of mark / scatter: 64 ballot words
+constexpr int kSelScanThreads = 256;   // tiles one pass of the scan's single workgroup takes
+static inline long long sel_tiles(long long n) { return (n + kSelTile - 1) / kSelTile; }
+struct SelectArgs {
+  long long n;                          // events of the source range
+  int W;
+  const uint32_t *src_xy;               // the range's packed words / timestamps / polarity bytes (null: the stores hold none)
+  const long long *src_t;
+  const unsigned char *src_pol;
+  const unsigned char *keep;            // criteria: [n] or null (not given) ...
+  const float *score;
+  float min_score;
+  const unsigned char *flags;
+  unsigned char flags_mask, flags_value;
+  const unsigned char *pixel_keep;      // ... [W * H] or null
+  unsigned long long *ballot;           // [sel_tiles(n) * 64]
+  unsigned *counts;                     // [sel_tiles(n)]
+  long long *offsets;                   // [sel_tiles(n) + 1]
+  uint32_t *dst_xy;                     // the destination's first free slot
+  long long *dst_t;
+  unsigned char *dst_pol;
+};
+void launch_select_mark(const SelectArgs &a, hipStream_t s);
+void launch_select_scan(const unsigned *counts, long long ntiles, long long *offsets, hipStream_t s);
+void launch_select_scatter(const SelectArgs &a, hipStream_t s);
+void launch_pixel_counts(const uint32_t *xy, long long n, int W, uint32_t *counts, hipStream_t s);  // counts: W * H, zeroed
+
 // display path (cmx_display.hip): range = 2 words, both 0xffffffff before launch_display_range; every launch reads what the one
 // before it wrote, on the same stream
 void launch_display_range(const float *p0, const float *p1 /* or null */, size_t n, unsigned *range, hipStream_t s);

@@ -43,6 +43,12 @@ def _pol_bytes(polarity):
     return np.ascontiguousarray(p > 0).view(np.uint8)
 
 
+def _on_device(a, name):
+    """a tensor handed to a *_device call of the event store lives in device memory (an object that cannot say is taken at its word)"""
+    if getattr(a, "is_cuda", True) is False:
+        raise ValueError("%s: a tensor in device memory expected, got one on %s" % (name, getattr(a, "device", "the host")))
+
+
 def _pol_offset(ev, field):
     dt, off = ev.dtype.fields[field][:2]
     if dt.itemsize != 1:
@@ -281,6 +287,7 @@ class EventStore:
         (cmx_events_create_group); a group handle over the same list cuts its windows from it member by member."""
         self._L = _lib.lib()
         self._h = C.c_void_p()
+        self.W, self.H = int(W), int(H)
         if devices is None:
             check(None, self._L.cmx_events_create(C.byref(self._h), int(device), int(W), int(H), int(capacity)))
         else:
@@ -329,6 +336,72 @@ class EventStore:
 
     def drop_before(self, global_index):
         self._ck(self._L.cmx_events_drop_before(self._h, int(global_index)))
+
+    def select(self, src, first, count, keep=None, score=None, min_score=None, flags=None, flags_mask=3, flags_value=3,
+               pixel_keep=None):
+        """cmx_events_select*: append to THIS store the events of src[first, first+count) for which every given criterion holds, in
+        their order (a stable compaction on the device); returns how many were kept.  keep: `count` bytes, nonzero = keep.  score with
+        min_score: `count` float32, keep when score >= min_score (NaN is dropped).  flags: `count` bytes, keep when
+        (flags & flags_mask) == flags_value -- the default 3 / 3 is "the event voted", the bit pair of reconstruct_warp / _score.
+        pixel_keep: (H, W) bytes, nonzero = the pixel's events are kept.  No criterion: a device-side copy of the range.
+        numpy arrays take the host form; objects with data_ptr() (torch tensors on the stores' device, contiguous: uint8 / bool, float32)
+        the device form, in which nothing crosses the host.  The two kinds cannot be mixed."""
+        first, count = int(first), int(count)
+        if (score is None) != (min_score is None):
+            raise ValueError("score and min_score are given together")
+        given = [a for a in (keep, score, flags, pixel_keep) if a is not None]
+        on_device = [hasattr(a, "data_ptr") for a in given]
+        if any(on_device) and not all(on_device):
+            raise ValueError("criteria are all host arrays or all device tensors")
+        device = bool(on_device) and on_device[0]
+        hold = []  # (the host arrays must outlive the call)
+
+        def ptr(a, name, n, host_dtype, itemsize):
+            if a is None:
+                return None
+            if device:
+                _on_device(a, name)
+                if int(a.numel()) != n or int(a.element_size()) != itemsize or not a.is_contiguous():
+                    raise ValueError("%s: %d contiguous elements of %d byte(s) expected" % (name, n, itemsize))
+                return a.data_ptr()
+            a = np.asarray(a)
+            if host_dtype == np.uint8 and a.dtype == np.bool_:
+                a = a.view(np.uint8)
+            a = _c(a, host_dtype).reshape(-1)
+            if a.size != n:
+                raise ValueError("%s: %d elements expected, got %d" % (name, n, a.size))
+            hold.append(a)
+            return a.ctypes.data
+
+        sel = _lib.Select(C.sizeof(_lib.Select), ptr(keep, "keep", count, np.uint8, 1), ptr(score, "score", count, np.float32, 4),
+                          float(min_score) if min_score is not None else 0.0, ptr(flags, "flags", count, np.uint8, 1),
+                          int(flags_mask) & 255, int(flags_value) & 255, ptr(pixel_keep, "pixel_keep", self.W * self.H, np.uint8, 1))
+        kept = C.c_int64(0)
+        fn = self._L.cmx_events_select_device if device else self._L.cmx_events_select
+        self._ck(fn(self._h, src._h, first, count, C.byref(sel), C.byref(kept)))
+        return int(kept.value)
+
+    def pixel_counts(self, first, count, out=None):
+        """cmx_events_pixel_counts*: (H, W) uint32, the number of events of [first, first+count) at every pixel -- what a hot-pixel mask
+        is made from.  out: a tensor of W*H 32-bit words on the store's device, filled and returned instead."""
+        if out is not None:
+            _on_device(out, "out")
+            if int(out.numel()) != self.W * self.H or int(out.element_size()) != 4 or not out.is_contiguous():
+                raise ValueError("out: W*H contiguous 32-bit elements expected")
+            self._ck(self._L.cmx_events_pixel_counts_device(self._h, int(first), int(count), out.data_ptr()))
+            return out
+        counts = np.empty((self.H, self.W), np.uint32)
+        self._ck(self._L.cmx_events_pixel_counts(self._h, int(first), int(count), counts.ctypes.data))
+        return counts
+
+    def read(self, first, count):
+        """cmx_events_read: (x, y, t_ns, polarity or None) of [first, first+count), the inverse of push."""
+        n = max(int(count), 0)
+        x, y, t = np.empty(n, np.uint16), np.empty(n, np.uint16), np.empty(n, np.int64)
+        p = np.empty(n, np.uint8) if self.has_polarity else None
+        self._ck(self._L.cmx_events_read(self._h, int(first), int(count), x.ctypes.data_as(c_u16p), y.ctypes.data_as(c_u16p),
+                                         t.ctypes.data_as(c_i64p), p.ctypes.data_as(_lib.c_u8p) if p is not None else None))
+        return x, y, t, p
 
     @property
     def begin(self):

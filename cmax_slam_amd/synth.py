@@ -302,6 +302,8 @@ class EventStream:
     grid_ns: int             # ground-truth sampling step
     grid_quat: np.ndarray    # world<-camera orientation (x,y,z,w) at T0_NS + k*grid_ns
     grid_omega: np.ndarray   # body-frame angular velocity at the same stamps [rad/s]
+    is_hot: np.ndarray = None  # per event: fired by one of the hot pixels (all False without any)
+    hot_xy: np.ndarray = None  # (hot_pixels, 2) their positions (x, y)
 
     @property
     def lut(self):
@@ -317,11 +319,13 @@ class EventStream:
 
 
 def event_stream(rate, T, W, H, fx, fy, cx, cy, seed=SEED0, noise=0.10, n_arcs=400, omega_mean=(0.1, 0.9, 0.15),
-                 omega_amp=(0.5, 0.4, 0.5), omega_hz=(1.3, 0.7, 1.9), yaw0_deg=0.0):
+                 omega_amp=(0.5, 0.4, 0.5), omega_hz=(1.3, 0.7, 1.9), yaw0_deg=0.0, hot_pixels=0, hot_share=0.0):
     """rate*T events over [t0, t0+T) seen by a camera whose body-frame angular velocity is
     omega_mean + omega_amp*sin(2 pi f t + phase): R(t+h) = R(t) exp(omega h) (the post-multiplied integration the
     back end itself uses, pose_graph_optimizer.cpp:205-210), world<-camera, R(t0) = rotation by yaw0 about Y
-    (pose_graph_optimizer.cpp:88-93).  Scene = great-circle arcs spread over the band the camera sweeps."""
+    (pose_graph_optimizer.cpp:88-93).  Scene = great-circle arcs spread over the band the camera sweeps.
+    hot_pixels > 0: that many pixels at fixed random positions fire hot_share of the rate*T events at uniform random times (the
+    sensor defect a per-pixel event count finds); their draws come after every other draw, so the default call is unchanged."""
     rng = np.random.default_rng(seed)
     grid_ns = 10_000
     n_grid = int(T * 1e9) // grid_ns + 2
@@ -341,7 +345,8 @@ def event_stream(rate, T, W, H, fx, fy, cx, cy, seed=SEED0, noise=0.10, n_arcs=4
     axes = grid_R[:: max(n_grid // 24, 1), :, 2]
     cone = 1.25 * np.arctan(np.hypot(W / 2 / fx, H / 2 / fy))
     scene = _Scene(rng, n_arcs, axes, cone)
-    N = int(round(rate * T))
+    n_hot = int(round(rate * T * hot_share)) if hot_pixels > 0 else 0
+    N = int(round(rate * T)) - n_hot
     n_sig = int(round(N * (1 - noise)))
     xs, ys, ts = [], [], []
     need = n_sig
@@ -361,5 +366,15 @@ def event_stream(rate, T, W, H, fx, fy, cx, cy, seed=SEED0, noise=0.10, n_arcs=4
     x = np.concatenate([x, rng.integers(0, W, n_noise)])
     y = np.concatenate([y, rng.integers(0, H, n_noise)])
     tn = np.concatenate([tn, T0_NS + np.floor(rng.random(n_noise) * T * 1e9).astype(np.int64)])
+    is_hot = np.zeros(len(x), bool)
+    hot_xy = np.zeros((0, 2), np.int64)
+    if hot_pixels > 0:
+        hot_xy = np.stack([rng.integers(0, W, hot_pixels), rng.integers(0, H, hot_pixels)], axis=1)
+        which = rng.integers(0, hot_pixels, n_hot)
+        x = np.concatenate([x, hot_xy[which, 0]])
+        y = np.concatenate([y, hot_xy[which, 1]])
+        tn = np.concatenate([tn, T0_NS + np.floor(rng.random(n_hot) * T * 1e9).astype(np.int64)])
+        is_hot = np.concatenate([is_hot, np.ones(n_hot, bool)])
     o = np.argsort(tn, kind="stable")
-    return EventStream(W, H, fx, fy, cx, cy, x[o].astype(np.uint16), y[o].astype(np.uint16), tn[o], grid_ns, quats, omega)
+    return EventStream(W, H, fx, fy, cx, cy, x[o].astype(np.uint16), y[o].astype(np.uint16), tn[o], grid_ns, quats, omega,
+                       is_hot[o], hot_xy)

@@ -162,6 +162,7 @@ def refine_trajectory_online(be, traj, x, y, t, prm, store, stride_s, free=8, lo
 
 
 POLARITY_SEED = 2024  # --polarity-map: the synthetic stream's polarities are drawn, not modelled
+HOT_FACTOR = 20.0  # --reject-outliers with --hot-pixels: a pixel with more than this many times the mean event count is masked
 CROP_SIZE = (512, 384)  # --crop: the view's grid (a quarter of the sensor's field of view on about twice its pixels)
 
 
@@ -185,7 +186,7 @@ def reconstruct_panorama(be, traj, x, y, t, prm, store=None, knots=None):
 def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefix=None, reconstruct=False, refine_global=False,
                  refine_bound=False, refine_native=False, freeze_head=None, refine_online=None, online_free=8, export_warped=None,
                  polarity_map=None, frames=None, frame_ms=20.0, crop=None, voxels=None, voxel_ms=20.0, voxel_bins=5,
-                 time_surfaces=None, surface_ms=20.0, surface_tau_ms=None, score_events=None, score_sigma=1.0):
+                 time_surfaces=None, surface_ms=20.0, surface_tau_ms=None, score_events=None, score_sigma=1.0, reject_outliers=None):
     """stream: synth.EventStream (or anything with x, y, t_ns, W, H, fx, fy, cx, cy, lut).  Returns a dict.
     display_prefix: write the final panorama with the last pose's FOV and the last packet's local-IWE pair there.
     reconstruct: after the last window, re-warp all events along the whole refined trajectory (res["recon"]; with
@@ -222,8 +223,13 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
     blurred with score_sigma (BackendEvaluator.reconstruct_score_*): the panorama read back where the event lands, an event that
     voted without its own vote -- many companions on a sharp edge, none for noise and hot pixels.  Written to PATH.npz as score
     (float32) and flags (as export_warped); res["scores"] = (score, flags).  The quartiles and the share of voting events with less
-    than one vote of support are logged; nothing is asserted."""
-    reconstruct = (reconstruct or score_events is not None or export_warped is not None or polarity_map is not None or frames is not None or crop is not None
+    than one vote of support are logged; nothing is asserted.
+    reject_outliers = MIN_SCORE (implies reconstruct): after everything else, the voting events whose leave-one-out support (at
+    score_sigma) is at least MIN_SCORE are selected ON THE DEVICE into a second store (EventStore.select on the scores' and flags'
+    device tensors; host arrays without torch), the panorama is reconstructed again from the cleaned store and, with refine_native,
+    the trajectory is solved again on it (reject_outliers_pass; res["reject"]).  A stream with hot pixels (stream.is_hot) also gets
+    the share of their events removed and of the other events kept.  Logged; nothing is asserted."""
+    reconstruct = (reconstruct or reject_outliers is not None or score_events is not None or export_warped is not None or polarity_map is not None or frames is not None or crop is not None
                    or voxels is not None or time_surfaces is not None)
     prm = prm or Params()
     x, y, t = stream.x, stream.y, stream.t_ns
@@ -540,8 +546,98 @@ def run_pipeline(stream, prm=None, use_event_store=True, log=None, display_prefi
                 log("time surfaces: %d of %.3g ms, tau %.3g ms, %d to %d events each, in %.2f ms -> %s %s" %
                     (len(views), surface_ms, tau_ms, int(counts.min()), int(counts.max()), (time.perf_counter() - t0) * 1e3, path,
                      decayed.shape))
-        be.reconstruct_end()
+        if reject_outliers is not None:
+            be.reconstruct_restart(knots_rec)  # (whatever ran above, the count panorama of the whole range once more)
+            st = store
+            if st is None:  # (the selection reads its events from a device-resident store)
+                st = evaluator.EventStore(be.W, be.H, max(n_rec, 1))
+                st.push(x[i_rec:i_rec + n_rec], y[i_rec:i_rec + n_rec], t[i_rec:i_rec + n_rec])
+            first = i_rec if store is not None else 0
+            try:
+                res["reject"] = reject_outliers_pass(be, traj, st, first, n_rec, prm, float(reject_outliers), score_sigma, knots_rec,
+                                                     getattr(stream, "is_hot", None), i_rec, refine_native, log)
+            finally:
+                if store is None:
+                    st.close()
+        else:
+            be.reconstruct_end()
     return res
+
+
+def reject_outliers_pass(be, traj, store, first, count, prm, min_score, score_sigma, knots, is_hot, i_stream, refine, log):
+    """--reject-outliers: with the reconstruction begun and empty, vote store[first, first+count), score every event against the
+    panorama (leave-one-out, blurred with score_sigma), SELECT the voting events with score >= min_score into a second store on the
+    device (EventStore.select: the events never leave it; device tensors when torch is importable, host arrays otherwise),
+    reconstruct again from the cleaned store and, with refine, solve the trajectory again on it.  Closes the reconstruction.
+    A stream that says it has hot pixels (is_hot) also gets a sensor mask from the per-pixel event counts of the range
+    (EventStore.pixel_counts): a pixel with more than HOT_FACTOR times the mean count is dropped -- a hot pixel's events line up
+    along the camera's own path and support each other, so the score alone keeps them.
+    Returns a dict: kept, share, contrast_before / _after (variance contrast at sigma 1), recon (the cleaned panorama), and with hot
+    pixels in the stream hot_removed / hot_removed_by_score / others_kept, with refine knots + report.  It reports; nothing is asserted."""
+    try:
+        import torch
+    except ImportError:
+        torch = None
+    out = {}
+    clean = evaluator.EventStore(be.W, be.H, max(count, 1))
+    try:
+        be.reconstruct_add_from(store, first, count)
+        out["contrast_before"] = be.reconstruct_contrast(1.0)
+        be.reconstruct_score_open(score_sigma)
+        pixel_keep = None
+        mask_hot = is_hot is not None and np.any(is_hot)
+        if torch is not None:
+            if mask_hot:
+                d_c = torch.empty((be.H, be.W), dtype=torch.int32, device="cuda")
+                torch.cuda.synchronize()
+                store.pixel_counts(first, count, out=d_c)
+                pixel_keep = (d_c.double() <= HOT_FACTOR * count / (be.W * be.H)).to(torch.uint8).contiguous()
+                torch.cuda.synchronize()
+            d_s = torch.empty(count, dtype=torch.float32, device="cuda")
+            d_f = torch.empty(count, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            be.reconstruct_score_from(store, first, count, loo=True, out=(d_s, d_f))
+            kept = clean.select(store, first, count, score=d_s, min_score=min_score, flags=d_f, pixel_keep=pixel_keep)
+        else:
+            if mask_hot:
+                pixel_keep = (store.pixel_counts(first, count) <= HOT_FACTOR * count / (be.W * be.H)).astype(np.uint8)
+            s, f = be.reconstruct_score_from(store, first, count, loo=True)
+            kept = clean.select(store, first, count, score=s, min_score=min_score, flags=f, pixel_keep=pixel_keep)
+        out["kept"], out["share"] = kept, kept / max(count, 1)
+        be.reconstruct_restart(knots)
+        be.reconstruct_add_from(clean, 0, kept)
+        out["recon"] = be.reconstruct_get()
+        out["contrast_after"] = be.reconstruct_contrast(1.0)
+        be.reconstruct_end()
+        if log:
+            log("outlier rejection: %d of %d events kept (%.1f %%) at leave-one-out support >= %g (%s form); variance contrast at "
+                "sigma 1: %.6g -> %.6g" % (kept, count, 100.0 * out["share"], min_score, "device" if torch is not None else "host",
+                                          out["contrast_before"], out["contrast_after"]))
+        if mask_hot:  # (which events went: the same predicate in numpy, on host copies of the criteria)
+            hot = np.asarray(is_hot[i_stream:i_stream + count], bool)
+            if torch is not None:
+                s, f, pixel_keep = d_s.cpu().numpy(), d_f.cpu().numpy(), pixel_keep.cpu().numpy()
+            ex, ey = store.read(first, count)[:2]
+            keep = (s >= np.float32(min_score)) & ((f & 3) == 3) & (pixel_keep.reshape(-1)[ey.astype(np.int64) * be.W + ex] != 0)
+            by_score = (s >= np.float32(min_score)) & ((f & 3) == 3)  # (what the score and the flags alone would have kept)
+            out["hot_removed"] = float(np.mean(~keep[hot])) if hot.any() else 0.0
+            out["hot_removed_by_score"] = float(np.mean(~by_score[hot])) if hot.any() else 0.0
+            out["others_kept"] = float(np.mean(keep[~hot])) if (~hot).any() else 0.0
+            if log:
+                log("  hot pixels: %.1f %% of their %d events removed (%.1f %% by the score and flags alone, the rest by the pixel mask), "
+                    "%.1f %% of the other events kept" %
+                    (100.0 * out["hot_removed"], int(hot.sum()), 100.0 * out["hot_removed_by_score"], 100.0 * out["others_kept"]))
+        if refine and kept > 0:
+            t_clean = clean.read(0, kept)[2]
+            out["knots"], out["report"] = refine_trajectory(be, traj, None, None, t_clean, prm, clean, native=True)
+            if log:
+                r = out["report"]
+                log("  refinement on the cleaned store: %d events, %d iterations; contrast %.6g -> %.6g" %
+                    (r["events"], r["iterations"], r["contrast_before"], r["contrast_after"]))
+    finally:
+        be.reconstruct_end()
+        clean.close()
+    return out
 
 
 def _quat_from_matrix(R):
@@ -605,6 +701,12 @@ def main():
                     help="after the reconstruction (or any refine mode), write PATH.npz: the leave-one-out support score of every event "
                          "against the final panorama (score) and its flags; prints the quartiles and the share of voting events with "
                          "less than one vote of support (implies --reconstruct)")
+    ap.add_argument("--reject-outliers", type=float, metavar="MIN_SCORE", default=None,
+                    help="after the reconstruction (or any refine mode), select the voting events with leave-one-out support >= MIN_SCORE "
+                         "into a second event store on the device, reconstruct again from it and print the kept share and the variance "
+                         "contrast before and after; with --refine-native also solve again on the cleaned store (implies --reconstruct)")
+    ap.add_argument("--hot-pixels", type=int, metavar="N", default=0,
+                    help="N hot pixels fire 2 %% of the events each; --reject-outliers then prints how many of their events it removed")
     ap.add_argument("--score-sigma", type=float, default=1.0, help="blur of the panorama the scores are read from (0: none)")
     ap.add_argument("--polarity-map", metavar="PREFIX", default=None,
                     help="after the reconstruction, write the signed panorama ON - OFF as PREFIX.pgm and PREFIX.ppm (implies "
@@ -653,7 +755,7 @@ def main():
     if not a.surface_ms > 0 or (a.surface_tau_ms is not None and not a.surface_tau_ms > 0):
         ap.error("--surface-ms and --surface-tau-ms must be > 0")
     stream = synth.event_stream(a.rate, a.seconds, 240, 180, 200.0, 200.0, 119.5, 89.5, omega_mean=(0.2, 1.8, 0.3),
-                                omega_amp=(1.0, 0.8, 1.0))
+                                omega_amp=(1.0, 0.8, 1.0), hot_pixels=a.hot_pixels, hot_share=0.02 * a.hot_pixels)
     prm = Params()
     prm.spline_degree = a.degree
     prm.deterministic = a.deterministic
@@ -663,7 +765,7 @@ def main():
                        freeze_head=a.freeze_head, refine_online=a.refine_online, online_free=a.online_free, export_warped=a.export_warped,
                        polarity_map=a.polarity_map, frames=a.frames, frame_ms=a.frame_ms, crop=a.crop, voxels=a.voxels, voxel_ms=a.voxel_ms,
                        voxel_bins=a.voxel_bins, time_surfaces=a.time_surfaces, surface_ms=a.surface_ms, surface_tau_ms=a.surface_tau_ms,
-                       score_events=a.score_events, score_sigma=a.score_sigma)
+                       score_events=a.score_events, score_sigma=a.score_sigma, reject_outliers=a.reject_outliers)
     wall = time.perf_counter() - t0
     m = evaluate_against_truth(stream, res)
     print("%.2f s of events (%d) processed in %.2f s wall" % (a.seconds, len(stream.x), wall))
@@ -684,6 +786,10 @@ def main():
         m3 = evaluate_against_truth(stream, res)
         print("online refinement: contrast %.6g; orientation error rms %.3f deg -> %.3f deg; at most %d sampled events resident of %d" %
               (r["contrast_after"], m["ba_err_deg_rms"], m3["ba_err_deg_rms"], r["resident_max"], r["events"]))
+    if "knots" in res.get("reject", {}):
+        res["traj"].knots = res["reject"]["knots"]
+        m4 = evaluate_against_truth(stream, res)
+        print("refinement on the cleaned store: orientation error rms %.3f deg -> %.3f deg" % (m["ba_err_deg_rms"], m4["ba_err_deg_rms"]))
     if "recon" in res:
         print("reconstruction along the whole trajectory: %.0f votes, %.0f%% of pixels touched" %
               (float(res["recon"].sum(dtype=np.float64)), 100.0 * float((res["recon"] > 0).mean())))

@@ -308,6 +308,55 @@ int cmx_events_has_polarity(const cmx_events *ev);
 int cmx_events_drop_before(cmx_events *ev, int64_t global_index);
 int64_t cmx_events_begin(const cmx_events *ev); /* global index of the oldest event held */
 int64_t cmx_events_end(const cmx_events *ev);   /* one past the newest */
+/* Selection on the device: a STABLE stream compaction from a range of one store into another store -- what acts on the scores and
+ * flags of cmx_backend_recon_score_from_device (outlier rejection, hot-pixel removal) without the events leaving the device.  The
+ * result is an ordinary store: packets, windows, recon_add_from, bind_from, bind_append_from, warp_from, score_from, pol_add_from,
+ * views, voxels and surfaces read it by (store, first, count) like any other.
+ *   select      An event of src[first, first + count) is kept when EVERY criterion that is given (non-NULL) holds:
+ *                 keep        count bytes, nonzero = keep
+ *                 score       count floats, keep when score >= min_score, compared in fp32 (a NaN score is dropped)
+ *                 flags       count bytes, keep when (flags & flags_mask) == flags_value (the export's bit pair: mask = value = 3,
+ *                             "the event voted")
+ *                 pixel_keep  W*H bytes at y*W+x, nonzero = the events of this pixel are kept
+ *               With every pointer NULL everything is kept: a device-side store-to-store copy.  cmx_select::size = sizeof(cmx_select).
+ *               The kept events are APPENDED to dst in their source order (equal timestamps keep their order; dst stays
+ *               time-sorted); *n_kept (may be NULL) = their number.  Afterwards dst is indistinguishable from a store into which the
+ *               same events were pushed from host arrays: packed words, timestamps, polarity bytes, the host mirror of the
+ *               timestamps.  src is read only.  An empty dst takes src's polarity form, as the first push does.
+ *               Synchronous: the work runs on dst's own stream and the call returns when dst is complete.  select takes host
+ *               arrays (uploaded into scratch of dst); select_device takes device pointers on the stores' device for every non-NULL
+ *               member, and work of the caller's that still writes them must be finished (the rule of recon_warp_from_device).
+ *               Three launches -- predicate + per-tile count, scan of the tile counts, scatter -- and the host reads the total in
+ *               between: the scatter runs only when everything fits.
+ *   errors      each leaves dst exactly as it was (begin, end, contents).  CMX_ERR_INVALID_ARG: dst == src, a NULL store, sel NULL or
+ *               sel->size not the struct's; W / H differ; a range src does not hold; either store has more than one replica (group
+ *               stores are out of scope) or the two are on different devices; dst->size + kept > capacity ("event store full").
+ *               CMX_ERR_STATE: dst is non-empty and its polarity form differs from src's.  CMX_ERR_TIME_ORDER: the first KEPT event
+ *               is earlier than dst's last event.
+ *   pixel_counts  counts[y*W+x] = the number of events of the range at that pixel: W*H words, written, not accumulated (count == 0:
+ *               all zero); exact for any distribution (one integer atomic per event).  _device: d_counts on the store's device.
+ *               Synchronous, on the store's stream.  A group store: its first replica.
+ *   read        the inverse of cmx_events_push_pol: x, y unpacked from the packed words, pol 0 / 1.  Any of x, y, t_ns may be NULL;
+ *               pol is NULL or count bytes (CMX_ERR_STATE when the store holds no polarity).  A test and export call, sliced through
+ *               the store's pinned staging.
+ *   threads     pixel_counts* and read take a const store but use its stream, its pinned staging and its error text: like every
+ *               other call on a store they are not thread-safe against each other or against push, drop_before or select on the
+ *               same store (as source or destination). */
+typedef struct {
+  size_t size;                     /* sizeof(cmx_select): lets the struct grow without an ABI bump */
+  const unsigned char *keep;       /* count bytes or NULL: nonzero = keep */
+  const float *score;              /* count floats or NULL: keep when score >= min_score in fp32 (NaN: dropped) */
+  float min_score;
+  const unsigned char *flags;      /* count bytes or NULL: keep when (flags & flags_mask) == flags_value */
+  unsigned char flags_mask, flags_value;
+  const unsigned char *pixel_keep; /* W*H bytes at y*W+x or NULL: nonzero = events of this pixel are kept */
+} cmx_select;
+int cmx_events_select(cmx_events *dst, const cmx_events *src, int64_t first, int64_t count, const cmx_select *sel, int64_t *n_kept);
+int cmx_events_select_device(cmx_events *dst, const cmx_events *src, int64_t first, int64_t count, const cmx_select *sel,
+                             int64_t *n_kept);
+int cmx_events_pixel_counts(const cmx_events *ev, int64_t first, int64_t count, uint32_t *counts);
+int cmx_events_pixel_counts_device(const cmx_events *ev, int64_t first, int64_t count, uint32_t *d_counts);
+int cmx_events_read(const cmx_events *ev, int64_t first, int64_t count, uint16_t *x, uint16_t *y, int64_t *t_ns, unsigned char *pol);
 int cmx_frontend_set_packet_from(cmx_ctx *ctx, const cmx_events *ev, int64_t first, int64_t count, int64_t t_ref_ns,
                                  double fx, double fy, double cx, double cy, int event_batch_size, double blur_sigma,
                                  int contrast_measure);
@@ -1042,7 +1091,8 @@ int cmx_get_stats(cmx_ctx *ctx, double *stats, int n_stats); /* writes min(n_sta
  *     added without a bump (no signature or buffer layout changed): the seven cmx_backend_recon_* entry points, then
  *     recon_restart / _contrast / _grad_add[_aos|_from] / _grad_get / _eval_from, then recon_bind_from / _unbind / _eval_bound /
  *     _bound_info, then recon_freeze_head / _frozen_info / _solve, then recon_extend / _bind_append_from / _advance_head /
- *     _release_head / _online_info and the value CMX_RECON_KEEP_HEAD of recon_solve's freeze_head) */
+ *     _release_head / _online_info and the value CMX_RECON_KEEP_HEAD of recon_solve's freeze_head; the entry points of the later features (recon_warp*, recon_pol_*,
+ *     recon_view_*, recon_voxel_*, recon_surface_*, recon_score*) likewise; then cmx_events_select[_device] / _pixel_counts[_device] / _read with cmx_select) */
 #define CMX_ABI_VERSION 6
 int cmx_abi_version(void);
 int cmx_timing_enable(cmx_ctx *ctx, int on);

@@ -104,15 +104,19 @@ extern "C" {
 int cmx_set_stream_priority(cmx_ctx *ctx, int level);
 int cmx_set_cu_mask(cmx_ctx *ctx, const uint32_t *mask, int n_words);
 
-/* Process-wide test switches (read when a context / group is created; CMX_DIAG_RECON_SLICE_EVENTS: at every cmx_backend_recon_add*).
+/* Process-wide test switches (read when a context / group is created; CMX_DIAG_RECON_SLICE_EVENTS: at every cmx_backend_recon_add*;
+ * CMX_DIAG_EVENTS_STAGE_SLICE: at every call it acts on).
  *   CMX_DIAG_FORCE_CROSS_DEVICE  1: a group whose members share ONE device is set up as if they sat on several -- the peer kernels
  *                                take their system-scope acquire (xdev) variants and the exchange's events release to system scope --
  *                                so that a one-GPU box executes the code paths of a multi-GPU group.  Results
  *                                are unchanged; the collectives get slower.
  *   CMX_DIAG_RECON_SLICE_EVENTS  n > 0: the internal slices of cmx_backend_recon_add* hold about n events (whole batches, at least
  *                                one) instead of 2^22, so that a small input runs the multi-slice, double-buffered path; 0: the
- *                                default.  Results are unchanged (bitwise in deterministic mode). */
-enum { CMX_DIAG_FORCE_CROSS_DEVICE = 1, CMX_DIAG_RECON_SLICE_EVENTS = 2 };
+ *                                default.  Results are unchanged (bitwise in deterministic mode).
+ *   CMX_DIAG_EVENTS_STAGE_SLICE  n > 0: a slice of cmx_events_read and of the timestamps' read-back of cmx_events_select* holds at
+ *                                most n events instead of what the store's pinned staging holds, so that a small store runs the
+ *                                multi-slice loops; 0: the default; read at every such call.  Results are unchanged. */
+enum { CMX_DIAG_FORCE_CROSS_DEVICE = 1, CMX_DIAG_RECON_SLICE_EVENTS = 2, CMX_DIAG_EVENTS_STAGE_SLICE = 3 };
 int cmx_diag_set(int key, int value);
 
 /* Of the last cmx_backend_recon_solve on this context: the evaluations it made (the closing cost-only one included) and the times a
