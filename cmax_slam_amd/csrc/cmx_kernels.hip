@@ -1869,32 +1869,10 @@ __global__ __launch_bounds__(256) void be_gather_kernel(BeGatherArgs g) {
       const BeWarp w = be_warp_event<2>(a, i);
       batch = w.batch;
       if (w.ok) {
-        float A, B;
-        bilinear_grad(g.itilde, a.Wp, w.xx, w.yy, w.dx, w.dy, A, B);
-        V0 = (double)A * (double)w.m[0] + (double)B * (double)w.m[3];
-        V1 = (double)A * (double)w.m[1] + (double)B * (double)w.m[4];
-        V2 = (double)A * (double)w.m[2] + (double)B * (double)w.m[5];
-        float Ac, Bc;
-        border_grad(g.cx, g.cy, a.Wp, a.Hp, g.r, w.xx, w.yy, w.dx, w.dy, Ac, Bc);
-        if (Ac != 0.f || Bc != 0.f) {  // rare: votes within r of the panorama border
-          U0 = (double)Ac * (double)w.m[0] + (double)Bc * (double)w.m[3];
-          U1 = (double)Ac * (double)w.m[1] + (double)Bc * (double)w.m[4];
-          U2 = (double)Ac * (double)w.m[2] + (double)Bc * (double)w.m[5];
-        }
+        be_grad_vote(w, g.itilde, g.cx, g.cy, a.Wp, a.Hp, g.r, V0, V1, V2, U0, U1, U2);
       }
     }
-    const bool any_u = __any(U0 != 0.0 || U1 != 0.0 || U2 != 0.0);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const double t0 = __shfl_down(V0, o, 64), t1 = __shfl_down(V1, o, 64), t2 = __shfl_down(V2, o, 64);
-      const int bo = __shfl_down(batch, o, 64);
-      const bool same = lane + o < 64 && bo == batch;
-      if (same) { V0 += t0; V1 += t1; V2 += t2; }
-      if (any_u) {  // wave-uniform
-        const double u0 = __shfl_down(U0, o, 64), u1 = __shfl_down(U1, o, 64), u2 = __shfl_down(U2, o, 64);
-        if (same) { U0 += u0; U1 += u1; U2 += u2; }
-      }
-    }
+    run_sum(batch, lane, V0, V1, V2, U0, U1, U2);
     const int bprev = __shfl_up(batch, 1, 64);
     if (batch >= 0 && (lane == 0 || bprev != batch)) {
       const int part = (base >> g.slice_shift) - ((batch * a.per_batch) >> g.slice_shift);
@@ -1925,29 +1903,10 @@ __global__ __launch_bounds__(256) void be_gather4_kernel(BeGatherArgs g) {
   const BeSplatArgs &a = g.ev;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nwaves = gridDim.x * 4;
-#ifdef CMX_BE_GATHER_LDS_POSE
-  // EXPERIMENT (measured, rejected: profiles/r06_be_lds_pose.txt): the rotations of the batches a wave pass meets
-  // (<= kPoseRuns) fetched ONE PASS AHEAD into a per-wave LDS slot by 9 x kPoseRuns lanes -- one 72-byte load per batch run instead of
-  // one per lane, off the pass's critical path, no registers held across the warp -- and read back from LDS by every lane.
-  constexpr int kPoseRuns = 4;  // 256 events of a pass span at most 256 / per_batch + 2 batches; the launcher's per_batch >= 100
-  __shared__ double shR[2][4][kPoseRuns * 9];
-  auto load_pose = [&](int base_next) -> double {  // (the value stays in ONE register pair across the pass: the LDS write comes at its end)
-    if (lane < kPoseRuns * 9 && base_next < a.n) {
-      const int b = min(base_next / a.per_batch + lane / 9, (a.n - 1) / a.per_batch);
-      return a.poseR[b].R[lane % 9];
-    }
-    return 0.0;
-  };
-  int pslot = 0;
-  if (lane < kPoseRuns * 9) shR[0][wave][lane] = load_pose((blockIdx.x * 4 + wave) * 256);
-#endif
   for (int base = (blockIdx.x * 4 + wave) * 256; base < a.n; base += nwaves * 256) {
     const int i0 = base + lane * 4;
     double V0 = 0, V1 = 0, V2 = 0, U0 = 0, U1 = 0, U2 = 0;
     int batch = -1;
-#ifdef CMX_BE_GATHER_LDS_POSE
-    const double rnext = load_pose(base + nwaves * 256);  // the NEXT pass's rotations: in flight while this pass warps
-#endif
     if (i0 < a.n) {
       batch = i0 / a.per_batch;
       uint32_t e[4];
@@ -1959,16 +1918,8 @@ __global__ __launch_bounds__(256) void be_gather4_kernel(BeGatherArgs g) {
         for (int u = 0; u < 4; u++) e[u] = (i0 + u < a.n) ? a.xy[i0 + u] : 0u;
       }
       double R[9];
-#ifdef CMX_BE_GATHER_LDS_POSE
-      {
-        const double *Rl = shR[pslot][wave] + (batch - base / a.per_batch) * 9;
-#pragma unroll
-        for (int k = 0; k < 9; k++) R[k] = Rl[k];
-      }
-#else
 #pragma unroll
       for (int k = 0; k < 9; k++) R[k] = a.poseR[batch].R[k];
-#endif
       double rx[4], ry[4], rz[4];  // e_ray_w = R * bearing of the lane's four events
       if (g.tb && i0 + 3 < a.n) {  // 64 contiguous bytes per lane from the time-ordered bearing stream: (x, y), z = 1
 #pragma unroll
@@ -1988,7 +1939,8 @@ __global__ __launch_bounds__(256) void be_gather4_kernel(BeGatherArgs g) {
       for (int u = 0; u < 4; u++) {
         if (i0 + u >= a.n) break;
         const BeWarp w = be_project<2>(a, e[u], batch, rx[u], ry[u], rz[u]);
-        if (w.ok) {
+        if (w.ok) {  // (restates be_grad_vote and, below, run_sum of cmx_warp.hpp, accumulating over the lane's four events with explicit
+                     //  FMAs: through the helpers the folded form measured 2 % longer, profiles/handoff_primitives_refactor.txt)
 #pragma clang fp contract(fast)  // the fp64 sums of fp32 x fp32 products (exact in fp64): two FMAs per component instead of two multiplies + two adds
           float A, B;
           bilinear_grad(g.itilde, a.Wp, w.xx, w.yy, w.dx, w.dy, A, B);
@@ -2006,10 +1958,6 @@ __global__ __launch_bounds__(256) void be_gather4_kernel(BeGatherArgs g) {
         }
       }
     }
-#ifdef CMX_BE_GATHER_LDS_POSE
-    pslot ^= 1;
-    if (lane < kPoseRuns * 9) shR[pslot][wave][lane] = rnext;
-#endif
     const bool any_u = __any(U0 != 0.0 || U1 != 0.0 || U2 != 0.0);
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {

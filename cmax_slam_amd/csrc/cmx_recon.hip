@@ -941,32 +941,10 @@ __global__ __launch_bounds__(kReconThreads) void recon_gather_kernel(const Recon
       const BeWarp w = be_warp_math<2>(a.cam, e, b, v0, v1, v2, R);
       if (w.ok) {
         inside++;
-        float A, B;
-        bilinear_grad(g.itilde, a.cam.Wp, w.xx, w.yy, w.dx, w.dy, A, B);
-        V0 = (double)A * (double)w.m[0] + (double)B * (double)w.m[3];
-        V1 = (double)A * (double)w.m[1] + (double)B * (double)w.m[4];
-        V2 = (double)A * (double)w.m[2] + (double)B * (double)w.m[5];
-        float Ac, Bc;
-        border_grad(g.cx, g.cy, a.cam.Wp, a.cam.Hp, g.r, w.xx, w.yy, w.dx, w.dy, Ac, Bc);
-        if (Ac != 0.f || Bc != 0.f) {  // rare: votes within r of the panorama border
-          U0 = (double)Ac * (double)w.m[0] + (double)Bc * (double)w.m[3];
-          U1 = (double)Ac * (double)w.m[1] + (double)Bc * (double)w.m[4];
-          U2 = (double)Ac * (double)w.m[2] + (double)Bc * (double)w.m[5];
-        }
+        be_grad_vote(w, g.itilde, g.cx, g.cy, a.cam.Wp, a.cam.Hp, g.r, V0, V1, V2, U0, U1, U2);
       }
     }
-    const bool any_u = __any(U0 != 0.0 || U1 != 0.0 || U2 != 0.0);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const double t0 = __shfl_down(V0, o, 64), t1 = __shfl_down(V1, o, 64), t2 = __shfl_down(V2, o, 64);
-      const int jo = __shfl_down(j, o, 64);
-      const bool same = lane + o < 64 && jo == j;
-      if (same) { V0 += t0; V1 += t1; V2 += t2; }
-      if (any_u) {  // wave-uniform
-        const double u0 = __shfl_down(U0, o, 64), u1 = __shfl_down(U1, o, 64), u2 = __shfl_down(U2, o, 64);
-        if (same) { U0 += u0; U1 += u1; U2 += u2; }
-      }
-    }
+    const bool any_u = run_sum(j, lane, V0, V1, V2, U0, U1, U2);
     const int jprev = __shfl_up(j, 1, 64);
     const bool head = j >= 0 && (lane == 0 || jprev != j);  // (one head per batch and wave: distinct LDS cells within a wave)
     double *dst = sh_vu + 6 * (j < 0 ? 0 : j);

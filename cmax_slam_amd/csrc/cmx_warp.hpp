@@ -254,4 +254,43 @@ __device__ __forceinline__ void border_grad(const float *cx, const float *cy, in
   }
 }
 
+// back end and reconstruction: per event V = (dItilde/dx, dItilde/dy) * dpm_ddrot (3-vector, BeWarp::m), and its border twin U
+// against c = G^T 1 (zero but for votes within r of the panorama border).  fp64 sums of fp32 x fp32 products (exact in fp64).
+// V and U are ASSIGNED the products' sums (one event per lane: be_gather_kernel, recon_gather_kernel).  be_gather4_kernel, four events
+// per lane, accumulates with explicit FMAs under a contract pragma and keeps its own text (it measured 2 % longer through a helper).
+__device__ __forceinline__ void be_grad_vote(const BeWarp &w, const float *itilde, const float *cx, const float *cy, int Wp, int Hp, int r,
+                                             double &V0, double &V1, double &V2, double &U0, double &U1, double &U2) {
+  float A, B;
+  bilinear_grad(itilde, Wp, w.xx, w.yy, w.dx, w.dy, A, B);
+  V0 = (double)A * (double)w.m[0] + (double)B * (double)w.m[3];
+  V1 = (double)A * (double)w.m[1] + (double)B * (double)w.m[4];
+  V2 = (double)A * (double)w.m[2] + (double)B * (double)w.m[5];
+  float Ac, Bc;
+  border_grad(cx, cy, Wp, Hp, r, w.xx, w.yy, w.dx, w.dy, Ac, Bc);
+  if (Ac != 0.f || Bc != 0.f) {  // rare: votes within r of the panorama border
+    U0 = (double)Ac * (double)w.m[0] + (double)Bc * (double)w.m[3];
+    U1 = (double)Ac * (double)w.m[1] + (double)Bc * (double)w.m[4];
+    U2 = (double)Ac * (double)w.m[2] + (double)Bc * (double)w.m[5];
+  }
+}
+
+// segmented wave reduction of V and U over the runs of equal `run` (a batch index, -1 = no event; events of a run are adjacent
+// lanes): afterwards the first lane of every run holds the run's sums.  Returns whether any lane of the wave had a non-zero U
+// (wave-uniform; U's shuffles are skipped otherwise).
+__device__ __forceinline__ bool run_sum(int run, int lane, double &V0, double &V1, double &V2, double &U0, double &U1, double &U2) {
+  const bool any_u = __any(U0 != 0.0 || U1 != 0.0 || U2 != 0.0);
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double t0 = __shfl_down(V0, o, 64), t1 = __shfl_down(V1, o, 64), t2 = __shfl_down(V2, o, 64);
+    const int ro = __shfl_down(run, o, 64);
+    const bool same = lane + o < 64 && ro == run;
+    if (same) { V0 += t0; V1 += t1; V2 += t2; }
+    if (any_u) {  // wave-uniform
+      const double u0 = __shfl_down(U0, o, 64), u1 = __shfl_down(U1, o, 64), u2 = __shfl_down(U2, o, 64);
+      if (same) { U0 += u0; U1 += u1; U2 += u2; }
+    }
+  }
+  return any_u;
+}
+
 }  // namespace cmx
